@@ -18,7 +18,7 @@ and 4 (segment g comes from seed 1234 + g whatever N is).  Two partitions of tha
                  prefix) and meet at the bucket's owner through an RCCL all-to-all inside libgasm (gasm_pool_exchange_build:
                  grouped ncclSend / ncclRecv on the library's stream), the merged edge list goes on to the segment's owner,
                  so do the segment's reads (SURVEY §8(e) mode 2).
-With N > 1 and the default mode a few pooled steps are timed as well and reported under "pooled" in the same JSON line
+With N > 1, the default mode and --full a few pooled steps are timed as well and reported under "pooled" in the same JSON line
 (a watchdog prints the line without them and exits with status 3 if an exchange stalls, naming the stage and rank).
 torch.distributed is bootstrap only (gloo: barrier, max over ranks, the 128-byte RCCL id); no tensor of the data path is torch's.
 
@@ -27,7 +27,14 @@ numpy MT19937(seed = 1234 + global segment id) with 20 copies of one 300-bp bloc
 1-kb tandem repeat of a 6-bp unit planted at seeded offsets; reads = ceil(cov*L/rl) uniform starts from
 MT19937(10000019 + seed), starts whose read would run past the end dropped, forward strand, no errors.
 
-Prints ONE JSON line (rank 0).  roofline: the dominant kernel's algorithmic bytes per launch / its mean launch time
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line (`value`,
+`ms_per_step`, config); `roofline`, `cpu_baseline` and `verified` are null there.  --full adds everything below (the pass
+with one step in flight, the warm second upload of `pcie_inclusive`, the pooled steps at N > 1, the CPU baseline and the
+self-check against the oracle).  --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy
+(float64, float32 for contig bases): per-segment and per-contig arrays in full, the distinct k-mers (64-bit key words as
+two exact 32-bit halves), their multiplicities and the contigs' bases of a fixed seeded sample of segments (_write_outputs).
+
+roofline (--full): the dominant kernel's algorithmic bytes per launch / its mean launch time
 from HIP events recorded on the library's own streams.  Consecutive steps of the timed region overlap (step slots), which
 makes a launch's duration THERE a residence time on a shared chip; the kernel's own duration comes from a short pass with
 one step in flight right after the timed region (roofline.measured says so; roofline.timed_region keeps the other figures;
@@ -63,7 +70,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--alone-steps", type=int, default=10, help="untimed extra steps with ONE step in flight, for the kernels' own durations (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, the warm second upload, the pooled steps at N > 1, the CPU baseline and the "
+                    "self-check against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--alone-steps", type=int, default=10, help="--full: untimed extra steps with ONE step in flight, for the kernels' own durations (0 = skip)")
     ap.add_argument("--steps", type=int, default=100)      # (a step is ~1 ms: 20 of them were over before the clocks had settled)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
@@ -75,7 +85,10 @@ def parse_args():
     ap.add_argument("--no-pooled", action="store_true", help="N > 1: skip the additional pooled steps")
     ap.add_argument("--cpu-sample-segments", type=int, default=3)
     ap.add_argument("--breakdown", action="store_true", help="also print a per-kernel time table to stderr")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -212,6 +225,7 @@ def main():
     pcie = None
     guided_info = None
     pooled_main = None
+    outputs = None
     if args.mode == "segments":
         # rank r owns the contiguous block of global segments parallel.shard_bounds(nseg * world, world)[r]
         reads, seg_off, genomes = synth.make_batch(nseg, L, rl, cov, seed0=1234 + seg_lo, planted=True)
@@ -234,34 +248,39 @@ def main():
         for _ in range(4):
             step()
             batch.distinct()
-        dt, prof = timed(step, args.steps, args.warmup, profile=profiled)
-        seg, keys, mult, _w = batch.distinct()
+        # per-kernel HIP events in the timed region feed only the roofline: a plain run records none
+        dt, prof = timed(step, args.steps, args.warmup, profile=profiled if args.full else None)
+        seg, keys, mult, w = batch.distinct()
         n_distinct = int(seg[-1])
-        sc_all = batch.scores()
-        # Consecutive steps of a one-block batch are in flight together (step slots, capi.hip): inside the timed region a
-        # kernel shares the chip with the other steps' kernels and its launch duration says how long it was resident, not
-        # what it moves per second when it has the chip.  A short untimed pass with one step in flight (GASM_PINGPONG=0,
-        # read by every gasm_batch_build) gives the kernels' own durations; both go into `roofline`.
-        prof_alone = dt_alone = None
-        if args.alone_steps > 0 and os.environ.get("GASM_PINGPONG", "1") != "0" and nseg > 0:
-            keep = os.environ.get("GASM_SCORE_LANE")
-            os.environ["GASM_PINGPONG"] = os.environ["GASM_SCORE_LANE"] = "0"       # (nor the last step's scoring beside the partition)
-            dt_alone, prof_alone = timed(step, args.alone_steps, 3, profile=profiled)
-            del os.environ["GASM_PINGPONG"], os.environ["GASM_SCORE_LANE"]
-            if keep is not None:
-                os.environ["GASM_SCORE_LANE"] = keep
-        # a second upload, timed warm (the first one pays the allocations): what a caller that hands over host buffers sees
-        t_up2 = time.perf_counter()
-        b2 = ga.SegmentBatch.from_packed(words, seg_off, fixed_len=rl, ctx=ctx)
-        ctx.sync()
-        t_up2 = time.perf_counter() - t_up2
-        b2.close()
-        step_s = dt / args.steps
-        pcie = {"upload_ms": round(min(t_up, t_up2) * 1e3, 3), "bytes": int(words.nbytes), "what": "2-bit packed reads, pageable host memory",
-                "value_incl_upload": round(n_kmers * world / (step_s + min(t_up, t_up2)), 1), "unit": "k-mers/s"}
-        # SURVEY §8(d) bytes of the scoring: packed reads + packed paths + 16 B per hit + 32 B of results per path
-        score_bytes = (n_reads * rl / 4.0 + float(np.sum(sc_all["sequence_len"])) / 4.0 + 16.0 * float(np.sum(sc_all["kmer_breaks"]))
-                       + 32.0 * len(sc_all["kmer_breaks"]))
+        if args.dump_outputs:
+            cseg, coff, raw = batch.contigs_raw()
+            outputs = dict(seg=seg, keys=keys, words=w, mult=mult, cseg=cseg, coff=coff, raw=raw, scores=batch.scores())
+        score_bytes = None
+        if args.full:
+            sc_all = batch.scores()
+            # Consecutive steps of a one-block batch are in flight together (step slots, capi.hip): inside the timed region a
+            # kernel shares the chip with the other steps' kernels and its launch duration says how long it was resident, not
+            # what it moves per second when it has the chip.  A short untimed pass with one step in flight (GASM_PINGPONG=0,
+            # read by every gasm_batch_build) gives the kernels' own durations; both go into `roofline`.
+            if args.alone_steps > 0 and os.environ.get("GASM_PINGPONG", "1") != "0" and nseg > 0:
+                keep = os.environ.get("GASM_SCORE_LANE")
+                os.environ["GASM_PINGPONG"] = os.environ["GASM_SCORE_LANE"] = "0"       # (nor the last step's scoring beside the partition)
+                dt_alone, prof_alone = timed(step, args.alone_steps, 3, profile=profiled)
+                del os.environ["GASM_PINGPONG"], os.environ["GASM_SCORE_LANE"]
+                if keep is not None:
+                    os.environ["GASM_SCORE_LANE"] = keep
+            # a second upload, timed warm (the first one pays the allocations): what a caller that hands over host buffers sees
+            t_up2 = time.perf_counter()
+            b2 = ga.SegmentBatch.from_packed(words, seg_off, fixed_len=rl, ctx=ctx)
+            ctx.sync()
+            t_up2 = time.perf_counter() - t_up2
+            b2.close()
+            step_s = dt / args.steps
+            pcie = {"upload_ms": round(min(t_up, t_up2) * 1e3, 3), "bytes": int(words.nbytes), "what": "2-bit packed reads, pageable host memory",
+                    "value_incl_upload": round(n_kmers * world / (step_s + min(t_up, t_up2)), 1), "unit": "k-mers/s"}
+            # SURVEY §8(d) bytes of the scoring: packed reads + packed paths + 16 B per hit + 32 B of results per path
+            score_bytes = (n_reads * rl / 4.0 + float(np.sum(sc_all["sequence_len"])) / 4.0 + 16.0 * float(np.sum(sc_all["kmer_breaks"]))
+                           + 32.0 * len(sc_all["kmer_breaks"]))
         if args.guided:
             # configs[4]'s combined mode: build + score + breakage-score-guided traversal (row A16; not in the reference)
             def gstep():
@@ -274,11 +293,15 @@ def main():
                            "what": "build + score + guided traversal (gasm_batch_guided waits for the scores it steers by: one host round trip per step)"}
     else:
         be, comm, step, pstate, n_kmers, n_reads = pooled_setup()
-        dt, prof = timed(step, args.steps, args.warmup, profile=profiled)
+        dt, prof = timed(step, args.steps, args.warmup, profile=profiled if args.full else None)
         score_bytes = None
         res = be.results(with_scores=True)
         n_distinct = sum(len(d["counts"]) for d in res)
         pooled_main = (be, comm, pstate, res)
+        if args.dump_outputs:
+            outputs = _pooled_outputs(res, k)
+    if args.dump_outputs:
+        _write_outputs(args.dump_outputs, outputs, f"rank{rank}_" if world > 1 else "", max(1, 16 // world), 64_000_000 // world)
 
     # ---- roofline of the dominant kernel (HIP events on the library's stream, timed steps only)
     key_bytes = 8.0 if k <= 31 else 16.0      # W of SURVEY §8(d)
@@ -289,9 +312,11 @@ def main():
         # read the key back (W bytes per k-mer) + write (key, multiplicity) per distinct k-mer
         "k_bucket_dedup": n_kmers * key_bytes + n_distinct * (key_bytes + 4.0),
     }
-    dom = max(dominant, key=lambda n: prof.get(n, (0.0, 0))[0])
-    ms, launches = prof.get(dom, (0.0, 0))
     roofline = None
+    ms, launches = 0.0, 0
+    if prof:                                  # (--full only: a plain run records no per-kernel events)
+        dom = max(dominant, key=lambda n: prof.get(n, (0.0, 0))[0])
+        ms, launches = prof.get(dom, (0.0, 0))
     if launches:
         avg_s = ms / launches / 1e3
         ach = alg_bytes[dom] / avg_s / 1e9
@@ -375,7 +400,7 @@ def main():
 
     # ---- additional pooled steps at N > 1 (default mode), guarded: a stalled exchange must not cost the main line
     pooled_info = None
-    if world > 1 and args.mode == "segments" and not args.no_pooled and not one_gpu:
+    if world > 1 and args.mode == "segments" and args.full and not args.no_pooled and not one_gpu:
         psteps = max(1, min(5, args.steps))
         # watchdog thread (a signal handler would not run while the main thread sits in a blocking runtime call): after
         # 180 s rank 0 prints the line without the pooled figures and every rank leaves with status 3
@@ -407,7 +432,7 @@ def main():
 
     # ---- CPU baseline + self-check: the oracle on a bounded sample (rank 0, N=1 only)
     cpu, verified = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import orc  # checker / baseline only
         keys_s = qtable.keys()
         if args.mode == "segments":
@@ -482,6 +507,56 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def _pooled_outputs(res, k):
+    """the pooled backend's per-segment results in the flat form of SegmentBatch's fetches (k-mers packed again as gasm.h packs
+    them: 2 bits per base, base 0 most significant)"""
+    words = 1 if k <= 31 else 2
+    kmers = [km for d in res for km in d["distinct"]]
+    codes = np.zeros(256, dtype=np.uint64)
+    codes[np.frombuffer(b"CGT", dtype=np.uint8)] = np.arange(1, 4, dtype=np.uint64)
+    bases = codes[np.frombuffer("".join(kmers).encode(), dtype=np.uint8)].reshape(len(kmers), k)
+    keys = np.zeros((len(kmers), words), dtype=np.uint64)
+    for j in range(k):
+        bit = 2 * (k - 1 - j)
+        keys[:, words - 1 - bit // 64] |= bases[:, j] << np.uint64(bit % 64)
+    contigs = [c.encode() for d in res for c in d["contigs"]]
+    cat = lambda name: np.concatenate([d[name] for d in res]) if res else np.zeros(0)
+    return dict(seg=np.concatenate([[0], np.cumsum([len(d["counts"]) for d in res])]).astype(np.uint64), keys=keys.reshape(-1), words=words,
+                mult=cat("counts"), cseg=np.concatenate([[0], np.cumsum([len(d["contigs"]) for d in res])]).astype(np.uint64),
+                coff=np.concatenate([[0], np.cumsum([len(c) for c in contigs])]).astype(np.uint64), raw=b"".join(contigs),
+                scores={n: cat(n) for n in ("bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len", "kmer_breaks", "sequence_len")})
+
+
+def _write_outputs(dirname, o, prefix, n_sample, budget):
+    """--dump-outputs: the results of the last timed step as float64 .npy files (contig bases as float32), every value exact.
+    Per-segment and per-contig arrays are written whole; the distinct k-mers (each 64-bit key word as its high and low 32
+    bits), their multiplicities and the contigs' bases only for `n_sample` segments drawn with a fixed seed."""
+    seg, cseg, coff = (np.asarray(o[n], dtype=np.int64) for n in ("seg", "cseg", "coff"))
+    n_seg = len(seg) - 1
+    sample = np.sort(np.random.default_rng(0).permutation(n_seg)[:n_sample])
+    ix = np.concatenate([np.arange(seg[s], seg[s + 1]) for s in sample]) if n_seg else np.zeros(0, dtype=np.int64)
+    key_words = np.asarray(o["keys"], dtype=np.uint64).reshape(-1, o["words"])[ix]
+    raw = np.frombuffer(o["raw"], dtype=np.uint8)
+    bases = [raw[coff[cseg[s]]:coff[cseg[s + 1]]] for s in sample]
+    arrays = {
+        "distinct_kmers_per_segment": np.diff(seg),
+        "contigs_per_segment": np.diff(cseg),
+        **{n: o["scores"][n] for n in ("sequence_len", "kmer_breaks", "bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len")},
+        "sample_segments": sample,
+        "sample_kmer_key_hi32": key_words >> np.uint64(32),
+        "sample_kmer_key_lo32": key_words & np.uint64(0xFFFFFFFF),
+        "sample_kmer_multiplicity": np.asarray(o["mult"])[ix],
+    }
+    arrays = {n: np.asarray(a).astype(np.float64) for n, a in arrays.items()}
+    arrays["sample_contig_bases"] = np.concatenate(bases).astype(np.float32) if bases else np.zeros(0, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {budget} allowed")
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, prefix + n + ".npy"), a)
 
 
 def _print_line(args, world, nseg, L, rl, cov, k, n_kmers, n_reads, n_distinct, dt, roofline, cpu, breakdown, pooled_info, verified, pcie, guided_info):

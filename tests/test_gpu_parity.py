@@ -677,13 +677,13 @@ def _check_batch_properties(b, seg_off, rl, k, n_seg):
 def test_bench_prints_one_json_line_with_the_contract_keys():
     """bench.py on the smallest workload: file descriptor 1 carries exactly ONE line, a JSON object with the keys of the
     contract (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline /
-    dtype / data / config.workload) plus `roofline` (bound, achieved, peak, unit, frac, traffic; the kernel's own duration and the
-    timed region's residence times) — whatever libraries print on the way (RCCL and Gloo banners) goes to stderr."""
+    dtype / data / config.workload) plus, with --full, `roofline` (bound, achieved, peak, unit, frac, traffic; the kernel's own
+    duration and the timed region's residence times) — whatever libraries print on the way (RCCL and Gloo banners) goes to stderr."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [x for x in p.stdout.split("\n") if x.strip()]
@@ -699,6 +699,37 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
         assert key in r, key
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
 
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints the contract keys with the --full-only parts
+    null, and --dump-outputs writes float32 / float64 .npy files of at most 64 MB that two runs with the same arguments
+    write alike."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / run)], cwd=root, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = [x for x in p.stdout.split("\n") if x.strip()]
+        assert len(out) == 1, p.stdout[:500]
+        lines.append(json.loads(out[0]))
+        names = sorted(os.listdir(tmp_path / run))
+        dumps.append({n: np.load(tmp_path / run / n) for n in names})
+    j = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in j, key
+    assert j["steps"] == 7 and j["warmup"] == 2 and j["roofline"] is None and j["cpu_baseline"] is None and j["verified"] is None
+    assert j["value"] > 0 and abs(j["value"] - j["config"]["kmers_per_step"] / (j["ms_per_step"] * 1e-3)) < 1e-3 * j["value"]
+    a, b = dumps
+    assert sorted(a) == sorted(b) and "bp_score.npy" in a and "sample_kmer_key_lo32.npy" in a
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]), n
+    assert a["distinct_kmers_per_segment.npy"].tolist() == [j["config"]["distinct_kmers_rank0"]]
+    assert a["sample_kmer_multiplicity.npy"].sum() == j["config"]["kmers_per_step"]
 
 def test_more_segments_than_cus(qtable):
     """A batch with more segments than the chip has CUs (configs[3] on fewer GPUs than eight looks like this): the other side
