@@ -102,6 +102,9 @@ SYMBOLS = {
     "gasm_batch_fetch_contigs": (_int, [_vp, _PP, _PP, _PP]),
     "gasm_batch_fetch_graph": (_int, [_vp, _PP, _PP]),
     "gasm_batch_fetch_scores": (_int, [_vp, _PP, _PP, _PP, _PP, _PP]),
+    "gasm_batch_count_read_kmers": (_int, [_vp]),
+    "gasm_batch_fetch_read_kmer_counts": (_int, [_vp, _PP]),
+    "gasm_count_read_kmers": (_int, [_vp, _vp, _vp, _u64, _int, _vp, _vp, _u64, _vp]),
     "gasm_pool_create": (_int, [_vp, _vp, _u64, _u32, _vp, _u32, _PP]),
     "gasm_pool_free": (None, [_vp]),
     "gasm_pool_key_words": (_int, [_vp]),

@@ -282,6 +282,23 @@ def calc_breakscore(path, sequencing_reads, true_solution, kmer, bp_kmer, bp_pro
     return out
 
 
+def count_read_kmers(sequencing_reads, kmer, bp_kmer=None, ctx=None):
+    """count_read_kmers (lib/DeNovoAssembler.R:135-168, the reference's only_kmers_from_reads mode): occurrences of every
+    kmer-long window (kmer in 2, 4, 6, 8) lying inside one read, as np.uint32 aligned to bp_kmer (duplicates allowed, absent
+    k-mers 0).  bp_kmer=None: all 4**kmer k-mers in lexicographic ACGT order, the row order of the breakage table of that
+    length.  Counted on the GPU (gasm_count_read_kmers)."""
+    ctx = ctx or default_context()
+    rb, ro = _pack(sequencing_reads)
+    if bp_kmer is None:
+        out = np.zeros(4 ** int(kmer) if kmer in (2, 4, 6, 8) else 0, dtype=np.uint32)
+        check(lib().gasm_count_read_kmers(ctx.h, rb, _ptr(ro), len(sequencing_reads), int(kmer), None, None, 0, _ptr(out)))
+    else:
+        kb, ko = _pack(bp_kmer)
+        out = np.zeros(len(bp_kmer), dtype=np.uint32)
+        check(lib().gasm_count_read_kmers(ctx.h, rb, _ptr(ro), len(sequencing_reads), int(kmer), kb, _ptr(ko), len(bp_kmer), _ptr(out)))
+    return out
+
+
 def coverage_percent(starts, lens, seq_len, ctx=None):
     """contig_frac_len (lib/DeNovoAssembler.R:432-445): percentage of [1, seq_len] covered by the union of the inclusive
     ranges [start, start + len]"""

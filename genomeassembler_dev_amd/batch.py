@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import qtable
+from . import qtable, readkmers
 from ._lib import check, default_context, lib
 from .api import unpack_kmers
 
@@ -116,6 +116,24 @@ class SegmentBatch:
         self._table = t
         check(lib().gasm_batch_score(self.h, int(kmer), t.ctypes.data_as(C.c_void_p)))
         return self
+
+    def count_read_kmers(self):
+        """break-k-mer counts of every segment's reads (count_read_kmers, lib/DeNovoAssembler.R:135-168, for k = 2, 4, 6 and 8
+        at once): (n_segments, 69 904) uint32 in breakage-table order.  Reads only the packed reads: any build and score of the
+        batch are unaffected, before or after."""
+        check(lib().gasm_batch_count_read_kmers(self.h))
+        p = C.c_void_p()
+        check(lib().gasm_batch_fetch_read_kmer_counts(self.h, C.byref(p)))
+        n = self.n_segments * qtable.ROWS
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        self._rkc = a.reshape(self.n_segments, qtable.ROWS)
+        return self._rkc
+
+    def read_kmer_counts(self, segment, kmer):
+        """the 4**kmer counts of one segment and length from the last count_read_kmers() (counted now if there was none)"""
+        if getattr(self, "_rkc", None) is None:
+            self.count_read_kmers()
+        return self._rkc[segment, readkmers.table_slice(kmer)]
 
     def total_kmers(self):
         return int(lib().gasm_batch_total_kmers(self.h))

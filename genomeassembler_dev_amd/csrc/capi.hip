@@ -93,6 +93,9 @@ struct SubBatch {
     gasm_ctx* score_cx_last = nullptr;      // where the last scoring was queued (fetches read from there)
     hipEvent_t ev_built = nullptr, ev_scored = nullptr;
     bool lane_last = false;                 // the last build recorded ev_built for the lane (GASM_SCORE_LANE is read per build)
+    // break-k-mer counts of the reads (gasm_batch_count_read_kmers): GASM_TABLE_ROWS per segment; reads only d_words / d_read_off
+    DBuf d_rkc;
+    bool rkc_checked = false;               // read_kmer_windows_check passed (the reads never change)
 };
 
 static bool score_lane_wanted(const gasm_batch* b);
@@ -123,6 +126,9 @@ struct gasm_batch {
     std::vector<u32> h_read_start;
     std::vector<int64_t> h_fx;
     std::vector<u64> h_sim_seg_off;
+    // gasm_batch_count_read_kmers
+    bool rkc_counted = false;
+    std::vector<u32> h_rkc;
 };
 
 // Read the report of a sub-batch's queued build (repeating the build if it failed, and then the scoring queued behind it).
@@ -787,7 +793,7 @@ void gasm_batch_free(gasm_batch* b) {
         if (sb.ev_built) (void)hipEventDestroy(sb.ev_built);
         if (sb.ev_scored) (void)hipEventDestroy(sb.ev_scored);
         for (StepSlot& x : sb.slot) { if (x.cx && x.cx != sb.cx) (void)hipStreamSynchronize(x.cx->stream); if (x.ev_streamed) (void)hipEventDestroy(x.ev_streamed); x.bs.release(); x.dp.release(); x.ss.release(); }
-        sb.rd.release(); sb.tb.release(); sb.guided.release();
+        sb.rd.release(); sb.tb.release(); sb.guided.release(); sb.d_rkc.release();
         if (sb.ev_streamed) (void)hipEventDestroy(sb.ev_streamed);
     }
     delete b;
@@ -916,6 +922,92 @@ int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) 
     HIPCHK(hipStreamSynchronize(sb.S().cx->stream));
     *fx = b->h_fx.data();
     *shift = sb.tb.fix_shift;
+    return GASM_OK;
+    API_GUARD_END
+}
+
+// ---- count_read_kmers (lib/DeNovoAssembler.R:135-168): break-k-mer counts of the reads, kernels_count.hip
+int gasm_batch_count_read_kmers(gasm_batch* b) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    for (SubBatch& sb : b->sub) {
+        if (!sb.rkc_checked) GCHK(read_kmer_windows_check(sb.rd));
+        sb.rkc_checked = true;
+    }
+    // on the stream the block's reads were made on: behind them in stream order, beside whatever the step slots run (the kernel
+    // only reads the packed stream and its offsets, which no build or score writes)
+    for (SubBatch& sb : b->sub) {
+        HIPCHK(hipSetDevice(sb.cx->device));
+        GCHK(sb.d_rkc.ensure((size_t)(sb.seg1 - sb.seg0) * GASM_TABLE_ROWS * 4));
+        GCHK(launch_read_kmer_count(sb.cx, sb.rd, sb.d_rkc.as<u32>()));
+    }
+    b->rkc_counted = true;
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_read_kmer_counts(gasm_batch* b, const uint32_t** counts) {
+    API_GUARD_BEGIN
+    if (!b || !counts) { gasm_set_error("gasm_batch_fetch_read_kmer_counts: null argument"); return GASM_ERR_INVALID; }
+    if (!b->rkc_counted) { gasm_set_error("gasm_batch_fetch_read_kmer_counts before gasm_batch_count_read_kmers"); return GASM_ERR_STATE; }
+    b->h_rkc.resize((size_t)b->n_segments * GASM_TABLE_ROWS);
+    for (SubBatch& sb : b->sub) {
+        HIPCHK(hipSetDevice(sb.cx->device));
+        HIPCHK(hipMemcpyAsync(b->h_rkc.data() + (size_t)sb.seg0 * GASM_TABLE_ROWS, sb.d_rkc.p, (size_t)(sb.seg1 - sb.seg0) * GASM_TABLE_ROWS * 4,
+                              hipMemcpyDeviceToHost, sb.cx->stream));
+    }
+    for (SubBatch& sb : b->sub) HIPCHK(hipStreamSynchronize(sb.cx->stream));
+    *counts = b->h_rkc.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+static const u32 kRkcRow[9] = {0, 0, 0, 0, 16, 0, 272, 0, 4368};      // first breakage-table row of each length
+
+int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int kmer, const char* keys,
+                          const uint64_t* key_off, uint64_t n_keys, uint32_t* counts) {
+    API_GUARD_BEGIN
+    if (!ctx || (n_reads && (!reads || !read_off)) || (keys && n_keys && !key_off)) { gasm_set_error("gasm_count_read_kmers: null argument"); return GASM_ERR_INVALID; }
+    if (kmer != 2 && kmer != 4 && kmer != 6 && kmer != 8) { gasm_set_error("kmer must be 2, 4, 6 or 8 (got %d)", kmer); return GASM_ERR_INVALID; }
+    const u64 n_out = keys ? n_keys : (1ull << (2 * kmer));
+    if (n_out && !counts) { gasm_set_error("gasm_count_read_kmers: counts is null"); return GASM_ERR_INVALID; }
+    // the table row of every key (base-4 value = lexicographic rank)
+    std::vector<u32> row;
+    if (keys) {
+        row.resize(n_keys);
+        for (u64 i = 0; i < n_keys; ++i) {
+            if (key_off[i + 1] < key_off[i] || key_off[i + 1] - key_off[i] != (u64)kmer) {
+                gasm_set_error("key %llu is not %d bases long", (unsigned long long)i, kmer);
+                return GASM_ERR_INVALID;
+            }
+            u32 v = 0;
+            for (u64 j = key_off[i]; j < key_off[i + 1]; ++j) {
+                const u8 c = (u8)keys[j];
+                if (c != 'A' && c != 'C' && c != 'G' && c != 'T') { gasm_set_error("key %llu holds a byte outside upper-case ACGT", (unsigned long long)i); return GASM_ERR_NON_ACGT; }
+                v = v << 2 | (((c >> 1) & 3u) ^ ((c >> 2) & 1u));
+            }
+            row[i] = v;
+        }
+    }
+    std::vector<u32> tab(1ull << (2 * kmer), 0);
+    if (n_reads && read_off[n_reads] > read_off[0]) {
+        // one segment of ragged reads through the batch kernel
+        DevReads rd;
+        DBuf d;
+        struct Rel { DevReads& r; DBuf& d; ~Rel() { r.release(); d.release(); } } rel{rd, d};
+        const u64 seg_off[2] = {0, n_reads};
+        GCHK(rd.upload(ctx, reads, read_off, n_reads, 0, seg_off, 1));
+        GCHK(read_kmer_windows_check(rd));
+        GCHK(d.ensure((size_t)GASM_TABLE_ROWS * 4));
+        GCHK(launch_read_kmer_count(ctx, rd, d.as<u32>()));
+        HIPCHK(hipMemcpyAsync(tab.data(), d.as<u32>() + kRkcRow[kmer], tab.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    } else if (n_reads) {
+        for (u64 r = 0; r < n_reads; ++r)
+            if (read_off[r + 1] < read_off[r]) { gasm_set_error("read_off not monotone"); return GASM_ERR_INVALID; }
+    }
+    if (keys) for (u64 i = 0; i < n_keys; ++i) counts[i] = tab[row[i]];
+    else memcpy(counts, tab.data(), tab.size() * 4);
     return GASM_OK;
     API_GUARD_END
 }

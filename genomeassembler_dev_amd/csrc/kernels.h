@@ -161,6 +161,10 @@ __global__ void k_sim_draw(const u64* cum, const u64* woff, const u64* doff, con
 __global__ void k_sim_compact(const u32* start, const u32* keep, const u32* rank, const u64* doff, const u64* seg_read_off, u32* kept_start);
 __global__ void k_sim_extract(const u64* gwords, const u64* gbase, const u64* seg_read_off, const u32* kept_start, u32 read_len, unsigned long long* out);
 
+// ---- kernels_count.hip: break-k-mer counts of the reads, GASM_TABLE_ROWS per segment; 2^LS workgroups per segment
+template <int LS>
+__global__ void k_read_kmer_count(const u64* words, const u64* read_off, const u64* seg_read_off, u32 fixed_len, u32 n_segments, u32* out);
+
 // ---- kernels_score.hip
 struct SeedTable {
     u64* seed;            // slot -> seed value

@@ -172,6 +172,13 @@ int pipeline_ks(gasm_ctx* ctx, DevPaths& dp, ScoreState& ss, const ScoreTable& t
 int pipeline_coverage(gasm_ctx* ctx, const long long* start, const long long* len, u64 n, long long seq_len, double* percent);
 int pipeline_levenshtein(gasm_ctx* ctx, DevPaths& dp, const char* target, u64 target_len, bool infix, std::vector<int32_t>& lev, bool* done);
 
+// count_read_kmers (kernels_count.hip): every segment's GASM_TABLE_ROWS window counts into d_out, queued on the ctx stream.
+// read_kmer_windows_check (host, once per set of reads): GASM_ERR_CAPACITY where a segment holds 2^32 or more windows of
+// length 2, the only way a u32 counter could wrap.  read_kmer_split: workgroups per segment (GASM_RKC_SPLIT)
+int read_kmer_windows_check(const DevReads& rd);
+int launch_read_kmer_count(gasm_ctx* ctx, const DevReads& rd, u32* d_out);
+int read_kmer_split();
+
 // wait for `ticket` to appear at `word` (pinned memory written last by a kernel of the ctx stream); spin, then poll with a deadline
 int gasm_wait_word32(gasm_ctx* ctx, const volatile u32* word, u32 ticket);
 int gasm_wait_word64(gasm_ctx* ctx, const volatile u64* word, u64 ticket);

@@ -261,6 +261,30 @@ int gasm_batch_fetch_scores(gasm_batch* b, const double** bp_score, const double
                             const double** norm_by_len, const int32_t** kmer_breaks, const int32_t** sequence_len);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * count_read_kmers(sequencing_reads, kmer)                      replaces lib/DeNovoAssembler.R:135-168
+ *   (the reference's only_kmers_from_reads mode: table() of every kmer-long window of the reads, match()ed onto the
+ *   breakage table of that length, absent k-mers 0 — table_read_kmer_prob)
+ * A window counts only if it lies inside one read; a read shorter than kmer has none.
+ * gasm_batch_count_read_kmers   every segment's counts of all four lengths at once: GASM_TABLE_ROWS u32 per segment in
+ *                               breakage-table order (rows 0 / 16 / 272 / 4368 start k = 2 / 4 / 6 / 8, each lexicographic).
+ *                               Queued on the stream the batch's reads were made on; no host wait.  Reads only the packed
+ *                               reads: it works before any build, between a build and its score and after both, and changes
+ *                               no build or score result.  GASM_ERR_CAPACITY where a segment holds 2^32 or more windows of
+ *                               length 2 (below that no counter can wrap).  GASM_RKC_SPLIT in the environment: workgroups per
+ *                               segment (2, 4 or 8; the bins are split between them by the leading bits of the k-mer).
+ * gasm_batch_fetch_read_kmer_counts   n_segments x GASM_TABLE_ROWS counts of the last count, segment after segment; the host
+ *                               copy stays valid until the next count or free.  GASM_ERR_STATE before any count.
+ * gasm_count_read_kmers         the string form (what the Rcpp glue calls), one segment through the same kernel: counts[i] =
+ *                               occurrences of key i (duplicates allowed; each key kmer ACGT bytes, else GASM_ERR_INVALID /
+ *                               GASM_ERR_NON_ACGT); keys == NULL: all 4^kmer k-mers in lexicographic order (the order of the
+ *                               reference's df_prob[[kmer_k]]) and n_keys is not read.  kmer must be 2, 4, 6 or 8.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int gasm_batch_count_read_kmers(gasm_batch* b);
+int gasm_batch_fetch_read_kmer_counts(gasm_batch* b, const uint32_t** counts);
+int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int kmer, const char* keys,
+                          const uint64_t* key_off, uint64_t n_keys, uint32_t* counts);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Pooled builds over several GPUs: the reads of every segment are spread over the ranks, k-mers are bucketed by
  * (segment, first bits of the k-mer) and every bucket's records are brought together on one rank by an all-to-all before
  * the global edge-list merge (SURVEY.md §8(e) mode 2; the reference has no counterpart: it loops over segments on one

@@ -82,6 +82,24 @@ std::vector<std::vector<std::string>> get_contigs_from_reads(const std::vector<s
     return m;
 }
 
+// count_read_kmers (lib/DeNovoAssembler.R:135-168, only_kmers_from_reads = TRUE): the count of every kmer-long window of the
+// reads (kmer 2, 4, 6 or 8) for all 4^kmer k-mers in lexicographic order — the row order of df_prob[[paste0("kmer_", kmer)]] —,
+// 0 where a k-mer never occurs; counted on the GPU.  In DeNovoAssembler.R: count_vals <- count_read_kmers(
+// self$sequencing_reads$read_one, self$kmer) in place of the table() + match() steps
+// [[Rcpp::export]]
+std::vector<int> count_read_kmers(const std::vector<std::string>& sequencing_reads, const int& kmer) {
+    Flat f(sequencing_reads);
+    if (kmer != 2 && kmer != 4 && kmer != 6 && kmer != 8) Rcpp::stop("count_read_kmers: kmer must be 2, 4, 6 or 8");
+    std::vector<uint32_t> c((size_t)1 << (2 * kmer));
+    check(gasm_count_read_kmers(the_ctx(), f.data.data(), f.off.data(), sequencing_reads.size(), kmer, nullptr, nullptr, 0, c.data()));
+    std::vector<int> out(c.size());
+    for (size_t i = 0; i < c.size(); ++i) {
+        if (c[i] > 2147483647u) Rcpp::stop("count_read_kmers: a count exceeds R's integer range");
+        out[i] = (int)c[i];
+    }
+    return out;
+}
+
 // replaces lib/DeNovoAssembler.cpp:215-305
 // [[Rcpp::export]]
 std::vector<std::string> assemble_contigs(const std::vector<std::vector<std::string>>& contig_matrix, const int& dbg_kmer) {
