@@ -857,7 +857,7 @@ int gasm_batch_score(gasm_batch* b, int kmer, const double* table) {
             sb.table_set = true;
         }
         // reads shorter than k (or none): the general scorer, which sizes its tables on the host — after the build's report
-        const bool through_graph = pipeline_score_uses_graph(sb.rd, sb.S().bs);
+        const bool through_graph = pipeline_score_uses_graph(sb.rd, sb.S().bs, sb.tb);
         if (!through_graph) GCHK(sub_finish(b, sb));
         // through the graph: on the lane, behind the build (its queue, not its completion: stream order does the rest)
         gasm_ctx* const own = sb.S().cx;
@@ -913,7 +913,11 @@ int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) 
     if (b->sub.size() != 1 || !b->scored) { gasm_set_error("gasm_batch_fetch_score_fixed needs a scored, unsplit batch"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
     SubBatch& sb = b->sub[0];
-    if (!sb.S().ss.graph) { gasm_set_error("the batch was not scored through its graph"); return GASM_ERR_STATE; }
+    if (!sb.S().ss.graph) {
+        gasm_set_error("the batch was scored in FP64, not in fixed point (reads shorter than k, or a table with NaN / infinite entries or a "
+                       "range the 64-bit fixed point cannot hold): there are no fixed-point sums");
+        return GASM_ERR_STATE;
+    }
     const u32 P = sb.S().bs.n_contigs;
     b->h_fx.resize(P);
     const size_t fx_off = (sb.S().ss.stride * 4 + 15) & ~(size_t)15;

@@ -149,6 +149,13 @@ int assemble(const std::vector<std::string>& contigs, const u32* perm, u64 rows,
 bool assemble_signatures(const std::vector<std::string>& contigs, const u32* perm, u64 rows, u64 row_len, int k, std::vector<std::string>& sigs);
 // Myers bit-parallel edit distance; infix = edlib HW mode, else NW.
 int levenshtein(const char* q, u64 nq, const char* t, u64 nt, bool infix);
+// Shift of the batch scorer's 64-bit fixed point: weights round(p * 2^shift), summed over at most
+// `max_terms` reads per path.  absmax = max |p| over the finite entries, finite = no NaN or infinity in the table.
+// Returns the shift with absmax * max(1, max_terms) * 2^shift in (2^60, 2^61], or -1 when no such shift lies in
+// [0, 1000] or the table is not all finite (the caller then scores in FP64).  A table of zeros gets 62.
+int fixed_point_shift(double absmax, bool finite, u64 max_terms);
+// one pass over a table for fixed_point_shift: *absmax = max |t[i]| over the finite entries; returns whether all are finite
+bool table_range(const double* t, size_t n, double* absmax);
 // reads of sequence files, packed 2-bit back to back (seqio.cpp)
 struct PackedReads {
     std::vector<u64> words;        // 32 bases per word, first base most significant

@@ -13,11 +13,39 @@
 #include <random>
 #include <thread>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 
 #include "gasm_internal.h"
 
 namespace gasm_host {
+
+// x = absmax * n exactly as a 117-bit integer times a power of two; shift = 61 - ceil(log2 x) puts x * 2^shift in
+// (2^60, 2^61], so n weights of at most 2^61 + 1/2 sum to less than 2^62.  Upper limit 1000: 2^-shift stays a normal
+// double, so bp_score = fx * 2^-shift rounds once (in the conversion of fx).
+int fixed_point_shift(double absmax, bool finite, u64 max_terms) {
+    if (!finite || !(absmax >= 0.0)) return -1;
+    if (absmax == 0.0) return 62;
+    int e = 0;
+    const double f = std::frexp(absmax, &e);                                     // absmax = f * 2^e, f in [0.5, 1)
+    const unsigned __int128 x = (unsigned __int128)(u64)std::ldexp(f, 53) * std::max<u64>(1, max_terms);   // absmax * n = x * 2^(e - 53)
+    int bits = 0;
+    for (unsigned __int128 t = x; t; t >>= 1) ++bits;
+    const bool pow2 = (x & (x - 1)) == 0;
+    const int shift = 61 - ((pow2 ? bits - 1 : bits) + e - 53);
+    return shift >= 0 && shift <= 1000 ? shift : -1;
+}
+
+bool table_range(const double* t, size_t n, double* absmax) {
+    bool finite = true;
+    double mx = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        if (std::isfinite(t[i])) mx = std::max(mx, std::fabs(t[i]));
+        else finite = false;
+    }
+    *absmax = mx;
+    return finite;
+}
 
 void shuffle_perm(u64 n, int seed, u64 rows, std::vector<u32>& perm) {
     perm.resize(rows * n);

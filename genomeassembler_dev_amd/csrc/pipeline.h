@@ -115,10 +115,13 @@ struct ScoreTable {
     DBuf d_prob, d_row, d_fix;
     std::vector<double> h_prob;   // direct-address table as uploaded
     std::vector<double> h_row_prob;   // the caller's table, row by row (KS statistic: rows in ascending-probability order)
-    double h_absmax = 0;          // max |prob| (set with the table)
+    double h_absmax = 0;          // max |prob| over the finite entries (set with the table)
+    bool h_finite = false;        // no NaN or infinity in the table (set_standard)
     int fix_shift = -1;           // d_fix = round(prob * 2^fix_shift), -1 = not built
     u32 n_table = 0;
-    int set_fixed(gasm_ctx* ctx, u64 max_terms);
+    // the fixed-point shift for at most max_terms reads per path, -1 = the table needs the FP64 scorer (gasm_host::fixed_point_shift)
+    int fixed_shift(u64 max_terms) const;
+    int set_fixed(gasm_ctx* ctx, int shift);
     int set(gasm_ctx* ctx, const char* bp_kmer, const u64* bp_off, u64 n_table, const double* bp_prob);
     int set_standard(gasm_ctx* ctx, const double* table69904);
     void release();
@@ -162,7 +165,8 @@ int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, c
                           bool want_pd, ScoreState& ss, const BuildState* graph);
 int pipeline_score_fetch(gasm_ctx* ctx, ScoreState& ss);
 // batch scoring can go through the build's graph (queued without waiting for the build) when every read holds a k-mer
-bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph);
+// and the table has a fixed-point shift for these reads (ScoreTable::fixed_shift); otherwise it takes the FP64 position path
+bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, const ScoreTable& tb);
 // Levenshtein distance of every path of `dp` against `target` (ASCII) on the GPU (k_levenshtein).  *done = false when
 // the target holds a byte outside ACGT (the packed form cannot represent it): the caller then uses the host routine.
 // Two-sample KS statistic of every path's path_freq against the genome's per-position window probabilities

@@ -1051,23 +1051,17 @@ int ScoreTable::set_standard(gasm_ctx* ctx, const double* t) {
     GCHK(h2d(ctx, d_row, row.data(), row.size() * 4));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     h_prob = prob;
-    h_absmax = 0;
-    for (double v : h_prob) h_absmax = std::max(h_absmax, std::fabs(v));
+    h_finite = gasm_host::table_range(h_prob.data(), h_prob.size(), &h_absmax);
     fix_shift = -1;
     return GASM_OK;
 }
 
-// 64-bit fixed-point copy of the table for the batch scorer: round(prob * 2^shift), shift chosen so that the sum over
-// `max_terms` reads cannot overflow 62 bits.
-int ScoreTable::set_fixed(gasm_ctx* ctx, u64 max_terms) {
-    const double mx = h_absmax;
-    int shift = 62;
-    if (mx > 0) {
-        const double need = std::log2(mx * (double)std::max<u64>(1, max_terms));
-        shift = (int)std::floor(62.0 - need) - 1;
-    }
-    shift = std::max(0, std::min(1000, shift));
-    if (shift > 1000) shift = 1000;
+int ScoreTable::fixed_shift(u64 max_terms) const { return gasm_host::fixed_point_shift(h_absmax, h_finite, max_terms); }
+
+// 64-bit fixed-point copy of the table for the batch scorer: round(prob * 2^shift), shift from fixed_shift (the sum
+// over a segment's reads cannot pass 2^62)
+int ScoreTable::set_fixed(gasm_ctx* ctx, int shift) {
+    if (shift < 0 || !h_finite) { gasm_set_error("the table has no fixed-point shift for these reads"); return GASM_ERR_STATE; }
     if (shift == fix_shift) return GASM_OK;
     std::vector<long long> fx(h_prob.size());
     for (size_t i = 0; i < fx.size(); ++i) fx[i] = std::llrint(std::ldexp(h_prob[i], shift));
@@ -1227,6 +1221,12 @@ int pipeline_coverage(gasm_ctx* ctx, const long long* start, const long long* le
 // ---------------------------------------------------------------------------------------------------------------
 // score: pipeline_score_launch queues everything on the stream; pipeline_score_fetch copies the results back.
 // ---------------------------------------------------------------------------------------------------------------
+static u64 max_seg_reads(const DevReads& rd) {
+    u64 m = 0;
+    for (u32 s = 0; s < rd.n_segments; ++s) m = std::max(m, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
+    return m;
+}
+
 // Batch scoring of a build's own contigs (gasm_batch_score): queued behind the build without waiting for it.  The number
 // of paths is read on the device (graph.d_seg_cstart[S]); outputs are allocated at the build's upper bound.
 static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, ScoreState& ss, const BuildState& graph) {
@@ -1255,9 +1255,8 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     gv.k = graph.k;
     gv.bbits = graph.bbits;
     gv.fbits = graph.fbits;
-    u64 max_reads = 0;
-    for (u32 s = 0; s < S; ++s) max_reads = std::max(max_reads, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
-    GCHK(const_cast<ScoreTable&>(tb).set_fixed(ctx, max_reads));
+    const u64 max_reads = max_seg_reads(rd);
+    GCHK(const_cast<ScoreTable&>(tb).set_fixed(ctx, tb.fixed_shift(max_reads)));
     // GASM_SCORE_VERIFY=1: compare every read with the contig text where the graph says it lies (kernels_score.hip, graph_match);
     // a mismatch raises flags[2] of the build and pipeline_score_fetch refuses the scores
     const int verify = env_int("GASM_SCORE_VERIFY", 0);
@@ -1290,8 +1289,8 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     return GASM_OK;
 }
 
-bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph) {
-    return graph.n_kmers > 0 && rd.n_reads > rd.n_empty && rd.min_len >= (u32)graph.k;
+bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, const ScoreTable& tb) {
+    return graph.n_kmers > 0 && rd.n_reads > rd.n_empty && rd.min_len >= (u32)graph.k && tb.fixed_shift(max_seg_reads(rd)) >= 0;
 }
 
 int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_freq, bool want_pd,
@@ -1305,7 +1304,7 @@ int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, c
     ss.want_freq = want_freq && tb.n_table;
     ss.want_pd = want_pd;
     ss.graph = nullptr;
-    if (graph && !want_freq && !want_pd && pipeline_score_uses_graph(rd, *graph)) return score_launch_graph(ctx, rd, dp, kmer, tb, ss, *graph);
+    if (graph && !want_freq && !want_pd && pipeline_score_uses_graph(rd, *graph, tb)) return score_launch_graph(ctx, rd, dp, kmer, tb, ss, *graph);
     // ---- arbitrary paths (or reads that do not all hold a k-mer): host-side sizes are needed — the caller has uploaded
     // the paths or, for a build's contigs, read the build's report (pipeline_contig_paths_host)
     ss.n_paths = dp.n_paths;

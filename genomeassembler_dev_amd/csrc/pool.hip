@@ -79,7 +79,7 @@ int pool_score_launch(gasm_pool* p, int kmer, const double* table, bool wait_for
         p->table_set = true;
     }
     // through the graph (every read holds a k-mer) the scoring needs no size from the host and is queued behind the build as it is
-    const bool through_graph = p->n_local && pipeline_score_uses_graph(p->own, p->bs);
+    const bool through_graph = p->n_local && pipeline_score_uses_graph(p->own, p->bs, p->tb);
     if (wait_for_build || !through_graph) GCHK(pipeline_build_finish_n(ctx, nullptr, p->n_local, p->bs, nullptr));
     if (!p->paths_ready) {
         GCHK(pipeline_contig_paths(ctx, p->own, p->bs, p->dp));

@@ -344,7 +344,8 @@ int scaffolds_as_paths(const gasm_scaffolds* sc, DevPaths& dp) {
 // ---------------------------------------------------------------------------------------------------------------
 int guided_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DevPaths& cp, ScoreState& cs, const ScoreTable& tb, int kmer, GuidedState& g) {
     g.valid = false;
-    if (!cs.graph || cs.graph != &bs) { gasm_set_error("guided traversal needs the batch scored through its graph (reads of at least k bases)"); return GASM_ERR_STATE; }
+    if (!cs.graph || cs.graph != &bs) { gasm_set_error("guided traversal needs the batch scored through its graph in fixed point (reads of at least k bases, a finite "
+                                                             "table the 64-bit fixed point can hold)"); return GASM_ERR_STATE; }
     if (rd.n_empty) { gasm_set_error("guided traversal: empty reads are not supported"); return GASM_ERR_INVALID; }
     HIPCHK(hipSetDevice(ctx->device));
     const u32 S = rd.n_segments, P = bs.n_contigs;

@@ -135,8 +135,11 @@ void gasm_strlist_free(gasm_strlist* s);
  * (n_paths x n_table doubles, in bp_kmer order — the reference emits them in hash-iteration order, so only the
  * multiset per path is defined there).
  * bp_kmer keys must be distinct ACGT strings of length 1..8 (the reference tables hold lengths 2,4,6,8).
- * Scores are FP64, summed in a fixed order (deterministic run to run); the reference sums in hash-iteration order,
- * hence the 1e-9 absolute tolerance of the parity tests.
+ * Scores are FP64, summed in a fixed order (deterministic run to run); the reference sums in hash-iteration order.
+ * Numeric contract (u = 2^-53, per path m = kmer_breaks and S = sum |p * c| over the hit rows): bp_score and
+ * norm_by_break_freqs lie within (m+2) u S (S / kmer_breaks for the latter) of the exact sums, whatever the summation order;
+ * norm_by_len == bp_score / len and every path_freq entry == the correctly rounded count / kmer_breaks, bit for bit; NaN and
+ * infinite table rows that are hit follow IEEE double arithmetic.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define GASM_SCORE_OWN 0
 #define GASM_SCORE_VELVET 1
@@ -191,7 +194,14 @@ int gasm_levenshtein(const char* query, uint64_t nq, const char* target, uint64_
  * gasm_batch_build(k)  : k-mers -> distinct k-mers + multiplicities -> (k-1)-mer graph -> contigs, per segment
  *                        (get_contigs without the shuffle; results identical to calling it per segment)
  * gasm_batch_score     : calc_breakscore (own variant, without Levenshtein/path_freq) of every segment's contigs
- *                        against that segment's reads; table = GASM_TABLE_ROWS normalised probabilities
+ *                        against that segment's reads; table = GASM_TABLE_ROWS normalised probabilities (any doubles).
+ *                        Fixed point when every read holds a k-mer, the table is all finite and a shift with
+ *                        max|p| * (most reads of a segment) * 2^shift in [2^60, 2^62) lies in [0, 1000]: per path
+ *                        fx = sum round(p * 2^shift) exactly, bp_score == fx * 2^-shift, norm_by_break_freqs ==
+ *                        bp_score / kmer_breaks (0 without hits), norm_by_len == bp_score / len, bit for bit, and
+ *                        |bp_score - exact| <= m 2^-(shift+1) + u |exact|.  Otherwise the FP64 scorer of
+ *                        gasm_calc_breakscore, with its contract; gasm_batch_fetch_score_fixed and gasm_batch_guided then
+ *                        return GASM_ERR_STATE.
  * Both queue work on the ctx stream and return; gasm_ctx_sync (or any fetch) waits.
  * ---------------------------------------------------------------------------------------------------------------- */
 int gasm_batch_create(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, uint32_t fixed_len,
@@ -382,7 +392,9 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
 int gasm_batch_guided(gasm_batch* b);
 int gasm_batch_fetch_guided(gasm_batch* b, const uint64_t** seg_off /*n_segments+1*/, const uint64_t** off, const char** data,
                             const double** bp_score, const double** norm_by_len, const int32_t** kmer_breaks);
-/* the exact fixed-point sums behind the batch scores: bp_score[c] == fx[c] * 2^-shift */
+/* the exact fixed-point sums behind the batch scores: bp_score[c] == fx[c] * 2^-shift.  GASM_ERR_STATE when the last
+ * gasm_batch_score took the FP64 scorer (reads shorter than k, or a table the fixed point cannot hold: see gasm_batch_score);
+ * gasm_batch_guided needs the same sums and fails the same way */
 int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift);
 
 /* Per-kernel device time of the stages of build/score, accumulated with HIP events on the ctx stream since the last

@@ -14,26 +14,12 @@ breakage table, k, the break k-mer size (8) and the fixed-point shift of the bat
   the index of their first contig."""
 from fractions import Fraction
 
-
-def break_window_prob(path, pos, kmer, table):
-    """lib/DeNovoAssembler.cpp:366-386 (+ a window cut short by the end of the path to a length the table does not hold: 0)"""
-    start = max(0, pos - kmer // 2)
-    width = 8
-    if start == 0 and pos in (1, 2, 3):
-        width = 2 * pos
-    return table.get(path[start:start + width], 0.0)
+from oracle import exact_scores
 
 
 def fixed_sums(contigs, reads, table, kmer, shift):
-    out = []
-    for c in contigs:
-        fx = 0
-        for r in reads:
-            p = c.find(r)
-            if p >= 0:
-                fx += int(round(break_window_prob(c, p, kmer, table) * 2.0 ** shift))
-        out.append(fx)
-    return out
+    """fx(c) of every contig: the exact integer sums of oracle/exact_scores.py"""
+    return [e.fixed_sum(shift) for e in exact_scores.score_paths(contigs, reads, table, kmer)]
 
 
 def guided_paths(contigs, fx, k):

@@ -1,10 +1,11 @@
 // san_driver.cpp — host algorithms of libgasm (host_algos.cpp, seqio.cpp) and the oracle, compiled together with
 // -fsanitize=address,undefined by tests/test_sanitizers.py and run on randomised inputs: shuffle matrix, greedy merge in
 // both forms (index form and string form, incl. the substr-out-of-range case), signatures, Myers edit distance in both
-// modes against the oracle's DP, the sequence-file reader.  Exit code 0 = every comparison held and no sanitizer report.
+// modes against the oracle's DP, the sequence-file reader, the batch scorer's fixed-point shift (--tables=FILE).  Exit code 0 = every comparison held and no sanitizer report.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <string>
 #include <vector>
@@ -98,6 +99,22 @@ int main(int argc, char** argv) {
         }
     }
     for (int i = 1; i < argc; ++i) {
+        if (!strncmp(argv[i], "--tables=", 9)) {
+            // the batch scorer's fixed-point decision (table_range + fixed_point_shift) for tables of GASM_TABLE_ROWS doubles
+            FILE* f = fopen(argv[i] + 9, "rb");
+            if (!f) { fprintf(stderr, "%s: cannot open\n", argv[i]); return 1; }
+            std::vector<double> t(GASM_TABLE_ROWS);
+            for (int n = 0; fread(t.data(), 8, t.size(), f) == t.size(); ++n) {
+                double mx = -1;
+                const bool finite = gasm_host::table_range(t.data(), t.size(), &mx);
+                for (u64 terms : {0ull, 1ull, 150ull, 16667ull, 20000ull, 1ull << 40})
+                    printf("table %d: finite %d, terms %llu, shift %d\n", n, (int)finite, (unsigned long long)terms,
+                           gasm_host::fixed_point_shift(mx, finite, terms));
+                ++checks;
+            }
+            fclose(f);
+            continue;
+        }
         gasm_host::PackedReads pr;
         u64 kept = 0, dropped = 0;
         const int st = gasm_host::read_sequence_file(argv[i], false, pr, &kept, &dropped);

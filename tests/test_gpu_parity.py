@@ -1,6 +1,7 @@
 """GPU parity: the HIP path (through the C ABI) against the CPU oracle on the same seeded inputs.
 Bit-exact: distinct k-mers + multiplicities, edge lists, contigs, shuffle matrix, scaffolds, kmer_breaks, Levenshtein.
-FP64 scores: within 1e-9 absolute (north-star tolerance; the reference sums in hash-iteration order)."""
+FP64 scores: within 1e-9 absolute (north-star tolerance; the reference sums in hash-iteration order) and within 2^-36
+relative, exact zeros included (tests/test_score_exact_gpu.py holds them to the exact sums)."""
 import json
 import os
 
@@ -9,7 +10,7 @@ import pytest
 
 import genomeassembler_dev_amd as ga
 from genomeassembler_dev_amd import qtable, synth
-from oracle import orc
+from oracle import exact_scores, orc
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -28,6 +29,7 @@ def _check_scores(mine, ref, with_lev=True):
         assert np.array_equal(np.isnan(a), np.isnan(b)), key
         ok = ~np.isnan(a)
         assert np.abs(a[ok] - b[ok]).max(initial=0.0) < TOL, key
+        assert exact_scores.rel_close(a[ok], b[ok]).all(), (key, np.flatnonzero(~exact_scores.rel_close(a[ok], b[ok]))[:5])
     if with_lev:
         assert mine["lev_dist_vs_true"].tolist() == ref["lev_dist_vs_true"].tolist()
 

@@ -6,7 +6,7 @@ import pytest
 
 import genomeassembler_dev_amd as ga
 from genomeassembler_dev_amd import pooled, synth
-from oracle import orc
+from oracle import exact_scores, orc
 
 pytestmark = pytest.mark.gpu
 
@@ -118,7 +118,9 @@ def test_pooled_with_empty_ranks(qtable):
 # The same step through the library's own exchange (gasm_pool_exchange_build, csrc/exchange.hip): plans on the device, the
 # three all-to-alls inside libgasm — device copies between virtual ranks here, ncclSend / ncclRecv between processes.
 # ---------------------------------------------------------------------------------------------------------------------
-def _check_against_single(be, own, single, n_seg, tag):
+def _check_against_single(be, own, single, n_seg, tag, same_bits=False):
+    """same_bits: every rank's fixed-point shift equals the single batch's, so the integer sums and the doubles derived from
+    them are identical (integer additions commute); otherwise the shifts may differ and the doubles agree to rounding"""
     s_contigs, s_sc = single.contigs(), single.scores()
     seen = 0
     for r, (a, b) in own.items():
@@ -134,6 +136,9 @@ def _check_against_single(be, own, single, n_seg, tag):
             assert d["sequence_len"].tolist() == s_sc["sequence_len"][ca:ce].tolist(), (tag, s)
             for kk in ("bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len"):
                 assert np.abs(d[kk] - s_sc[kk][ca:ce]).max(initial=0.0) < 1e-12, (tag, s, kk)
+                assert exact_scores.rel_close(d[kk], s_sc[kk][ca:ce]).all(), (tag, s, kk)
+                if same_bits:
+                    assert np.asarray(d[kk]).tobytes() == s_sc[kk][ca:ce].tobytes(), (tag, s, kk)
             seen += 1
     assert seen == n_seg, tag
 
@@ -248,7 +253,9 @@ def test_exchange_build_headline_shape(qtable):
     be = [pooled.GasmBackend(*_shard_reads(reads, seg_off, r, world), rl) for r in range(world)]
     stats, own = pooled.exchange_build(comm, be, k, bbits, kmer=8, table=prob)
     assert stats["attempts"] == 1
-    _check_against_single(dict(enumerate(be)), own, single, n_seg, "headline")
+    n_reads = np.diff(seg_off.astype(np.int64))
+    assert exact_scores.fixed_shift(prob, n_reads.min()) == exact_scores.fixed_shift(prob, n_reads.max()) == single.score_fixed()[1]
+    _check_against_single(dict(enumerate(be)), own, single, n_seg, "headline", same_bits=True)
     s_contigs, s_sc = single.contigs(), single.scores()
     for s in (0, 63, 64, 99):
         rs = _strs(reads[int(seg_off[s]):int(seg_off[s + 1])])
@@ -257,6 +264,7 @@ def test_exchange_build_headline_shape(qtable):
         ca, ce = int(s_sc["seg_contig_off"][s]), int(s_sc["seg_contig_off"][s + 1])
         assert s_sc["kmer_breaks"][ca:ce].tolist() == o["kmer_breaks"].tolist(), s
         assert np.abs(s_sc["bp_score"][ca:ce] - o["bp_score"]).max(initial=0.0) < 1e-9, s
+        assert exact_scores.rel_close(s_sc["bp_score"][ca:ce], o["bp_score"]).all(), s
     for b in be:
         b.close()
     comm.close()

@@ -1,10 +1,15 @@
 """Host algorithms of libgasm + the oracle under AddressSanitizer and UndefinedBehaviorSanitizer (CPU build only: g++
 -fsanitize=address,undefined; the GPU pool has no sanitizer support).  tests/san_driver.cpp runs the greedy merge in both
-forms, the shuffle, the signatures, Myers' edit distance and the sequence-file reader on randomised inputs and compares
-with the oracle; any sanitizer report fails the run."""
+forms, the shuffle, the signatures, Myers' edit distance, the sequence-file reader and the batch scorer's fixed-point shift
+on randomised inputs and compares with the oracle; any sanitizer report fails the run."""
 import gzip
 import os
 import subprocess
+
+import numpy as np
+
+from genomeassembler_dev_amd import qtable
+from oracle import exact_scores
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,11 +37,43 @@ def test_host_algorithms_under_asan_ubsan(tmp_path):
     whole = gzip.compress("".join(f">r{i}\n{''.join(rnd.choice('ACGT') for _ in range(80))}\n" for i in range(4000)).encode())
     cut = tmp_path / "d.fa.gz"
     cut.write_bytes(whole[:len(whole) // 2])
+    tables = _shift_tables()
+    tb = tmp_path / "tables.bin"
+    tb.write_bytes(b"".join(np.ascontiguousarray(t, dtype="<f8").tobytes() for _, t in tables))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, str(fq), str(fa), str(bad), str(cut)], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([exe, str(fq), str(fa), str(bad), str(cut), "--tables=" + str(tb)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "checks ok" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
     assert "a.fastq: status 0, 2 reads kept, 1 dropped, 10 bases" in r.stdout
     assert "b.fa.gz: status 0, 3 reads kept, 0 dropped, 20010 bases" in r.stdout
     assert "c.txt: status -1" in r.stdout
     assert "d.fa.gz: status -1" in r.stdout, r.stdout
+
+    # the fixed-point shift (gasm_host::table_range + fixed_point_shift) against its exact restatement, and the decisions
+    # DESIGN.md §3 names: the standard table keeps shift 60 at 16 667 reads; NaN, +-inf, x 1e300 and x 1e-300 go to FP64
+    got = {}
+    for line in r.stdout.splitlines():
+        if line.startswith("table "):
+            head, rest = line.split(": ", 1)
+            fin, terms, shift = (int(x.split()[-1]) for x in rest.split(", "))
+            got[(int(head.split()[1]), terms)] = (fin, shift)
+    assert len(got) == 6 * len(tables), r.stdout
+    for i, (name, t) in enumerate(tables):
+        for terms in (0, 1, 150, 16667, 20000, 1 << 40):
+            want = exact_scores.fixed_shift(t, terms)
+            assert got[(i, terms)] == (int(bool(np.isfinite(t).all())), -1 if want is None else want), (name, terms)
+    shift = {name: got[(i, 16667)][1] for i, (name, _) in enumerate(tables)}
+    assert shift["standard"] == 60 and shift["zeros"] == 62 and shift["mixed sign"] >= 0 and shift["log"] >= 0
+    assert shift["nan"] == shift["+inf"] == shift["-inf"] == shift["x1e300"] == shift["x1e-300"] == -1, shift
+    assert got[(len(tables) - 1, 16667)] == (0, -1)          # (an unhit NaN row too: the table is not all finite)
+
+
+def _shift_tables():
+    std = qtable.load_normalised()
+    t_nan, t_pinf, t_ninf = std.copy(), std.copy(), std.copy()
+    t_nan[100], t_pinf[5000], t_ninf[7] = np.nan, np.inf, -np.inf
+    t_unhit = std.copy()
+    t_unhit[-1] = np.nan
+    return [("standard", std), ("uniform", qtable.uniform()), ("nan", t_nan), ("+inf", t_pinf), ("-inf", t_ninf), ("x1e300", std * 1e300),
+            ("x1e-300", std * 1e-300), ("zeros", np.zeros_like(std)), ("mixed sign", std * np.where(np.arange(std.size) % 2, 1.0, -1.0)),
+            ("log", np.log(std)), ("nan unhit", t_unhit)]
