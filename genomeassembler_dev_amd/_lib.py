@@ -10,6 +10,9 @@ GASM_OK = 0
 STATUS = {0: "GASM_OK", -1: "GASM_ERR_INVALID", -2: "GASM_ERR_NON_ACGT", -3: "GASM_ERR_NO_DEVICE", -4: "GASM_ERR_HIP",
           -5: "GASM_ERR_CAPACITY", -6: "GASM_ERR_RANGE", -7: "GASM_ERR_STATE"}
 TABLE_ROWS = 69904
+# one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
+PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
+               "rank_global", "tile_g", "offset_rounds", "distinct_attempts", "graph_attempts", "k", "segments")
 SCORE_OWN, SCORE_VELVET = 0, 1
 WANT_LEV, WANT_FREQ, WANT_KS = 1, 2, 4
 
@@ -81,6 +84,7 @@ SYMBOLS = {
     "gasm_batch_guided": (_int, [_vp]),
     "gasm_batch_fetch_guided": (_int, [_vp, _PP, _PP, _PP, _PP, _PP, _PP]),
     "gasm_batch_fetch_score_fixed": (_int, [_vp, _PP, C.POINTER(_int)]),
+    "gasm_batch_build_plan": (_int, [_vp, C.POINTER(_i32), _int]),
     "gasm_batch_simulate": (_int, [_vp, _vp, _vp, _u32, _u32, C.c_double, _u64, _int, _vp, _PP]),
     "gasm_batch_fetch_read_starts": (_int, [_vp, _PP, _PP]),
     "gasm_read_files": (_int, [_vp, _u32, _int, _PP]),

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import check, default_context, lib
+from ._lib import PLAN_FIELDS, check, default_context, lib
 from .api import unpack_kmers
 
 
@@ -108,6 +108,18 @@ class SegmentBatch:
         check(lib().gasm_batch_build(self.h, int(k), int(genome_len_hint)))
         self.k = int(k)
         return self
+
+    def build_plan(self):
+        """the path the last build took (gasm_batch_build_plan; finishes a pending build first): a dict of the PLAN_FIELDS of
+        the final attempt — of the first block of segments, with every block's row under "blocks" (one unless the batch is
+        split into sub-batches)"""
+        rows = lib().gasm_batch_build_plan(self.h, None, 0)
+        if rows < 0:
+            check(rows)
+        out = (C.c_int32 * (rows * len(PLAN_FIELDS)))()
+        check(min(0, lib().gasm_batch_build_plan(self.h, out, len(out))))
+        blocks = [dict(zip(PLAN_FIELDS, out[j * len(PLAN_FIELDS):(j + 1) * len(PLAN_FIELDS)])) for j in range(rows)]
+        return dict(blocks[0], blocks=blocks)
 
     def score(self, kmer=8, table=None):
         t = np.ascontiguousarray(qtable.load_normalised() if table is None else table, dtype=np.float64)

@@ -930,6 +930,18 @@ int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) 
     API_GUARD_END
 }
 
+// ---- the path of the last build (host fields of every block's BuildState; pipeline_build_plan)
+int gasm_batch_build_plan(gasm_batch* b, int32_t* out, int n) {
+    API_GUARD_BEGIN
+    if (!b || n < 0 || (n > 0 && !out)) { gasm_set_error("gasm_batch_build_plan: bad argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_build_plan before gasm_batch_build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    const int rows = (int)b->sub.size(), fit = std::min(rows, n / GASM_PLAN_FIELDS);
+    for (int j = 0; j < fit; ++j) pipeline_build_plan(b->sub[j].rd, b->sub[j].S().bs, out + (size_t)j * GASM_PLAN_FIELDS);
+    return rows;
+    API_GUARD_END
+}
+
 // ---- count_read_kmers (lib/DeNovoAssembler.R:135-168): break-k-mer counts of the reads, kernels_count.hip
 int gasm_batch_count_read_kmers(gasm_batch* b) {
     API_GUARD_BEGIN

@@ -78,6 +78,13 @@ struct BuildState {
     u64 D_cap = 0, maxD_cap = 0, bases_cap = 0;
     u32 maxD_est = 1, paths_est = 0;
     bool have_actual = false;               // maxD_est / paths_est / the partition come from a finished build of the same reads
+    // ---- what the last attempt ran, for gasm_batch_build_plan (host fields only, set where the launches are chosen)
+    u32 tile_orr = 1;                       // offset rounds of the tile kernels (plan_build)
+    bool part_single = false;               // the partition ran in one pass (k_bucket_partition), else count + scan + scatter
+    bool scan_in_dedup = false;             // the buckets' offsets came from the de-duplication's last workgroup, else k_scan_excl
+    u32 ruler_shift = 0;                    // LDS list ranking: rulers every 2^ruler_shift-th edge (0: not ranked in LDS)
+    u32 attempts_distinct = 0;              // launch_distinct calls of the last build (1 + partition / table retries)
+    u32 attempts_graph = 0;                 // graph-only repeats of the last build (the LDS ranking gave up)
     // ---- optional stream choreography of sub-batches (capi.hip): wait for this event before the first kernel, record
     // that one once the streaming kernels (partition + de-duplication) are queued
     hipEvent_t ev_wait = nullptr, ev_streamed = nullptr;
@@ -148,6 +155,8 @@ struct ScoreState {
 int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
+// one row of gasm_batch_build_plan (GASM_PLAN_FIELDS words, include/gasm.h) from a finished build's host fields
+void pipeline_build_plan(const DevReads& rd, const BuildState& bs, int32_t* row);
 // building blocks shared with the pooled build (pool.hip)
 int plan_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs);
 void distinct_caps(BuildState& bs, u32 n_segments);

@@ -326,6 +326,8 @@ int DevReads::simulate(gasm_ctx* ctx, const char* genomes, const u64* genome_off
 }
 
 // Tile table: a tile = up to ipt consecutive reads of one segment at one of orr offset rounds (kernels_build.hip, "Tiles").
+// The table is shared by every step slot of the batch, and a slot whose build finds it cached waits for nothing on the
+// uploading slot's stream: so an upload (first build, or a new tile geometry) is complete before this returns.
 int DevReads::set_tiles(gasm_ctx* ctx, u32 ipt, u32 orr) {
     if (tiles_ipt == ipt && tiles_orr == orr) return GASM_OK;
     std::vector<u32>& t = h_seg_tile_start;
@@ -350,6 +352,7 @@ int DevReads::set_tiles(gasm_ctx* ctx, u32 ipt, u32 orr) {
             e[0] = s; e[1] = (u32)std::min<u64>(left, ipt); e[2] = (u32)first; e[3] = (u32)(first >> 32) | (o << 16);
         }
     GCHK(h2d(ctx, d_tile_info, info.data(), info.size() * 4));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     tiles_ipt = ipt;
     tiles_orr = orr;
     return GASM_OK;
@@ -514,6 +517,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     u64 n_alloc;
     const u32* d_blen = nullptr;              // single pass: the buckets' padded lengths (the partition's cursors)
     const bool single = bs.single_pass && !bs.multi_pass && nb <= GASM_TILE_WG;
+    bs.part_single = single;
     if (single) {
         // ---- one pass (k_bucket_partition): a region of fixed capacity per (segment, bucket) — the segment's k-mers per
         // bucket with `part_slack` percent to spare, room for Poisson noise and for the padding of its tiles' runs, in whole
@@ -605,6 +609,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     // the buckets' distinct counts -> dstart by the de-duplication's last workgroup (a word of the build's zeroed flags counts
     // the finished ones); beyond 16 384 buckets one workgroup of 256 is too slow a scanner: k_scan_excl in a launch of its own
     const bool scan_in_dedup = !bs.multi_pass && nbt <= 16384 && env_int("GASM_SCAN_IN_DEDUP", 1) != 0;
+    bs.scan_in_dedup = scan_in_dedup;
     u32* const d_scan_out = scan_in_dedup ? bs.d_dstart.as<u32>() : nullptr;
     bs.fbits = (bs.small_tbl && !bs.multi_pass) ? 9 : 10;   // bins of the de-duplication kernel's counting sort = TBL / 4 (the multi-pass kernel: 4096 slots)
     GCHK(bs.d_fdir.ensure((size_t)nbt * ((1u << bs.fbits) + 1) * 2));
@@ -709,10 +714,12 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
     u32* const act = d_fl + 16;     // "still active" words of the k_link_jump launches
     const u32 jchunks = (u32)ceil_div_u64(est, GASM_WG * 4);      // GASM_JUMP_ILP links per thread
     bs.ranked_in_lds = est <= 65534 && !bs.rank_global && !knobs().rank_global;
+    bs.ruler_shift = 0;
     if (bs.ranked_in_lds) {
         // every second edge (the rulers) is ranked inside LDS, the others then need a step or two (kernels_build.hip)
         // rulers: every 2nd edge when every CU has a segment of its own to rank, every 4th when segments are few
         const u32 rshift = knobs().ruler_shift ? (u32)knobs().ruler_shift : (S >= (u32)ctx->n_cu / 4 ? 1u : 2u);
+        bs.ruler_shift = rshift;
         const u32 rchunks = (u32)ceil_div_u64((est + (1u << rshift) - 1) >> rshift, GASM_WG);
         // LDS list of a segment: everything a workgroup can have while a CU only ever holds one of them, else the
         // estimate with a quarter to spare (a segment that does not fit raises flags[1]: pipeline_build_finish)
@@ -806,6 +813,7 @@ int plan_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs) {
     // offset rounds: more than one only for reads with more than g*KT k-mers; every (read group, round) is a tile
     const u32 orr = std::max(1u, (nk_max + g * KT - 1) / (g * KT));
     if (orr > 0xFFFFu) { gasm_set_error("reads longer than %u bases are not supported", GASM_TILE_WG * KT * 0xFFFFu); return GASM_ERR_CAPACITY; }
+    bs.tile_orr = orr;
     GCHK(rd.set_tiles(ctx, ipt, orr));
     // bucket bits: aim at <= ~900 distinct k-mers per bucket (2048-slot LDS table in two-slot sets, limit 1408)
     bs.bb_cap = std::min(10, 2 * (k - 1));
@@ -843,6 +851,10 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs)
     GCHK(plan_build(ctx, rd, k, hint, bs));
     const u32 S = rd.n_segments;
     zero_results(bs, S);
+    bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
+    bs.ruler_shift = 0;
+    bs.attempts_distinct = bs.n_kmers ? 1 : 0;
+    bs.attempts_graph = 0;
     if (bs.n_kmers == 0) {
         // nothing to do on the device; the directories the scorer borrows exist and are zero
         bs.bbits = 0; bs.D_cap = 0; bs.maxD_cap = 0;
@@ -905,9 +917,11 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
                 return GASM_ERR_CAPACITY;
             }
             distinct_caps(bs, S);
+            ++bs.attempts_distinct;
             GCHK(launch_distinct(ctx, *rd, bs));
         } else {
             bs.rank_global = true;        // whole-GPU pointer doubling instead of the LDS ranking
+            ++bs.attempts_graph;
         }
         GCHK(launch_graph(ctx, S, bs));
     }
@@ -928,6 +942,25 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
     for (u32 s = 0; s < S; ++s) bs.paths_est = std::max(bs.paths_est, bs.h_seg_cstart[s + 1] - bs.h_seg_cstart[s]);
     bs.have_actual = true;
     return GASM_OK;
+}
+
+// the path the last build took, from host fields only (GASM_PLAN_* in include/gasm.h)
+void pipeline_build_plan(const DevReads& rd, const BuildState& bs, int32_t* row) {
+    row[GASM_PLAN_KEY_WORDS] = bs.words;
+    row[GASM_PLAN_BUCKET_BITS] = bs.bbits;
+    row[GASM_PLAN_TABLE_SLOTS] = bs.small_tbl ? 2048 : 4096;
+    row[GASM_PLAN_SINGLE_PASS] = bs.part_single;
+    row[GASM_PLAN_MULTI_PASS] = bs.multi_pass;
+    row[GASM_PLAN_SCAN_IN_DEDUP] = bs.scan_in_dedup;
+    row[GASM_PLAN_RANKED_IN_LDS] = bs.ranked_in_lds;
+    row[GASM_PLAN_RULER_SHIFT] = (int32_t)bs.ruler_shift;
+    row[GASM_PLAN_RANK_GLOBAL] = bs.rank_global || knobs().rank_global;
+    row[GASM_PLAN_TILE_G] = (int32_t)bs.tile_g;
+    row[GASM_PLAN_OFFSET_ROUNDS] = (int32_t)bs.tile_orr;
+    row[GASM_PLAN_DISTINCT_ATTEMPTS] = (int32_t)bs.attempts_distinct;
+    row[GASM_PLAN_GRAPH_ATTEMPTS] = (int32_t)bs.attempts_graph;
+    row[GASM_PLAN_K] = bs.k;
+    row[GASM_PLAN_SEGMENTS] = (int32_t)rd.n_segments;
 }
 
 int pipeline_fetch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {

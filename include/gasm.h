@@ -405,6 +405,29 @@ int gasm_profile_filter(gasm_ctx* ctx, const char* names);
 int gasm_profile_reset(gasm_ctx* ctx);
 int gasm_profile_read(gasm_ctx* ctx, int* n, const char* const** names, const double** ms, const uint64_t** launches);
 
+/* The path the last finished gasm_batch_build took: one row of GASM_PLAN_FIELDS int32 words per block of segments (one
+ * unless GASM_SUBBATCHES splits the batch), describing the final attempt of each block's build.  A pending build is
+ * finished first, as the fetches do.  Host bookkeeping only: no device reads, no effect on the pipeline.
+ * Returns the number of rows (>= 1) and writes as many whole rows as fit in n words (out may be NULL when n == 0);
+ * a negative value is a GASM_ERR status (GASM_ERR_STATE before the first build). */
+#define GASM_PLAN_FIELDS 15
+#define GASM_PLAN_KEY_WORDS 0          /* 1: 64-bit keys (k <= 31), 2: 128-bit keys */
+#define GASM_PLAN_BUCKET_BITS 1        /* buckets per segment = 2^bits */
+#define GASM_PLAN_TABLE_SLOTS 2        /* LDS table of the one-pass de-duplication: 2048 or 4096 slots */
+#define GASM_PLAN_SINGLE_PASS 3        /* 1: one-pass partition (k_bucket_partition); 0: count + scan + scatter */
+#define GASM_PLAN_MULTI_PASS 4         /* 1: de-duplication in passes over key sub-ranges (k_bucket_dedup_multi) */
+#define GASM_PLAN_SCAN_IN_DEDUP 5      /* 1: bucket offsets from the de-duplication's last workgroup; 0: k_scan_excl */
+#define GASM_PLAN_RANKED_IN_LDS 6      /* 1: list ranking in LDS (k_rank_rulers, k_rank_lds, k_link_jump) */
+#define GASM_PLAN_RULER_SHIFT 7        /* LDS ranking: rulers every 2^shift-th edge; 0 when not ranked in LDS */
+#define GASM_PLAN_RANK_GLOBAL 8        /* 1: whole-GPU ranking forced (GASM_RANK_GLOBAL, or after the LDS ranking gave up) */
+#define GASM_PLAN_TILE_G 9             /* threads per read of the tile kernels */
+#define GASM_PLAN_OFFSET_ROUNDS 10     /* offset rounds (tiles) per group of reads */
+#define GASM_PLAN_DISTINCT_ATTEMPTS 11 /* partition + de-duplication attempts (1 + overflow retries; 0: no k-mers) */
+#define GASM_PLAN_GRAPH_ATTEMPTS 12    /* graph-only repeats (the LDS ranking gave up) */
+#define GASM_PLAN_K 13
+#define GASM_PLAN_SEGMENTS 14          /* segments of the block */
+int gasm_batch_build_plan(gasm_batch* b, int32_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,15 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in L.gasm_version()
 
 
+def test_build_plan_fields_match_the_header():
+    """SegmentBatch.build_plan names the words of a gasm_batch_build_plan row in the order of the GASM_PLAN_* indices"""
+    hdr = open(os.path.join(ROOT, "include", "gasm.h")).read()
+    idx = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define GASM_PLAN_([A-Z_]+)\s+(\d+)", hdr)}
+    n = idx.pop("fields")
+    assert n == len(_lib.PLAN_FIELDS) and sorted(idx.values()) == list(range(n)), idx
+    assert [_lib.PLAN_FIELDS[i] for i in sorted(idx.values())] == [f for f, _ in sorted(idx.items(), key=lambda t: t[1])]
+
+
 def test_no_device_fails_loudly():
     import torch
     if torch.cuda.is_available():

@@ -216,6 +216,10 @@ def test_overflow_retry_and_skewed_bins():
             assert b.contigs(0) == ref["contigs"], (k, alphabet, hint)
             dk, dm = b.distinct_kmers(0)
             assert dk == ref["distinct"] and dm.tolist() == ref["counts"].tolist(), (k, alphabet, hint)
+            if hint == 50:      # one-bucket plan (two bits) -> overflow -> 4096-slot table (64-bit keys) -> more bucket bits
+                p = b.build_plan()
+                assert p["distinct_attempts"] >= 3 and p["bucket_bits"] > 2, (k, alphabet, p)
+                assert p["table_slots"] == (4096 if k <= 31 else 2048), (k, alphabet, p)
             b.close()
 
 
@@ -277,8 +281,11 @@ def test_buckets_no_table_can_hold():
         assert b.contigs(0) == ref["contigs"], k
         dk, dm = b.distinct_kmers(0)
         assert dk == ref["distinct"] and dm.tolist() == ref["counts"].tolist(), k
+        p = b.build_plan()
+        assert (p["multi_pass"], p["bucket_bits"], p["scan_in_dedup"]) == (1, 10, 0), (k, p)
         b.build(k, genome_len_hint=L)                               # again: the partition that worked is kept
         assert b.contigs(0) == ref["contigs"], k
+        assert b.build_plan()["multi_pass"] == 1, k
         b.close()
 
 
@@ -332,6 +339,8 @@ def test_large_segment_long_reads_and_cycles(qtable):
     b = ga.SegmentBatch(reads.reshape(-1), np.array([0, reads.shape[0]], dtype=np.uint64), fixed_len=120)
     b.build(k, genome_len_hint=90000).score(8, prob)
     assert len(ref["distinct"]) > 65534
+    p = b.build_plan()
+    assert (p["ranked_in_lds"], p["rank_global"], p["graph_attempts"]) == (0, 0, 0), p      # whole-GPU from the start
     assert b.contigs(0) == ref["contigs"]
     dk, dm = b.distinct_kmers(0)
     assert dk == ref["distinct"] and dm.tolist() == ref["counts"].tolist()
@@ -347,6 +356,8 @@ def test_large_segment_long_reads_and_cycles(qtable):
     b = ga.SegmentBatch(reads.reshape(-1), np.array([0, reads.shape[0]], dtype=np.uint64), fixed_len=100)
     b.build(k, genome_len_hint=700000)
     assert len(ref["distinct"]) > 512 * 900
+    p = b.build_plan()
+    assert (p["bucket_bits"], p["single_pass"]) == (10, 0), p      # 1024 buckets: past the one-pass partition's 512
     assert b.contigs(0) == ref["contigs"]
     dk, dm = b.distinct_kmers(0)
     assert dk == ref["distinct"] and dm.tolist() == ref["counts"].tolist()
@@ -360,6 +371,8 @@ def test_large_segment_long_reads_and_cycles(qtable):
         segs = [long_reads + short, [(circ * 4)[i:i + 150] for i in range(0, 800, 7)]]
         b = ga.SegmentBatch.from_strings(segs)
         b.build(k)
+        p = b.build_plan()
+        assert (p["tile_g"], p["offset_rounds"]) == (512, 3 if k == 21 else 5), (k, p)      # several offset rounds per read
         for s, rs2 in enumerate(segs):
             ref = orc.get_contigs(orc.kmers_from_reads(rs2, k), k, 1, rows=1)
             assert b.contigs(s) == ref["contigs"], (k, s)
@@ -744,6 +757,8 @@ def test_more_segments_than_cus(qtable):
     b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=rl)
     b.build(k, genome_len_hint=L).score(8, prob)
     b.build(k, genome_len_hint=L).score(8, prob)
+    p = b.build_plan()
+    assert (p["ranked_in_lds"], p["ruler_shift"], p["graph_attempts"]) == (1, 1, 0), p      # LDS, rulers every 2nd edge
     contigs, sc = _check_batch_properties(b, seg_off, rl, k, n_seg)
     _check_segments_vs_oracle(b, reads, seg_off, genomes, [0, 1, 63, 64, 255, 256, 257, 511, 512, 598, 599], k, keys, prob, contigs, sc)
     b.close()
@@ -782,6 +797,8 @@ def test_partition_paths_against_oracle(qtable, monkeypatch, mode, n_seg, L, rl,
     b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=rl)
     for _ in range(2):
         b.build(k, genome_len_hint=L).score(8, prob)
+        p = b.build_plan()      # the two-pass partition in the end; after a region overflow in the second attempt
+        assert (p["single_pass"], p["distinct_attempts"]) == (0, 1 if mode == "two_pass" else 2), (mode, p)
         contigs, sc = _check_batch_properties(b, seg_off, rl, k, n_seg)
         _check_segments_vs_oracle(b, reads, seg_off, genomes, range(n_seg), k, keys, prob, contigs, sc)
     b.close()
