@@ -111,8 +111,7 @@ class SegmentBatch:
 
     def build_plan(self):
         """the path the last build took (gasm_batch_build_plan; finishes a pending build first): a dict of the PLAN_FIELDS of
-        the final attempt — of the first block of segments, with every block's row under "blocks" (one unless the batch is
-        split into sub-batches)"""
+        the final attempt, and the same row as the one entry of its "blocks" list"""
         rows = lib().gasm_batch_build_plan(self.h, None, 0)
         if rows < 0:
             check(rows)

@@ -40,73 +40,36 @@ struct gasm_scores {
     int lev_device = 0;      // who computed lev: 0 nobody (not asked), 1 the GPU (k_levenshtein), 2 host threads (gasm_host::levenshtein)
 };
 
-// A batch runs as one or more sub-batches — contiguous blocks of its segments, each with its own reads, build and
-// scoring state on its own stream (a lane of the context).  Segments are independent, so this changes nothing in the
-// results; it lets the latency-bound graph phase of one block run under the bandwidth-bound partition/de-duplication
-// phase of the next: block j's first kernel waits (stream event) until block j-1's streaming kernels are queued, and
-// with builds queued ahead of their reports the blocks of consecutive steps interleave the same way.
-// What one step (build + scoring) of a block owns: the graph, the contigs as paths, the scores — and the stream it runs on.
+// What one step (build + scoring) of a batch owns: the graph, the contigs as paths, the scores — and the stream it runs on.
 struct StepSlot {
     gasm_ctx* cx = nullptr;
-    hipEvent_t ev_streamed = nullptr;       // its build's streaming kernels (partition, de-duplication) are done
     BuildState bs;
     DevPaths dp;
     ScoreState ss;
     bool paths_ready = false;
 };
 
-struct SubBatch {
-    gasm_ctx* cx = nullptr;                 // the lane it runs on (lane 0 = the batch's context itself)
-    u32 seg0 = 0, seg1 = 0;                 // its block of the batch's segments
+struct gasm_batch {
+    gasm_ctx* ctx = nullptr;
+    u32 n_segments = 0;
+    u64 n_reads = 0;
     DevReads rd;
     ScoreTable tb;
-    bool table_set = false;
-    hipEvent_t ev_streamed = nullptr;
     GuidedState guided;
-    // Two step slots, taken in turn (round 3; one-block batches, GASM_PINGPONG=0 switches it off): consecutive steps of a
-    // resident pipeline are independent of each other — same reads, own graph, own scores — so step n + 1 is queued on the
-    // other slot's stream with the other slot's buffers and its streaming kernels (partition, de-duplication: HBM and LDS)
-    // run beside step n's graph and scoring kernels (latency-bound, a few waves per CU).  Results are always those of the
-    // slot the last gasm_batch_build took.
+    // Step slots, taken in turn (GASM_PINGPONG=0 switches it off): consecutive steps of a resident pipeline are independent
+    // of each other — same reads, own graph, own scores — so step n + 1 is queued on the next slot's stream with that slot's
+    // buffers, and its streaming kernels (partition, de-duplication: HBM and LDS) run beside the graph and scoring kernels
+    // of the steps before it (latency-bound, a few waves per CU).  GASM_STEP_SLOTS of them (2..4, default 3).  Results are
+    // always those of the slot the last gasm_batch_build took.
     StepSlot slot[4];
     int cur = 0, n_slots = 2;
-    bool pingpong = false;
-    // GASM_PINGPONG=1 (default): whole steps on equal streams, GASM_STEP_SLOTS of them (2..4, default 3).
-    // GASM_PINGPONG=2: every step's streaming kernels on the block's own stream, back to back, and each slot's graph, contigs
-    // and scoring on a tail lane of its own, whose stream the dispatcher serves first.  Measured: the
-    // persistent streaming workgroups hold the CUs' LDS, the small kernels beside them run several times slower, and the
-    // next-but-one partition waits for them — 0.92-0.98 ms/step against 0.88 with equal streams.
-    int pp_mode = 1;
     StepSlot& S() {
         StepSlot& x = slot[cur];
-        if (!x.cx && pingpong && pp_mode == 2) x.cx = cx->tail_lane(cur);
-        if (!x.cx) x.cx = cur ? cx->lane((size_t)cur) : cx;
-        if (!x.cx) x.cx = cx;                // (no second stream to be had: both slots on the block's own)
+        if (!x.cx) x.cx = cur ? ctx->lane((size_t)cur) : ctx;      // (lane 0 stays idle: the streams the slots were measured on)
+        if (!x.cx) x.cx = ctx;                // (no second stream to be had: every slot on the batch's own)
         return x;
     }
     const StepSlot& S() const { return slot[cur]; }
-    // Scoring on a stream of its own (one-block batches without ping-pong): the graph-indexed scoring of step n only reads what
-    // build n left behind and what the NEXT build does not touch before its de-duplication (which rewrites the directories the
-    // scorer searches) — so it runs on a lane beside the next build's partition instead of in front of it.  ev_built: the build
-    // is queued in full (the scorer's lane waits for it); ev_scored: the scoring is done (the next de-duplication waits for it).
-    gasm_ctx* scx = nullptr;                // the lane
-    gasm_ctx* score_cx_last = nullptr;      // where the last scoring was queued (fetches read from there)
-    hipEvent_t ev_built = nullptr, ev_scored = nullptr;
-    bool lane_last = false;                 // the last build recorded ev_built for the lane (GASM_SCORE_LANE is read per build)
-    // break-k-mer counts of the reads (gasm_batch_count_read_kmers): GASM_TABLE_ROWS per segment; reads only d_words / d_read_off
-    DBuf d_rkc;
-    bool rkc_checked = false;               // read_kmer_windows_check passed (the reads never change)
-};
-
-static bool score_lane_wanted(const gasm_batch* b);
-// the lane and its events, on first use; false: no lane (more than one block, switched off, or no resources)
-static bool score_lane(gasm_batch* b, SubBatch& sb);
-
-struct gasm_batch {
-    gasm_ctx* ctx = nullptr;
-    std::vector<SubBatch> sub;
-    u32 n_segments = 0;
-    u64 n_reads = 0;
     bool built = false;
     std::vector<double> table_copy;
     bool table_given = false;
@@ -114,44 +77,31 @@ struct gasm_batch {
     bool scored = false;
     int score_kmer = 0;
     int last_k = 0;                         // k of the last gasm_batch_build
-    // concatenated host results of the sub-batches (fetch)
-    std::vector<u64> h_seg_doff, h_dk_key, h_seg_coff, h_c_off;
-    std::vector<u32> h_dk_cnt, h_nxt;
-    std::vector<u8> h_eflag;
-    std::vector<char> h_contigs;
-    std::vector<double> h_bp, h_nf, h_nl;
-    std::vector<int32_t> h_breaks, h_len;
     // simulated batches: the start of every read in its genome
     DBuf d_read_start;
     std::vector<u32> h_read_start;
     std::vector<int64_t> h_fx;
     std::vector<u64> h_sim_seg_off;
-    // gasm_batch_count_read_kmers
+    // break-k-mer counts of the reads (gasm_batch_count_read_kmers): GASM_TABLE_ROWS per segment; reads only d_words / d_read_off
+    DBuf d_rkc;
+    bool rkc_checked = false;               // read_kmer_windows_check passed (the reads never change)
     bool rkc_counted = false;
     std::vector<u32> h_rkc;
 };
 
-// Read the report of a sub-batch's queued build (repeating the build if it failed, and then the scoring queued behind it).
-static int sub_finish(gasm_batch* b, SubBatch& sb) {
-    bool rebuilt = false;
-    GCHK(pipeline_build_finish(sb.S().cx, sb.rd, sb.S().bs, &rebuilt));
-    if (rebuilt) {
-        sb.S().paths_ready = false;
-        if (b->scored) {
-            GCHK(pipeline_contig_paths(sb.S().cx, sb.rd, sb.S().bs, sb.S().dp));
-            sb.S().paths_ready = true;
-            pipeline_contig_paths_host(sb.rd, sb.S().bs, sb.S().dp);
-            if (sb.scx) HIPCHK(hipStreamSynchronize(sb.scx->stream));      // (the first attempt's scoring: its buffers are reused)
-            GCHK(pipeline_score_launch(sb.S().cx, sb.rd, sb.S().dp, b->score_kmer, sb.tb, false, false, sb.S().ss, &sb.S().bs));
-            sb.score_cx_last = sb.S().cx;
-        }
-    }
-    return GASM_OK;
-}
+// Read the report of the batch's queued build (repeating the build if it failed, and then the scoring queued behind it).
 static int batch_finish(gasm_batch* b) {
-    for (SubBatch& sb : b->sub) {
-        GCHK(sub_finish(b, sb));
-        if (sb.scx) HIPCHK(hipStreamSynchronize(sb.scx->stream));      // whatever the lane still scores: results are asked for
+    StepSlot& x = b->S();
+    bool rebuilt = false;
+    GCHK(pipeline_build_finish(x.cx, b->rd, x.bs, &rebuilt));
+    if (rebuilt) {
+        x.paths_ready = false;
+        if (b->scored) {
+            GCHK(pipeline_contig_paths(x.cx, b->rd, x.bs, x.dp));
+            x.paths_ready = true;
+            pipeline_contig_paths_host(b->rd, x.bs, x.dp);
+            GCHK(pipeline_score_launch(x.cx, b->rd, x.dp, b->score_kmer, b->tb, false, false, x.ss, &x.bs));
+        }
     }
     return GASM_OK;
 }
@@ -165,21 +115,6 @@ static int batch_finish(gasm_batch* b) {
         gasm_set_error("internal error: %s", e.what());                        \
         return GASM_ERR_INVALID;                                               \
     }
-
-static bool score_lane_wanted(const gasm_batch* b) {
-    const char* v = getenv("GASM_SCORE_LANE");
-    return b->sub.size() == 1 && !(v && *v == '0');
-}
-static bool score_lane(gasm_batch* b, SubBatch& sb) {
-    if (!score_lane_wanted(b)) return false;
-    if (sb.scx && sb.ev_built && sb.ev_scored) return true;
-    if (hipSetDevice(sb.cx->device) != hipSuccess) return false;
-    if (!sb.scx) sb.scx = sb.cx->lane(0);
-    if (!sb.scx) return false;
-    if (!sb.ev_built && hipEventCreateWithFlags(&sb.ev_built, hipEventDisableTiming) != hipSuccess) { sb.ev_built = nullptr; return false; }
-    if (!sb.ev_scored && hipEventCreateWithFlags(&sb.ev_scored, hipEventDisableTiming) != hipSuccess) { sb.ev_scored = nullptr; return false; }
-    return true;
-}
 
 static void strlist_from(const std::vector<std::string>& v, std::vector<char>& data, std::vector<u64>& off) {
     off.assign(v.size() + 1, 0);
@@ -583,13 +518,6 @@ int gasm_coverage_percent(gasm_ctx* ctx, const int64_t* start, const int64_t* le
 void gasm_scores_free(gasm_scores* s) { delete s; }
 
 // ------------------------------------------------------------------------------------------------------ batches
-static u32 sub_batches_for(u32 n_segments) {
-    // GASM_SUBBATCHES=n forces the number of blocks (1 = the whole batch on the context's own stream)
-    if (const char* v = getenv("GASM_SUBBATCHES")) return (u32)std::max(1, std::min(8, atoi(v)));
-    (void)n_segments;
-    return 1u;      // measured (cfg2, 2-4 blocks): 1.32-1.35 ms per step against 1.34 — the half-size streaming kernels lose what the overlap gains
-}
-
 int gasm_batch_create(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, uint32_t fixed_len,
                       const uint64_t* seg_read_off, uint32_t n_segments, gasm_batch** out) {
     API_GUARD_BEGIN
@@ -602,56 +530,21 @@ int gasm_batch_create(gasm_ctx* ctx, const char* reads, const uint64_t* read_off
     b->ctx = ctx;
     b->n_segments = n_segments;
     b->n_reads = n_reads;
-    const u32 nsub = std::min<u32>(sub_batches_for(n_segments), n_segments);
-    b->sub.resize(nsub);
-    // blocks of segments with about the same number of reads each
-    u32 seg = 0;
-    int st = GASM_OK;
-    for (u32 j = 0; j < nsub && st == GASM_OK; ++j) {
-        SubBatch& sb = b->sub[j];
-        sb.seg0 = seg;
-        const u64 want = n_reads * (u64)(j + 1) / nsub;
-        u32 e = seg + 1;
-        while (e < n_segments - (nsub - 1 - j) && seg_read_off[e] < want) ++e;
-        if (j + 1 == nsub) e = n_segments;
-        sb.seg1 = e;
-        seg = e;
-        sb.cx = j == 0 ? ctx : ctx->lane(j - 1);
-        if (!sb.cx) { st = GASM_ERR_HIP; break; }
-        std::vector<u64> so(sb.seg1 - sb.seg0 + 1);
-        const u64 r0 = seg_read_off[sb.seg0];
-        for (u32 i = 0; i < so.size(); ++i) so[i] = seg_read_off[sb.seg0 + i] - r0;
-        const char* rbase = reads;
-        const u64* ro = nullptr;
-        if (read_off) ro = read_off + r0;            // DevReads::upload rebases ragged offsets to ro[0]
-        else rbase = reads ? reads + r0 * (u64)fixed_len : reads;
-        st = sb.rd.upload(sb.cx, rbase, ro, so.back(), fixed_len, so.data(), (u32)so.size() - 1);
-        if (st == GASM_OK && nsub > 1 && hipEventCreateWithFlags(&sb.ev_streamed, hipEventDisableTiming) != hipSuccess) {
-            gasm_set_error("hipEventCreate failed");
-            st = GASM_ERR_HIP;
-        }
-    }
+    const int st = b->rd.upload(ctx, reads, read_off, n_reads, fixed_len, seg_read_off, n_segments);
     if (st != GASM_OK) { gasm_batch_free(b); return st; }
-    for (u32 j = 0; j < nsub; ++j) {
-        b->sub[j].slot[0].bs.ev_streamed = b->sub[j].ev_streamed;
-        b->sub[j].slot[0].bs.ev_wait = j ? b->sub[j - 1].ev_streamed : nullptr;
-    }
     *out = b;
     return GASM_OK;
     API_GUARD_END
 }
 
-// one block on the context's own stream, from reads that are packed already
+// a batch from reads that are packed already
 static int batch_from_packed(gasm_ctx* ctx, const u64* words, const u64* read_off, u64 n_reads, u32 fixed_len, const u64* seg_read_off,
                              u32 n_segments, gasm_batch** out) {
     gasm_batch* b = new gasm_batch();
     b->ctx = ctx;
     b->n_segments = n_segments;
     b->n_reads = n_reads;
-    b->sub.resize(1);
-    SubBatch& sb = b->sub[0];
-    sb.cx = ctx; sb.seg0 = 0; sb.seg1 = n_segments;
-    const int st = sb.rd.upload_packed(ctx, words, read_off, n_reads, fixed_len, seg_read_off, n_segments);
+    const int st = b->rd.upload_packed(ctx, words, read_off, n_reads, fixed_len, seg_read_off, n_segments);
     if (st != GASM_OK) { gasm_batch_free(b); return st; }
     *out = b;
     return GASM_OK;
@@ -740,10 +633,7 @@ int gasm_batch_from_files(gasm_ctx* ctx, const char* const* paths, uint32_t n_fi
     b->ctx = ctx;
     b->n_segments = n_files;
     b->n_reads = n;
-    b->sub.resize(1);
-    SubBatch& sb = b->sub[0];
-    sb.cx = ctx; sb.seg0 = 0; sb.seg1 = n_files;
-    const int st = sb.rd.adopt_packed(ctx, d_words, fixed ? nullptr : read_off.data(), n, fixed ? flen : 0, seg.data(), n_files);
+    const int st = b->rd.adopt_packed(ctx, d_words, fixed ? nullptr : read_off.data(), n, fixed ? flen : 0, seg.data(), n_files);
     if (st != GASM_OK) { gasm_batch_free(b); return st; }
     *out = b;
     return GASM_OK;
@@ -758,13 +648,10 @@ int gasm_batch_simulate(gasm_ctx* ctx, const char* genomes, const uint64_t* geno
     gasm_batch* b = new gasm_batch();
     b->ctx = ctx;
     b->n_segments = n_segments;
-    b->sub.resize(1);
-    SubBatch& sb = b->sub[0];
-    sb.cx = ctx; sb.seg0 = 0; sb.seg1 = n_segments;
-    const int st = sb.rd.simulate(ctx, genomes, genome_off, n_segments, read_len, coverage, seed, kmer, table, b->d_read_start);
+    const int st = b->rd.simulate(ctx, genomes, genome_off, n_segments, read_len, coverage, seed, kmer, table, b->d_read_start);
     if (st != GASM_OK) { gasm_batch_free(b); return st; }
-    b->n_reads = sb.rd.n_reads;
-    b->h_sim_seg_off = sb.rd.h_seg_read_off;
+    b->n_reads = b->rd.n_reads;
+    b->h_sim_seg_off = b->rd.h_seg_read_off;
     *out = b;
     return GASM_OK;
     API_GUARD_END
@@ -787,15 +674,10 @@ int gasm_batch_fetch_read_starts(gasm_batch* b, const uint64_t** seg_read_off, c
 void gasm_batch_free(gasm_batch* b) {
     if (!b) return;
     b->d_read_start.release();
-    for (SubBatch& sb : b->sub) {
-        if (sb.cx) { (void)hipSetDevice(sb.cx->device); (void)hipStreamSynchronize(sb.cx->stream); }
-        if (sb.scx) (void)hipStreamSynchronize(sb.scx->stream);
-        if (sb.ev_built) (void)hipEventDestroy(sb.ev_built);
-        if (sb.ev_scored) (void)hipEventDestroy(sb.ev_scored);
-        for (StepSlot& x : sb.slot) { if (x.cx && x.cx != sb.cx) (void)hipStreamSynchronize(x.cx->stream); if (x.ev_streamed) (void)hipEventDestroy(x.ev_streamed); x.bs.release(); x.dp.release(); x.ss.release(); }
-        sb.rd.release(); sb.tb.release(); sb.guided.release(); sb.d_rkc.release();
-        if (sb.ev_streamed) (void)hipEventDestroy(sb.ev_streamed);
-    }
+    (void)hipSetDevice(b->ctx->device);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    for (StepSlot& x : b->slot) { if (x.cx && x.cx != b->ctx) (void)hipStreamSynchronize(x.cx->stream); x.bs.release(); x.dp.release(); x.ss.release(); }
+    b->rd.release(); b->tb.release(); b->guided.release(); b->d_rkc.release();
     delete b;
 }
 
@@ -803,38 +685,19 @@ int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint) {
     API_GUARD_BEGIN
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
     b->built = false; b->scored = false;
-    for (SubBatch& sb : b->sub) {
-        // consecutive steps take the two slots in turn (one-block batches): this build does not wait for the last step's graph
-        // and scoring, it runs beside them.  A change of k rewrites the tile tables both slots read: everything drains first.
-        const int pp = env_int("GASM_PINGPONG", 1);
-        sb.pingpong = b->sub.size() == 1 && pp != 0;
-        if (sb.pingpong && sb.slot[0].cx == nullptr && sb.slot[1].cx == nullptr) {       // (fixed with the first build)
-            sb.pp_mode = pp;
-            sb.n_slots = std::max(2, std::min(4, env_int("GASM_STEP_SLOTS", 3)));
-        }
-        if (sb.pingpong) {
-            if (b->last_k && b->last_k != k) for (StepSlot& x : sb.slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));
-            sb.cur = (sb.cur + 1) % sb.n_slots;
-        }
-        StepSlot& st = sb.S();
-        st.paths_ready = false; st.ss.valid = false; st.ss.launched = false;
-        if (sb.pingpong) {
-            // the streaming kernels of consecutive steps take turns (two of them at once only share the HBM they are both bound by):
-            // this build's partition waits for the other slot's de-duplication, and runs beside that slot's graph and scoring
-            StepSlot& other = sb.slot[(sb.cur + sb.n_slots - 1) % sb.n_slots];
-            const bool chain = sb.pp_mode != 2 && env_flag("GASM_PINGPONG_CHAIN", false);
-            st.bs.stream_ctx = sb.pp_mode == 2 ? sb.cx : nullptr;
-            if (chain && !st.ev_streamed && hipEventCreateWithFlags(&st.ev_streamed, hipEventDisableTiming) != hipSuccess) st.ev_streamed = nullptr;
-            st.bs.ev_streamed = chain ? st.ev_streamed : nullptr;
-            st.bs.ev_wait = chain ? other.ev_streamed : nullptr;      // (never recorded yet: no wait)
-        }
-        const bool lane = !sb.pingpong && score_lane(b, sb);
-        const bool lane_before = sb.lane_last;      // (the lane switched off between two builds: its last scoring is still waited for)
-        sb.lane_last = lane;
-        st.bs.ev_before_dedup = (lane || lane_before) ? sb.ev_scored : nullptr;      // the last step's scoring still searches the directories this build's de-duplication rewrites
-        GCHK(pipeline_build(st.cx, sb.rd, k, genome_len_hint, st.bs));
-        if (lane) HIPCHK(hipEventRecord(sb.ev_built, st.cx->stream));
+    // consecutive steps take the slots in turn: this build does not wait for the last steps' graph and scoring, it runs
+    // beside them.  A change of k rewrites the tile tables every slot reads: everything drains first.  GASM_PINGPONG=0: the
+    // build stays on the slot the last build took, behind whatever that slot still has queued.
+    const bool pingpong = env_int("GASM_PINGPONG", 1) != 0;
+    if (pingpong && b->slot[0].cx == nullptr && b->slot[1].cx == nullptr)       // (fixed with the first build)
+        b->n_slots = std::max(2, std::min(4, env_int("GASM_STEP_SLOTS", 3)));
+    if (pingpong) {
+        if (b->last_k && b->last_k != k) for (StepSlot& x : b->slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));
+        b->cur = (b->cur + 1) % b->n_slots;
     }
+    StepSlot& st = b->S();
+    st.paths_ready = false; st.ss.valid = false; st.ss.launched = false;
+    GCHK(pipeline_build(st.cx, b->rd, k, genome_len_hint, st.bs));
     b->last_k = k;
     b->built = true;
     return GASM_OK;
@@ -845,34 +708,23 @@ int gasm_batch_score(gasm_batch* b, int kmer, const double* table) {
     API_GUARD_BEGIN
     if (!b || !table) { gasm_set_error("gasm_batch_score: null argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("gasm_batch_score before gasm_batch_build"); return GASM_ERR_STATE; }
-    const bool new_table = !b->table_given || memcmp(b->table_copy.data(), table, GASM_TABLE_ROWS * sizeof(double)) != 0;
-    if (new_table) {
+    if (!b->table_given || memcmp(b->table_copy.data(), table, GASM_TABLE_ROWS * sizeof(double)) != 0) {
+        for (StepSlot& x : b->slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));      // (whatever still scores with the old table)
+        GCHK(b->tb.set_standard(b->ctx, table));
         b->table_copy.assign(table, table + GASM_TABLE_ROWS);
         b->table_given = true;
     }
-    for (SubBatch& sb : b->sub) {
-        if (new_table || !sb.table_set) {
-            for (StepSlot& x : sb.slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));      // (whatever still scores with the old table)
-            GCHK(sb.tb.set_standard(sb.cx, table));
-            sb.table_set = true;
-        }
-        // reads shorter than k (or none): the general scorer, which sizes its tables on the host — after the build's report
-        const bool through_graph = pipeline_score_uses_graph(sb.rd, sb.S().bs, sb.tb);
-        if (!through_graph) GCHK(sub_finish(b, sb));
-        // through the graph: on the lane, behind the build (its queue, not its completion: stream order does the rest)
-        gasm_ctx* const own = sb.S().cx;
-        gasm_ctx* const cx = (sb.lane_last && through_graph && !getenv("GASM_SCORE_VERIFY")) ? sb.scx : own;
-        if (cx != own) HIPCHK(hipStreamWaitEvent(cx->stream, sb.ev_built, 0));
-        else if (sb.scx) HIPCHK(hipStreamSynchronize(sb.scx->stream));
-        if (!sb.S().paths_ready) {
-            GCHK(pipeline_contig_paths(cx, sb.rd, sb.S().bs, sb.S().dp));
-            sb.S().paths_ready = true;
-        }
-        if (!through_graph) pipeline_contig_paths_host(sb.rd, sb.S().bs, sb.S().dp);
-        GCHK(pipeline_score_launch(cx, sb.rd, sb.S().dp, kmer, sb.tb, false, false, sb.S().ss, &sb.S().bs));
-        sb.score_cx_last = cx;
-        if (sb.ev_scored) HIPCHK(hipEventRecord(sb.ev_scored, cx->stream));
+    // reads shorter than k (or none): the general scorer, which sizes its tables on the host — after the build's report
+    const bool through_graph = pipeline_score_uses_graph(b->rd, b->S().bs, b->tb);
+    if (!through_graph) GCHK(batch_finish(b));
+    // on the stream of the build's slot, behind the build (its queue, not its completion: stream order does the rest)
+    StepSlot& x = b->S();
+    if (!x.paths_ready) {
+        GCHK(pipeline_contig_paths(x.cx, b->rd, x.bs, x.dp));
+        x.paths_ready = true;
     }
+    if (!through_graph) pipeline_contig_paths_host(b->rd, x.bs, x.dp);
+    GCHK(pipeline_score_launch(x.cx, b->rd, x.dp, kmer, b->tb, false, false, x.ss, &x.bs));
     b->scored = true;
     b->score_kmer = kmer;
     return GASM_OK;
@@ -884,11 +736,10 @@ int gasm_batch_guided(gasm_batch* b) {
     API_GUARD_BEGIN
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
     if (!b->built || !b->scored) { gasm_set_error("gasm_batch_guided needs gasm_batch_build and gasm_batch_score first"); return GASM_ERR_STATE; }
-    if (b->sub.size() != 1) { gasm_set_error("gasm_batch_guided: batches split into sub-batches are not supported"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    SubBatch& sb = b->sub[0];
-    GCHK(pipeline_score_fetch(sb.score_cx_last ? sb.score_cx_last : sb.S().cx, sb.S().ss));
-    return guided_build(sb.S().cx, sb.rd, sb.S().bs, sb.S().dp, sb.S().ss, sb.tb, b->score_kmer, sb.guided);
+    StepSlot& x = b->S();
+    GCHK(pipeline_score_fetch(x.cx, x.ss));
+    return guided_build(x.cx, b->rd, x.bs, x.dp, x.ss, b->tb, b->score_kmer, b->guided);
     API_GUARD_END
 }
 
@@ -896,9 +747,9 @@ int gasm_batch_fetch_guided(gasm_batch* b, const uint64_t** seg_off, const uint6
                             const double** norm_by_len, const int32_t** kmer_breaks) {
     API_GUARD_BEGIN
     if (!b || !seg_off || !off || !data || !bp_score || !norm_by_len || !kmer_breaks) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (b->sub.size() != 1 || !b->sub[0].guided.valid) { gasm_set_error("fetch before gasm_batch_guided"); return GASM_ERR_STATE; }
-    GuidedState& g = b->sub[0].guided;
-    GCHK(guided_fetch_text(b->sub[0].S().cx, g));
+    if (!b->guided.valid) { gasm_set_error("fetch before gasm_batch_guided"); return GASM_ERR_STATE; }
+    GuidedState& g = b->guided;
+    GCHK(guided_fetch_text(b->S().cx, g));
     *seg_off = g.h_seg_off.data(); *off = g.h_text_off.data(); *data = g.h_text.data();
     *bp_score = g.ss.h_bp.data(); *norm_by_len = g.ss.h_nl.data(); *kmer_breaks = g.ss.h_breaks.data();
     return GASM_OK;
@@ -910,35 +761,34 @@ int gasm_batch_fetch_guided(gasm_batch* b, const uint64_t** seg_off, const uint6
 int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) {
     API_GUARD_BEGIN
     if (!b || !fx || !shift) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (b->sub.size() != 1 || !b->scored) { gasm_set_error("gasm_batch_fetch_score_fixed needs a scored, unsplit batch"); return GASM_ERR_STATE; }
+    if (!b->scored) { gasm_set_error("gasm_batch_fetch_score_fixed needs a scored batch"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    SubBatch& sb = b->sub[0];
-    if (!sb.S().ss.graph) {
+    StepSlot& x = b->S();
+    if (!x.ss.graph) {
         gasm_set_error("the batch was scored in FP64, not in fixed point (reads shorter than k, or a table with NaN / infinite entries or a "
                        "range the 64-bit fixed point cannot hold): there are no fixed-point sums");
         return GASM_ERR_STATE;
     }
-    const u32 P = sb.S().bs.n_contigs;
+    const u32 P = x.bs.n_contigs;
     b->h_fx.resize(P);
-    const size_t fx_off = (sb.S().ss.stride * 4 + 15) & ~(size_t)15;
-    HIPCHK(hipSetDevice(sb.cx->device));
-    if (P) HIPCHK(hipMemcpyAsync(b->h_fx.data(), static_cast<const char*>(sb.S().ss.d_total.p) + fx_off, (size_t)P * 8, hipMemcpyDeviceToHost, sb.S().cx->stream));
-    HIPCHK(hipStreamSynchronize(sb.S().cx->stream));
+    const size_t fx_off = (x.ss.stride * 4 + 15) & ~(size_t)15;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    if (P) HIPCHK(hipMemcpyAsync(b->h_fx.data(), static_cast<const char*>(x.ss.d_total.p) + fx_off, (size_t)P * 8, hipMemcpyDeviceToHost, x.cx->stream));
+    HIPCHK(hipStreamSynchronize(x.cx->stream));
     *fx = b->h_fx.data();
-    *shift = sb.tb.fix_shift;
+    *shift = b->tb.fix_shift;
     return GASM_OK;
     API_GUARD_END
 }
 
-// ---- the path of the last build (host fields of every block's BuildState; pipeline_build_plan)
+// ---- the path of the last build (host fields of its BuildState; pipeline_build_plan): one row
 int gasm_batch_build_plan(gasm_batch* b, int32_t* out, int n) {
     API_GUARD_BEGIN
     if (!b || n < 0 || (n > 0 && !out)) { gasm_set_error("gasm_batch_build_plan: bad argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("gasm_batch_build_plan before gasm_batch_build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    const int rows = (int)b->sub.size(), fit = std::min(rows, n / GASM_PLAN_FIELDS);
-    for (int j = 0; j < fit; ++j) pipeline_build_plan(b->sub[j].rd, b->sub[j].S().bs, out + (size_t)j * GASM_PLAN_FIELDS);
-    return rows;
+    if (n >= GASM_PLAN_FIELDS) pipeline_build_plan(b->rd, b->S().bs, out);
+    return 1;
     API_GUARD_END
 }
 
@@ -946,17 +796,13 @@ int gasm_batch_build_plan(gasm_batch* b, int32_t* out, int n) {
 int gasm_batch_count_read_kmers(gasm_batch* b) {
     API_GUARD_BEGIN
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    for (SubBatch& sb : b->sub) {
-        if (!sb.rkc_checked) GCHK(read_kmer_windows_check(sb.rd));
-        sb.rkc_checked = true;
-    }
-    // on the stream the block's reads were made on: behind them in stream order, beside whatever the step slots run (the kernel
-    // only reads the packed stream and its offsets, which no build or score writes)
-    for (SubBatch& sb : b->sub) {
-        HIPCHK(hipSetDevice(sb.cx->device));
-        GCHK(sb.d_rkc.ensure((size_t)(sb.seg1 - sb.seg0) * GASM_TABLE_ROWS * 4));
-        GCHK(launch_read_kmer_count(sb.cx, sb.rd, sb.d_rkc.as<u32>()));
-    }
+    if (!b->rkc_checked) GCHK(read_kmer_windows_check(b->rd));
+    b->rkc_checked = true;
+    // on the stream the reads were made on: behind them in stream order, beside whatever the step slots run (the kernel only
+    // reads the packed stream and its offsets, which no build or score writes)
+    HIPCHK(hipSetDevice(b->ctx->device));
+    GCHK(b->d_rkc.ensure((size_t)b->n_segments * GASM_TABLE_ROWS * 4));
+    GCHK(launch_read_kmer_count(b->ctx, b->rd, b->d_rkc.as<u32>()));
     b->rkc_counted = true;
     return GASM_OK;
     API_GUARD_END
@@ -967,12 +813,9 @@ int gasm_batch_fetch_read_kmer_counts(gasm_batch* b, const uint32_t** counts) {
     if (!b || !counts) { gasm_set_error("gasm_batch_fetch_read_kmer_counts: null argument"); return GASM_ERR_INVALID; }
     if (!b->rkc_counted) { gasm_set_error("gasm_batch_fetch_read_kmer_counts before gasm_batch_count_read_kmers"); return GASM_ERR_STATE; }
     b->h_rkc.resize((size_t)b->n_segments * GASM_TABLE_ROWS);
-    for (SubBatch& sb : b->sub) {
-        HIPCHK(hipSetDevice(sb.cx->device));
-        HIPCHK(hipMemcpyAsync(b->h_rkc.data() + (size_t)sb.seg0 * GASM_TABLE_ROWS, sb.d_rkc.p, (size_t)(sb.seg1 - sb.seg0) * GASM_TABLE_ROWS * 4,
-                              hipMemcpyDeviceToHost, sb.cx->stream));
-    }
-    for (SubBatch& sb : b->sub) HIPCHK(hipStreamSynchronize(sb.cx->stream));
+    HIPCHK(hipSetDevice(b->ctx->device));
+    HIPCHK(hipMemcpyAsync(b->h_rkc.data(), b->d_rkc.p, b->h_rkc.size() * 4, hipMemcpyDeviceToHost, b->ctx->stream));
+    HIPCHK(hipStreamSynchronize(b->ctx->stream));
     *counts = b->h_rkc.data();
     return GASM_OK;
     API_GUARD_END
@@ -1028,11 +871,7 @@ int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read
     API_GUARD_END
 }
 
-uint64_t gasm_batch_total_kmers(const gasm_batch* b) {
-    u64 n = 0;
-    if (b) for (const SubBatch& sb : b->sub) n += sb.S().bs.n_kmers;
-    return n;
-}
+uint64_t gasm_batch_total_kmers(const gasm_batch* b) { return b ? b->S().bs.n_kmers : 0; }
 uint64_t gasm_batch_total_reads(const gasm_batch* b) { return b ? b->n_reads : 0; }
 
 int gasm_batch_fetch_distinct(gasm_batch* b, const uint64_t** seg_off, const uint64_t** keys, const uint32_t** mult, int* words) {
@@ -1040,23 +879,10 @@ int gasm_batch_fetch_distinct(gasm_batch* b, const uint64_t** seg_off, const uin
     if (!b || !seg_off || !keys || !mult || !words) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("fetch before build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    for (SubBatch& sb : b->sub) GCHK(pipeline_fetch_distinct(sb.S().cx, sb.rd, sb.S().bs));
-    *words = b->sub[0].S().bs.words;
-    if (b->sub.size() == 1) {
-        BuildState& bs = b->sub[0].S().bs;
-        *seg_off = bs.h_seg_doff.data(); *keys = bs.h_dk_key.data(); *mult = bs.h_dk_cnt.data();
-        return GASM_OK;
-    }
-    b->h_seg_doff.assign((size_t)b->n_segments + 1, 0);
-    b->h_dk_key.clear(); b->h_dk_cnt.clear();
-    u64 base = 0;
-    for (SubBatch& sb : b->sub) {
-        for (u32 s = sb.seg0; s <= sb.seg1; ++s) b->h_seg_doff[s] = base + sb.S().bs.h_seg_doff[s - sb.seg0];
-        base += sb.S().bs.d_total;
-        b->h_dk_key.insert(b->h_dk_key.end(), sb.S().bs.h_dk_key.begin(), sb.S().bs.h_dk_key.end());
-        b->h_dk_cnt.insert(b->h_dk_cnt.end(), sb.S().bs.h_dk_cnt.begin(), sb.S().bs.h_dk_cnt.end());
-    }
-    *seg_off = b->h_seg_doff.data(); *keys = b->h_dk_key.data(); *mult = b->h_dk_cnt.data();
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_distinct(b->S().cx, b->rd, bs));
+    *words = bs.words;
+    *seg_off = bs.h_seg_doff.data(); *keys = bs.h_dk_key.data(); *mult = bs.h_dk_cnt.data();
     return GASM_OK;
     API_GUARD_END
 }
@@ -1066,19 +892,9 @@ int gasm_batch_fetch_graph(gasm_batch* b, const uint8_t** edge_flags, const uint
     if (!b || !edge_flags || !edge_next) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("fetch before build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    for (SubBatch& sb : b->sub) GCHK(pipeline_fetch_graph(sb.S().cx, sb.rd, sb.S().bs));
-    if (b->sub.size() == 1) {
-        *edge_flags = b->sub[0].S().bs.h_eflag.data(); *edge_next = b->sub[0].S().bs.h_nxt.data();
-        return GASM_OK;
-    }
-    b->h_eflag.clear(); b->h_nxt.clear();
-    u32 base = 0;
-    for (SubBatch& sb : b->sub) {
-        b->h_eflag.insert(b->h_eflag.end(), sb.S().bs.h_eflag.begin(), sb.S().bs.h_eflag.end());
-        for (u32 v : sb.S().bs.h_nxt) b->h_nxt.push_back(v == 0xFFFFFFFFu ? v : v + base);
-        base += sb.S().bs.d_total;
-    }
-    *edge_flags = b->h_eflag.data(); *edge_next = b->h_nxt.data();
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_graph(b->S().cx, b->rd, bs));
+    *edge_flags = bs.h_eflag.data(); *edge_next = bs.h_nxt.data();
     return GASM_OK;
     API_GUARD_END
 }
@@ -1088,24 +904,9 @@ int gasm_batch_fetch_contigs(gasm_batch* b, const uint64_t** seg_contig_off, con
     if (!b || !seg_contig_off || !off || !data) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("fetch before build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    for (SubBatch& sb : b->sub) GCHK(pipeline_fetch_contigs(sb.S().cx, sb.rd, sb.S().bs));
-    if (b->sub.size() == 1) {
-        BuildState& bs = b->sub[0].S().bs;
-        *seg_contig_off = bs.h_seg_coff.data(); *off = bs.h_c_off.data(); *data = bs.h_contigs.data();
-        return GASM_OK;
-    }
-    b->h_seg_coff.assign((size_t)b->n_segments + 1, 0);
-    b->h_c_off.clear(); b->h_contigs.clear();
-    u64 cbase = 0, bbase = 0;
-    for (SubBatch& sb : b->sub) {
-        for (u32 s = sb.seg0; s <= sb.seg1; ++s) b->h_seg_coff[s] = cbase + sb.S().bs.h_seg_coff[s - sb.seg0];
-        for (u32 c = 0; c < sb.S().bs.n_contigs; ++c) b->h_c_off.push_back(bbase + sb.S().bs.h_c_off[c]);
-        cbase += sb.S().bs.n_contigs;
-        bbase += sb.S().bs.contig_bases;
-        b->h_contigs.insert(b->h_contigs.end(), sb.S().bs.h_contigs.begin(), sb.S().bs.h_contigs.end());
-    }
-    b->h_c_off.push_back(bbase);
-    *seg_contig_off = b->h_seg_coff.data(); *off = b->h_c_off.data(); *data = b->h_contigs.data();
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_contigs(b->S().cx, b->rd, bs));
+    *seg_contig_off = bs.h_seg_coff.data(); *off = bs.h_c_off.data(); *data = bs.h_contigs.data();
     return GASM_OK;
     API_GUARD_END
 }
@@ -1115,24 +916,10 @@ int gasm_batch_fetch_scores(gasm_batch* b, const double** bp_score, const double
     API_GUARD_BEGIN
     if (!b || !bp_score || !norm_by_break_freqs || !norm_by_len || !kmer_breaks || !sequence_len) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     GCHK(batch_finish(b));
-    for (SubBatch& sb : b->sub) GCHK(pipeline_score_fetch(sb.score_cx_last ? sb.score_cx_last : sb.S().cx, sb.S().ss));
-    if (b->sub.size() == 1) {
-        ScoreState& ss = b->sub[0].S().ss;
-        *bp_score = ss.h_bp.data(); *norm_by_break_freqs = ss.h_nf.data(); *norm_by_len = ss.h_nl.data();
-        *kmer_breaks = ss.h_breaks.data(); *sequence_len = ss.h_len.data();
-        return GASM_OK;
-    }
-    b->h_bp.clear(); b->h_nf.clear(); b->h_nl.clear(); b->h_breaks.clear(); b->h_len.clear();
-    for (SubBatch& sb : b->sub) {
-        ScoreState& ss = sb.S().ss;
-        b->h_bp.insert(b->h_bp.end(), ss.h_bp.begin(), ss.h_bp.end());
-        b->h_nf.insert(b->h_nf.end(), ss.h_nf.begin(), ss.h_nf.end());
-        b->h_nl.insert(b->h_nl.end(), ss.h_nl.begin(), ss.h_nl.end());
-        b->h_breaks.insert(b->h_breaks.end(), ss.h_breaks.begin(), ss.h_breaks.end());
-        b->h_len.insert(b->h_len.end(), ss.h_len.begin(), ss.h_len.end());
-    }
-    *bp_score = b->h_bp.data(); *norm_by_break_freqs = b->h_nf.data(); *norm_by_len = b->h_nl.data();
-    *kmer_breaks = b->h_breaks.data(); *sequence_len = b->h_len.data();
+    ScoreState& ss = b->S().ss;
+    GCHK(pipeline_score_fetch(b->S().cx, ss));
+    *bp_score = ss.h_bp.data(); *norm_by_break_freqs = ss.h_nf.data(); *norm_by_len = ss.h_nl.data();
+    *kmer_breaks = ss.h_breaks.data(); *sequence_len = ss.h_len.data();
     return GASM_OK;
     API_GUARD_END
 }

@@ -85,14 +85,6 @@ struct BuildState {
     u32 ruler_shift = 0;                    // LDS list ranking: rulers every 2^ruler_shift-th edge (0: not ranked in LDS)
     u32 attempts_distinct = 0;              // launch_distinct calls of the last build (1 + partition / table retries)
     u32 attempts_graph = 0;                 // graph-only repeats of the last build (the LDS ranking gave up)
-    // ---- optional stream choreography of sub-batches (capi.hip): wait for this event before the first kernel, record
-    // that one once the streaming kernels (partition + de-duplication) are queued
-    hipEvent_t ev_wait = nullptr, ev_streamed = nullptr;
-    // the streaming kernels (partition, de-duplication, gather) on another context's stream (capi.hip: step slots), the
-    // graph on the build's own; ev_slot / ev_dense order the two streams (created on first use, owned by this state)
-    gasm_ctx* stream_ctx = nullptr;
-    hipEvent_t ev_slot = nullptr, ev_dense = nullptr;
-    hipEvent_t ev_before_dedup = nullptr;   // waited for between the partition and the de-duplication (the last step's scoring on its lane: capi.hip)
     // ---- report: written by the last kernels of a build into pinned memory, read by pipeline_build_finish
     u32* h_report = nullptr;
     size_t h_report_words = 0;

@@ -436,8 +436,6 @@ void BuildState::release() {
         b->release();
     part_valid = false;         // (d_bstart no longer holds the partition's region layout)
     if (h_report) { (void)hipHostFree(h_report); h_report = nullptr; h_report_words = 0; }
-    if (ev_slot) { (void)hipEventDestroy(ev_slot); ev_slot = nullptr; }
-    if (ev_dense) { (void)hipEventDestroy(ev_dense); ev_dense = nullptr; }
 }
 
 void ScoreState::release() {
@@ -589,8 +587,6 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
                     bs.d_bstart.as<u64>(), bs.d_toff.as<u32>(), bs.d_tcnt.as<ushort4>(), bs.d_keys.as<K128>(), n_alloc);
         }
     }
-    // (what still reads the directories and dense arrays the de-duplication and everything behind it rewrite)
-    if (bs.ev_before_dedup) HIPCHK(hipStreamWaitEvent(ctx->stream, bs.ev_before_dedup, 0));
     unsigned long long* d_stamps = nullptr;
     static DBuf stamp_buf;
     if (knobs().stamps) {   // diagnostic: per-phase cycle totals of k_bucket_dedup to stderr
@@ -868,20 +864,7 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs)
         return GASM_OK;
     }
     distinct_caps(bs, S);
-    gasm_ctx* const sx = bs.stream_ctx && bs.stream_ctx != ctx ? bs.stream_ctx : ctx;
-    if (sx != ctx) {
-        if (!bs.ev_slot) HIPCHK(hipEventCreateWithFlags(&bs.ev_slot, hipEventDisableTiming));
-        if (!bs.ev_dense) HIPCHK(hipEventCreateWithFlags(&bs.ev_dense, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(bs.ev_slot, ctx->stream));          // whatever this state's last build left queued (graph, scoring, fetches)
-        HIPCHK(hipStreamWaitEvent(sx->stream, bs.ev_slot, 0));
-    }
-    if (bs.ev_wait) HIPCHK(hipStreamWaitEvent(sx->stream, bs.ev_wait, 0));
-    GCHK(launch_distinct(sx, rd, bs));
-    if (bs.ev_streamed) HIPCHK(hipEventRecord(bs.ev_streamed, sx->stream));
-    if (sx != ctx) {
-        HIPCHK(hipEventRecord(bs.ev_dense, sx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, bs.ev_dense, 0));
-    }
+    GCHK(launch_distinct(ctx, rd, bs));
     GCHK(launch_graph(ctx, S, bs));
     if (knobs().sync_build) GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
     return GASM_OK;

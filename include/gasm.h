@@ -244,8 +244,8 @@ uint64_t gasm_packed_dropped(const gasm_packed* g);
 void gasm_packed_free(gasm_packed* g);
 void gasm_batch_free(gasm_batch* b);
 /* genome_len_hint: expected distinct k-mers per segment (0 = derive from the k-mer count); only sizes buckets.
- * build and score only QUEUE their work (no host wait); the fetches below wait for it.  A batch that runs as one block
- * keeps up to four "step slots" — everything a step writes, on a stream of its own — and consecutive builds take them in
+ * build and score only QUEUE their work (no host wait); the fetches below wait for it.  A batch keeps up to four
+ * "step slots" — everything a step writes, on a stream of its own — and consecutive builds take them in
  * turn, so `build; score; build; score; ...` without a fetch in between runs step n + 1's streaming kernels beside step n's
  * graph and scoring kernels.  Every step still does all of its work, and every fetch returns the results of the LAST build
  * and score, bit for bit what one step at a time gives (GASM_PINGPONG=0 in the environment: exactly that; GASM_STEP_SLOTS:
@@ -405,11 +405,10 @@ int gasm_profile_filter(gasm_ctx* ctx, const char* names);
 int gasm_profile_reset(gasm_ctx* ctx);
 int gasm_profile_read(gasm_ctx* ctx, int* n, const char* const** names, const double** ms, const uint64_t** launches);
 
-/* The path the last finished gasm_batch_build took: one row of GASM_PLAN_FIELDS int32 words per block of segments (one
- * unless GASM_SUBBATCHES splits the batch), describing the final attempt of each block's build.  A pending build is
- * finished first, as the fetches do.  Host bookkeeping only: no device reads, no effect on the pipeline.
- * Returns the number of rows (>= 1) and writes as many whole rows as fit in n words (out may be NULL when n == 0);
- * a negative value is a GASM_ERR status (GASM_ERR_STATE before the first build). */
+/* The path the last finished gasm_batch_build took: one row of GASM_PLAN_FIELDS int32 words that describes the final
+ * attempt of the build.  A pending build is finished first, as the fetches do.  Host bookkeeping only: no device reads,
+ * no effect on the pipeline.  Returns the number of rows (always 1) and writes the row when it fits in n words (out may
+ * be NULL when n == 0); a negative value is a GASM_ERR status (GASM_ERR_STATE before the first build). */
 #define GASM_PLAN_FIELDS 15
 #define GASM_PLAN_KEY_WORDS 0          /* 1: 64-bit keys (k <= 31), 2: 128-bit keys */
 #define GASM_PLAN_BUCKET_BITS 1        /* buckets per segment = 2^bits */
@@ -425,7 +424,7 @@ int gasm_profile_read(gasm_ctx* ctx, int* n, const char* const** names, const do
 #define GASM_PLAN_DISTINCT_ATTEMPTS 11 /* partition + de-duplication attempts (1 + overflow retries; 0: no k-mers) */
 #define GASM_PLAN_GRAPH_ATTEMPTS 12    /* graph-only repeats (the LDS ranking gave up) */
 #define GASM_PLAN_K 13
-#define GASM_PLAN_SEGMENTS 14          /* segments of the block */
+#define GASM_PLAN_SEGMENTS 14          /* segments of the batch */
 int gasm_batch_build_plan(gasm_batch* b, int32_t* out, int n);
 
 #ifdef __cplusplus

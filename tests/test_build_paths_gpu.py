@@ -233,7 +233,6 @@ def test_build_path_matrix(qtable, monkeypatch, case):
     keys, prob = qtable
     # every launch on the batch's own context: the profiler counts them there
     monkeypatch.setenv("GASM_PINGPONG", "0")
-    monkeypatch.setenv("GASM_SCORE_LANE", "0")
     for n, v in env.items():
         monkeypatch.setenv(n, v)
     inp = make()
@@ -276,9 +275,8 @@ def test_build_path_matrix(qtable, monkeypatch, case):
         ctx.close()
 
 
-def test_build_plan_rows_per_block_and_state(monkeypatch):
-    """one plan row per block of segments (GASM_SUBBATCHES); asking before the first build is a state error"""
-    monkeypatch.setenv("GASM_SUBBATCHES", "3")
+def test_build_plan_rows_per_block_and_state():
+    """one plan row that covers every segment of the batch; asking before the first build is a state error"""
     inp = _fixed(11, 1500, 50, 15, 190)
     b = _batch(inp, None)
     with pytest.raises(ga.GasmError, match="GASM_ERR_STATE"):
@@ -286,7 +284,7 @@ def test_build_plan_rows_per_block_and_state(monkeypatch):
     b.build(21, genome_len_hint=1500)
     plan = b.build_plan()
     rows = plan["blocks"]
-    assert len(rows) == 3 and sum(r["segments"] for r in rows) == 11
+    assert len(rows) == 1 and rows[0]["segments"] == 11
     assert all(r["k"] == 21 and r["key_words"] == 1 and r["distinct_attempts"] == 1 for r in rows)
     segs = _segments(inp)
     for s in (0, 4, 10):
@@ -364,8 +362,8 @@ def test_distinct_batches_interleaved_on_one_context(qtable, monkeypatch):
     slots share the context's lane streams.  A: fixed length, k = 21 and then 15 (another tile shape); B: 70 segments, one
     of them large, k = 33 (128-bit keys), once with a far too small hint (the retry ladder runs while the others' steps are
     queued); C: ragged reads from strings.  Every fetch equals the same batch built alone without step slots, under the
-    default slots, two slots and tail lanes, and the oracle on a sample.  (The tile tables of a batch are uploaded once
-    per tile shape and shared by its slots: this exercises that pattern; it cannot force the race the upload once had.)"""
+    default slots and two slots, and the oracle on a sample.  (The tile tables of a batch are uploaded once per tile shape
+    and shared by its slots: this exercises that pattern; it cannot force the race the upload once had.)"""
     keys, prob = qtable
     A = _fixed(6, 2000, 50, 15, 200)
     B = _fixed_mixed([(800, 12)] * 35 + [(12000, 8)] + [(800, 12)] * 34, 60, 210)
@@ -394,7 +392,7 @@ def _interleaved_against_alone(prob, keys, A, B, C, ctx, monkeypatch):
             _check_oracle_and_exact(b, _segments(inp), k, sample, keys, prob, (k, hint))
         finally:
             b.close()
-    for env in ({}, {"GASM_PINGPONG": "1", "GASM_STEP_SLOTS": "2"}, {"GASM_PINGPONG": "2"}):
+    for env in ({}, {"GASM_PINGPONG": "1", "GASM_STEP_SLOTS": "2"}):
         monkeypatch.delenv("GASM_PINGPONG", raising=False)
         monkeypatch.delenv("GASM_STEP_SLOTS", raising=False)
         for n, v in env.items():

@@ -138,9 +138,9 @@ def _ragged_segments(seed0, n=5, L=1500):
     return segs
 
 
-def test_fp64_path_ragged_batch_and_sub_batches(qtable, monkeypatch):
+def test_fp64_path_ragged_batch_and_second_batch(qtable):
     """ragged reads (some shorter than k, some empty) send the batch scorer down the FP64 position path: every contig meets
-    the FP64 bound, fixed-point sums are refused, and two runs and a split into three sub-batches give the same bits"""
+    the FP64 bound, fixed-point sums are refused, and two runs and a second batch give the same bits"""
     keys, prob = qtable
     segs = _ragged_segments(8200)
     b = ga.SegmentBatch.from_strings(segs)
@@ -151,7 +151,6 @@ def test_fp64_path_ragged_batch_and_sub_batches(qtable, monkeypatch):
     b.build(13).score(8, prob)
     assert _bits(b.scores()) == _bits(sc1)
     b.close()
-    monkeypatch.setenv("GASM_SUBBATCHES", "3")
     b = ga.SegmentBatch.from_strings(segs)
     b.build(13).score(8, prob)
     assert _bits(b.scores()) == _bits(sc1)

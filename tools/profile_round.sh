@@ -20,7 +20,7 @@ stats() {  # name, bench args...
 }
 stats cfg2 --full || exit 2      # (the same command as the bench line — durations are residence times: steps overlap)
 # one step in flight and every kernel alone on the chip: the kernels' own durations (the bench line's roofline.one_step_in_flight)
-export GASM_PINGPONG=0 GASM_SCORE_LANE=0
+export GASM_PINGPONG=0
 stats cfg2_one_step_in_flight --alone-steps 0 || exit 2
 stats cfg4 --full --workload cfg4 --steps 5 --warmup 1 || exit 2
 stats pooled_n1 --full --mode pooled --steps 3 --warmup 1 || exit 2
@@ -31,5 +31,5 @@ rm -rf $out/pmc_fetch $out/pmc_write
 timeout -k 10 300 rocprofv3 --pmc SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAVES --kernel-trace --output-format csv -d $out/pmc_sq -- python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/pmc_sq.log 2>&1
 python3 $GRAFT_REPO_ROOT/tools/pmc_summary.py $out/pmc_sq k_bucket k_tile k_rank k_score > $out/pmc_sq_summary.txt 2>&1
 rm -rf $out/pmc_sq
-unset GASM_PINGPONG GASM_SCORE_LANE
+unset GASM_PINGPONG
 echo "profile $tag done"
