@@ -10,6 +10,7 @@ GASM_OK = 0
 STATUS = {0: "GASM_OK", -1: "GASM_ERR_INVALID", -2: "GASM_ERR_NON_ACGT", -3: "GASM_ERR_NO_DEVICE", -4: "GASM_ERR_HIP",
           -5: "GASM_ERR_CAPACITY", -6: "GASM_ERR_RANGE", -7: "GASM_ERR_STATE"}
 TABLE_ROWS = 69904
+MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
                "rank_global", "tile_g", "offset_rounds", "distinct_attempts", "graph_attempts", "k", "segments")
@@ -62,6 +63,11 @@ SYMBOLS = {
     "gasm_strlist_free": (None, [_vp]),
     "gasm_calc_breakscore": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _int, _vp, _vp, _u64, _vp, _int, _int,
                                     _PP]),
+    "gasm_calc_breakscore_tables": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _int, _vp, _vp, _u64, _vp, _u32, _int, _int, _PP]),
+    "gasm_calc_breakscore_tables_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _int, _vp, _vp, _u64, _vp, _u32, _int, _int, _PP]),
+    "gasm_batch_score_tables": (_int, [_vp, _int, _vp, _u32]),
+    "gasm_batch_fetch_scores_table": (_int, [_vp, _u32, _PP, _PP, _PP, _PP, _PP]),
+    "gasm_batch_fetch_score_fixed_table": (_int, [_vp, _u32, _PP, C.POINTER(_int)]),
     "gasm_scores_count": (_u64, [_vp]),
     "gasm_scores_sequence_len": (_vp, [_vp]),
     "gasm_scores_bp_score": (_vp, [_vp]),

@@ -256,30 +256,75 @@ def calc_breakscore(path, sequencing_reads, true_solution, kmer, bp_kmer, bp_pro
         check(lib().gasm_calc_breakscore(ctx.h, pb, _ptr(po), len(path), rb, _ptr(ro), len(sequencing_reads), t, len(t), int(kmer),
                                          kb, _ptr(ko), len(bp_kmer), _ptr(prob), _lib.SCORE_VELVET if velvet else _lib.SCORE_OWN,
                                          flags, C.byref(h)))
-    L = lib()
     try:
-        n = L.gasm_scores_count(h)
-        out = dict(sequence=(path if isinstance(path, Scaffolds) else list(path)),
-                   sequence_len=_arr(L.gasm_scores_sequence_len(h), C.c_int32, n),
-                   bp_score=_arr(L.gasm_scores_bp_score(h), C.c_double, n),
-                   bp_score_norm_by_break_freqs=_arr(L.gasm_scores_norm_by_break_freqs(h), C.c_double, n),
-                   bp_score_norm_by_len=_arr(L.gasm_scores_norm_by_len(h), C.c_double, n),
-                   kmer_breaks=_arr(L.gasm_scores_kmer_breaks(h), C.c_int32, n),
-                   lev_dist_vs_true=_arr(L.gasm_scores_lev_dist(h), C.c_int32, n))
-        if velvet:
-            out["path_prob_dist_startpos"] = _arr(L.gasm_scores_startpos(h), C.c_int32, n)
-            off = _arr(L.gasm_scores_prob_dist_offsets(h), C.c_uint64, n + 1)
-            pd = _arr(L.gasm_scores_prob_dist(h), C.c_double, int(off[-1]) if n else 0)
-            out["path_prob_dist"] = [pd[int(off[i]):int(off[i + 1])] for i in range(n)]
-        elif with_freq:
-            f = _arr(L.gasm_scores_path_freq(h), C.c_double, n * len(bp_kmer))
-            out["path_freq"] = f.reshape(n, len(bp_kmer))
-        if with_ks:
-            out["stat_test_KS"] = _arr(L.gasm_scores_ks(h), C.c_double, n)
-        out["lev_device"] = {0: None, 1: "gpu", 2: "host"}[L.gasm_scores_lev_device(h)]      # (not a reference column: who did the work)
+        return _scores_dict(h, path, len(bp_kmer), velvet, with_freq, with_ks)
     finally:
-        L.gasm_scores_free(h)
+        lib().gasm_scores_free(h)
+
+
+def _scores_dict(h, path, n_table, velvet, with_freq, with_ks, path_freq=None):
+    """a gasm_scores object as calc_breakscore's dict; path_freq: an array to use instead of copying the object's (the
+    results of one calc_breakscore_tables call share it)"""
+    L = lib()
+    n = L.gasm_scores_count(h)
+    out = dict(sequence=(path if isinstance(path, Scaffolds) else list(path)),
+               sequence_len=_arr(L.gasm_scores_sequence_len(h), C.c_int32, n),
+               bp_score=_arr(L.gasm_scores_bp_score(h), C.c_double, n),
+               bp_score_norm_by_break_freqs=_arr(L.gasm_scores_norm_by_break_freqs(h), C.c_double, n),
+               bp_score_norm_by_len=_arr(L.gasm_scores_norm_by_len(h), C.c_double, n),
+               kmer_breaks=_arr(L.gasm_scores_kmer_breaks(h), C.c_int32, n),
+               lev_dist_vs_true=_arr(L.gasm_scores_lev_dist(h), C.c_int32, n))
+    if velvet:
+        out["path_prob_dist_startpos"] = _arr(L.gasm_scores_startpos(h), C.c_int32, n)
+        off = _arr(L.gasm_scores_prob_dist_offsets(h), C.c_uint64, n + 1)
+        pd = _arr(L.gasm_scores_prob_dist(h), C.c_double, int(off[-1]) if n else 0)
+        out["path_prob_dist"] = [pd[int(off[i]):int(off[i + 1])] for i in range(n)]
+    elif with_freq:
+        if path_freq is None:
+            path_freq = _arr(L.gasm_scores_path_freq(h), C.c_double, n * n_table).reshape(n, n_table)
+        out["path_freq"] = path_freq
+    if with_ks:
+        out["stat_test_KS"] = _arr(L.gasm_scores_ks(h), C.c_double, n)
+    out["lev_device"] = {0: None, 1: "gpu", 2: "host"}[L.gasm_scores_lev_device(h)]      # (not a reference column: who did the work)
     return out
+
+
+def calc_breakscore_tables(path, sequencing_reads, true_solution, kmer, bp_kmer, bp_probs, variant="own", with_lev=True,
+                           with_freq=True, with_ks=False, ctx=None):
+    """calc_breakscore under several breakage tables at once (gasm_calc_breakscore_tables): bp_probs is a sequence of 1 to
+    _lib.MAX_TABLES probability vectors over the same bp_kmer — what score_solutions() passes one after the other
+    (lib/DeNovoAssembler.R:325-355: the true table, then the uniform one).  Returns a list with, per table, the dict
+    calc_breakscore returns for it, bit for bit; the reads are matched once (and Levenshtein, the KS test's genome side and
+    path_freq computed once: the dicts share one path_freq array).  `path` may be a Scaffolds handle."""
+    ctx = ctx or default_context()
+    velvet = variant == "velvet"
+    if variant not in ("own", "velvet"):
+        raise ValueError("variant must be 'own' or 'velvet'")
+    probs = np.ascontiguousarray(bp_probs, dtype=np.float64)
+    if probs.ndim != 2 or probs.shape[1] != len(bp_kmer):
+        raise ValueError("bp_probs must hold one row of len(bp_kmer) probabilities per table")
+    T = probs.shape[0]
+    rb, ro = _pack(sequencing_reads)
+    kb, ko = _pack(bp_kmer)
+    t = true_solution.encode() if isinstance(true_solution, str) else bytes(true_solution)
+    flags = (_lib.WANT_LEV if with_lev else 0) | (_lib.WANT_FREQ if with_freq and not velvet else 0) | (_lib.WANT_KS if with_ks else 0)
+    hs = (C.c_void_p * max(T, 1))()
+    v = _lib.SCORE_VELVET if velvet else _lib.SCORE_OWN
+    if isinstance(path, Scaffolds):
+        check(lib().gasm_calc_breakscore_tables_dev(ctx.h, path.h, rb, _ptr(ro), len(sequencing_reads), t, len(t), int(kmer), kb, _ptr(ko), len(bp_kmer),
+                                                    _ptr(probs), T, v, flags, hs))
+    else:
+        pb, po = _pack(path)
+        check(lib().gasm_calc_breakscore_tables(ctx.h, pb, _ptr(po), len(path), rb, _ptr(ro), len(sequencing_reads), t, len(t), int(kmer),
+                                                kb, _ptr(ko), len(bp_kmer), _ptr(probs), T, v, flags, hs))
+    try:
+        out = []
+        for h in hs:
+            out.append(_scores_dict(h, path, len(bp_kmer), velvet, with_freq, with_ks, path_freq=out[0].get("path_freq") if out else None))
+        return out
+    finally:
+        for h in hs:
+            lib().gasm_scores_free(h)
 
 
 def count_read_kmers(sequencing_reads, kmer, bp_kmer=None, ctx=None):

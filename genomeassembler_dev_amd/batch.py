@@ -128,6 +128,17 @@ class SegmentBatch:
         check(lib().gasm_batch_score(self.h, int(kmer), t.ctypes.data_as(C.c_void_p)))
         return self
 
+    def score_tables(self, kmer, tables):
+        """score the last build under 1 to _lib.MAX_TABLES breakage tables at once (gasm_batch_score_tables): the reads are
+        matched once, every table gets its own sums — table t's scores(table=t) / score_fixed(table=t) are bit for bit what
+        score(kmer, tables[t]) gives.  scores(), score_fixed() and guided() refer to tables[0]."""
+        t = np.ascontiguousarray(tables, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != qtable.ROWS:
+            raise ValueError(f"tables must be rows of {qtable.ROWS} probabilities")
+        self._table = t[0] if len(t) else None
+        check(lib().gasm_batch_score_tables(self.h, int(kmer), t.ctypes.data_as(C.c_void_p), t.shape[0]))
+        return self
+
     def count_read_kmers(self):
         """break-k-mer counts of every segment's reads (count_read_kmers, lib/DeNovoAssembler.R:135-168, for k = 2, 4, 6 and 8
         at once): (n_segments, 69 904) uint32 in breakage-table order.  Reads only the packed reads: any build and score of the
@@ -193,10 +204,10 @@ class SegmentBatch:
         out = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in rng]
         return out if segment is None else out[0]
 
-    def scores(self):
-        """dict of per-contig arrays, in contigs_raw() order"""
+    def scores(self, table=0):
+        """dict of per-contig arrays, in contigs_raw() order; table: which table of the last score_tables"""
         ps = [C.c_void_p() for _ in range(5)]
-        check(lib().gasm_batch_fetch_scores(self.h, *[C.byref(p) for p in ps]))
+        check(lib().gasm_batch_fetch_scores_table(self.h, int(table), *[C.byref(p) for p in ps]))
         seg, _, _ = self.contigs_raw()
         n = int(seg[-1])
 
@@ -206,10 +217,11 @@ class SegmentBatch:
                     bp_score_norm_by_len=arr(ps[2], C.c_double), kmer_breaks=arr(ps[3], C.c_int32),
                     sequence_len=arr(ps[4], C.c_int32), seg_contig_off=seg)
 
-    def score_fixed(self):
-        """(int64 fixed-point breakage sums per contig, shift): bp_score == fx * 2**-shift exactly"""
+    def score_fixed(self, table=0):
+        """(int64 fixed-point breakage sums per contig, shift): bp_score == fx * 2**-shift exactly; table: which table of
+        the last score_tables (each has its own shift)"""
         p, sh = C.c_void_p(), C.c_int()
-        check(lib().gasm_batch_fetch_score_fixed(self.h, C.byref(p), C.byref(sh)))
+        check(lib().gasm_batch_fetch_score_fixed_table(self.h, int(table), C.byref(p), C.byref(sh)))
         seg, _, _ = self.contigs_raw()
         n = int(seg[-1])
         fx = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(n,)).copy() if n else np.zeros(0, np.int64)

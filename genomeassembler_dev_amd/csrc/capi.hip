@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -34,7 +35,10 @@ struct gasm_packed {
 struct gasm_scores {
     u64 n = 0;
     std::vector<int32_t> len, breaks, lev, startpos;
-    std::vector<double> bp, nf, nl, freq, pd, ks;
+    std::vector<double> bp, nf, nl, pd, ks;
+    // path_freq does not depend on the table: the results of one gasm_calc_breakscore_tables call share one buffer (at
+    // 22 000 scaffolds a dense copy per table would be several GB)
+    std::shared_ptr<const std::vector<double>> freq;
     std::vector<u64> pd_off;
     bool has_freq = false, velvet = false, has_ks = false;
     int lev_device = 0;      // who computed lev: 0 nobody (not asked), 1 the GPU (k_levenshtein), 2 host threads (gasm_host::levenshtein)
@@ -73,9 +77,14 @@ struct gasm_batch {
     bool built = false;
     std::vector<double> table_copy;
     bool table_given = false;
-    // the last gasm_batch_score, kept to queue it again behind a build that had to be repeated
+    // tables 1 .. n - 1 of gasm_batch_score_tables (table 0 is `tb`) and what they were set from (empty: never)
+    ScoreTable tbx[GASM_MAX_TABLES - 1];
+    std::vector<double> table_copy_x[GASM_MAX_TABLES - 1];
+    void table_ptrs(ScoreTable** tbs) { tbs[0] = &tb; for (int t = 1; t < GASM_MAX_TABLES; ++t) tbs[t] = &tbx[t - 1]; }
+    // the last gasm_batch_score(_tables), kept to queue it again behind a build that had to be repeated
     bool scored = false;
     int score_kmer = 0;
+    u32 score_tables = 1;
     int last_k = 0;                         // k of the last gasm_batch_build
     // simulated batches: the start of every read in its genome
     DBuf d_read_start;
@@ -89,6 +98,14 @@ struct gasm_batch {
     std::vector<u32> h_rkc;
 };
 
+// the last gasm_batch_score or gasm_batch_score_tables on slot x
+static int batch_queue_score(gasm_batch* b, StepSlot& x) {
+    if (b->score_tables == 1) return pipeline_score_launch(x.cx, b->rd, x.dp, b->score_kmer, b->tb, false, false, x.ss, &x.bs);
+    ScoreTable* tbs[GASM_MAX_TABLES];
+    b->table_ptrs(tbs);
+    return pipeline_score_launch_tables(x.cx, b->rd, x.dp, b->score_kmer, tbs, b->score_tables, false, false, x.ss, &x.bs);
+}
+
 // Read the report of the batch's queued build (repeating the build if it failed, and then the scoring queued behind it).
 static int batch_finish(gasm_batch* b) {
     StepSlot& x = b->S();
@@ -100,7 +117,7 @@ static int batch_finish(gasm_batch* b) {
             GCHK(pipeline_contig_paths(x.cx, b->rd, x.bs, x.dp));
             x.paths_ready = true;
             pipeline_contig_paths_host(b->rd, x.bs, x.dp);
-            GCHK(pipeline_score_launch(x.cx, b->rd, x.dp, b->score_kmer, b->tb, false, false, x.ss, &x.bs));
+            GCHK(batch_queue_score(b, x));
         }
     }
     return GASM_OK;
@@ -128,8 +145,8 @@ extern "C" {
 
 static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std::string(u64)>& path_text, uint64_t n_paths, const char* reads,
                            const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
-                           const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_prob, int variant,
-                           int flags, gasm_scores** out);
+                           const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
+                           bool tables_form, int variant, int flags, gasm_scores** out);
 
 // ------------------------------------------------------------------------------------------------- get_contigs
 // reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix
@@ -332,16 +349,24 @@ void gasm_scaffolds_free(gasm_scaffolds* s) {
     delete s;
 }
 
-int gasm_calc_breakscore_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, const char* reads, const uint64_t* read_off, uint64_t n_reads,
-                             const char* true_solution, uint64_t true_len, int kmer, const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table,
-                             const double* bp_prob, int variant, int flags, gasm_scores** out) {
-    API_GUARD_BEGIN
-    if (!ctx || !out || !paths || !read_off || !bp_off || (n_table && (!bp_kmer || !bp_prob)) || (true_len && !true_solution)) {
-        gasm_set_error("gasm_calc_breakscore_dev: null argument");
+// out[t] = NULL for the entries a tables call may hand back; false (and the error set) when n_tables is out of range
+static bool tables_out_clear(const char* who, gasm_scores** out, uint32_t n_tables) {
+    if (out) for (uint32_t t = 0; t < std::min<uint32_t>(n_tables, GASM_MAX_TABLES); ++t) out[t] = nullptr;
+    if (n_tables >= 1 && n_tables <= GASM_MAX_TABLES) return true;
+    gasm_set_error("%s: n_tables must be 1..%d (got %u)", who, GASM_MAX_TABLES, n_tables);
+    return false;
+}
+
+// gasm_calc_breakscore_dev (one table, tables_form = false) and gasm_calc_breakscore_tables_dev
+static int breakscore_dev(const char* who, gasm_ctx* ctx, const gasm_scaffolds* paths, const char* reads, const uint64_t* read_off, uint64_t n_reads,
+                          const char* true_solution, uint64_t true_len, int kmer, const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table,
+                          const double* bp_probs, uint32_t n_tables, bool tables_form, int variant, int flags, gasm_scores** out) {
+    if (!tables_out_clear(who, out, n_tables)) return GASM_ERR_INVALID;
+    if (!ctx || !out || !paths || !read_off || !bp_off || (n_table && (!bp_kmer || !bp_probs)) || (true_len && !true_solution)) {
+        gasm_set_error("%s: null argument", who);
         return GASM_ERR_INVALID;
     }
     if (variant != GASM_SCORE_OWN && variant != GASM_SCORE_VELVET) { gasm_set_error("unknown variant %d", variant); return GASM_ERR_INVALID; }
-    *out = nullptr;
     DevPaths dp;
     int st = scaffolds_as_paths(paths, dp);
     // text of single paths is rarely needed (velvet startpos, host Levenshtein): fetched once, on first use
@@ -355,10 +380,27 @@ int gasm_calc_breakscore_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, const c
         return toff.size() > p + 1 ? std::string(txt.data() + toff[p], txt.data() + toff[p + 1]) : std::string();
     };
     if (st == GASM_OK)
-        st = breakscore_impl(ctx, dp, path_text, paths->n, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_prob,
-                             variant, flags, out);
+        st = breakscore_impl(ctx, dp, path_text, paths->n, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_probs,
+                             n_tables, tables_form, variant, flags, out);
     dp.release();
     return st;
+}
+
+int gasm_calc_breakscore_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, const char* reads, const uint64_t* read_off, uint64_t n_reads,
+                             const char* true_solution, uint64_t true_len, int kmer, const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table,
+                             const double* bp_prob, int variant, int flags, gasm_scores** out) {
+    API_GUARD_BEGIN
+    return breakscore_dev("gasm_calc_breakscore_dev", ctx, paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_prob, 1,
+                          false, variant, flags, out);
+    API_GUARD_END
+}
+
+int gasm_calc_breakscore_tables_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, const char* reads, const uint64_t* read_off, uint64_t n_reads,
+                                    const char* true_solution, uint64_t true_len, int kmer, const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table,
+                                    const double* bp_probs, uint32_t n_tables, int variant, int flags, gasm_scores** out) {
+    API_GUARD_BEGIN
+    return breakscore_dev("gasm_calc_breakscore_tables_dev", ctx, paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table,
+                          bp_probs, n_tables, true, variant, flags, out);
     API_GUARD_END
 }
 
@@ -379,31 +421,52 @@ int gasm_levenshtein(const char* query, uint64_t nq, const char* target, uint64_
 // calc_breakscore proper.  `dp` holds the paths on the device (uploaded text or the scaffolds of a device-side
 // assemble_contigs); path_text(p) hands out path p as text for the few host-side steps that want it (the velvet variant's
 // startpos find, the host Levenshtein routine for a target outside ACGT).
+// bp_probs holds n_tables rows of n_table probabilities.  tables_form = false (one table): the single-table launch sequence of
+// gasm_calc_breakscore; true: the match once and the sums per table (pipeline_score_launch_tables), out[0 .. n_tables).
+// Everything below that does not read a probability runs once and is copied (or, for path_freq, shared) between the results.
 static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std::string(u64)>& path_text, uint64_t n_paths, const char* reads,
                            const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
-                           const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_prob, int variant,
-                           int flags, gasm_scores** out) {
+                           const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
+                           bool tables_form, int variant, int flags, gasm_scores** out) {
     const bool velvet = variant == GASM_SCORE_VELVET;
+    const u32 T = n_tables;
     DevReads rd;
-    ScoreTable tb;
+    ScoreTable tb[GASM_MAX_TABLES];
+    ScoreTable* tbs[GASM_MAX_TABLES];
+    for (u32 t = 0; t < GASM_MAX_TABLES; ++t) tbs[t] = &tb[t];
     ScoreState ss;
     const u64 seg_off[2] = {0, n_reads};
     static const char empty = 0;
     int st = rd.upload(ctx, reads ? reads : &empty, read_off, n_reads, 0, seg_off, 1);
-    if (st == GASM_OK) st = tb.set(ctx, bp_kmer, bp_off, n_table, bp_prob);
-    if (st == GASM_OK) st = pipeline_score_launch(ctx, rd, dp, kmer, tb, !velvet && (flags & GASM_WANT_FREQ), velvet, ss, nullptr);
+    for (u32 t = 0; t < T && st == GASM_OK; ++t) st = tb[t].set(ctx, bp_kmer, bp_off, n_table, bp_probs + (size_t)t * n_table);
+    const bool want_freq = !velvet && (flags & GASM_WANT_FREQ);
+    if (st == GASM_OK)
+        st = tables_form ? pipeline_score_launch_tables(ctx, rd, dp, kmer, tbs, T, want_freq, velvet, ss, nullptr)
+                         : pipeline_score_launch(ctx, rd, dp, kmer, tb[0], want_freq, velvet, ss, nullptr);
     if (st == GASM_OK) st = pipeline_score_fetch(ctx, ss);
-    gasm_scores* s = nullptr;
+    std::vector<gasm_scores*> res(T, nullptr);
+    gasm_scores* s = nullptr;               // table 0's result: what is computed once lands here first
     if (st == GASM_OK) {
-        s = new gasm_scores();
-        s->n = n_paths;
-        s->velvet = velvet;
-        s->len = ss.h_len; s->breaks = ss.h_breaks; s->bp = ss.h_bp; s->nf = ss.h_nf; s->nl = ss.h_nl;
-        s->lev.assign(n_paths, 0);
-        if (!velvet && (flags & GASM_WANT_FREQ)) { s->freq = ss.h_freq; s->has_freq = true; }
+        std::shared_ptr<const std::vector<double>> freq;
+        if (want_freq) freq = std::make_shared<const std::vector<double>>(std::move(ss.h_freq));
+        const size_t P = n_paths, pd_n = ss.h_pd_off.empty() ? 0 : (size_t)ss.h_pd_off.back();
+        for (u32 t = 0; t < T; ++t) {
+            gasm_scores* r = res[t] = new gasm_scores();
+            r->n = n_paths;
+            r->velvet = velvet;
+            r->len = ss.h_len; r->breaks = ss.h_breaks;
+            r->bp.assign(ss.h_bp.begin() + t * P, ss.h_bp.begin() + (t + 1) * P);
+            r->nf.assign(ss.h_nf.begin() + t * P, ss.h_nf.begin() + (t + 1) * P);
+            r->nl.assign(ss.h_nl.begin() + t * P, ss.h_nl.begin() + (t + 1) * P);
+            r->lev.assign(n_paths, 0);
+            if (want_freq) { r->freq = freq; r->has_freq = true; }
+            if (velvet) {
+                if (ss.h_pd.size() >= (t + 1) * pd_n) r->pd.assign(ss.h_pd.begin() + t * pd_n, ss.h_pd.begin() + (t + 1) * pd_n);
+                r->pd_off = ss.h_pd_off;
+            }
+        }
+        s = res[0];
         if (velvet) {
-            s->pd = ss.h_pd;
-            s->pd_off = ss.h_pd_off;
             // lib/BreakageScorer.cpp:273-274: start of the path inside the true solution, taken only when a read matched
             s->startpos.assign(n_paths, 0);
             const std::string truth(true_solution ? true_solution : "", true_len);
@@ -413,9 +476,12 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
             }
         }
         if (flags & GASM_WANT_KS) {
-            // lib/DeNovoAssembler.R:414-424: ks.test(path_freq, kmer_from_seq)$statistic per path
-            st = pipeline_ks(ctx, dp, ss, tb, true_solution ? true_solution : "", true_len, kmer, s->ks);
-            s->has_ks = st == GASM_OK;
+            // lib/DeNovoAssembler.R:414-424: ks.test(path_freq, kmer_from_seq)$statistic per path.  The genome's windows are
+            // counted per table row once; the ranking of the rows by probability and the paths' side are per table
+            std::vector<u32> hist;
+            if (n_paths) st = pipeline_ks_genome_hist(ctx, tb[0], true_solution ? true_solution : "", true_len, kmer, hist);
+            for (u32 t = 0; t < T && st == GASM_OK; ++t) st = pipeline_ks_paths(ctx, dp, ss, tb[t], hist, kmer, res[t]->ks);
+            for (u32 t = 0; t < T; ++t) res[t]->has_ks = st == GASM_OK;
         }
         bool lev_done = false;
         // GPU or host?  One wave walks a path's bands column by column (~0.25 us per column and band, whatever the number
@@ -465,11 +531,35 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
                 for (auto& t : th) t.join();
             }
         }
+        for (u32 t = 1; t < T; ++t) { res[t]->lev = s->lev; res[t]->lev_device = s->lev_device; res[t]->startpos = s->startpos; }
     }
-    rd.release(); tb.release(); ss.release();
-    if (st != GASM_OK) { delete s; return st; }
-    *out = s;
+    rd.release(); ss.release();
+    for (ScoreTable& x : tb) x.release();
+    if (st != GASM_OK) { for (gasm_scores* r : res) delete r; return st; }
+    for (u32 t = 0; t < T; ++t) out[t] = res[t];
     return GASM_OK;
+}
+
+// gasm_calc_breakscore (one table, tables_form = false) and gasm_calc_breakscore_tables
+static int breakscore_strings(const char* who, gasm_ctx* ctx, const char* paths, const uint64_t* path_off, uint64_t n_paths, const char* reads,
+                              const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
+                              const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
+                              bool tables_form, int variant, int flags, gasm_scores** out) {
+    if (!tables_out_clear(who, out, n_tables)) return GASM_ERR_INVALID;
+    if (!ctx || !out || !path_off || !read_off || !bp_off || (n_table && (!bp_kmer || !bp_probs)) || (true_len && !true_solution)) {
+        gasm_set_error("%s: null argument", who);
+        return GASM_ERR_INVALID;
+    }
+    if (variant != GASM_SCORE_OWN && variant != GASM_SCORE_VELVET) { gasm_set_error("unknown variant %d", variant); return GASM_ERR_INVALID; }
+    if (n_paths > 0xFFFFFFF0ull) { gasm_set_error("too many paths"); return GASM_ERR_CAPACITY; }
+    static const char empty = 0;
+    DevPaths dp;
+    int st = dp.upload_ascii(ctx, paths ? paths : &empty, path_off, (u32)n_paths);
+    if (st == GASM_OK)
+        st = breakscore_impl(ctx, dp, [&](u64 p) { return std::string(paths + path_off[p], paths + path_off[p + 1]); }, n_paths, reads, read_off, n_reads,
+                             true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_probs, n_tables, tables_form, variant, flags, out);
+    dp.release();
+    return st;
 }
 
 int gasm_calc_breakscore(gasm_ctx* ctx, const char* paths, const uint64_t* path_off, uint64_t n_paths, const char* reads,
@@ -477,21 +567,18 @@ int gasm_calc_breakscore(gasm_ctx* ctx, const char* paths, const uint64_t* path_
                          const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_prob, int variant,
                          int flags, gasm_scores** out) {
     API_GUARD_BEGIN
-    if (!ctx || !out || !path_off || !read_off || !bp_off || (n_table && (!bp_kmer || !bp_prob)) || (true_len && !true_solution)) {
-        gasm_set_error("gasm_calc_breakscore: null argument");
-        return GASM_ERR_INVALID;
-    }
-    if (variant != GASM_SCORE_OWN && variant != GASM_SCORE_VELVET) { gasm_set_error("unknown variant %d", variant); return GASM_ERR_INVALID; }
-    if (n_paths > 0xFFFFFFF0ull) { gasm_set_error("too many paths"); return GASM_ERR_CAPACITY; }
-    *out = nullptr;
-    static const char empty = 0;
-    DevPaths dp;
-    int st = dp.upload_ascii(ctx, paths ? paths : &empty, path_off, (u32)n_paths);
-    if (st == GASM_OK)
-        st = breakscore_impl(ctx, dp, [&](u64 p) { return std::string(paths + path_off[p], paths + path_off[p + 1]); }, n_paths, reads, read_off, n_reads,
-                             true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_prob, variant, flags, out);
-    dp.release();
-    return st;
+    return breakscore_strings("gasm_calc_breakscore", ctx, paths, path_off, n_paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off,
+                              n_table, bp_prob, 1, false, variant, flags, out);
+    API_GUARD_END
+}
+
+int gasm_calc_breakscore_tables(gasm_ctx* ctx, const char* paths, const uint64_t* path_off, uint64_t n_paths, const char* reads,
+                                const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
+                                const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
+                                int variant, int flags, gasm_scores** out) {
+    API_GUARD_BEGIN
+    return breakscore_strings("gasm_calc_breakscore_tables", ctx, paths, path_off, n_paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer,
+                              bp_off, n_table, bp_probs, n_tables, true, variant, flags, out);
     API_GUARD_END
 }
 
@@ -502,7 +589,7 @@ const double* gasm_scores_norm_by_break_freqs(const gasm_scores* s) { return s ?
 const double* gasm_scores_norm_by_len(const gasm_scores* s) { return s ? s->nl.data() : nullptr; }
 const int32_t* gasm_scores_kmer_breaks(const gasm_scores* s) { return s ? s->breaks.data() : nullptr; }
 const int32_t* gasm_scores_lev_dist(const gasm_scores* s) { return s ? s->lev.data() : nullptr; }
-const double* gasm_scores_path_freq(const gasm_scores* s) { return s && s->has_freq ? s->freq.data() : nullptr; }
+const double* gasm_scores_path_freq(const gasm_scores* s) { return s && s->has_freq && s->freq ? s->freq->data() : nullptr; }
 const int32_t* gasm_scores_startpos(const gasm_scores* s) { return s && s->velvet ? s->startpos.data() : nullptr; }
 const double* gasm_scores_prob_dist(const gasm_scores* s) { return s && s->velvet ? s->pd.data() : nullptr; }
 const uint64_t* gasm_scores_prob_dist_offsets(const gasm_scores* s) { return s && s->velvet ? s->pd_off.data() : nullptr; }
@@ -678,6 +765,7 @@ void gasm_batch_free(gasm_batch* b) {
     (void)hipStreamSynchronize(b->ctx->stream);
     for (StepSlot& x : b->slot) { if (x.cx && x.cx != b->ctx) (void)hipStreamSynchronize(x.cx->stream); x.bs.release(); x.dp.release(); x.ss.release(); }
     b->rd.release(); b->tb.release(); b->guided.release(); b->d_rkc.release();
+    for (ScoreTable& t : b->tbx) t.release();
     delete b;
 }
 
@@ -727,6 +815,51 @@ int gasm_batch_score(gasm_batch* b, int kmer, const double* table) {
     GCHK(pipeline_score_launch(x.cx, b->rd, x.dp, kmer, b->tb, false, false, x.ss, &x.bs));
     b->scored = true;
     b->score_kmer = kmer;
+    b->score_tables = 1;
+    return GASM_OK;
+    API_GUARD_END
+}
+
+// the same step with n_tables tables over one match (table 0 lives where gasm_batch_score keeps its table: what
+// gasm_batch_guided and the plain fetches read)
+int gasm_batch_score_tables(gasm_batch* b, int kmer, const double* tables, uint32_t n_tables) {
+    API_GUARD_BEGIN
+    if (!b || !tables) { gasm_set_error("gasm_batch_score_tables: null argument"); return GASM_ERR_INVALID; }
+    if (n_tables < 1 || n_tables > GASM_MAX_TABLES) { gasm_set_error("gasm_batch_score_tables: n_tables must be 1..%d (got %u)", GASM_MAX_TABLES, n_tables); return GASM_ERR_INVALID; }
+    if (n_tables == 1) return gasm_batch_score(b, kmer, tables);
+    if (!b->built) { gasm_set_error("gasm_batch_score_tables before gasm_batch_build"); return GASM_ERR_STATE; }
+    ScoreTable* tbs[GASM_MAX_TABLES];
+    b->table_ptrs(tbs);
+    bool same[GASM_MAX_TABLES], all_same = true;
+    for (u32 t = 0; t < n_tables; ++t) {
+        const std::vector<double>& have = t ? b->table_copy_x[t - 1] : b->table_copy;
+        same[t] = (t ? !have.empty() : b->table_given) && memcmp(have.data(), tables + (size_t)t * GASM_TABLE_ROWS, GASM_TABLE_ROWS * sizeof(double)) == 0;
+        all_same = all_same && same[t];
+    }
+    if (!all_same) {
+        for (StepSlot& x : b->slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));      // (whatever still scores with the old tables)
+        for (u32 t = 0; t < n_tables; ++t) {
+            if (same[t]) continue;
+            const double* src = tables + (size_t)t * GASM_TABLE_ROWS;
+            GCHK(tbs[t]->set_standard(b->ctx, src));
+            (t ? b->table_copy_x[t - 1] : b->table_copy).assign(src, src + GASM_TABLE_ROWS);
+            if (t == 0) b->table_given = true;
+        }
+    }
+    // reads shorter than k (or none), or a table without a fixed-point shift: every table through the general scorer, which
+    // sizes its arrays on the host — after the build's report
+    const bool through_graph = pipeline_score_tables_use_graph(b->rd, b->S().bs, tbs, n_tables);
+    if (!through_graph) GCHK(batch_finish(b));
+    StepSlot& x = b->S();
+    if (!x.paths_ready) {
+        GCHK(pipeline_contig_paths(x.cx, b->rd, x.bs, x.dp));
+        x.paths_ready = true;
+    }
+    if (!through_graph) pipeline_contig_paths_host(b->rd, x.bs, x.dp);
+    GCHK(pipeline_score_launch_tables(x.cx, b->rd, x.dp, kmer, tbs, n_tables, false, false, x.ss, &x.bs));
+    b->scored = true;
+    b->score_kmer = kmer;
+    b->score_tables = n_tables;
     return GASM_OK;
     API_GUARD_END
 }
@@ -758,10 +891,10 @@ int gasm_batch_fetch_guided(gasm_batch* b, const uint64_t** seg_off, const uint6
 
 // the fixed-point breakage sums behind the last gasm_batch_score: bp_score[c] = fx[c] * 2^-shift exactly (what the guided
 // traversal compares, and what its CPU restatement recomputes)
-int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) {
-    API_GUARD_BEGIN
+static int batch_fetch_fixed(gasm_batch* b, uint32_t t, const int64_t** fx, int* shift) {
     if (!b || !fx || !shift) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!b->scored) { gasm_set_error("gasm_batch_fetch_score_fixed needs a scored batch"); return GASM_ERR_STATE; }
+    if (t >= b->score_tables) { gasm_set_error("table %u of a score with %u table(s)", t, b->score_tables); return GASM_ERR_INVALID; }
     GCHK(batch_finish(b));
     StepSlot& x = b->S();
     if (!x.ss.graph) {
@@ -773,11 +906,22 @@ int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) 
     b->h_fx.resize(P);
     const size_t fx_off = (x.ss.stride * 4 + 15) & ~(size_t)15;
     HIPCHK(hipSetDevice(b->ctx->device));
-    if (P) HIPCHK(hipMemcpyAsync(b->h_fx.data(), static_cast<const char*>(x.ss.d_total.p) + fx_off, (size_t)P * 8, hipMemcpyDeviceToHost, x.cx->stream));
+    if (P) HIPCHK(hipMemcpyAsync(b->h_fx.data(), static_cast<const char*>(x.ss.d_total.p) + fx_off + (size_t)t * x.ss.stride * 8, (size_t)P * 8, hipMemcpyDeviceToHost, x.cx->stream));
     HIPCHK(hipStreamSynchronize(x.cx->stream));
     *fx = b->h_fx.data();
-    *shift = b->tb.fix_shift;
+    *shift = (t ? b->tbx[t - 1] : b->tb).fix_shift;
     return GASM_OK;
+}
+
+int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift) {
+    API_GUARD_BEGIN
+    return batch_fetch_fixed(b, 0, fx, shift);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_score_fixed_table(gasm_batch* b, uint32_t t, const int64_t** fx, int* shift) {
+    API_GUARD_BEGIN
+    return batch_fetch_fixed(b, t, fx, shift);
     API_GUARD_END
 }
 
@@ -919,6 +1063,21 @@ int gasm_batch_fetch_scores(gasm_batch* b, const double** bp_score, const double
     ScoreState& ss = b->S().ss;
     GCHK(pipeline_score_fetch(b->S().cx, ss));
     *bp_score = ss.h_bp.data(); *norm_by_break_freqs = ss.h_nf.data(); *norm_by_len = ss.h_nl.data();
+    *kmer_breaks = ss.h_breaks.data(); *sequence_len = ss.h_len.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_scores_table(gasm_batch* b, uint32_t t, const double** bp_score, const double** norm_by_break_freqs, const double** norm_by_len,
+                                  const int32_t** kmer_breaks, const int32_t** sequence_len) {
+    API_GUARD_BEGIN
+    if (!b || !bp_score || !norm_by_break_freqs || !norm_by_len || !kmer_breaks || !sequence_len) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (t >= b->score_tables) { gasm_set_error("table %u of a score with %u table(s)", t, b->score_tables); return GASM_ERR_INVALID; }
+    GCHK(batch_finish(b));
+    ScoreState& ss = b->S().ss;
+    GCHK(pipeline_score_fetch(b->S().cx, ss));
+    const size_t at = (size_t)t * ss.n_paths;           // (the host arrays hold table after table)
+    *bp_score = ss.h_bp.data() + at; *norm_by_break_freqs = ss.h_nf.data() + at; *norm_by_len = ss.h_nl.data() + at;
     *kmer_breaks = ss.h_breaks.data(); *sequence_len = ss.h_len.data();
     return GASM_OK;
     API_GUARD_END

@@ -130,6 +130,10 @@ struct ScoreState {
     DBuf d_tbl_off, d_seed, d_gpos, d_poscnt, d_total, d_out_f64, d_out_i32, d_freq, d_pd_off, d_pd, d_seg_empty, d_fxsum, d_first, d_first_off;
     std::vector<u64> h_toff;
     u32 n_paths = 0, n_table = 0;
+    // breakage tables of the last launch (pipeline_score_launch: 1).  Table t's bp / nf / nl arrays lie at d_out_f64 +
+    // 3 t stride, its fixed-point sums at t * stride behind table 0's, its prob_dist at t * h_pd_off[n_paths]; on the host
+    // h_bp / h_nf / h_nl / h_pd hold table after table (table 0 first: what single-table readers see)
+    u32 n_tables = 1;
     size_t stride = 1;                      // entries per output array on the device (paths + 1, or their upper bound + 1)
     const BuildState* graph = nullptr;      // batch scoring of a build's own contigs: the number of paths comes with its report
     bool want_freq = false, want_pd = false, launched = false;
@@ -165,6 +169,12 @@ void pipeline_contig_paths_host(const DevReads& rd, const BuildState& bs, DevPat
 int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_freq,
                           bool want_pd, ScoreState& ss, const BuildState* graph);
 int pipeline_score_fetch(gasm_ctx* ctx, ScoreState& ss);
+// the same match scored with n_tables tables (1 .. GASM_MAX_TABLES) that share their keys (tbs[0]'s rows serve path_freq):
+// position counters / graph match once, sums (and prob_dist) per table; table t bit for bit what pipeline_score_launch gives
+// with tbs[t].  Through the graph only when every table has a fixed-point shift, else all tables in FP64.
+int pipeline_score_launch_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 n_tables, bool want_freq,
+                                 bool want_pd, ScoreState& ss, const BuildState* graph);
+bool pipeline_score_tables_use_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 n_tables);
 // batch scoring can go through the build's graph (queued without waiting for the build) when every read holds a k-mer
 // and the table has a fixed-point shift for these reads (ScoreTable::fixed_shift); otherwise it takes the FP64 position path
 bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, const ScoreTable& tb);
@@ -173,6 +183,10 @@ bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, cons
 // Two-sample KS statistic of every path's path_freq against the genome's per-position window probabilities
 // (lib/DeNovoAssembler.R:414-424); needs the position counters of a general (non-graph) pipeline_score_launch.
 int pipeline_ks(gasm_ctx* ctx, DevPaths& dp, ScoreState& ss, const ScoreTable& tb, const char* genome, u64 genome_len, int kmer, std::vector<double>& ks);
+// its two halves: the genome's windows counted per table row (does not depend on the probabilities), and the statistic of
+// every path under one table's probabilities
+int pipeline_ks_genome_hist(gasm_ctx* ctx, const ScoreTable& tb, const char* genome, u64 genome_len, int kmer, std::vector<u32>& hist);
+int pipeline_ks_paths(gasm_ctx* ctx, DevPaths& dp, ScoreState& ss, const ScoreTable& tb, const std::vector<u32>& hist, int kmer, std::vector<double>& ks);
 // contig_frac_len (lib/DeNovoAssembler.R:432-445)
 int pipeline_coverage(gasm_ctx* ctx, const long long* start, const long long* len, u64 n, long long seq_len, double* percent);
 int pipeline_levenshtein(gasm_ctx* ctx, DevPaths& dp, const char* target, u64 target_len, bool infix, std::vector<int32_t>& lev, bool* done);

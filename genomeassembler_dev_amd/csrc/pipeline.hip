@@ -56,6 +56,9 @@ static const Knobs& knobs() { static const Knobs k; return k; }
 // knobs read at every build (tests switch them inside one process):
 //   GASM_SINGLE_PASS=0     two-pass partition (count, scan, scatter) from the start       GASM_PART_SLACK=percent   room per bucket region (100)
 //   GASM_DBG_PART_CAP=n    force the capacity of every bucket region to n keys (exercises the overflow path)
+// and at every multi-table batch score:
+//   GASM_DBG_SCORE_LDS_PATHS=n   cap the paths per segment whose accumulators k_score_reads_graph_tables keeps in LDS (segments
+//                                with more go to global atomics: same numbers; exercises that branch)
 
 // Wait for a report a kernel writes into pinned host memory: the kernel's last store is `ticket` at `word`.  Spinning on
 // that word costs a few microseconds; waking up from hipStreamSynchronize costs 15-20 us (more on a busy host) — twice
@@ -462,6 +465,11 @@ static int ensure_lds_attrs(gasm_ctx* ctx) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<K128>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
+#define GASM_TABLES_LDS_ATTR(T)                                                                                                                                              \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph_tables<u64, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));  \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph_tables<K128, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
+    GASM_TABLES_LDS_ATTR(2) GASM_TABLES_LDS_ATTR(3) GASM_TABLES_LDS_ATTR(4) GASM_TABLES_LDS_ATTR(5) GASM_TABLES_LDS_ATTR(6) GASM_TABLES_LDS_ATTR(7) GASM_TABLES_LDS_ATTR(8)
+#undef GASM_TABLES_LDS_ATTR
     ctx->lds_attrs_set = true;
     return GASM_OK;
 }
@@ -1143,14 +1151,19 @@ void ScoreTable::release() { d_prob.release(); d_row.release(); d_fix.release();
 // F4: KS statistic and coverage (kernels_score.hip)
 // ---------------------------------------------------------------------------------------------------------------
 int pipeline_ks(gasm_ctx* ctx, DevPaths& dp, ScoreState& ss, const ScoreTable& tb, const char* genome, u64 genome_len, int kmer, std::vector<double>& ks) {
-    const u32 P = dp.n_paths, NT = tb.n_table;
-    ks.assign(P, std::nan(""));
-    if (P == 0) return GASM_OK;
-    if (tb.h_row_prob.size() != NT) { gasm_set_error("the KS statistic needs the table rows (ScoreTable::set)"); return GASM_ERR_STATE; }
+    ks.assign(dp.n_paths, std::nan(""));
+    if (dp.n_paths == 0) return GASM_OK;
+    std::vector<u32> h_hist;
+    GCHK(pipeline_ks_genome_hist(ctx, tb, genome, genome_len, kmer, h_hist));
+    return pipeline_ks_paths(ctx, dp, ss, tb, h_hist, kmer, ks);
+}
+
+// ---- the genome's side: rows of its kmer-long windows, counted (the table's rows, not its probabilities)
+int pipeline_ks_genome_hist(gasm_ctx* ctx, const ScoreTable& tb, const char* genome, u64 genome_len, int kmer, std::vector<u32>& h_hist) {
+    const u32 NT = tb.n_table;
     HIPCHK(hipSetDevice(ctx->device));
-    DBuf ascii, err, gwords, hist, d_pv, d_cumy, scratch, d_out;
-    struct Rel { std::vector<DBuf*> v; ~Rel() { for (DBuf* b : v) b->release(); } } rel{{&ascii, &err, &gwords, &hist, &d_pv, &d_cumy, &scratch, &d_out}};
-    // ---- the genome's side: rows of its kmer-long windows, counted, in ascending-probability order, prefix-summed
+    DBuf ascii, err, gwords, hist;
+    struct Rel { std::vector<DBuf*> v; ~Rel() { for (DBuf* b : v) b->release(); } } rel{{&ascii, &err, &gwords, &hist}};
     GCHK(err.ensure(8));
     HIPCHK(hipMemsetAsync(err.p, 0, 8, ctx->stream));
     GCHK(h2d(ctx, ascii, genome, genome_len));
@@ -1159,12 +1172,24 @@ int pipeline_ks(gasm_ctx* ctx, DevPaths& dp, ScoreState& ss, const ScoreTable& t
     HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)std::max<u32>(NT, 1) * 4, ctx->stream));
     GLAUNCH(ctx, "k_ks_genome_hist", k_ks_genome_hist, dim3(std::max(1u, std::min<u32>(ceil_div_u64(genome_len + 1, GASM_WG), (u32)ctx->n_cu * 8u))), dim3(GASM_WG), 0,
             gwords.as<u64>(), genome_len, kmer, tb.d_row.as<int32_t>(), hist.as<u32>());
-    std::vector<u32> h_hist(NT);
+    h_hist.assign(NT, 0);
     u32 herr = 0;
     HIPCHK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (NT) HIPCHK(hipMemcpyAsync(h_hist.data(), hist.p, (size_t)NT * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (herr) { gasm_set_error("true_solution holds a base outside upper-case ACGT: the KS statistic needs its window probabilities"); return GASM_ERR_NON_ACGT; }
+    return GASM_OK;
+}
+
+// ---- one table's probabilities: the genome's rows in ascending-probability order, prefix-summed; then the paths' side
+int pipeline_ks_paths(gasm_ctx* ctx, DevPaths& dp, ScoreState& ss, const ScoreTable& tb, const std::vector<u32>& h_hist, int kmer, std::vector<double>& ks) {
+    const u32 P = dp.n_paths, NT = tb.n_table;
+    ks.assign(P, std::nan(""));
+    if (P == 0) return GASM_OK;
+    if (tb.h_row_prob.size() != NT || h_hist.size() != NT) { gasm_set_error("the KS statistic needs the table rows (ScoreTable::set)"); return GASM_ERR_STATE; }
+    HIPCHK(hipSetDevice(ctx->device));
+    DBuf d_pv, d_cumy, scratch, d_out;
+    struct Rel { std::vector<DBuf*> v; ~Rel() { for (DBuf* b : v) b->release(); } } rel{{&d_pv, &d_cumy, &scratch, &d_out}};
     std::vector<u32> order(NT);
     for (u32 i = 0; i < NT; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 b) { return tb.h_row_prob[a] < tb.h_row_prob[b]; });
@@ -1309,27 +1334,18 @@ bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, cons
     return graph.n_kmers > 0 && rd.n_reads > rd.n_empty && rd.min_len >= (u32)graph.k && tb.fixed_shift(max_seg_reads(rd)) >= 0;
 }
 
-int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_freq, bool want_pd,
-                          ScoreState& ss, const BuildState* graph) {
-    if (kmer < 0) { gasm_set_error("kmer must be >= 0"); return GASM_ERR_INVALID; }
-    if (rd.n_segments != dp.n_segments) { gasm_set_error("reads and paths disagree on the number of segments"); return GASM_ERR_INVALID; }
-    HIPCHK(hipSetDevice(ctx->device));
-    GasmRange range("gasm:score");
-    ss.valid = false;
-    ss.n_table = tb.n_table;
-    ss.want_freq = want_freq && tb.n_table;
-    ss.want_pd = want_pd;
-    ss.graph = nullptr;
-    if (graph && !want_freq && !want_pd && pipeline_score_uses_graph(rd, *graph, tb)) return score_launch_graph(ctx, rd, dp, kmer, tb, ss, *graph);
-    // ---- arbitrary paths (or reads that do not all hold a k-mer): host-side sizes are needed — the caller has uploaded
-    // the paths or, for a build's contigs, read the build's report (pipeline_contig_paths_host)
+// The part of the general scorer no table enters: the first occurrence of every read in every path as position counters
+// (ss.d_poscnt, ss.d_total), and the output arrays for n_tables tables.  Arbitrary paths (or reads that do not all hold a
+// k-mer): host-side sizes are needed — the caller has uploaded the paths or, for a build's contigs, read the build's report
+// (pipeline_contig_paths_host)
+static int score_positions(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, ScoreState& ss, u32 n_tables) {
     ss.n_paths = dp.n_paths;
     const u32 S = rd.n_segments, P = dp.n_paths;
     const u64 TB = dp.total_bases;
     ss.stride = (size_t)P + 1;
     GCHK(ss.d_poscnt.ensure((TB + 1) * 4));
     GCHK(ss.d_total.ensure(((size_t)P + 1) * 4));
-    GCHK(ss.d_out_f64.ensure(((size_t)P + 1) * 8 * 3));
+    GCHK(ss.d_out_f64.ensure(((size_t)P + 1) * 8 * 3 * n_tables));
     GCHK(ss.d_out_i32.ensure(((size_t)P + 1) * 4 * 2));
     HIPCHK(hipMemsetAsync(ss.d_poscnt.p, 0, (TB + 1) * 4, ctx->stream));
     HIPCHK(hipMemsetAsync(ss.d_total.p, 0, ((size_t)P + 1) * 4, ctx->stream));
@@ -1405,15 +1421,13 @@ int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, c
         if (maxp) hipLaunchKernelGGL(k_add_empty_reads, dim3(ceil_div_u64(maxp, GASM_WG), S), dim3(GASM_WG), 0, ctx->stream, ps,
                                      ss.d_seg_empty.as<u64>(), ss.d_poscnt.as<u32>(), ss.d_total.as<u32>());
     }
-    double* o_bp = ss.d_out_f64.as<double>();
-    double* o_nf = o_bp + (P + 1);
-    double* o_nl = o_nf + (P + 1);
-    int32_t* o_br = ss.d_out_i32.as<int32_t>();
-    int32_t* o_ln = o_br + (P + 1);
-    if (P) {
-        GLAUNCH(ctx, "k_path_reduce", k_path_reduce, dim3(P), dim3(GASM_WG), 0, ps, ss.d_poscnt.as<u32>(),
-                ss.d_total.as<u32>(), tb.d_prob.as<double>(), kmer, o_bp, o_nf, o_nl, o_br, o_ln, P);
-    }
+    return GASM_OK;
+}
+
+// path_freq counts (table rows, not probabilities) and the prob_dist offsets: the same for every table of a call
+static int score_freq_and_pd_offsets(gasm_ctx* ctx, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_pd, ScoreState& ss) {
+    const u32 P = dp.n_paths;
+    const PathSet ps = dp.view();
     if (P && ss.want_freq) {
         const size_t cells = (size_t)P * tb.n_table;
         GCHK(ss.d_freq.ensure(cells * 4));
@@ -1428,12 +1442,165 @@ int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, c
             const u64 len = dp.h_p_off[p + 1] - dp.h_p_off[p];
             ss.h_pd_off[p + 1] = ss.h_pd_off[p] + (len >= (u64)kmer ? len - kmer + 1 : 0);
         }
-        if (P) {
-            GCHK(h2d(ctx, ss.d_pd_off, ss.h_pd_off.data(), ss.h_pd_off.size() * 8));
-            GCHK(ss.d_pd.ensure((ss.h_pd_off[P] + 1) * 8));
-            GLAUNCH(ctx, "k_prob_dist", k_prob_dist, dim3(ceil_div_u64(P, GASM_WG / 64)), dim3(GASM_WG), 0, ps, tb.d_prob.as<double>(), kmer,
-                    ss.d_pd_off.as<u64>(), ss.d_pd.as<double>(), P);
-        }
+        if (P) GCHK(h2d(ctx, ss.d_pd_off, ss.h_pd_off.data(), ss.h_pd_off.size() * 8));
+    }
+    return GASM_OK;
+}
+
+int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_freq, bool want_pd,
+                          ScoreState& ss, const BuildState* graph) {
+    if (kmer < 0) { gasm_set_error("kmer must be >= 0"); return GASM_ERR_INVALID; }
+    if (rd.n_segments != dp.n_segments) { gasm_set_error("reads and paths disagree on the number of segments"); return GASM_ERR_INVALID; }
+    HIPCHK(hipSetDevice(ctx->device));
+    GasmRange range("gasm:score");
+    ss.valid = false;
+    ss.n_table = tb.n_table;
+    ss.n_tables = 1;
+    ss.want_freq = want_freq && tb.n_table;
+    ss.want_pd = want_pd;
+    ss.graph = nullptr;
+    if (graph && !want_freq && !want_pd && pipeline_score_uses_graph(rd, *graph, tb)) return score_launch_graph(ctx, rd, dp, kmer, tb, ss, *graph);
+    GCHK(score_positions(ctx, rd, dp, ss, 1));
+    const u32 P = dp.n_paths;
+    const PathSet ps = dp.view();
+    double* o_bp = ss.d_out_f64.as<double>();
+    double* o_nf = o_bp + (P + 1);
+    double* o_nl = o_nf + (P + 1);
+    int32_t* o_br = ss.d_out_i32.as<int32_t>();
+    int32_t* o_ln = o_br + (P + 1);
+    if (P) {
+        GLAUNCH(ctx, "k_path_reduce", k_path_reduce, dim3(P), dim3(GASM_WG), 0, ps, ss.d_poscnt.as<u32>(),
+                ss.d_total.as<u32>(), tb.d_prob.as<double>(), kmer, o_bp, o_nf, o_nl, o_br, o_ln, P);
+    }
+    GCHK(score_freq_and_pd_offsets(ctx, dp, kmer, tb, want_pd, ss));
+    if (want_pd && P) {
+        GCHK(ss.d_pd.ensure((ss.h_pd_off[P] + 1) * 8));
+        GLAUNCH(ctx, "k_prob_dist", k_prob_dist, dim3(ceil_div_u64(P, GASM_WG / 64)), dim3(GASM_WG), 0, ps, tb.d_prob.as<double>(), kmer,
+                ss.d_pd_off.as<u64>(), ss.d_pd.as<double>(), P);
+    }
+    ss.launched = true;
+    return GASM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// several tables over one match (gasm_batch_score_tables, gasm_calc_breakscore_tables)
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(GASM_SCORE_MAX_TABLES == GASM_MAX_TABLES, "kernels.h and gasm.h disagree on the number of tables");
+
+bool pipeline_score_tables_use_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 n_tables) {
+    for (u32 t = 0; t < n_tables; ++t) if (!pipeline_score_uses_graph(rd, graph, *tbs[t])) return false;
+    return true;
+}
+
+#define GASM_TABLES_SWITCH(T, FIRST, CASE)                                                                     \
+    switch (T) {                                                                                               \
+        FIRST case 2: CASE(2); break; case 3: CASE(3); break; case 4: CASE(4); break; case 5: CASE(5); break;  \
+        case 6: CASE(6); break; case 7: CASE(7); break; default: CASE(8); break;                               \
+    }
+
+// score_launch_graph for T >= 2 tables: one k_score_zero_tables, one k_score_reads_graph_tables, a k_score_finish per table
+// (tiny; each with its table's own fixed-point shift).  One count array, the sums of table t at t * stride behind table 0's.
+static int score_launch_graph_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 T, ScoreState& ss,
+                                     const BuildState& graph) {
+    GasmRange range("gasm:score (graph-indexed, several tables)");
+    GCHK(ensure_lds_attrs(ctx));
+    const u32 S = rd.n_segments;
+    const size_t PC = (size_t)graph.D_cap + 1;
+    ss.stride = PC;
+    ss.graph = &graph;
+    ss.n_paths = 0;
+    const size_t fx_off = (PC * 4 + 15) & ~(size_t)15;
+    GCHK(ss.d_total.ensure(fx_off + PC * 8 * T));
+    GCHK(ss.d_out_f64.ensure(PC * 8 * 3 * T));
+    GCHK(ss.d_out_i32.ensure(PC * 4 * 2));
+    unsigned long long* const d_fx = reinterpret_cast<unsigned long long*>(static_cast<char*>(ss.d_total.p) + fx_off);
+    const u32* const n_paths_p = graph.d_seg_cstart.as<u32>() + S;
+    const u64 p_est = graph.have_actual ? std::max<u64>(graph.n_contigs, 1) : (u64)S * 256;
+    const u32 grid_p = (u32)std::max<u64>(1, std::min<u64>(ceil_div_u64(p_est, GASM_WG), (u64)ctx->n_cu * 8));
+    GLAUNCH(ctx, "k_score_zero_tables", k_score_zero_tables, dim3(grid_p), dim3(GASM_WG), 0, ss.d_total.as<u32>(), d_fx, (u64)PC, T, n_paths_p);
+    const PathSet ps = dp.view();
+    GraphView gv;
+    gv.dk_key = graph.d_dk_key.p;
+    gv.dstart = graph.d_dstart.as<u32>();
+    gv.fdir = graph.d_fdir.as<u16>();
+    gv.k = graph.k;
+    gv.bbits = graph.bbits;
+    gv.fbits = graph.fbits;
+    const u64 max_reads = max_seg_reads(rd);
+    FixTables ft = {};
+    for (u32 t = 0; t < T; ++t) {
+        GCHK(tbs[t]->set_fixed(ctx, tbs[t]->fixed_shift(max_reads)));
+        ft.p[t] = tbs[t]->d_fix.as<long long>();
+    }
+    const int verify = env_int("GASM_SCORE_VERIFY", 0);
+    ss.verify = verify != 0;
+    const u32 reads_per_wg = 256;
+    const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);
+    // the LDS request stays within k_score_reads_graph's largest: 4 + 8 T bytes per path instead of 12
+    u32 lds_paths = std::min<u32>(std::max<u32>(graph.have_actual ? graph.paths_est : 1024u, 1u), (u32)(GASM_SCORE_PATH_CAP * 12 / (4 + 8 * T)));
+    if (const int cap = env_int("GASM_DBG_SCORE_LDS_PATHS", 0)) lds_paths = std::min<u32>(lds_paths, (u32)std::max(1, cap));
+    const size_t lds_bytes = (size_t)lds_paths * (4 + 8 * (size_t)T);
+#define GASM_LAUNCH_SCORE_TABLES(TT)                                                                                                                 \
+    do {                                                                                                                                             \
+        const auto kern = graph.words == 1 ? k_score_reads_graph_tables<u64, TT> : k_score_reads_graph_tables<K128, TT>;                             \
+        GLAUNCH(ctx, "k_score_reads_graph_tables", kern, seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), gv, graph.d_link.as<u64>(),      \
+                graph.d_ecid.as<u32>(), ps, ft, kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(), d_fx, (u64)PC, verify,                 \
+                graph.d_flags.as<u32>() + 2);                                                                                                        \
+    } while (0)
+    GASM_TABLES_SWITCH(T, , GASM_LAUNCH_SCORE_TABLES)
+#undef GASM_LAUNCH_SCORE_TABLES
+    int32_t* o_br = ss.d_out_i32.as<int32_t>();
+    int32_t* o_ln = o_br + PC;
+    const u64* d_se = nullptr;
+    if (rd.n_empty) { GCHK(h2d(ctx, ss.d_seg_empty, rd.h_seg_empty.data(), (size_t)S * 8)); d_se = ss.d_seg_empty.as<u64>(); }
+    for (u32 t = 0; t < T; ++t) {
+        double* o_bp = ss.d_out_f64.as<double>() + (size_t)t * 3 * PC;
+        GLAUNCH(ctx, "k_score_finish", k_score_finish, dim3(grid_p), dim3(GASM_WG), 0, ps, ss.d_total.as<u32>(), d_fx + (size_t)t * PC, ft.p[t], d_se, kmer,
+                std::ldexp(1.0, -tbs[t]->fix_shift), o_bp, o_bp + PC, o_bp + 2 * PC, o_br, o_ln, n_paths_p);
+    }
+    ss.h_pd_off.clear();
+    ss.launched = true;
+    return GASM_OK;
+}
+
+int pipeline_score_launch_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 T, bool want_freq, bool want_pd,
+                                 ScoreState& ss, const BuildState* graph) {
+    if (T < 1 || T > GASM_MAX_TABLES) { gasm_set_error("n_tables must be 1..%d (got %u)", GASM_MAX_TABLES, T); return GASM_ERR_INVALID; }
+    if (kmer < 0) { gasm_set_error("kmer must be >= 0"); return GASM_ERR_INVALID; }
+    if (rd.n_segments != dp.n_segments) { gasm_set_error("reads and paths disagree on the number of segments"); return GASM_ERR_INVALID; }
+    for (u32 t = 1; t < T; ++t) if (tbs[t]->n_table != tbs[0]->n_table) { gasm_set_error("the tables differ in their number of rows"); return GASM_ERR_INVALID; }
+    HIPCHK(hipSetDevice(ctx->device));
+    GasmRange range("gasm:score (several tables)");
+    ss.valid = false;
+    ss.n_table = tbs[0]->n_table;
+    ss.n_tables = T;
+    ss.want_freq = want_freq && tbs[0]->n_table;
+    ss.want_pd = want_pd;
+    ss.graph = nullptr;
+    if (graph && T >= 2 && !want_freq && !want_pd && pipeline_score_tables_use_graph(rd, *graph, tbs, T))
+        return score_launch_graph_tables(ctx, rd, dp, kmer, tbs, T, ss, *graph);
+    GCHK(score_positions(ctx, rd, dp, ss, T));
+    const u32 P = dp.n_paths;
+    const PathSet ps = dp.view();
+    const size_t stride = ss.stride;
+    double* o_bp = ss.d_out_f64.as<double>();
+    int32_t* o_br = ss.d_out_i32.as<int32_t>();
+    ProbTables pt = {};
+    for (u32 t = 0; t < T; ++t) pt.p[t] = tbs[t]->d_prob.as<double>();
+    if (P) {
+#define GASM_LAUNCH_REDUCE_TABLES(TT)                                                                                                                     \
+    GLAUNCH(ctx, "k_path_reduce_tables", k_path_reduce_tables<TT>, dim3(P), dim3(GASM_WG), 0, ps, ss.d_poscnt.as<u32>(), ss.d_total.as<u32>(), pt, kmer, o_bp, \
+            o_bp + stride, o_bp + 2 * stride, (u64)(3 * stride), o_br, o_br + stride, P)
+        GASM_TABLES_SWITCH(T, case 1: GASM_LAUNCH_REDUCE_TABLES(1); break;, GASM_LAUNCH_REDUCE_TABLES)
+#undef GASM_LAUNCH_REDUCE_TABLES
+    }
+    GCHK(score_freq_and_pd_offsets(ctx, dp, kmer, *tbs[0], want_pd, ss));
+    if (want_pd && P) {
+        const u64 per_table = ss.h_pd_off[P];
+        GCHK(ss.d_pd.ensure((per_table * T + 1) * 8));
+        for (u32 t = 0; t < T; ++t)
+            GLAUNCH(ctx, "k_prob_dist", k_prob_dist, dim3(ceil_div_u64(P, GASM_WG / 64)), dim3(GASM_WG), 0, ps, pt.p[t], kmer, ss.d_pd_off.as<u64>(),
+                    ss.d_pd.as<double>() + per_table * t, P);
     }
     ss.launched = true;
     return GASM_OK;
@@ -1452,19 +1619,21 @@ int pipeline_score_fetch(gasm_ctx* ctx, ScoreState& ss) {
             if (bad) { gasm_set_error("GASM_SCORE_VERIFY: a read that fits its contig by the graph differs from the contig's text"); return GASM_ERR_STATE; }
         }
     }
-    const u32 P = ss.n_paths;
-    double* o_bp = ss.d_out_f64.as<double>();
-    double* o_nf = o_bp + ss.stride;
-    double* o_nl = o_nf + ss.stride;
+    const u32 P = ss.n_paths, T = ss.n_tables;
     int32_t* o_br = ss.d_out_i32.as<int32_t>();
     int32_t* o_ln = o_br + ss.stride;
-    ss.h_bp.resize(P); ss.h_nf.resize(P); ss.h_nl.resize(P); ss.h_breaks.resize(P); ss.h_len.resize(P);
+    ss.h_bp.resize((size_t)P * T); ss.h_nf.resize((size_t)P * T); ss.h_nl.resize((size_t)P * T); ss.h_breaks.resize(P); ss.h_len.resize(P);
     ss.h_freq.clear(); ss.h_pd.clear();
     std::vector<u32> h_fc;
     if (P) {
-        HIPCHK(hipMemcpyAsync(ss.h_bp.data(), o_bp, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ss.h_nf.data(), o_nf, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ss.h_nl.data(), o_nl, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        for (u32 t = 0; t < T; ++t) {           // (one table: the three arrays, as ever)
+            double* o_bp = ss.d_out_f64.as<double>() + (size_t)t * 3 * ss.stride;
+            double* o_nf = o_bp + ss.stride;
+            double* o_nl = o_nf + ss.stride;
+            HIPCHK(hipMemcpyAsync(ss.h_bp.data() + (size_t)t * P, o_bp, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(ss.h_nf.data() + (size_t)t * P, o_nf, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(ss.h_nl.data() + (size_t)t * P, o_nl, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
         HIPCHK(hipMemcpyAsync(ss.h_breaks.data(), o_br, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(ss.h_len.data(), o_ln, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (ss.want_freq) {
@@ -1472,8 +1641,8 @@ int pipeline_score_fetch(gasm_ctx* ctx, ScoreState& ss) {
             HIPCHK(hipMemcpyAsync(h_fc.data(), ss.d_freq.p, h_fc.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         if (ss.want_pd && ss.h_pd_off[P]) {
-            ss.h_pd.resize(ss.h_pd_off[P]);
-            HIPCHK(hipMemcpyAsync(ss.h_pd.data(), ss.d_pd.p, ss.h_pd_off[P] * 8, hipMemcpyDeviceToHost, ctx->stream));
+            ss.h_pd.resize(ss.h_pd_off[P] * T);
+            HIPCHK(hipMemcpyAsync(ss.h_pd.data(), ss.d_pd.p, ss.h_pd_off[P] * 8 * T, hipMemcpyDeviceToHost, ctx->stream));
         }
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -18,9 +18,13 @@ def score_solutions_one(paths, reads, true_solution, kmer, bp_kmer, bp_prob, seq
     """One pass of the lapply in score_solutions() (DeNovoAssembler.R:325-459), own-assembler mode: calc_breakscore, rows
     ordered by descending bp_score (stable, as data.table's setorder), path_freq_startpos = 0 for every row, KS per row,
     contig_frac_len from the ranges [0, sequence_len]."""
-    seq_len = len(true_solution) if seq_len is None else seq_len
     r = api.calc_breakscore(paths, reads, true_solution, kmer, bp_kmer, bp_prob, variant="own", with_lev=True, with_freq=False,
                             with_ks=True, ctx=ctx)
+    return _one_pass(r, len(true_solution) if seq_len is None else seq_len, ctx)
+
+
+def _one_pass(r, seq_len, ctx):
+    """what score_solutions() does with one calc_breakscore result (DeNovoAssembler.R:336-459)"""
     order = np.argsort(-np.asarray(r["bp_score"]), kind="stable")
     out = {c: (np.asarray(r[c])[order] if c != "sequence" else [r[c][i] for i in order]) for c in _BASE if c in r}
     n = len(order)
@@ -54,10 +58,12 @@ def join_true_random(true_res, random_res):
 
 
 def score_solutions(paths, reads, true_solution, kmer=8, ctx=None):
-    """both passes (true table, then 1/N for every row: DeNovoAssembler.R:326-333) and the join"""
-    keys = qtable.keys()
-    t = score_solutions_one(paths, reads, true_solution, kmer, keys, qtable.load_normalised(), ctx=ctx)
-    u = score_solutions_one(paths, reads, true_solution, kmer, keys, qtable.uniform(), ctx=ctx)
+    """both passes (true table, then 1/N for every row: DeNovoAssembler.R:326-333) and the join.  The two passes differ in
+    bp_prob only, so they are one calc_breakscore_tables call: reads matched, Levenshtein and the KS test's genome side
+    computed once; the same numbers as two score_solutions_one calls."""
+    r = api.calc_breakscore_tables(paths, reads, true_solution, kmer, qtable.keys(), [qtable.load_normalised(), qtable.uniform()],
+                                   variant="own", with_lev=True, with_freq=False, with_ks=True, ctx=ctx)
+    t, u = (_one_pass(x, len(true_solution), ctx) for x in r)
     return join_true_random(t, u)
 
 

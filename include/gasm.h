@@ -174,6 +174,32 @@ const double* gasm_scores_ks(const gasm_scores* s);
 int gasm_scores_lev_device(const gasm_scores* s);
 void gasm_scores_free(gasm_scores* s);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * calc_breakscore under several breakage tables at once: what score_solutions() needs (lib/DeNovoAssembler.R:325-355 runs
+ * calc_breakscore twice per experiment, `for random_prob in (FALSE, TRUE)`: same paths, reads and true solution, only
+ * bp_prob differs — the true table, then the uniform one).
+ *   bp_probs: n_tables rows of n_table probabilities (row-major), all for the keys bp_kmer; n_tables in 1..GASM_MAX_TABLES,
+ *   else GASM_ERR_INVALID.  out: n_tables entries; out[t] is an ordinary gasm_scores (every accessor above; free each with
+ *   gasm_scores_free) holding bit for bit what gasm_calc_breakscore(..., bp_probs + t * n_table, ...) returns with the same
+ *   variant and flags.  On any error every out[t] is NULL.
+ * Done once per call (none of it depends on the table): read upload and index, the first occurrence of every read in every
+ * path, kmer_breaks, sequence_len, lev_dist_vs_true (GPU or host, as gasm_calc_breakscore chooses), the velvet variant's
+ * startpos, the genome's row histogram for the KS statistic, and the path_freq counts — count / total, one dense buffer
+ * shared by the n_tables result objects (gasm_scores_path_freq returns the same pointer for each; it lives until the last
+ * of them is freed).  Done per table: bp_score, norm_by_break_freqs, norm_by_len (one kernel gathers the T probabilities of
+ * a hit position; per table the summation order of the single-table call), the KS statistic (it ranks the table's
+ * probabilities) and the velvet variant's path_prob_dist.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAX_TABLES 8
+int gasm_calc_breakscore_tables(gasm_ctx* ctx, const char* paths, const uint64_t* path_off, uint64_t n_paths, const char* reads,
+                                const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
+                                const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
+                                int variant, int flags, gasm_scores** out);
+int gasm_calc_breakscore_tables_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, const char* reads, const uint64_t* read_off,
+                                    uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer, const char* bp_kmer,
+                                    const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables, int variant,
+                                    int flags, gasm_scores** out);
+
 /* contig_frac_len of lib/DeNovoAssembler.R:432-445: percentage of [1, seq_len] covered by the union of the inclusive
  * ranges [start_i, start_i + len_i] (GRanges reduce + setdiff). */
 int gasm_coverage_percent(gasm_ctx* ctx, const int64_t* start, const int64_t* len, uint64_t n, int64_t seq_len, double* percent);
@@ -396,6 +422,26 @@ int gasm_batch_fetch_guided(gasm_batch* b, const uint64_t** seg_off /*n_segments
  * gasm_batch_score took the FP64 scorer (reads shorter than k, or a table the fixed point cannot hold: see gasm_batch_score);
  * gasm_batch_guided needs the same sums and fails the same way */
 int gasm_batch_fetch_score_fixed(gasm_batch* b, const int64_t** fx, int* shift);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * gasm_batch_score under several tables at once (the batch form of gasm_calc_breakscore_tables: the true and the uniform
+ * table of lib/DeNovoAssembler.R:325-355 over one match).  tables: n_tables x GASM_TABLE_ROWS, row-major; n_tables in
+ * 1..GASM_MAX_TABLES (else GASM_ERR_INVALID); n_tables == 1 is gasm_batch_score.  Queued on the build's step slot like
+ * gasm_batch_score (no host wait on the fixed-point path; `build; score_tables; build; score_tables` overlaps the same way).
+ * Shared by the tables: each read's k-mer lookup, link, contig and break window, and the per-contig hit count.  Per table:
+ * the gather of the window's weight and the 64-bit sum, each table with its own fixed-point shift by gasm_batch_score's
+ * rule.  The graph-indexed fixed-point scorer runs when the reads allow it and EVERY table has a valid shift; otherwise all
+ * tables go through the FP64 position scorer (gasm_batch_fetch_score_fixed_table then returns GASM_ERR_STATE for each).
+ * Table t's results are bit for bit those of gasm_batch_score with table t whenever both take the same scorer (always,
+ * except for a table that has a shift of its own while another table of the call sent them all to the FP64 scorer).
+ * gasm_batch_fetch_scores_table / gasm_batch_fetch_score_fixed_table: table t of the last score; t must be below its table
+ * count (1 after a plain gasm_batch_score), else GASM_ERR_INVALID.  gasm_batch_fetch_scores, gasm_batch_fetch_score_fixed
+ * and gasm_batch_guided refer to table 0.  Each fetch's host copy stays valid until the next fetch of the batch.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int gasm_batch_score_tables(gasm_batch* b, int kmer, const double* tables, uint32_t n_tables);
+int gasm_batch_fetch_scores_table(gasm_batch* b, uint32_t t, const double** bp_score, const double** norm_by_break_freqs,
+                                  const double** norm_by_len, const int32_t** kmer_breaks, const int32_t** sequence_len);
+int gasm_batch_fetch_score_fixed_table(gasm_batch* b, uint32_t t, const int64_t** fx, int* shift);
 
 /* Per-kernel device time of the stages of build/score, accumulated with HIP events on the ctx stream since the last
  * reset (profiling on costs one event pair per launch).  names/ms/launches point into library storage. */

@@ -68,3 +68,45 @@ Rcpp::List calc_breakscore(const std::vector<std::string>& path, const std::vect
     gasm_scores_free(s);
     return out;
 }
+
+// the same under several breakage tables in one call (bp_prob_list: one probability vector per table over bp_kmer): the
+// reads are matched once and the infix Levenshtein distances and start positions computed once (gasm_calc_breakscore_tables);
+// a list with, per table, the list calc_breakscore returns for it
+// [[Rcpp::export]]
+Rcpp::List calc_breakscore_tables(const std::vector<std::string>& path, const std::vector<std::string>& sequencing_reads,
+                                  const std::string& true_solution, const int& kmer, const std::vector<std::string>& bp_kmer,
+                                  const std::vector<std::vector<double>>& bp_prob_list) {
+    Flat p(path), r(sequencing_reads), t(bp_kmer);
+    const uint64_t nt = bp_kmer.size(), n_tables = bp_prob_list.size();
+    if (n_tables < 1 || n_tables > GASM_MAX_TABLES) Rcpp::stop("calc_breakscore_tables: bp_prob_list must hold 1 to 8 tables");
+    std::vector<double> probs;
+    for (const auto& v : bp_prob_list) {
+        if (v.size() != nt) Rcpp::stop("calc_breakscore_tables: every table needs one probability per bp_kmer");
+        probs.insert(probs.end(), v.begin(), v.end());
+    }
+    gasm_scores* s[GASM_MAX_TABLES] = {nullptr};
+    check(gasm_calc_breakscore_tables(the_ctx(), p.data.data(), p.off.data(), path.size(), r.data.data(), r.off.data(), sequencing_reads.size(),
+                                      true_solution.data(), true_solution.size(), kmer, t.data.data(), t.off.data(), nt, probs.data(),
+                                      (uint32_t)n_tables, GASM_SCORE_VELVET, GASM_WANT_LEV, s));
+    const uint64_t n = gasm_scores_count(s[0]);
+    auto ivec = [&](const int32_t* a) { return std::vector<int>(a, a + n); };
+    auto dvec = [&](const double* a) { return std::vector<double>(a, a + n); };
+    Rcpp::List all(n_tables);
+    for (uint64_t j = 0; j < n_tables; ++j) {
+        const uint64_t* po = gasm_scores_prob_dist_offsets(s[j]);
+        const double* pd = gasm_scores_prob_dist(s[j]);
+        std::vector<std::vector<double>> dist(n);
+        for (uint64_t i = 0; i < n; ++i) dist[i].assign(pd + po[i], pd + po[i + 1]);
+        all[j] = Rcpp::List::create(
+            Rcpp::Named("sequence") = path, Rcpp::Named("sequence_len") = ivec(gasm_scores_sequence_len(s[j])),
+            Rcpp::Named("bp_score") = dvec(gasm_scores_bp_score(s[j])),
+            Rcpp::Named("bp_score_norm_by_break_freqs") = dvec(gasm_scores_norm_by_break_freqs(s[j])),
+            Rcpp::Named("bp_score_norm_by_len") = dvec(gasm_scores_norm_by_len(s[j])),
+            Rcpp::Named("kmer_breaks") = ivec(gasm_scores_kmer_breaks(s[j])),
+            Rcpp::Named("lev_dist_vs_true") = ivec(gasm_scores_lev_dist(s[j])),
+            Rcpp::Named("path_prob_dist_startpos") = ivec(gasm_scores_startpos(s[j])),
+            Rcpp::Named("path_prob_dist") = Rcpp::wrap(dist));
+        gasm_scores_free(s[j]);
+    }
+    return all;
+}

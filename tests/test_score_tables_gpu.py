@@ -1,0 +1,405 @@
+"""Several breakage tables scored in one pass over the matches (gasm_calc_breakscore_tables, gasm_batch_score_tables; the
+reference scores every experiment under the true and under the uniform table, lib/DeNovoAssembler.R:325-355).
+
+The acceptance is bit equality: table t of a multi-table call returns what the single-table call returns for table t —
+every array, NaN equal to NaN — on the string API (own and velvet variant, scaffold handle), on the batch's fixed-point
+path (both key widths, LDS and global-atomic accumulators) and on its FP64 fallback.  Independently of the single-table
+code the string API is also held against the oracle, and the batch against the exact sums (oracle/exact_scores.py)."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import genomeassembler_dev_amd as ga
+from genomeassembler_dev_amd import _lib, solutions, synth
+from genomeassembler_dev_amd import qtable as qt
+from oracle import exact_scores as xs
+from oracle import orc
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _strs(a):
+    return [r.tobytes().decode() for r in a]
+
+
+def _tables(prob, n=3):
+    """true, uniform, then seeded permutations of the true table's rows"""
+    rng = np.random.default_rng(2718)
+    return [prob, qt.uniform()] [:n] + [prob[rng.permutation(prob.size)] for _ in range(max(0, n - 2))]
+
+
+def _case(seed, L=1500, rl=24, cov=40, k=15, rows=60):
+    """as tests/test_solutions_gpu.py::_case, plus the paths that file adds: one nothing matches, one short piece, the truth"""
+    g = synth.make_segment(seed, L, n_short=3, short_len=60, n_long=1, long_len=150, tandem_len=60, planted=True)
+    reads = _strs(synth.simulate_reads(g, rl, cov, seed + 1))
+    m = ga.get_contigs(ga.get_kmers_from_reads(reads, k), k, 1234, matrix_rows=rows)
+    truth = g.tobytes().decode()
+    return truth, reads, m, k, ga.assemble_contigs(m, k) + ["ACGTACGTACGTTTTT", truth[:40], truth]
+
+
+_DOUBLES = ("bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len", "stat_test_KS", "path_freq")
+_INTS = ("sequence_len", "kmer_breaks", "lev_dist_vs_true", "path_prob_dist_startpos")
+
+
+def _assert_same_result(got, want, tag):
+    assert set(got) == set(want), (tag, set(got) ^ set(want))
+    for name, w in want.items():
+        g = got[name]
+        if name in _DOUBLES:
+            assert xs.same_array(g, w), (tag, name)
+        elif name in _INTS:
+            assert g.dtype == w.dtype and g.shape == w.shape and (g == w).all(), (tag, name)
+        elif name == "path_prob_dist":
+            assert len(g) == len(w) and all(xs.same_array(a, b) for a, b in zip(g, w)), (tag, name)
+        elif name == "sequence":
+            assert g is w or g == w, (tag, name)
+        else:
+            assert name == "lev_device" and g == w, (tag, name)
+
+
+# ------------------------------------------------------------------------------------------------ 1. string API, bit equality
+@pytest.mark.parametrize("variant", ["own", "velvet"])
+def test_string_api_equals_single_table_calls(qtable, variant):
+    keys, prob = qtable
+    own = variant == "own"
+    for seed in (41, 42):
+        truth, reads, m, k, paths = _case(seed)
+        tabs = _tables(prob)
+        kw = dict(variant=variant, with_lev=True, with_freq=own, with_ks=own)
+        single = [ga.calc_breakscore(paths, reads, truth, 8, keys, t, **kw) for t in tabs]
+        assert own or sum(len(x) for x in single[0]["path_prob_dist"]) > 0
+        assert int((single[0]["kmer_breaks"] == 0).sum()) >= 1 and len(paths) >= 5
+        for T in (1, 2, 3):
+            got = ga.calc_breakscore_tables(paths, reads, truth, 8, keys, tabs[:T], **kw)
+            assert len(got) == T
+            for t in range(T):
+                _assert_same_result(got[t], single[t], (seed, variant, T, t))
+            if own:
+                assert all(r["path_freq"] is got[0]["path_freq"] for r in got)      # one buffer for all tables
+        # without the optional outputs
+        got = ga.calc_breakscore_tables(paths, reads, truth, 8, keys, tabs, variant=variant, with_lev=False, with_freq=False)
+        for t in range(3):
+            _assert_same_result(got[t], ga.calc_breakscore(paths, reads, truth, 8, keys, tabs[t], variant=variant, with_lev=False, with_freq=False),
+                                (seed, variant, "plain", t))
+        # the same through the device scaffold handle
+        sc = ga.assemble_contigs(m, k, on_device=True)
+        try:
+            got = ga.calc_breakscore_tables(sc, reads, truth, 8, keys, tabs, **kw)
+            for t in range(3):
+                _assert_same_result(got[t], ga.calc_breakscore(sc, reads, truth, 8, keys, tabs[t], **kw), (seed, variant, "handle", t))
+            assert len(got[0]["bp_score"]) == len(sc) == len(paths) - 3
+        finally:
+            sc.close()
+
+
+# ------------------------------------------------------------------------------------------------ 2. string API against the oracle
+def test_string_api_against_the_oracle(qtable):
+    """independent of the single-table code: the comparisons of tests/test_solutions_gpu.py::test_solutions_table_and_csv, per table"""
+    keys, prob = qtable
+    truth, reads, _m, _k, paths = _case(51)
+    tabs = _tables(prob)
+    got = ga.calc_breakscore_tables(paths, reads, truth, 8, keys, tabs, with_lev=True, with_freq=True, with_ks=True)
+    for t, table in enumerate(tabs):
+        o = orc.calc_breakscore(paths, reads, truth, 8, keys, table, with_lev=True, with_freq=True)
+        y = orc.kmer_from_seq(truth, 8, keys, table)
+        r = got[t]
+        for name in ("kmer_breaks", "sequence_len", "lev_dist_vs_true"):
+            assert (np.asarray(r[name]) == np.asarray(o[name])).all(), (t, name)
+        for name in ("bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len"):
+            ok = xs.rel_close(r[name], o[name]) | (np.isnan(r[name]) & np.isnan(o[name]))
+            assert ok.all(), (t, name, np.asarray(r[name])[~ok], np.asarray(o[name])[~ok])
+        for i in range(len(paths)):
+            ref = orc.ks_statistic(o["path_freq"][i], y)
+            ks = r["stat_test_KS"][i]
+            assert (np.isnan(ref) and np.isnan(ks)) or abs(ks - ref) < 1e-9, (t, i, ks, ref)
+
+
+# ------------------------------------------------------------------------------------------------ 3. batch, fixed-point path
+_SCORES = ("bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len", "kmer_breaks", "sequence_len", "seg_contig_off")
+
+
+def _bits(sc):
+    return tuple(sc[n].tobytes() for n in _SCORES)
+
+
+def _seg_reads(reads, seg_off):
+    return [_strs(reads[int(seg_off[s]):int(seg_off[s + 1])]) for s in range(len(seg_off) - 1)]
+
+
+def _check_exact(b, t, segs, sample, keys, table, fixed, tag):
+    """table t of a scored batch against the exact sums, every contig of the segments in `sample`"""
+    contigs, sc = b.contigs(), b.scores(table=t)
+    if fixed:
+        fx, shift = b.score_fixed(table=t)
+        assert shift == xs.fixed_shift(table, max(len(r) for r in segs)), (tag, shift)
+    tab = dict(zip(keys, np.asarray(table, dtype=np.float64).tolist()))
+    for s in sample:
+        a, e = int(sc["seg_contig_off"][s]), int(sc["seg_contig_off"][s + 1])
+        assert e - a == len(contigs[s])
+        for i, x in enumerate(xs.score_paths(contigs[s], segs[s], tab, 8)):
+            c = a + i
+            assert int(sc["sequence_len"][c]) == x.length
+            args = (x, float(sc["bp_score"][c]), float(sc["bp_score_norm_by_break_freqs"][c]), float(sc["bp_score_norm_by_len"][c]))
+            if fixed:
+                xs.check_fixed(*args, fx[c], shift, breaks=sc["kmer_breaks"][c], tag=(tag, s, i))
+            else:
+                xs.check_fp64(*args, breaks=sc["kmer_breaks"][c], tag=(tag, s, i))
+
+
+def _assert_tables_equal_single(b, ref, k, tabs, tag, fixed=True, only=None):
+    """b holds score_tables(8, tabs): table by table the bits of score(8, table) on the second batch `ref`"""
+    for t, table in enumerate(tabs):
+        if only is not None and t not in only:
+            continue
+        ref.build(k).score(8, table)
+        assert _bits(b.scores(table=t)) == _bits(ref.scores()), (tag, t)
+        if fixed:
+            (fx, sh), (rfx, rsh) = b.score_fixed(table=t), ref.score_fixed()
+            assert sh == rsh and fx.tobytes() == rfx.tobytes(), (tag, t, sh, rsh)
+    assert _bits(b.scores()) == _bits(b.scores(table=0))
+
+
+@pytest.mark.parametrize("k", [15, 33], ids=["keys64", "keys128"])
+def test_batch_fixed_point_equals_single_table_and_exact_sums(qtable, k):
+    keys, prob = qtable
+    reads, seg_off, _ = synth.make_batch(5, 3000, 60, 15, seed0=4100 + k, planted=True)
+    segs = _seg_reads(reads, seg_off)
+    tabs = _tables(prob)
+    b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    ref = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    try:
+        b.build(k).score_tables(8, tabs)
+        _assert_tables_equal_single(b, ref, k, tabs, k)
+        shifts = [b.score_fixed(table=t)[1] for t in range(3)]
+        assert shifts[0] != shifts[1]                      # (each table has its own shift: the uniform table's largest entry is smaller)
+        for t, table in enumerate(tabs):
+            _check_exact(b, t, segs, (0, 4), keys, table, True, (k, t))
+        # two tables, and one (= gasm_batch_score)
+        b.build(k).score_tables(8, tabs[1:])
+        _assert_tables_equal_single(b, ref, k, tabs[1:], (k, "two"))
+        b.build(k).score_tables(8, tabs[2:])
+        _assert_tables_equal_single(b, ref, k, tabs[2:], (k, "one"))
+        with pytest.raises(ga.GasmError, match="GASM_ERR_INVALID"):
+            b.scores(table=1)
+    finally:
+        b.close()
+        ref.close()
+
+
+def test_batch_eight_tables_lds_and_global_atomic_accumulators(qtable, monkeypatch):
+    """T = 8: the LDS budget holds 6144 * 12 / 68 = 1084 paths of a segment.  GASM_DBG_SCORE_LDS_PATHS=2 leaves room for two,
+    so the segments with more contigs take the global-atomic branch; integer sums: the same bits either way"""
+    keys, prob = qtable
+    k = 21
+    reads, seg_off, _ = synth.make_batch(4, 9000, 60, 15, seed0=4200, planted=True)        # (planted repeats: dozens of contigs per segment)
+    segs = _seg_reads(reads, seg_off)
+    tabs = _tables(prob, 8)
+    b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    ref = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    try:
+        b.build(k).score_tables(8, tabs)
+        in_lds = [_bits(b.scores(table=t)) + (b.score_fixed(table=t)[0].tobytes(),) for t in range(8)]
+        n_contigs = [len(c) for c in b.contigs()]
+        assert max(n_contigs) > 2 and sum(n > 2 for n in n_contigs) >= 2, n_contigs      # (segments beyond the budget of two)
+        _assert_tables_equal_single(b, ref, k, tabs, "lds")
+        monkeypatch.setenv("GASM_DBG_SCORE_LDS_PATHS", "2")
+        b.build(k).score_tables(8, tabs)
+        assert [_bits(b.scores(table=t)) + (b.score_fixed(table=t)[0].tobytes(),) for t in range(8)] == in_lds
+        for t in (0, 7):
+            _check_exact(b, t, segs, (1, 2), keys, tabs[t], True, ("global", t))
+    finally:
+        b.close()
+        ref.close()
+
+
+# ------------------------------------------------------------------------------------------------ 4. batch, FP64 fallback
+def _ragged_segments(seed0, n=5, L=1500):
+    """as tests/test_score_exact_gpu.py::_ragged_segments: some reads shorter than k, some empty"""
+    rng = np.random.default_rng(seed0)
+    segs = []
+    for s in range(n):
+        g = _strs(synth.make_segment(seed0 + s, L, planted=False)[None, :])[0]
+        rs = [g[a:a + int(rng.integers(6, 60))] for a in rng.integers(0, L - 60, 300)]
+        segs.append(rs + (["", rs[0]] if s % 2 else []))
+    return segs
+
+
+def _assert_fp64(b, tabs, segs, keys, tag):
+    for t, table in enumerate(tabs):
+        _check_exact(b, t, segs, range(len(segs)), keys, table, False, (tag, t))
+        with pytest.raises(ga.GasmError, match="GASM_ERR_STATE"):
+            b.score_fixed(table=t)
+    return [_bits(b.scores(table=t)) for t in range(len(tabs))]
+
+
+def test_batch_fp64_fallback_ragged_reads(qtable):
+    keys, prob = qtable
+    segs = _ragged_segments(8300)
+    tabs = _tables(prob)
+    b = ga.SegmentBatch.from_strings(segs)
+    ref = ga.SegmentBatch.from_strings(segs)
+    try:
+        b.build(13).score_tables(8, tabs)
+        first = _assert_fp64(b, tabs, segs, keys, "ragged")
+        _assert_tables_equal_single(b, ref, 13, tabs, "ragged", fixed=False)
+        b.build(13).score_tables(8, tabs)
+        assert [_bits(b.scores(table=t)) for t in range(3)] == first
+    finally:
+        b.close()
+        ref.close()
+
+
+def test_batch_fp64_fallback_when_one_table_has_no_fixed_point(qtable):
+    """a NaN row in ONE table sends ALL tables of the call through the FP64 position scorer"""
+    keys, prob = qtable
+    reads, seg_off, _ = synth.make_batch(3, 3000, 60, 15, seed0=4300, planted=True)
+    segs = _seg_reads(reads, seg_off)
+    b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    ref = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    try:
+        b.build(21).score(8, prob)
+        sc, contigs = b.scores(), b.contigs()
+        c = int(np.argmax(sc["kmer_breaks"]))                       # a window that is hit: the NaN must reach a score
+        s = int(np.searchsorted(sc["seg_contig_off"], c, side="right")) - 1
+        contig = contigs[s][c - int(sc["seg_contig_off"][s])]
+        counts = xs.score_paths([contig], segs[s], dict(zip(keys, prob.tolist())), 8)[0].counts
+        window = next(w for w, n in counts.items() if n and len(w) == 8)
+        t_nan = prob.copy()
+        t_nan[keys.index(window)] = np.nan
+        tabs = [prob, t_nan, qt.uniform()]
+        b.build(21).score_tables(8, tabs)
+        first = _assert_fp64(b, tabs, segs, keys, "nan")
+        assert np.isnan(b.scores(table=1)["bp_score"]).any() and not np.isnan(b.scores(table=0)["bp_score"]).any()
+        # (alone, the NaN table takes the same scorer: the same bits; the finite tables alone would take the fixed-point one)
+        _assert_tables_equal_single(b, ref, 21, tabs, "nan", fixed=False, only=(1,))
+        b.build(21).score_tables(8, tabs)
+        assert [_bits(b.scores(table=t)) for t in range(3)] == first
+        # without the NaN table the same batch is back on the fixed-point path
+        b.build(21).score_tables(8, [prob, qt.uniform()])
+        assert b.score_fixed(table=1)[1] == xs.fixed_shift(qt.uniform(), max(len(r) for r in segs))
+    finally:
+        b.close()
+        ref.close()
+
+
+# ------------------------------------------------------------------------------------------------ 5. interleaving and state
+@pytest.mark.timeout(900)
+def test_step_slots_interleaving_in_child_processes():
+    """build; score_tables three times without a fetch, then fetch = one step at a time, with two and with three step slots
+    (GASM_STEP_SLOTS is fixed with a batch's first build: fresh child processes, one at a time; the first that fails ends the test)"""
+    child = os.path.join(ROOT, "tests", "score_tables_child.py")
+    base = {n: v for n, v in os.environ.items() if not n.startswith("GASM_")}
+    base["PYTHONPATH"] = ROOT + (os.pathsep + base["PYTHONPATH"] if base.get("PYTHONPATH") else "")
+    for slots in ("2", "3"):
+        try:
+            r = subprocess.run([sys.executable, child], env=dict(base, GASM_STEP_SLOTS=slots), cwd=ROOT, capture_output=True, text=True, timeout=300)
+        except subprocess.TimeoutExpired:
+            pytest.fail(f"GASM_STEP_SLOTS={slots}: the child did not finish within 300 s")
+        lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+        assert r.returncode == 0, f"GASM_STEP_SLOTS={slots}: exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-3000:]}"
+        verdict = json.loads(lines[-1])
+        assert verdict["ok"] and verdict["slots"] == slots, verdict
+
+
+def test_batch_state_guided_count_and_verify(qtable, monkeypatch):
+    keys, prob = qtable
+    k = 21
+    reads, seg_off, _ = synth.make_batch(4, 3000, 60, 15, seed0=4400, planted=True)
+    tabs = _tables(prob)
+    b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+    try:
+        b.build(k).score_tables(8, tabs)
+        want = [_bits(b.scores(table=t)) for t in range(3)]
+        guided_tables = b.guided()
+        # a plain score after score_tables: one table again
+        b.score(8, tabs[1])
+        assert _bits(b.scores()) == want[1] == _bits(b.scores(table=0))
+        for call in (lambda: b.scores(table=1), lambda: b.score_fixed(table=1)):
+            with pytest.raises(ga.GasmError, match="GASM_ERR_INVALID"):
+                call()
+        # guided() after score_tables reads table 0
+        b.build(k).score(8, tabs[0])
+        assert b.guided() == guided_tables
+        # count_read_kmers between build and score_tables changes nothing
+        b.build(k)
+        counts = b.count_read_kmers()
+        b.score_tables(8, tabs)
+        assert [_bits(b.scores(table=t)) for t in range(3)] == want
+        assert (b.count_read_kmers() == counts).all()
+        # every read compared with its contig's text where the graph puts it
+        monkeypatch.setenv("GASM_SCORE_VERIFY", "1")
+        b.build(k).score_tables(8, tabs)
+        assert [_bits(b.scores(table=t)) for t in range(3)] == want
+        monkeypatch.delenv("GASM_SCORE_VERIFY")
+        # score_tables before any build of a fresh batch
+        fresh = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=60)
+        with pytest.raises(ga.GasmError, match="GASM_ERR_STATE"):
+            fresh.score_tables(8, tabs)
+        fresh.close()
+    finally:
+        b.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6. argument errors
+def test_argument_errors_leave_no_objects(qtable):
+    keys, prob = qtable
+    truth, reads, _m, _k, paths = _case(61)
+    L = _lib.lib()
+    ctx = ga.default_context()
+    pb, po = ga.api._pack(paths)
+    rb, ro = ga.api._pack(reads)
+    kb, ko = ga.api._pack(keys)
+    tabs = np.ascontiguousarray(np.stack(_tables(prob, 3) * 3))          # nine rows
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    junk = 0x1000
+
+    def call(probs, n_tables):
+        hs = (C.c_void_p * 9)(*([junk] * 9))
+        st = L.gasm_calc_breakscore_tables(ctx.h, pb, p(po), len(paths), rb, p(ro), len(reads), truth.encode(), len(truth), 8, kb, p(ko), len(keys),
+                                           probs, n_tables, _lib.SCORE_OWN, _lib.WANT_LEV, hs)
+        return st, list(hs)
+    for n_tables in (0, 9):
+        st, hs = call(p(tabs), n_tables)
+        assert st == -1 and "n_tables" in L.gasm_last_error().decode()
+        assert hs == [None] * min(n_tables, 8) + [junk] * (9 - min(n_tables, 8))
+    st, hs = call(None, 2)
+    assert st == -1 and hs[:2] == [None, None]
+    st, hs = call(p(tabs), 8)
+    assert st == 0 and all(hs[:8]) and hs[8] == junk
+    for h in hs[:8]:
+        L.gasm_scores_free(h)
+    with pytest.raises(ValueError):
+        ga.calc_breakscore_tables(paths, reads, truth, 8, keys, prob)               # one vector is not a list of tables
+    for n in (0, 9):
+        with pytest.raises(ga.GasmError, match="GASM_ERR_INVALID"):
+            ga.calc_breakscore_tables(paths, reads, truth, 8, keys, tabs[:n])
+    b = ga.SegmentBatch.from_strings([reads])
+    try:
+        b.build(15)
+        for n in (0, 9):
+            with pytest.raises(ga.GasmError, match="GASM_ERR_INVALID"):
+                b.score_tables(8, tabs[:n])
+        assert L.gasm_batch_score_tables(b.h, 8, None, 2) == -1
+    finally:
+        b.close()
+
+
+# ------------------------------------------------------------------------------------------------ 7. solutions
+def test_score_solutions_equals_the_two_single_passes(qtable):
+    truth, reads, _m, _k, paths = _case(71, rows=200)
+    keys = qt.keys()
+    table = solutions.score_solutions(paths, reads, truth, 8)
+    t = solutions.score_solutions_one(paths, reads, truth, 8, keys, qt.load_normalised())
+    u = solutions.score_solutions_one(paths, reads, truth, 8, keys, qt.uniform())
+    want = solutions.join_true_random(t, u)
+    assert tuple(table) == tuple(want) == solutions.COLUMNS and len(table["sequence"]) == len(paths)
+    for col in want:
+        assert len(table[col]) == len(want[col]), col
+        for a, b in zip(table[col], want[col]):
+            assert (a == b) if isinstance(b, (str, int, np.integer)) else xs.same(float(a), float(b)), (col, a, b)
