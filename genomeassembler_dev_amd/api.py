@@ -232,30 +232,36 @@ def levenshtein(query, target, infix=False):
     return out.value
 
 
+def _breakscore_args(sequencing_reads, true_solution, bp_kmer, variant, with_lev, with_freq, with_ks):
+    """the argument packing calc_breakscore and calc_breakscore_tables share: (velvet, reads, their offsets, the keys, their
+    offsets, the true solution as bytes, the C variant, the flags); the arrays must outlive the C call"""
+    velvet = variant == "velvet"
+    if variant not in ("own", "velvet"):
+        raise ValueError("variant must be 'own' or 'velvet'")
+    rb, ro = _pack(sequencing_reads)
+    kb, ko = _pack(bp_kmer)
+    t = true_solution.encode() if isinstance(true_solution, str) else bytes(true_solution)
+    flags = (_lib.WANT_LEV if with_lev else 0) | (_lib.WANT_FREQ if with_freq and not velvet else 0) | (_lib.WANT_KS if with_ks else 0)
+    return velvet, rb, ro, kb, ko, t, _lib.SCORE_VELVET if velvet else _lib.SCORE_OWN, flags
+
+
 def calc_breakscore(path, sequencing_reads, true_solution, kmer, bp_kmer, bp_prob, variant="own", with_lev=True,
                     with_freq=True, with_ks=False, ctx=None):
     """Returns a dict with the names of the reference's Rcpp::List (lib/DeNovoAssembler.cpp:467-476 /
     lib/BreakageScorer.cpp:343-353).  path_freq rows follow bp_kmer order (the reference: hash order).
     with_ks adds stat_test_KS: what lib/DeNovoAssembler.R:419-424 computes from path_freq afterwards."""
     ctx = ctx or default_context()
-    velvet = variant == "velvet"
-    if variant not in ("own", "velvet"):
-        raise ValueError("variant must be 'own' or 'velvet'")
-    rb, ro = _pack(sequencing_reads)
-    kb, ko = _pack(bp_kmer)
+    velvet, rb, ro, kb, ko, t, v, flags = _breakscore_args(sequencing_reads, true_solution, bp_kmer, variant, with_lev, with_freq, with_ks)
     prob = np.ascontiguousarray(bp_prob, dtype=np.float64)
-    t = true_solution.encode() if isinstance(true_solution, str) else bytes(true_solution)
-    flags = (_lib.WANT_LEV if with_lev else 0) | (_lib.WANT_FREQ if with_freq and not velvet else 0) | (_lib.WANT_KS if with_ks else 0)
     h = C.c_void_p()
     if isinstance(path, Scaffolds):
         # the scaffolds are on the device already (assemble_contigs(..., on_device=True)): no text, no upload
         check(lib().gasm_calc_breakscore_dev(ctx.h, path.h, rb, _ptr(ro), len(sequencing_reads), t, len(t), int(kmer), kb, _ptr(ko), len(bp_kmer),
-                                             _ptr(prob), _lib.SCORE_VELVET if velvet else _lib.SCORE_OWN, flags, C.byref(h)))
+                                             _ptr(prob), v, flags, C.byref(h)))
     else:
         pb, po = _pack(path)
         check(lib().gasm_calc_breakscore(ctx.h, pb, _ptr(po), len(path), rb, _ptr(ro), len(sequencing_reads), t, len(t), int(kmer),
-                                         kb, _ptr(ko), len(bp_kmer), _ptr(prob), _lib.SCORE_VELVET if velvet else _lib.SCORE_OWN,
-                                         flags, C.byref(h)))
+                                         kb, _ptr(ko), len(bp_kmer), _ptr(prob), v, flags, C.byref(h)))
     try:
         return _scores_dict(h, path, len(bp_kmer), velvet, with_freq, with_ks)
     finally:
@@ -297,19 +303,12 @@ def calc_breakscore_tables(path, sequencing_reads, true_solution, kmer, bp_kmer,
     calc_breakscore returns for it, bit for bit; the reads are matched once (and Levenshtein, the KS test's genome side and
     path_freq computed once: the dicts share one path_freq array).  `path` may be a Scaffolds handle."""
     ctx = ctx or default_context()
-    velvet = variant == "velvet"
-    if variant not in ("own", "velvet"):
-        raise ValueError("variant must be 'own' or 'velvet'")
+    velvet, rb, ro, kb, ko, t, v, flags = _breakscore_args(sequencing_reads, true_solution, bp_kmer, variant, with_lev, with_freq, with_ks)
     probs = np.ascontiguousarray(bp_probs, dtype=np.float64)
     if probs.ndim != 2 or probs.shape[1] != len(bp_kmer):
         raise ValueError("bp_probs must hold one row of len(bp_kmer) probabilities per table")
     T = probs.shape[0]
-    rb, ro = _pack(sequencing_reads)
-    kb, ko = _pack(bp_kmer)
-    t = true_solution.encode() if isinstance(true_solution, str) else bytes(true_solution)
-    flags = (_lib.WANT_LEV if with_lev else 0) | (_lib.WANT_FREQ if with_freq and not velvet else 0) | (_lib.WANT_KS if with_ks else 0)
     hs = (C.c_void_p * max(T, 1))()
-    v = _lib.SCORE_VELVET if velvet else _lib.SCORE_OWN
     if isinstance(path, Scaffolds):
         check(lib().gasm_calc_breakscore_tables_dev(ctx.h, path.h, rb, _ptr(ro), len(sequencing_reads), t, len(t), int(kmer), kb, _ptr(ko), len(bp_kmer),
                                                     _ptr(probs), T, v, flags, hs))

@@ -58,7 +58,11 @@ struct gasm_batch {
     u32 n_segments = 0;
     u64 n_reads = 0;
     DevReads rd;
-    ScoreTable tb;
+    // the breakage tables of gasm_batch_score(_tables) (table 0: what gasm_batch_score, gasm_batch_guided and the plain
+    // fetches use) and what each was set from (empty: never); a table stays resident until another takes its place
+    ScoreTable tb[GASM_MAX_TABLES];
+    std::vector<double> table_copy[GASM_MAX_TABLES];
+    void table_ptrs(ScoreTable** tbs) { for (u32 t = 0; t < GASM_MAX_TABLES; ++t) tbs[t] = &tb[t]; }
     GuidedState guided;
     // Step slots, taken in turn (GASM_PINGPONG=0 switches it off): consecutive steps of a resident pipeline are independent
     // of each other — same reads, own graph, own scores — so step n + 1 is queued on the next slot's stream with that slot's
@@ -75,12 +79,6 @@ struct gasm_batch {
     }
     const StepSlot& S() const { return slot[cur]; }
     bool built = false;
-    std::vector<double> table_copy;
-    bool table_given = false;
-    // tables 1 .. n - 1 of gasm_batch_score_tables (table 0 is `tb`) and what they were set from (empty: never)
-    ScoreTable tbx[GASM_MAX_TABLES - 1];
-    std::vector<double> table_copy_x[GASM_MAX_TABLES - 1];
-    void table_ptrs(ScoreTable** tbs) { tbs[0] = &tb; for (int t = 1; t < GASM_MAX_TABLES; ++t) tbs[t] = &tbx[t - 1]; }
     // the last gasm_batch_score(_tables), kept to queue it again behind a build that had to be repeated
     bool scored = false;
     int score_kmer = 0;
@@ -100,10 +98,9 @@ struct gasm_batch {
 
 // the last gasm_batch_score or gasm_batch_score_tables on slot x
 static int batch_queue_score(gasm_batch* b, StepSlot& x) {
-    if (b->score_tables == 1) return pipeline_score_launch(x.cx, b->rd, x.dp, b->score_kmer, b->tb, false, false, x.ss, &x.bs);
     ScoreTable* tbs[GASM_MAX_TABLES];
     b->table_ptrs(tbs);
-    return pipeline_score_launch_tables(x.cx, b->rd, x.dp, b->score_kmer, tbs, b->score_tables, false, false, x.ss, &x.bs);
+    return pipeline_score_launch(x.cx, b->rd, x.dp, b->score_kmer, tbs, b->score_tables, false, false, x.ss, &x.bs);
 }
 
 // Read the report of the batch's queued build (repeating the build if it failed, and then the scoring queued behind it).
@@ -146,7 +143,7 @@ extern "C" {
 static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std::string(u64)>& path_text, uint64_t n_paths, const char* reads,
                            const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
                            const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
-                           bool tables_form, int variant, int flags, gasm_scores** out);
+                           int variant, int flags, gasm_scores** out);
 
 // ------------------------------------------------------------------------------------------------- get_contigs
 // reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix
@@ -357,10 +354,10 @@ static bool tables_out_clear(const char* who, gasm_scores** out, uint32_t n_tabl
     return false;
 }
 
-// gasm_calc_breakscore_dev (one table, tables_form = false) and gasm_calc_breakscore_tables_dev
+// gasm_calc_breakscore_dev (one table) and gasm_calc_breakscore_tables_dev
 static int breakscore_dev(const char* who, gasm_ctx* ctx, const gasm_scaffolds* paths, const char* reads, const uint64_t* read_off, uint64_t n_reads,
                           const char* true_solution, uint64_t true_len, int kmer, const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table,
-                          const double* bp_probs, uint32_t n_tables, bool tables_form, int variant, int flags, gasm_scores** out) {
+                          const double* bp_probs, uint32_t n_tables, int variant, int flags, gasm_scores** out) {
     if (!tables_out_clear(who, out, n_tables)) return GASM_ERR_INVALID;
     if (!ctx || !out || !paths || !read_off || !bp_off || (n_table && (!bp_kmer || !bp_probs)) || (true_len && !true_solution)) {
         gasm_set_error("%s: null argument", who);
@@ -381,7 +378,7 @@ static int breakscore_dev(const char* who, gasm_ctx* ctx, const gasm_scaffolds* 
     };
     if (st == GASM_OK)
         st = breakscore_impl(ctx, dp, path_text, paths->n, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_probs,
-                             n_tables, tables_form, variant, flags, out);
+                             n_tables, variant, flags, out);
     dp.release();
     return st;
 }
@@ -391,7 +388,7 @@ int gasm_calc_breakscore_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, const c
                              const double* bp_prob, int variant, int flags, gasm_scores** out) {
     API_GUARD_BEGIN
     return breakscore_dev("gasm_calc_breakscore_dev", ctx, paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_prob, 1,
-                          false, variant, flags, out);
+                          variant, flags, out);
     API_GUARD_END
 }
 
@@ -400,7 +397,7 @@ int gasm_calc_breakscore_tables_dev(gasm_ctx* ctx, const gasm_scaffolds* paths, 
                                     const double* bp_probs, uint32_t n_tables, int variant, int flags, gasm_scores** out) {
     API_GUARD_BEGIN
     return breakscore_dev("gasm_calc_breakscore_tables_dev", ctx, paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off, n_table,
-                          bp_probs, n_tables, true, variant, flags, out);
+                          bp_probs, n_tables, variant, flags, out);
     API_GUARD_END
 }
 
@@ -421,13 +418,13 @@ int gasm_levenshtein(const char* query, uint64_t nq, const char* target, uint64_
 // calc_breakscore proper.  `dp` holds the paths on the device (uploaded text or the scaffolds of a device-side
 // assemble_contigs); path_text(p) hands out path p as text for the few host-side steps that want it (the velvet variant's
 // startpos find, the host Levenshtein routine for a target outside ACGT).
-// bp_probs holds n_tables rows of n_table probabilities.  tables_form = false (one table): the single-table launch sequence of
-// gasm_calc_breakscore; true: the match once and the sums per table (pipeline_score_launch_tables), out[0 .. n_tables).
+// bp_probs holds n_tables rows of n_table probabilities: the match once and the sums per table (pipeline_score_launch),
+// out[0 .. n_tables); gasm_calc_breakscore is n_tables = 1.
 // Everything below that does not read a probability runs once and is copied (or, for path_freq, shared) between the results.
 static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std::string(u64)>& path_text, uint64_t n_paths, const char* reads,
                            const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
                            const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
-                           bool tables_form, int variant, int flags, gasm_scores** out) {
+                           int variant, int flags, gasm_scores** out) {
     const bool velvet = variant == GASM_SCORE_VELVET;
     const u32 T = n_tables;
     DevReads rd;
@@ -440,9 +437,7 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
     int st = rd.upload(ctx, reads ? reads : &empty, read_off, n_reads, 0, seg_off, 1);
     for (u32 t = 0; t < T && st == GASM_OK; ++t) st = tb[t].set(ctx, bp_kmer, bp_off, n_table, bp_probs + (size_t)t * n_table);
     const bool want_freq = !velvet && (flags & GASM_WANT_FREQ);
-    if (st == GASM_OK)
-        st = tables_form ? pipeline_score_launch_tables(ctx, rd, dp, kmer, tbs, T, want_freq, velvet, ss, nullptr)
-                         : pipeline_score_launch(ctx, rd, dp, kmer, tb[0], want_freq, velvet, ss, nullptr);
+    if (st == GASM_OK) st = pipeline_score_launch(ctx, rd, dp, kmer, tbs, T, want_freq, velvet, ss, nullptr);
     if (st == GASM_OK) st = pipeline_score_fetch(ctx, ss);
     std::vector<gasm_scores*> res(T, nullptr);
     gasm_scores* s = nullptr;               // table 0's result: what is computed once lands here first
@@ -540,11 +535,11 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
     return GASM_OK;
 }
 
-// gasm_calc_breakscore (one table, tables_form = false) and gasm_calc_breakscore_tables
+// gasm_calc_breakscore (one table) and gasm_calc_breakscore_tables
 static int breakscore_strings(const char* who, gasm_ctx* ctx, const char* paths, const uint64_t* path_off, uint64_t n_paths, const char* reads,
                               const uint64_t* read_off, uint64_t n_reads, const char* true_solution, uint64_t true_len, int kmer,
                               const char* bp_kmer, const uint64_t* bp_off, uint64_t n_table, const double* bp_probs, uint32_t n_tables,
-                              bool tables_form, int variant, int flags, gasm_scores** out) {
+                              int variant, int flags, gasm_scores** out) {
     if (!tables_out_clear(who, out, n_tables)) return GASM_ERR_INVALID;
     if (!ctx || !out || !path_off || !read_off || !bp_off || (n_table && (!bp_kmer || !bp_probs)) || (true_len && !true_solution)) {
         gasm_set_error("%s: null argument", who);
@@ -557,7 +552,7 @@ static int breakscore_strings(const char* who, gasm_ctx* ctx, const char* paths,
     int st = dp.upload_ascii(ctx, paths ? paths : &empty, path_off, (u32)n_paths);
     if (st == GASM_OK)
         st = breakscore_impl(ctx, dp, [&](u64 p) { return std::string(paths + path_off[p], paths + path_off[p + 1]); }, n_paths, reads, read_off, n_reads,
-                             true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_probs, n_tables, tables_form, variant, flags, out);
+                             true_solution, true_len, kmer, bp_kmer, bp_off, n_table, bp_probs, n_tables, variant, flags, out);
     dp.release();
     return st;
 }
@@ -568,7 +563,7 @@ int gasm_calc_breakscore(gasm_ctx* ctx, const char* paths, const uint64_t* path_
                          int flags, gasm_scores** out) {
     API_GUARD_BEGIN
     return breakscore_strings("gasm_calc_breakscore", ctx, paths, path_off, n_paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer, bp_off,
-                              n_table, bp_prob, 1, false, variant, flags, out);
+                              n_table, bp_prob, 1, variant, flags, out);
     API_GUARD_END
 }
 
@@ -578,7 +573,7 @@ int gasm_calc_breakscore_tables(gasm_ctx* ctx, const char* paths, const uint64_t
                                 int variant, int flags, gasm_scores** out) {
     API_GUARD_BEGIN
     return breakscore_strings("gasm_calc_breakscore_tables", ctx, paths, path_off, n_paths, reads, read_off, n_reads, true_solution, true_len, kmer, bp_kmer,
-                              bp_off, n_table, bp_probs, n_tables, true, variant, flags, out);
+                              bp_off, n_table, bp_probs, n_tables, variant, flags, out);
     API_GUARD_END
 }
 
@@ -764,8 +759,8 @@ void gasm_batch_free(gasm_batch* b) {
     (void)hipSetDevice(b->ctx->device);
     (void)hipStreamSynchronize(b->ctx->stream);
     for (StepSlot& x : b->slot) { if (x.cx && x.cx != b->ctx) (void)hipStreamSynchronize(x.cx->stream); x.bs.release(); x.dp.release(); x.ss.release(); }
-    b->rd.release(); b->tb.release(); b->guided.release(); b->d_rkc.release();
-    for (ScoreTable& t : b->tbx) t.release();
+    b->rd.release(); b->guided.release(); b->d_rkc.release();
+    for (ScoreTable& t : b->tb) t.release();
     delete b;
 }
 
@@ -792,48 +787,17 @@ int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint) {
     API_GUARD_END
 }
 
-int gasm_batch_score(gasm_batch* b, int kmer, const double* table) {
-    API_GUARD_BEGIN
-    if (!b || !table) { gasm_set_error("gasm_batch_score: null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_score before gasm_batch_build"); return GASM_ERR_STATE; }
-    if (!b->table_given || memcmp(b->table_copy.data(), table, GASM_TABLE_ROWS * sizeof(double)) != 0) {
-        for (StepSlot& x : b->slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));      // (whatever still scores with the old table)
-        GCHK(b->tb.set_standard(b->ctx, table));
-        b->table_copy.assign(table, table + GASM_TABLE_ROWS);
-        b->table_given = true;
-    }
-    // reads shorter than k (or none): the general scorer, which sizes its tables on the host — after the build's report
-    const bool through_graph = pipeline_score_uses_graph(b->rd, b->S().bs, b->tb);
-    if (!through_graph) GCHK(batch_finish(b));
-    // on the stream of the build's slot, behind the build (its queue, not its completion: stream order does the rest)
-    StepSlot& x = b->S();
-    if (!x.paths_ready) {
-        GCHK(pipeline_contig_paths(x.cx, b->rd, x.bs, x.dp));
-        x.paths_ready = true;
-    }
-    if (!through_graph) pipeline_contig_paths_host(b->rd, x.bs, x.dp);
-    GCHK(pipeline_score_launch(x.cx, b->rd, x.dp, kmer, b->tb, false, false, x.ss, &x.bs));
-    b->scored = true;
-    b->score_kmer = kmer;
-    b->score_tables = 1;
-    return GASM_OK;
-    API_GUARD_END
-}
-
-// the same step with n_tables tables over one match (table 0 lives where gasm_batch_score keeps its table: what
-// gasm_batch_guided and the plain fetches read)
-int gasm_batch_score_tables(gasm_batch* b, int kmer, const double* tables, uint32_t n_tables) {
-    API_GUARD_BEGIN
-    if (!b || !tables) { gasm_set_error("gasm_batch_score_tables: null argument"); return GASM_ERR_INVALID; }
-    if (n_tables < 1 || n_tables > GASM_MAX_TABLES) { gasm_set_error("gasm_batch_score_tables: n_tables must be 1..%d (got %u)", GASM_MAX_TABLES, n_tables); return GASM_ERR_INVALID; }
-    if (n_tables == 1) return gasm_batch_score(b, kmer, tables);
-    if (!b->built) { gasm_set_error("gasm_batch_score_tables before gasm_batch_build"); return GASM_ERR_STATE; }
+// gasm_batch_score (n_tables = 1) and gasm_batch_score_tables: the step's scoring under n_tables tables over one match
+static int batch_score(gasm_batch* b, const char* who, int kmer, const double* tables, uint32_t n_tables) {
+    if (!b || !tables) { gasm_set_error("%s: null argument", who); return GASM_ERR_INVALID; }
+    if (n_tables < 1 || n_tables > GASM_MAX_TABLES) { gasm_set_error("%s: n_tables must be 1..%d (got %u)", who, GASM_MAX_TABLES, n_tables); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("%s before gasm_batch_build", who); return GASM_ERR_STATE; }
     ScoreTable* tbs[GASM_MAX_TABLES];
     b->table_ptrs(tbs);
     bool same[GASM_MAX_TABLES], all_same = true;
     for (u32 t = 0; t < n_tables; ++t) {
-        const std::vector<double>& have = t ? b->table_copy_x[t - 1] : b->table_copy;
-        same[t] = (t ? !have.empty() : b->table_given) && memcmp(have.data(), tables + (size_t)t * GASM_TABLE_ROWS, GASM_TABLE_ROWS * sizeof(double)) == 0;
+        const std::vector<double>& have = b->table_copy[t];
+        same[t] = !have.empty() && memcmp(have.data(), tables + (size_t)t * GASM_TABLE_ROWS, GASM_TABLE_ROWS * sizeof(double)) == 0;
         all_same = all_same && same[t];
     }
     if (!all_same) {
@@ -842,25 +806,36 @@ int gasm_batch_score_tables(gasm_batch* b, int kmer, const double* tables, uint3
             if (same[t]) continue;
             const double* src = tables + (size_t)t * GASM_TABLE_ROWS;
             GCHK(tbs[t]->set_standard(b->ctx, src));
-            (t ? b->table_copy_x[t - 1] : b->table_copy).assign(src, src + GASM_TABLE_ROWS);
-            if (t == 0) b->table_given = true;
+            b->table_copy[t].assign(src, src + GASM_TABLE_ROWS);
         }
     }
     // reads shorter than k (or none), or a table without a fixed-point shift: every table through the general scorer, which
     // sizes its arrays on the host — after the build's report
-    const bool through_graph = pipeline_score_tables_use_graph(b->rd, b->S().bs, tbs, n_tables);
+    const bool through_graph = pipeline_score_uses_graph(b->rd, b->S().bs, tbs, n_tables);
     if (!through_graph) GCHK(batch_finish(b));
+    // on the stream of the build's slot, behind the build (its queue, not its completion: stream order does the rest)
     StepSlot& x = b->S();
     if (!x.paths_ready) {
         GCHK(pipeline_contig_paths(x.cx, b->rd, x.bs, x.dp));
         x.paths_ready = true;
     }
     if (!through_graph) pipeline_contig_paths_host(b->rd, x.bs, x.dp);
-    GCHK(pipeline_score_launch_tables(x.cx, b->rd, x.dp, kmer, tbs, n_tables, false, false, x.ss, &x.bs));
+    GCHK(pipeline_score_launch(x.cx, b->rd, x.dp, kmer, tbs, n_tables, false, false, x.ss, &x.bs));
     b->scored = true;
     b->score_kmer = kmer;
     b->score_tables = n_tables;
     return GASM_OK;
+}
+
+int gasm_batch_score(gasm_batch* b, int kmer, const double* table) {
+    API_GUARD_BEGIN
+    return batch_score(b, "gasm_batch_score", kmer, table, 1);
+    API_GUARD_END
+}
+
+int gasm_batch_score_tables(gasm_batch* b, int kmer, const double* tables, uint32_t n_tables) {
+    API_GUARD_BEGIN
+    return batch_score(b, "gasm_batch_score_tables", kmer, tables, n_tables);
     API_GUARD_END
 }
 
@@ -872,7 +847,7 @@ int gasm_batch_guided(gasm_batch* b) {
     GCHK(batch_finish(b));
     StepSlot& x = b->S();
     GCHK(pipeline_score_fetch(x.cx, x.ss));
-    return guided_build(x.cx, b->rd, x.bs, x.dp, x.ss, b->tb, b->score_kmer, b->guided);
+    return guided_build(x.cx, b->rd, x.bs, x.dp, x.ss, b->tb[0], b->score_kmer, b->guided);
     API_GUARD_END
 }
 
@@ -909,7 +884,7 @@ static int batch_fetch_fixed(gasm_batch* b, uint32_t t, const int64_t** fx, int*
     if (P) HIPCHK(hipMemcpyAsync(b->h_fx.data(), static_cast<const char*>(x.ss.d_total.p) + fx_off + (size_t)t * x.ss.stride * 8, (size_t)P * 8, hipMemcpyDeviceToHost, x.cx->stream));
     HIPCHK(hipStreamSynchronize(x.cx->stream));
     *fx = b->h_fx.data();
-    *shift = (t ? b->tbx[t - 1] : b->tb).fix_shift;
+    *shift = b->tb[t].fix_shift;
     return GASM_OK;
 }
 

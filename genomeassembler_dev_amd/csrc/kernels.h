@@ -175,18 +175,25 @@ __global__ void k_read_insert(ReadSet rs, SeedTable st, int w);
 __global__ void k_path_scan(ReadSet rs, PathSet ps, SeedTable st, const u64* seg_base_off, int w, const u64* first_off, u32* first, u32 seg0,
                             u32 path_lo, u32 path_hi);
 __global__ void k_first_to_poscnt(const u32* first, u64 n, u32* poscnt);
-template <class K>
-__global__ void k_score_reads_graph(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, PathSet ps, const long long* dfix,
-                                    int kmer, u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* cnt, unsigned long long* sum, int verify, u32* verify_flag);
+// the scorers take T = 1 .. GASM_SCORE_MAX_TABLES breakage tables over one match (one table: T = 1)
+#define GASM_SCORE_MAX_TABLES 8    // = GASM_MAX_TABLES of include/gasm.h (checked in pipeline.hip)
+struct FixTables { const long long* p[GASM_SCORE_MAX_TABLES]; };     // direct-address fixed-point tables (ScoreTable::d_fix)
+struct ProbTables { const double* p[GASM_SCORE_MAX_TABLES]; };       // direct-address probability tables (ScoreTable::d_prob)
+// sums of table t at sum + t * sum_stride; LDS: T * lds_paths u64 + lds_paths u32
+template <class K, int T>
+__global__ void k_score_reads_graph(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, PathSet ps, FixTables dfix, int kmer,
+                                    u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* cnt, unsigned long long* sum, u64 sum_stride, int verify,
+                                    u32* verify_flag);
 __global__ void k_levenshtein(PathSet ps, u32 n_paths, const u64* twords, u32 nt, int infix, u8* carry_ws, u64 carry_stride, int32_t* out);
 __global__ void k_levenshtein2(PathSet ps, u32 n_paths, const u64* twords, u32 nt, int infix, uint4* carry_ws, u64 carry_stride, int32_t* out);
-__global__ void k_score_zero(u32* cnt, unsigned long long* sum, const u32* n_paths_p);
+__global__ void k_score_zero(u32* cnt, unsigned long long* sum, u64 sum_stride, u32 n_tables, const u32* n_paths_p);
 __global__ void k_score_finish(PathSet ps, const u32* cnt, const unsigned long long* sum, const long long* dfix, const u64* seg_empty,
                                int kmer, double inv_scale, double* bp_score, double* norm_freq, double* norm_len, int32_t* kmer_breaks,
                                int32_t* seq_len, const u32* n_paths_p);
-__global__ void k_path_reduce(PathSet ps, const u32* poscnt, const u32* extra, const double* dprob, int kmer,
-                              double* bp_score, double* norm_freq, double* norm_len, int32_t* kmer_breaks,
-                              int32_t* seq_len, u32 n_paths);
+// outputs of table t at bp_score / norm_freq / norm_len + t * out_stride; kmer_breaks and seq_len once
+template <int T>
+__global__ void k_path_reduce(PathSet ps, const u32* poscnt, const u32* extra, ProbTables dprob, int kmer, double* bp_score, double* norm_freq,
+                              double* norm_len, u64 out_stride, int32_t* kmer_breaks, int32_t* seq_len, u32 n_paths);
 __global__ void k_path_freq(PathSet ps, const u32* poscnt, const u32* total, const int32_t* drow, int kmer, u32 n_table,
                             u32* freq_cnt, u32 n_paths);
 __global__ void k_ks_genome_hist(const u64* gwords, u64 glen, int kmer, const int32_t* drow, u32* hist);
@@ -197,20 +204,6 @@ __global__ void k_path_ks2(PathSet ps, const u32* poscnt, const int32_t* drow, i
 __global__ void k_cover_mark(const long long* start, const long long* len, u64 n, long long seq_len, int* diff);
 __global__ void k_cover_count(const int* diff, long long seq_len, unsigned long long* covered);
 __global__ void k_prob_dist(PathSet ps, const double* dprob, int kmer, const u64* pd_off, double* out, u32 n_paths);
-// ---- several breakage tables over one match (gasm_calc_breakscore_tables, gasm_batch_score_tables): T = 1 .. GASM_SCORE_MAX_TABLES
-#define GASM_SCORE_MAX_TABLES 8    // = GASM_MAX_TABLES of include/gasm.h (checked in pipeline.hip)
-struct FixTables { const long long* p[GASM_SCORE_MAX_TABLES]; };     // direct-address fixed-point tables (ScoreTable::d_fix)
-struct ProbTables { const double* p[GASM_SCORE_MAX_TABLES]; };       // direct-address probability tables (ScoreTable::d_prob)
-// sums of table t at sum + t * sum_stride; LDS: T * lds_paths u64 + lds_paths u32
-template <class K, int T>
-__global__ void k_score_reads_graph_tables(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, PathSet ps, FixTables dfix, int kmer,
-                                           u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* cnt, unsigned long long* sum, u64 sum_stride, int verify,
-                                           u32* verify_flag);
-__global__ void k_score_zero_tables(u32* cnt, unsigned long long* sum, u64 sum_stride, u32 n_tables, const u32* n_paths_p);
-// outputs of table t at bp_score / norm_freq / norm_len + t * out_stride; kmer_breaks and seq_len once
-template <int T>
-__global__ void k_path_reduce_tables(PathSet ps, const u32* poscnt, const u32* extra, ProbTables dprob, int kmer, double* bp_score, double* norm_freq,
-                                     double* norm_len, u64 out_stride, int32_t* kmer_breaks, int32_t* seq_len, u32 n_paths);
 
 // ---- kernels_pool.hip: exchange plans (exchange.hip)
 __global__ void k_x_flag_word(const u32* flags, u32* row_tail);

@@ -8,6 +8,8 @@
 //                  looks its window up, compares in full and keeps the first occurrence per (path, read); the first
 //                  occurrences become the position counters (lib/DeNovoAssembler.cpp:346-392: first find() per path)
 //   k_path_reduce  per path: sum over positions of count x prob(window(position)) in a fixed order (:394-426)
+// Both scorers (k_path_reduce, and k_score_reads_graph for a build's own contigs) take the number of breakage tables T as
+// a template parameter: the reads are matched once and the sums kept per table; one table is T = 1 of the same kernels.
 // Reads are not de-duplicated first: the reference does that (:334-337) only to save work, a read occurring c times
 // adds c to the same counter either way.
 // Counting per *position* instead of per table row makes the sums integer-exact up to the final FP64 reduction,
@@ -182,23 +184,29 @@ __device__ __forceinline__ u64 graph_match(const ReadSet& rs, const GraphView& g
     return g;
 }
 
-// Batch scoring without position counters.  bp_score of a path = sum over the reads that occur in it of
-// prob(window(hit position)) (lib/DeNovoAssembler.cpp:389-413 sums count x prob per table row: the same terms grouped
-// differently).  Each read adds 1 to its path's count and round(prob * 2^fx_shift) to its path's 64-bit fixed-point sum:
-// integer additions commute, so the result does not depend on the order the reads arrive in (bit-reproducible without a
-// fixed reduction tree).  A workgroup keeps the accumulators of its segment's paths in LDS (ds_add_u32 / ds_add_u64) and
-// flushes the non-zero ones with global atomics at the end; segments with more paths than fit go to global atomics
-// directly.  A workgroup = one slice of one segment's reads (seg_chunk, device_utils.h).
-template <class K>
+// Batch scoring without position counters, under T = 1 .. GASM_SCORE_MAX_TABLES breakage tables over ONE match
+// (gasm_batch_score is T = 1; gasm_batch_score_tables: the reference scores the same paths against the same reads under
+// the true and under the uniform table, lib/DeNovoAssembler.R:325-355).  bp_score of a path = sum over the reads that
+// occur in it of prob(window(hit position)) (lib/DeNovoAssembler.cpp:389-413 sums count x prob per table row: the same
+// terms grouped differently).  Where a read lies does not depend on the table, only the last step does: one graph_match
+// and one break_window per read, then T gathers (independent of each other: in flight together).  Each read adds 1 to
+// its path's count and round(prob * 2^fx_shift) to its path's 64-bit fixed-point sum of every table: integer additions
+// commute, so the result does not depend on the order the reads arrive in, nor on the branch taken (bit-reproducible
+// without a fixed reduction tree), and table t's numbers are bit for bit those of a T = 1 launch with table t.
+// Accumulators per path: one u32 count and T u64 sums (table t's at sum + t * sum_stride).  A workgroup keeps those of
+// its segment's paths in LDS ([t][path], then the counts; ds_add_u32 / ds_add_u64) when they fit into `lds_paths` and
+// flushes the non-zero ones with global atomics at the end; segments with more paths go to global atomics directly.
+// `lds_paths` is sized by the launch — a fixed 72 KB would leave two workgroups per CU, and this kernel is a chain of
+// dependent gathers that lives on occupancy —, with lds_paths * (4 + 8 T) at most GASM_SCORE_PATH_CAP * 12 bytes whatever
+// T is.  A workgroup = one slice of one segment's reads (seg_chunk, device_utils.h).
+template <class K, int T>
 __global__ void __launch_bounds__(GASM_WG) k_score_reads_graph(ReadSet rs, GraphView gv, const u64* __restrict__ link,
-                                                               const u32* __restrict__ e_cid, PathSet ps,
-                                                               const long long* __restrict__ dfix, int kmer, u32 reads_per_wg, u32 chunks,
-                                                               u32 lds_paths, u32* __restrict__ cnt, unsigned long long* __restrict__ sum, int verify,
+                                                               const u32* __restrict__ e_cid, PathSet ps, FixTables dfix, int kmer,
+                                                               u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* __restrict__ cnt,
+                                                               unsigned long long* __restrict__ sum, u64 sum_stride, int verify,
                                                                u32* __restrict__ verify_flag) {
-    // accumulators of the segment's paths: `lds_paths` (<= GASM_SCORE_PATH_CAP) of each, sized by the launch — a fixed
-    // 72 KB would leave two workgroups per CU, and this kernel is a chain of dependent gathers that lives on occupancy
     extern __shared__ unsigned long long s_sum[];
-    u32* s_cnt = reinterpret_cast<u32*>(s_sum + lds_paths);
+    u32* s_cnt = reinterpret_cast<u32*>(s_sum + (size_t)T * lds_paths);
     u32 seg, chunk;
     if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;      // a segment's graph and contigs stay in one XCD's L2
     const u64 r0 = rs.seg_read_off[seg] + (u64)chunk * reads_per_wg;
@@ -207,7 +215,11 @@ __global__ void __launch_bounds__(GASM_WG) k_score_reads_graph(ReadSet rs, Graph
     const u64 r1 = r0 + reads_per_wg < rseg_end ? r0 + reads_per_wg : rseg_end;
     const u32 pfirst = ps.seg_path_off[seg], np = ps.seg_path_off[seg + 1] - pfirst;
     const bool in_lds = np <= lds_paths;
-    if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) { s_sum[i] = 0; s_cnt[i] = 0; }
+    if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) s_sum[(size_t)t * lds_paths + i] = 0;
+        s_cnt[i] = 0;
+    }
     __syncthreads();
     for (u64 r = r0 + threadIdx.x; r < r1; r += GASM_WG) {
         u32 c = 0;
@@ -215,29 +227,50 @@ __global__ void __launch_bounds__(GASM_WG) k_score_reads_graph(ReadSet rs, Graph
         const u64 g = graph_match<K>(rs, gv, link, e_cid, ps, seg, r, &c, &pb, &pe, verify, verify_flag);
         if (g == ~0ull) continue;
         const u32 plen = (u32)(pe - pb);
-        u32 idx;
-        long long fx = 0;
-        if (break_window(ps.words, pb, plen, (u32)(g - pb), kmer, &idx)) fx = dfix[idx];
-        if (in_lds) { atomicAdd(&s_cnt[c - pfirst], 1u); atomicAdd(&s_sum[c - pfirst], (unsigned long long)fx); }
-        else { atomicAdd(&cnt[c], 1u); atomicAdd(&sum[c], (unsigned long long)fx); }
+        u32 idx = 0;
+        const bool hit = break_window(ps.words, pb, plen, (u32)(g - pb), kmer, &idx);
+        long long fx[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) fx[t] = hit ? dfix.p[t][idx] : 0;
+        if (in_lds) {
+            atomicAdd(&s_cnt[c - pfirst], 1u);
+#pragma unroll
+            for (int t = 0; t < T; ++t) atomicAdd(&s_sum[(size_t)t * lds_paths + (c - pfirst)], (unsigned long long)fx[t]);
+        } else {
+            atomicAdd(&cnt[c], 1u);
+#pragma unroll
+            for (int t = 0; t < T; ++t) atomicAdd(&sum[(u64)t * sum_stride + c], (unsigned long long)fx[t]);
+        }
     }
     __syncthreads();
     if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) {
         const u32 c = s_cnt[i];
-        if (c) { atomicAdd(&cnt[pfirst + i], c); atomicAdd(&sum[pfirst + i], s_sum[i]); }
+        if (c) {
+            atomicAdd(&cnt[pfirst + i], c);
+#pragma unroll
+            for (int t = 0; t < T; ++t) atomicAdd(&sum[(u64)t * sum_stride + pfirst + i], s_sum[(size_t)t * lds_paths + i]);
+        }
     }
 }
 
-template __global__ void k_score_reads_graph<u64>(ReadSet, GraphView, const u64*, const u32*, PathSet, const long long*, int, u32, u32, u32, u32*,
-                                                  unsigned long long*, int, u32*);
-template __global__ void k_score_reads_graph<K128>(ReadSet, GraphView, const u64*, const u32*, PathSet, const long long*, int, u32, u32, u32, u32*,
-                                                   unsigned long long*, int, u32*);
+#define GASM_INST_SCORE(K, T)                                                                                                         \
+    template __global__ void k_score_reads_graph<K, T>(ReadSet, GraphView, const u64*, const u32*, PathSet, FixTables, int, u32, u32, u32, u32*, \
+                                                       unsigned long long*, u64, int, u32*);
+#define GASM_INST_SCORE_K(K)                                                                                                           \
+    GASM_INST_SCORE(K, 1) GASM_INST_SCORE(K, 2) GASM_INST_SCORE(K, 3) GASM_INST_SCORE(K, 4) GASM_INST_SCORE(K, 5) GASM_INST_SCORE(K, 6) \
+    GASM_INST_SCORE(K, 7) GASM_INST_SCORE(K, 8)
+GASM_INST_SCORE_K(u64)
+GASM_INST_SCORE_K(K128)
 
-// The batch scorer's accumulators, cleared for the paths there are (*n_paths_p lives on the device: the contigs of a build
-// the host has not waited for; a memset would have to cover the upper bound).
-__global__ void __launch_bounds__(GASM_WG) k_score_zero(u32* __restrict__ cnt, unsigned long long* __restrict__ sum, const u32* __restrict__ n_paths_p) {
+// The batch scorer's accumulators (one count and n_tables sums per path), cleared for the paths there are (*n_paths_p
+// lives on the device: the contigs of a build the host has not waited for; a memset would have to cover the upper bound).
+__global__ void __launch_bounds__(GASM_WG) k_score_zero(u32* __restrict__ cnt, unsigned long long* __restrict__ sum, u64 sum_stride, u32 n_tables,
+                                                        const u32* __restrict__ n_paths_p) {
     const u32 n = *n_paths_p;
-    for (u32 p = blockIdx.x * GASM_WG + threadIdx.x; p < n; p += gridDim.x * GASM_WG) { cnt[p] = 0; sum[p] = 0; }
+    for (u32 p = blockIdx.x * GASM_WG + threadIdx.x; p < n; p += gridDim.x * GASM_WG) {
+        cnt[p] = 0;
+        for (u32 t = 0; t < n_tables; ++t) sum[(u64)t * sum_stride + p] = 0;
+    }
 }
 
 // Fixed-point sums -> the reference's per-path numbers.  `seg_empty`: empty reads of the path's segment, each a hit at
@@ -284,16 +317,21 @@ __device__ __forceinline__ double wave_sum_fixed(double v) {
     return v;
 }
 
-// One workgroup per path.  First the integer total of the path's position counters (= kmer_breaks; `extra` holds what
-// empty reads add to empty paths), then thread t sums positions t, t+256, ... in order, the 64 partials of a wave are
-// combined by a fixed butterfly and the four wave sums are added in wave order: a fixed summation order, so scores are
-// bit-reproducible.
-__global__ void __launch_bounds__(GASM_WG) k_path_reduce(PathSet ps, const u32* __restrict__ poscnt, const u32* __restrict__ extra,
-                                                         const double* __restrict__ dprob, int kmer, double* __restrict__ bp_score,
-                                                         double* __restrict__ norm_freq, double* __restrict__ norm_len,
-                                                         int32_t* __restrict__ kmer_breaks, int32_t* __restrict__ seq_len, u32 n_paths) {
+// One workgroup per path, T = 1 .. GASM_SCORE_MAX_TABLES tables (outputs of table t at bp_score / norm_freq / norm_len +
+// t * out_stride).  First the integer total of the path's position counters (= kmer_breaks; `extra` holds what empty
+// reads add to empty paths).  The position counters and the window index are read once and T probabilities gathered per
+// hit position; per table, thread i sums positions i, i + 256, ... in order with one fused multiply-add per term — fma()
+// written out, so that it does not hang on the compiler contracting `s += pr * c` alike in every instantiation —, the 64
+// partials of a wave are combined by a fixed butterfly and the four wave sums are added in wave order: a fixed summation
+// order, so scores are bit-reproducible and table t's are those of a T = 1 launch with table t.
+// ISA (gfx950): 2 T v_fmac_f64 in the loop, 32 + 6 T VGPRs (32 at T = 1, 68 at T = 8), no scratch.
+template <int T>
+__global__ void __launch_bounds__(GASM_WG) k_path_reduce(PathSet ps, const u32* __restrict__ poscnt, const u32* __restrict__ extra, ProbTables dprob,
+                                                         int kmer, double* __restrict__ bp_score, double* __restrict__ norm_freq,
+                                                         double* __restrict__ norm_len, u64 out_stride, int32_t* __restrict__ kmer_breaks,
+                                                         int32_t* __restrict__ seq_len, u32 n_paths) {
     __shared__ u32 s_t[4];
-    __shared__ double s_a[4], s_b[4];
+    __shared__ double s_a[T][4], s_b[T][4];
     const u32 p = blockIdx.x;
     if (p >= n_paths) return;
     const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -306,32 +344,47 @@ __global__ void __launch_bounds__(GASM_WG) k_path_reduce(PathSet ps, const u32* 
     __syncthreads();
     const u32 tot = s_t[0] + s_t[1] + s_t[2] + s_t[3] + extra[p];
     const double dtot = (double)tot;
-    double s1 = 0.0, s2 = 0.0;
+    double s1[T], s2[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) { s1[t] = 0.0; s2[t] = 0.0; }
     for (u32 j = threadIdx.x; j < len; j += GASM_WG) {
         const u32 c = poscnt[pb + j];
         if (c) {
             u32 idx;
             if (break_window(ps.words, pb, len, j, kmer, &idx)) {
-                const double pr = dprob[idx];
-                s1 += pr * (double)c;
-                s2 += pr * ((double)c / dtot);
+                const double dc = (double)c, q = (double)c / dtot;
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const double pr = dprob.p[t][idx];
+                    s1[t] = fma(pr, dc, s1[t]);
+                    s2[t] = fma(pr, q, s2[t]);
+                }
             }
         }
     }
-    s1 = wave_sum_fixed(s1);
-    s2 = wave_sum_fixed(s2);
-    if (lane == 0) { s_a[wv] = s1; s_b[wv] = s2; }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const double a = wave_sum_fixed(s1[t]), b = wave_sum_fixed(s2[t]);
+        if (lane == 0) { s_a[t][wv] = a; s_b[t][wv] = b; }
+    }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const double a = ((s_a[0] + s_a[1]) + s_a[2]) + s_a[3];
-        const double b = ((s_b[0] + s_b[1]) + s_b[2]) + s_b[3];
-        bp_score[p] = a;
-        norm_freq[p] = b;
-        norm_len[p] = a / (double)(int32_t)len;
-        kmer_breaks[p] = (int32_t)tot;
-        seq_len[p] = (int32_t)len;
+    if (threadIdx.x < (u32)T) {
+        const u32 t = threadIdx.x;
+        const double a = ((s_a[t][0] + s_a[t][1]) + s_a[t][2]) + s_a[t][3];
+        const double b = ((s_b[t][0] + s_b[t][1]) + s_b[t][2]) + s_b[t][3];
+        bp_score[(u64)t * out_stride + p] = a;
+        norm_freq[(u64)t * out_stride + p] = b;
+        norm_len[(u64)t * out_stride + p] = a / (double)(int32_t)len;
+        if (t == 0) {
+            kmer_breaks[p] = (int32_t)tot;
+            seq_len[p] = (int32_t)len;
+        }
     }
 }
+
+#define GASM_INST_REDUCE(T)                                                                                                                 \
+    template __global__ void k_path_reduce<T>(PathSet, const u32*, const u32*, ProbTables, int, double*, double*, double*, u64, int32_t*, int32_t*, u32);
+GASM_INST_REDUCE(1) GASM_INST_REDUCE(2) GASM_INST_REDUCE(3) GASM_INST_REDUCE(4) GASM_INST_REDUCE(5) GASM_INST_REDUCE(6) GASM_INST_REDUCE(7) GASM_INST_REDUCE(8)
 
 // Dense per-row break counts (for the reference's path_freq output): freq_cnt[p * n_table + row] += count.
 __global__ void __launch_bounds__(GASM_WG) k_path_freq(PathSet ps, const u32* __restrict__ poscnt, const u32* __restrict__ total,
@@ -1010,158 +1063,3 @@ __global__ void __launch_bounds__(1024) k_cover_count(const int* __restrict__ di
     __syncthreads();
     if (threadIdx.x == 0) { unsigned long long t = 0; for (u32 w = 0; w < 16; ++w) t += s_c[w]; *covered = t; }
 }
-
-// ================================================================================================================
-// Several breakage tables over ONE match (gasm_batch_score_tables, gasm_calc_breakscore_tables): the reference scores the
-// same paths against the same reads under the true and under the uniform table (lib/DeNovoAssembler.R:325-355).  Where a
-// read lies does not depend on the table; only the last step does (sum of prob[window] x count).  So a read is matched
-// once, its window taken once, and T table entries are gathered.  Table t's numbers are bit for bit those of the
-// single-table kernels with table t.
-// ================================================================================================================
-// k_score_reads_graph with T tables: one graph_match and one break_window per read, then T gathers (independent of each
-// other: in flight together) and T 64-bit adds.  Accumulators per path: one u32 count and T u64 sums — in LDS ([t][path],
-// then the counts) when the segment's paths fit into `lds_paths`, else global atomics.  The launch keeps
-// lds_paths * (4 + 8 T) within the most k_score_reads_graph ever asks for (GASM_SCORE_PATH_CAP * 12 bytes), so the
-// workgroups per CU this chain of dependent gathers lives on are no fewer than there.  Integer adds commute: the sums do
-// not depend on the order the reads arrive in, nor on the branch taken.
-template <class K, int T>
-__global__ void __launch_bounds__(GASM_WG) k_score_reads_graph_tables(ReadSet rs, GraphView gv, const u64* __restrict__ link,
-                                                                      const u32* __restrict__ e_cid, PathSet ps, FixTables dfix, int kmer,
-                                                                      u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* __restrict__ cnt,
-                                                                      unsigned long long* __restrict__ sum, u64 sum_stride, int verify,
-                                                                      u32* __restrict__ verify_flag) {
-    extern __shared__ unsigned long long s_sum[];
-    u32* s_cnt = reinterpret_cast<u32*>(s_sum + (size_t)T * lds_paths);
-    u32 seg, chunk;
-    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
-    const u64 r0 = rs.seg_read_off[seg] + (u64)chunk * reads_per_wg;
-    const u64 rseg_end = rs.seg_read_off[seg + 1];
-    if (r0 >= rseg_end) return;
-    const u64 r1 = r0 + reads_per_wg < rseg_end ? r0 + reads_per_wg : rseg_end;
-    const u32 pfirst = ps.seg_path_off[seg], np = ps.seg_path_off[seg + 1] - pfirst;
-    const bool in_lds = np <= lds_paths;
-    if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) s_sum[(size_t)t * lds_paths + i] = 0;
-        s_cnt[i] = 0;
-    }
-    __syncthreads();
-    for (u64 r = r0 + threadIdx.x; r < r1; r += GASM_WG) {
-        u32 c = 0;
-        u64 pb = 0, pe = 0;
-        const u64 g = graph_match<K>(rs, gv, link, e_cid, ps, seg, r, &c, &pb, &pe, verify, verify_flag);
-        if (g == ~0ull) continue;
-        const u32 plen = (u32)(pe - pb);
-        u32 idx = 0;
-        const bool hit = break_window(ps.words, pb, plen, (u32)(g - pb), kmer, &idx);
-        long long fx[T];
-#pragma unroll
-        for (int t = 0; t < T; ++t) fx[t] = hit ? dfix.p[t][idx] : 0;
-        if (in_lds) {
-            atomicAdd(&s_cnt[c - pfirst], 1u);
-#pragma unroll
-            for (int t = 0; t < T; ++t) atomicAdd(&s_sum[(size_t)t * lds_paths + (c - pfirst)], (unsigned long long)fx[t]);
-        } else {
-            atomicAdd(&cnt[c], 1u);
-#pragma unroll
-            for (int t = 0; t < T; ++t) atomicAdd(&sum[(u64)t * sum_stride + c], (unsigned long long)fx[t]);
-        }
-    }
-    __syncthreads();
-    if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) {
-        const u32 c = s_cnt[i];
-        if (c) {
-            atomicAdd(&cnt[pfirst + i], c);
-#pragma unroll
-            for (int t = 0; t < T; ++t) atomicAdd(&sum[(u64)t * sum_stride + pfirst + i], s_sum[(size_t)t * lds_paths + i]);
-        }
-    }
-}
-
-#define GASM_INST_SCORE_TABLES(K, T)                                                                                                      \
-    template __global__ void k_score_reads_graph_tables<K, T>(ReadSet, GraphView, const u64*, const u32*, PathSet, FixTables, int, u32, u32, u32, u32*, \
-                                                              unsigned long long*, u64, int, u32*);
-#define GASM_INST_SCORE_TABLES_K(K)                                                                                                        \
-    GASM_INST_SCORE_TABLES(K, 2) GASM_INST_SCORE_TABLES(K, 3) GASM_INST_SCORE_TABLES(K, 4) GASM_INST_SCORE_TABLES(K, 5) GASM_INST_SCORE_TABLES(K, 6) \
-    GASM_INST_SCORE_TABLES(K, 7) GASM_INST_SCORE_TABLES(K, 8)
-GASM_INST_SCORE_TABLES_K(u64)
-GASM_INST_SCORE_TABLES_K(K128)
-
-// k_score_zero for one count and n_tables sums per path
-__global__ void __launch_bounds__(GASM_WG) k_score_zero_tables(u32* __restrict__ cnt, unsigned long long* __restrict__ sum, u64 sum_stride, u32 n_tables,
-                                                               const u32* __restrict__ n_paths_p) {
-    const u32 n = *n_paths_p;
-    for (u32 p = blockIdx.x * GASM_WG + threadIdx.x; p < n; p += gridDim.x * GASM_WG) {
-        cnt[p] = 0;
-        for (u32 t = 0; t < n_tables; ++t) sum[(u64)t * sum_stride + p] = 0;
-    }
-}
-
-// k_path_reduce with T tables: the position counters and the window index are read once, T probabilities are gathered per
-// hit position.  Per table the summation is exactly k_path_reduce's: thread i sums positions i, i + 256, ... with one
-// fused multiply-add per term — what the compiler makes of k_path_reduce's `s1 += pr * c` and `s2 += pr * (c / dtot)`
-// (one v_fmac_f64 each in its ISA: HIP contracts by default), written out here with fma() so that it does not hang on the
-// compiler deciding alike in a loop of another shape —, the same wave butterfly, the four wave sums added in wave order.
-// ISA (gfx950): T = 1 has k_path_reduce's FP64 instruction mix exactly; 2 T v_fmac_f64 in the loop, 32 + 6 T VGPRs (68 at
-// T = 8), no scratch.
-template <int T>
-__global__ void __launch_bounds__(GASM_WG) k_path_reduce_tables(PathSet ps, const u32* __restrict__ poscnt, const u32* __restrict__ extra, ProbTables dprob,
-                                                                int kmer, double* __restrict__ bp_score, double* __restrict__ norm_freq,
-                                                                double* __restrict__ norm_len, u64 out_stride, int32_t* __restrict__ kmer_breaks,
-                                                                int32_t* __restrict__ seq_len, u32 n_paths) {
-    __shared__ u32 s_t[4];
-    __shared__ double s_a[T][4], s_b[T][4];
-    const u32 p = blockIdx.x;
-    if (p >= n_paths) return;
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u64 pb = ps.p_off[p];
-    const u32 len = (u32)(ps.p_off[p + 1] - pb);
-    u32 tsum = 0;
-    for (u32 j = threadIdx.x; j < len; j += GASM_WG) tsum += poscnt[pb + j];
-    tsum = wave_sum_u32(tsum);
-    if (lane == 0) s_t[wv] = tsum;
-    __syncthreads();
-    const u32 tot = s_t[0] + s_t[1] + s_t[2] + s_t[3] + extra[p];
-    const double dtot = (double)tot;
-    double s1[T], s2[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) { s1[t] = 0.0; s2[t] = 0.0; }
-    for (u32 j = threadIdx.x; j < len; j += GASM_WG) {
-        const u32 c = poscnt[pb + j];
-        if (c) {
-            u32 idx;
-            if (break_window(ps.words, pb, len, j, kmer, &idx)) {
-                const double dc = (double)c, q = (double)c / dtot;
-#pragma unroll
-                for (int t = 0; t < T; ++t) {
-                    const double pr = dprob.p[t][idx];
-                    s1[t] = fma(pr, dc, s1[t]);
-                    s2[t] = fma(pr, q, s2[t]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const double a = wave_sum_fixed(s1[t]), b = wave_sum_fixed(s2[t]);
-        if (lane == 0) { s_a[t][wv] = a; s_b[t][wv] = b; }
-    }
-    __syncthreads();
-    if (threadIdx.x < (u32)T) {
-        const u32 t = threadIdx.x;
-        const double a = ((s_a[t][0] + s_a[t][1]) + s_a[t][2]) + s_a[t][3];
-        const double b = ((s_b[t][0] + s_b[t][1]) + s_b[t][2]) + s_b[t][3];
-        bp_score[(u64)t * out_stride + p] = a;
-        norm_freq[(u64)t * out_stride + p] = b;
-        norm_len[(u64)t * out_stride + p] = a / (double)(int32_t)len;
-        if (t == 0) {
-            kmer_breaks[p] = (int32_t)tot;
-            seq_len[p] = (int32_t)len;
-        }
-    }
-}
-
-#define GASM_INST_REDUCE_TABLES(T)                                                                                                          \
-    template __global__ void k_path_reduce_tables<T>(PathSet, const u32*, const u32*, ProbTables, int, double*, double*, double*, u64, int32_t*, int32_t*, u32);
-GASM_INST_REDUCE_TABLES(1) GASM_INST_REDUCE_TABLES(2) GASM_INST_REDUCE_TABLES(3) GASM_INST_REDUCE_TABLES(4)
-GASM_INST_REDUCE_TABLES(5) GASM_INST_REDUCE_TABLES(6) GASM_INST_REDUCE_TABLES(7) GASM_INST_REDUCE_TABLES(8)

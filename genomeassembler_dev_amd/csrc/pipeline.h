@@ -130,7 +130,7 @@ struct ScoreState {
     DBuf d_tbl_off, d_seed, d_gpos, d_poscnt, d_total, d_out_f64, d_out_i32, d_freq, d_pd_off, d_pd, d_seg_empty, d_fxsum, d_first, d_first_off;
     std::vector<u64> h_toff;
     u32 n_paths = 0, n_table = 0;
-    // breakage tables of the last launch (pipeline_score_launch: 1).  Table t's bp / nf / nl arrays lie at d_out_f64 +
+    // breakage tables of the last launch.  Table t's bp / nf / nl arrays lie at d_out_f64 +
     // 3 t stride, its fixed-point sums at t * stride behind table 0's, its prob_dist at t * h_pd_off[n_paths]; on the host
     // h_bp / h_nf / h_nl / h_pd hold table after table (table 0 first: what single-table readers see)
     u32 n_tables = 1;
@@ -165,19 +165,17 @@ int pipeline_fetch_graph(gasm_ctx* ctx, DevReads& rd, BuildState& bs);    // h_e
 // of the same paths once the build's report has been read
 int pipeline_contig_paths(gasm_ctx* ctx, const DevReads& rd, const BuildState& bs, DevPaths& dp);
 void pipeline_contig_paths_host(const DevReads& rd, const BuildState& bs, DevPaths& dp);
-// graph != nullptr: dp holds the contigs of that build (same order), so reads are matched through the edge list
-int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_freq,
+// Scores the paths of `dp` against the reads under n_tables tables (1 .. GASM_MAX_TABLES) that share their keys (tbs[0]'s rows
+// serve path_freq): position counters / graph match once, sums (and prob_dist) per table; table t bit for bit what a call
+// with tbs[t] alone gives.  graph != nullptr: dp holds the contigs of that build (same order), so reads are matched through
+// the edge list.
+int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 n_tables, bool want_freq,
                           bool want_pd, ScoreState& ss, const BuildState* graph);
 int pipeline_score_fetch(gasm_ctx* ctx, ScoreState& ss);
-// the same match scored with n_tables tables (1 .. GASM_MAX_TABLES) that share their keys (tbs[0]'s rows serve path_freq):
-// position counters / graph match once, sums (and prob_dist) per table; table t bit for bit what pipeline_score_launch gives
-// with tbs[t].  Through the graph only when every table has a fixed-point shift, else all tables in FP64.
-int pipeline_score_launch_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 n_tables, bool want_freq,
-                                 bool want_pd, ScoreState& ss, const BuildState* graph);
-bool pipeline_score_tables_use_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 n_tables);
 // batch scoring can go through the build's graph (queued without waiting for the build) when every read holds a k-mer
-// and the table has a fixed-point shift for these reads (ScoreTable::fixed_shift); otherwise it takes the FP64 position path
-bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, const ScoreTable& tb);
+// and every table has a fixed-point shift for these reads (ScoreTable::fixed_shift); otherwise all tables take the FP64
+// position path
+bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 n_tables);
 // Levenshtein distance of every path of `dp` against `target` (ASCII) on the GPU (k_levenshtein).  *done = false when
 // the target holds a byte outside ACGT (the packed form cannot represent it): the caller then uses the host routine.
 // Two-sample KS statistic of every path's path_freq against the genome's per-position window probabilities

@@ -56,8 +56,8 @@ static const Knobs& knobs() { static const Knobs k; return k; }
 // knobs read at every build (tests switch them inside one process):
 //   GASM_SINGLE_PASS=0     two-pass partition (count, scan, scatter) from the start       GASM_PART_SLACK=percent   room per bucket region (100)
 //   GASM_DBG_PART_CAP=n    force the capacity of every bucket region to n keys (exercises the overflow path)
-// and at every multi-table batch score:
-//   GASM_DBG_SCORE_LDS_PATHS=n   cap the paths per segment whose accumulators k_score_reads_graph_tables keeps in LDS (segments
+// and at every batch score through the graph (one table or several):
+//   GASM_DBG_SCORE_LDS_PATHS=n   cap the paths per segment whose accumulators k_score_reads_graph keeps in LDS (segments
 //                                with more go to global atomics: same numbers; exercises that branch)
 
 // Wait for a report a kernel writes into pinned host memory: the kernel's last store is `ticket` at `word`.  Spinning on
@@ -463,13 +463,11 @@ static int ensure_lds_attrs(gasm_ctx* ctx) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist<K128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<K128>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
-#define GASM_TABLES_LDS_ATTR(T)                                                                                                                                              \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph_tables<u64, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));  \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph_tables<K128, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
-    GASM_TABLES_LDS_ATTR(2) GASM_TABLES_LDS_ATTR(3) GASM_TABLES_LDS_ATTR(4) GASM_TABLES_LDS_ATTR(5) GASM_TABLES_LDS_ATTR(6) GASM_TABLES_LDS_ATTR(7) GASM_TABLES_LDS_ATTR(8)
-#undef GASM_TABLES_LDS_ATTR
+#define GASM_SCORE_LDS_ATTR(T)                                                                                                                                        \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<u64, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));  \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<K128, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
+    GASM_SCORE_LDS_ATTR(1) GASM_SCORE_LDS_ATTR(2) GASM_SCORE_LDS_ATTR(3) GASM_SCORE_LDS_ATTR(4) GASM_SCORE_LDS_ATTR(5) GASM_SCORE_LDS_ATTR(6) GASM_SCORE_LDS_ATTR(7) GASM_SCORE_LDS_ATTR(8)
+#undef GASM_SCORE_LDS_ATTR
     ctx->lds_attrs_set = true;
     return GASM_OK;
 }
@@ -1268,36 +1266,46 @@ static u64 max_seg_reads(const DevReads& rd) {
     return m;
 }
 
-// Batch scoring of a build's own contigs (gasm_batch_score): queued behind the build without waiting for it.  The number
-// of paths is read on the device (graph.d_seg_cstart[S]); outputs are allocated at the build's upper bound.
-static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, ScoreState& ss, const BuildState& graph) {
+static_assert(GASM_SCORE_MAX_TABLES == GASM_MAX_TABLES, "kernels.h and gasm.h disagree on the number of tables");
+
+#define GASM_TABLES_SWITCH(T, CASE)                                                                                      \
+    switch (T) {                                                                                                         \
+        case 1: CASE(1); break; case 2: CASE(2); break; case 3: CASE(3); break; case 4: CASE(4); break; case 5: CASE(5); break;  \
+        case 6: CASE(6); break; case 7: CASE(7); break; default: CASE(8); break;                                         \
+    }
+
+// Batch scoring of a build's own contigs (gasm_batch_score, gasm_batch_score_tables) under T tables: queued behind the build
+// without waiting for it.  The number of paths is read on the device (graph.d_seg_cstart[S]); outputs are allocated at the
+// build's upper bound.  One k_score_zero, one k_score_reads_graph, a k_score_finish per table (tiny; each with its table's
+// own fixed-point shift).  One count array, the sums of table t at t * stride behind table 0's.
+static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 T, ScoreState& ss,
+                              const BuildState& graph) {
     GasmRange range("gasm:score (graph-indexed)");
+    GCHK(ensure_lds_attrs(ctx));
     const u32 S = rd.n_segments;
     const size_t PC = (size_t)graph.D_cap + 1;
     ss.stride = PC;
     ss.graph = &graph;
     ss.n_paths = 0;
     const size_t fx_off = (PC * 4 + 15) & ~(size_t)15;
-    GCHK(ss.d_total.ensure(fx_off + PC * 8));
-    GCHK(ss.d_out_f64.ensure(PC * 8 * 3));
+    GCHK(ss.d_total.ensure(fx_off + PC * 8 * T));
+    GCHK(ss.d_out_f64.ensure(PC * 8 * 3 * T));
     GCHK(ss.d_out_i32.ensure(PC * 4 * 2));
     unsigned long long* const d_fx = reinterpret_cast<unsigned long long*>(static_cast<char*>(ss.d_total.p) + fx_off);
     const u32* const n_paths_p = graph.d_seg_cstart.as<u32>() + S;
     const u64 p_est = graph.have_actual ? std::max<u64>(graph.n_contigs, 1) : (u64)S * 256;
     const u32 grid_p = (u32)std::max<u64>(1, std::min<u64>(ceil_div_u64(p_est, GASM_WG), (u64)ctx->n_cu * 8));
-    GLAUNCH(ctx, "k_score_zero", k_score_zero, dim3(grid_p), dim3(GASM_WG), 0, ss.d_total.as<u32>(), d_fx, n_paths_p);
+    GLAUNCH(ctx, "k_score_zero", k_score_zero, dim3(grid_p), dim3(GASM_WG), 0, ss.d_total.as<u32>(), d_fx, (u64)PC, T, n_paths_p);
     const PathSet ps = dp.view();
     // the paths are this build's contigs and every read holds a k-mer: the sorted edge list is the index, and the
     // per-path sums are accumulated per read in fixed point (no position counters)
-    GraphView gv;
-    gv.dk_key = graph.d_dk_key.p;
-    gv.dstart = graph.d_dstart.as<u32>();
-    gv.fdir = graph.d_fdir.as<u16>();
-    gv.k = graph.k;
-    gv.bbits = graph.bbits;
-    gv.fbits = graph.fbits;
+    const GraphView gv = graph_view(graph);
     const u64 max_reads = max_seg_reads(rd);
-    GCHK(const_cast<ScoreTable&>(tb).set_fixed(ctx, tb.fixed_shift(max_reads)));
+    FixTables ft = {};
+    for (u32 t = 0; t < T; ++t) {
+        GCHK(tbs[t]->set_fixed(ctx, tbs[t]->fixed_shift(max_reads)));
+        ft.p[t] = tbs[t]->d_fix.as<long long>();
+    }
     // GASM_SCORE_VERIFY=1: compare every read with the contig text where the graph says it lies (kernels_score.hip, graph_match);
     // a mismatch raises flags[2] of the build and pipeline_score_fetch refuses the scores
     const int verify = env_int("GASM_SCORE_VERIFY", 0);
@@ -1305,33 +1313,38 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     const u32 reads_per_wg = 256;     // one read per thread: the match is a chain of dependent loads
     const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);
     // per-path accumulators kept in LDS: sized from the last build of these reads (a segment with more paths than that
-    // goes to global atomics: slower, same numbers)
-    const u32 lds_paths = std::min<u32>(std::max<u32>(graph.have_actual ? graph.paths_est : 1024u, 1u), GASM_SCORE_PATH_CAP);
-    if (graph.words == 1) {
-        GLAUNCH(ctx, "k_score_reads_graph", k_score_reads_graph<u64>, seg_grid(rchunks, S), dim3(GASM_WG), (size_t)lds_paths * 12, rd.view(),
-                gv, graph.d_link.as<u64>(), graph.d_ecid.as<u32>(), ps, tb.d_fix.as<long long>(), kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(),
-                d_fx, verify, graph.d_flags.as<u32>() + 2);
-    } else {
-        GLAUNCH(ctx, "k_score_reads_graph", k_score_reads_graph<K128>, seg_grid(rchunks, S), dim3(GASM_WG), (size_t)lds_paths * 12, rd.view(),
-                gv, graph.d_link.as<u64>(), graph.d_ecid.as<u32>(), ps, tb.d_fix.as<long long>(), kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(),
-                d_fx, verify, graph.d_flags.as<u32>() + 2);
-    }
-    double* o_bp = ss.d_out_f64.as<double>();
-    double* o_nf = o_bp + PC;
-    double* o_nl = o_nf + PC;
+    // goes to global atomics: slower, same numbers); 4 + 8 T bytes per path, GASM_SCORE_PATH_CAP * 12 bytes at most
+    u32 lds_paths = std::min<u32>(std::max<u32>(graph.have_actual ? graph.paths_est : 1024u, 1u), (u32)(GASM_SCORE_PATH_CAP * 12 / (4 + 8 * T)));
+    if (const int cap = env_int("GASM_DBG_SCORE_LDS_PATHS", 0)) lds_paths = std::min<u32>(lds_paths, (u32)std::max(1, cap));
+    const size_t lds_bytes = (size_t)lds_paths * (4 + 8 * (size_t)T);
+#define GASM_LAUNCH_SCORE(TT)                                                                                                                 \
+    do {                                                                                                                                      \
+        const auto kern = graph.words == 1 ? k_score_reads_graph<u64, TT> : k_score_reads_graph<K128, TT>;                                    \
+        GLAUNCH(ctx, "k_score_reads_graph", kern, seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), gv, graph.d_link.as<u64>(),      \
+                graph.d_ecid.as<u32>(), ps, ft, kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(), d_fx, (u64)PC, verify,          \
+                graph.d_flags.as<u32>() + 2);                                                                                                 \
+    } while (0)
+    GASM_TABLES_SWITCH(T, GASM_LAUNCH_SCORE)
+#undef GASM_LAUNCH_SCORE
     int32_t* o_br = ss.d_out_i32.as<int32_t>();
     int32_t* o_ln = o_br + PC;
     const u64* d_se = nullptr;
     if (rd.n_empty) { GCHK(h2d(ctx, ss.d_seg_empty, rd.h_seg_empty.data(), (size_t)S * 8)); d_se = ss.d_seg_empty.as<u64>(); }
-    GLAUNCH(ctx, "k_score_finish", k_score_finish, dim3(grid_p), dim3(GASM_WG), 0, ps, ss.d_total.as<u32>(),
-            d_fx, tb.d_fix.as<long long>(), d_se, kmer, std::ldexp(1.0, -tb.fix_shift), o_bp, o_nf, o_nl, o_br, o_ln, n_paths_p);
+    for (u32 t = 0; t < T; ++t) {
+        double* o_bp = ss.d_out_f64.as<double>() + (size_t)t * 3 * PC;
+        GLAUNCH(ctx, "k_score_finish", k_score_finish, dim3(grid_p), dim3(GASM_WG), 0, ps, ss.d_total.as<u32>(), d_fx + (size_t)t * PC, ft.p[t], d_se, kmer,
+                std::ldexp(1.0, -tbs[t]->fix_shift), o_bp, o_bp + PC, o_bp + 2 * PC, o_br, o_ln, n_paths_p);
+    }
     ss.h_pd_off.clear();
     ss.launched = true;
     return GASM_OK;
 }
 
-bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, const ScoreTable& tb) {
-    return graph.n_kmers > 0 && rd.n_reads > rd.n_empty && rd.min_len >= (u32)graph.k && tb.fixed_shift(max_seg_reads(rd)) >= 0;
+bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 T) {
+    if (!(graph.n_kmers > 0 && rd.n_reads > rd.n_empty && rd.min_len >= (u32)graph.k)) return false;
+    const u64 max_reads = max_seg_reads(rd);
+    for (u32 t = 0; t < T; ++t) if (tbs[t]->fixed_shift(max_reads) < 0) return false;
+    return true;
 }
 
 // The part of the general scorer no table enters: the first occurrence of every read in every path as position counters
@@ -1447,138 +1460,21 @@ static int score_freq_and_pd_offsets(gasm_ctx* ctx, DevPaths& dp, int kmer, cons
     return GASM_OK;
 }
 
-int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, const ScoreTable& tb, bool want_freq, bool want_pd,
+int pipeline_score_launch(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 T, bool want_freq, bool want_pd,
                           ScoreState& ss, const BuildState* graph) {
-    if (kmer < 0) { gasm_set_error("kmer must be >= 0"); return GASM_ERR_INVALID; }
-    if (rd.n_segments != dp.n_segments) { gasm_set_error("reads and paths disagree on the number of segments"); return GASM_ERR_INVALID; }
-    HIPCHK(hipSetDevice(ctx->device));
-    GasmRange range("gasm:score");
-    ss.valid = false;
-    ss.n_table = tb.n_table;
-    ss.n_tables = 1;
-    ss.want_freq = want_freq && tb.n_table;
-    ss.want_pd = want_pd;
-    ss.graph = nullptr;
-    if (graph && !want_freq && !want_pd && pipeline_score_uses_graph(rd, *graph, tb)) return score_launch_graph(ctx, rd, dp, kmer, tb, ss, *graph);
-    GCHK(score_positions(ctx, rd, dp, ss, 1));
-    const u32 P = dp.n_paths;
-    const PathSet ps = dp.view();
-    double* o_bp = ss.d_out_f64.as<double>();
-    double* o_nf = o_bp + (P + 1);
-    double* o_nl = o_nf + (P + 1);
-    int32_t* o_br = ss.d_out_i32.as<int32_t>();
-    int32_t* o_ln = o_br + (P + 1);
-    if (P) {
-        GLAUNCH(ctx, "k_path_reduce", k_path_reduce, dim3(P), dim3(GASM_WG), 0, ps, ss.d_poscnt.as<u32>(),
-                ss.d_total.as<u32>(), tb.d_prob.as<double>(), kmer, o_bp, o_nf, o_nl, o_br, o_ln, P);
-    }
-    GCHK(score_freq_and_pd_offsets(ctx, dp, kmer, tb, want_pd, ss));
-    if (want_pd && P) {
-        GCHK(ss.d_pd.ensure((ss.h_pd_off[P] + 1) * 8));
-        GLAUNCH(ctx, "k_prob_dist", k_prob_dist, dim3(ceil_div_u64(P, GASM_WG / 64)), dim3(GASM_WG), 0, ps, tb.d_prob.as<double>(), kmer,
-                ss.d_pd_off.as<u64>(), ss.d_pd.as<double>(), P);
-    }
-    ss.launched = true;
-    return GASM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// several tables over one match (gasm_batch_score_tables, gasm_calc_breakscore_tables)
-// ---------------------------------------------------------------------------------------------------------------
-static_assert(GASM_SCORE_MAX_TABLES == GASM_MAX_TABLES, "kernels.h and gasm.h disagree on the number of tables");
-
-bool pipeline_score_tables_use_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 n_tables) {
-    for (u32 t = 0; t < n_tables; ++t) if (!pipeline_score_uses_graph(rd, graph, *tbs[t])) return false;
-    return true;
-}
-
-#define GASM_TABLES_SWITCH(T, FIRST, CASE)                                                                     \
-    switch (T) {                                                                                               \
-        FIRST case 2: CASE(2); break; case 3: CASE(3); break; case 4: CASE(4); break; case 5: CASE(5); break;  \
-        case 6: CASE(6); break; case 7: CASE(7); break; default: CASE(8); break;                               \
-    }
-
-// score_launch_graph for T >= 2 tables: one k_score_zero_tables, one k_score_reads_graph_tables, a k_score_finish per table
-// (tiny; each with its table's own fixed-point shift).  One count array, the sums of table t at t * stride behind table 0's.
-static int score_launch_graph_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 T, ScoreState& ss,
-                                     const BuildState& graph) {
-    GasmRange range("gasm:score (graph-indexed, several tables)");
-    GCHK(ensure_lds_attrs(ctx));
-    const u32 S = rd.n_segments;
-    const size_t PC = (size_t)graph.D_cap + 1;
-    ss.stride = PC;
-    ss.graph = &graph;
-    ss.n_paths = 0;
-    const size_t fx_off = (PC * 4 + 15) & ~(size_t)15;
-    GCHK(ss.d_total.ensure(fx_off + PC * 8 * T));
-    GCHK(ss.d_out_f64.ensure(PC * 8 * 3 * T));
-    GCHK(ss.d_out_i32.ensure(PC * 4 * 2));
-    unsigned long long* const d_fx = reinterpret_cast<unsigned long long*>(static_cast<char*>(ss.d_total.p) + fx_off);
-    const u32* const n_paths_p = graph.d_seg_cstart.as<u32>() + S;
-    const u64 p_est = graph.have_actual ? std::max<u64>(graph.n_contigs, 1) : (u64)S * 256;
-    const u32 grid_p = (u32)std::max<u64>(1, std::min<u64>(ceil_div_u64(p_est, GASM_WG), (u64)ctx->n_cu * 8));
-    GLAUNCH(ctx, "k_score_zero_tables", k_score_zero_tables, dim3(grid_p), dim3(GASM_WG), 0, ss.d_total.as<u32>(), d_fx, (u64)PC, T, n_paths_p);
-    const PathSet ps = dp.view();
-    GraphView gv;
-    gv.dk_key = graph.d_dk_key.p;
-    gv.dstart = graph.d_dstart.as<u32>();
-    gv.fdir = graph.d_fdir.as<u16>();
-    gv.k = graph.k;
-    gv.bbits = graph.bbits;
-    gv.fbits = graph.fbits;
-    const u64 max_reads = max_seg_reads(rd);
-    FixTables ft = {};
-    for (u32 t = 0; t < T; ++t) {
-        GCHK(tbs[t]->set_fixed(ctx, tbs[t]->fixed_shift(max_reads)));
-        ft.p[t] = tbs[t]->d_fix.as<long long>();
-    }
-    const int verify = env_int("GASM_SCORE_VERIFY", 0);
-    ss.verify = verify != 0;
-    const u32 reads_per_wg = 256;
-    const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);
-    // the LDS request stays within k_score_reads_graph's largest: 4 + 8 T bytes per path instead of 12
-    u32 lds_paths = std::min<u32>(std::max<u32>(graph.have_actual ? graph.paths_est : 1024u, 1u), (u32)(GASM_SCORE_PATH_CAP * 12 / (4 + 8 * T)));
-    if (const int cap = env_int("GASM_DBG_SCORE_LDS_PATHS", 0)) lds_paths = std::min<u32>(lds_paths, (u32)std::max(1, cap));
-    const size_t lds_bytes = (size_t)lds_paths * (4 + 8 * (size_t)T);
-#define GASM_LAUNCH_SCORE_TABLES(TT)                                                                                                                 \
-    do {                                                                                                                                             \
-        const auto kern = graph.words == 1 ? k_score_reads_graph_tables<u64, TT> : k_score_reads_graph_tables<K128, TT>;                             \
-        GLAUNCH(ctx, "k_score_reads_graph_tables", kern, seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), gv, graph.d_link.as<u64>(),      \
-                graph.d_ecid.as<u32>(), ps, ft, kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(), d_fx, (u64)PC, verify,                 \
-                graph.d_flags.as<u32>() + 2);                                                                                                        \
-    } while (0)
-    GASM_TABLES_SWITCH(T, , GASM_LAUNCH_SCORE_TABLES)
-#undef GASM_LAUNCH_SCORE_TABLES
-    int32_t* o_br = ss.d_out_i32.as<int32_t>();
-    int32_t* o_ln = o_br + PC;
-    const u64* d_se = nullptr;
-    if (rd.n_empty) { GCHK(h2d(ctx, ss.d_seg_empty, rd.h_seg_empty.data(), (size_t)S * 8)); d_se = ss.d_seg_empty.as<u64>(); }
-    for (u32 t = 0; t < T; ++t) {
-        double* o_bp = ss.d_out_f64.as<double>() + (size_t)t * 3 * PC;
-        GLAUNCH(ctx, "k_score_finish", k_score_finish, dim3(grid_p), dim3(GASM_WG), 0, ps, ss.d_total.as<u32>(), d_fx + (size_t)t * PC, ft.p[t], d_se, kmer,
-                std::ldexp(1.0, -tbs[t]->fix_shift), o_bp, o_bp + PC, o_bp + 2 * PC, o_br, o_ln, n_paths_p);
-    }
-    ss.h_pd_off.clear();
-    ss.launched = true;
-    return GASM_OK;
-}
-
-int pipeline_score_launch_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kmer, ScoreTable* const* tbs, u32 T, bool want_freq, bool want_pd,
-                                 ScoreState& ss, const BuildState* graph) {
     if (T < 1 || T > GASM_MAX_TABLES) { gasm_set_error("n_tables must be 1..%d (got %u)", GASM_MAX_TABLES, T); return GASM_ERR_INVALID; }
     if (kmer < 0) { gasm_set_error("kmer must be >= 0"); return GASM_ERR_INVALID; }
     if (rd.n_segments != dp.n_segments) { gasm_set_error("reads and paths disagree on the number of segments"); return GASM_ERR_INVALID; }
     for (u32 t = 1; t < T; ++t) if (tbs[t]->n_table != tbs[0]->n_table) { gasm_set_error("the tables differ in their number of rows"); return GASM_ERR_INVALID; }
     HIPCHK(hipSetDevice(ctx->device));
-    GasmRange range("gasm:score (several tables)");
+    GasmRange range("gasm:score");
     ss.valid = false;
     ss.n_table = tbs[0]->n_table;
     ss.n_tables = T;
     ss.want_freq = want_freq && tbs[0]->n_table;
     ss.want_pd = want_pd;
     ss.graph = nullptr;
-    if (graph && T >= 2 && !want_freq && !want_pd && pipeline_score_tables_use_graph(rd, *graph, tbs, T))
-        return score_launch_graph_tables(ctx, rd, dp, kmer, tbs, T, ss, *graph);
+    if (graph && !want_freq && !want_pd && pipeline_score_uses_graph(rd, *graph, tbs, T)) return score_launch_graph(ctx, rd, dp, kmer, tbs, T, ss, *graph);
     GCHK(score_positions(ctx, rd, dp, ss, T));
     const u32 P = dp.n_paths;
     const PathSet ps = dp.view();
@@ -1588,11 +1484,11 @@ int pipeline_score_launch_tables(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int 
     ProbTables pt = {};
     for (u32 t = 0; t < T; ++t) pt.p[t] = tbs[t]->d_prob.as<double>();
     if (P) {
-#define GASM_LAUNCH_REDUCE_TABLES(TT)                                                                                                                     \
-    GLAUNCH(ctx, "k_path_reduce_tables", k_path_reduce_tables<TT>, dim3(P), dim3(GASM_WG), 0, ps, ss.d_poscnt.as<u32>(), ss.d_total.as<u32>(), pt, kmer, o_bp, \
+#define GASM_LAUNCH_REDUCE(TT)                                                                                                                  \
+    GLAUNCH(ctx, "k_path_reduce", k_path_reduce<TT>, dim3(P), dim3(GASM_WG), 0, ps, ss.d_poscnt.as<u32>(), ss.d_total.as<u32>(), pt, kmer, o_bp, \
             o_bp + stride, o_bp + 2 * stride, (u64)(3 * stride), o_br, o_br + stride, P)
-        GASM_TABLES_SWITCH(T, case 1: GASM_LAUNCH_REDUCE_TABLES(1); break;, GASM_LAUNCH_REDUCE_TABLES)
-#undef GASM_LAUNCH_REDUCE_TABLES
+        GASM_TABLES_SWITCH(T, GASM_LAUNCH_REDUCE)
+#undef GASM_LAUNCH_REDUCE
     }
     GCHK(score_freq_and_pd_offsets(ctx, dp, kmer, *tbs[0], want_pd, ss));
     if (want_pd && P) {

@@ -79,14 +79,15 @@ int pool_score_launch(gasm_pool* p, int kmer, const double* table, bool wait_for
         p->table_set = true;
     }
     // through the graph (every read holds a k-mer) the scoring needs no size from the host and is queued behind the build as it is
-    const bool through_graph = p->n_local && pipeline_score_uses_graph(p->own, p->bs, p->tb);
+    ScoreTable* const tb = &p->tb;
+    const bool through_graph = p->n_local && pipeline_score_uses_graph(p->own, p->bs, &tb, 1);
     if (wait_for_build || !through_graph) GCHK(pipeline_build_finish_n(ctx, nullptr, p->n_local, p->bs, nullptr));
     if (!p->paths_ready) {
         GCHK(pipeline_contig_paths(ctx, p->own, p->bs, p->dp));
         p->paths_ready = true;
     }
     if (!p->bs.pending) pipeline_contig_paths_host(p->own, p->bs, p->dp);
-    GCHK(pipeline_score_launch(ctx, p->own, p->dp, kmer, p->tb, false, false, p->ss, &p->bs));
+    GCHK(pipeline_score_launch(ctx, p->own, p->dp, kmer, &tb, 1, false, false, p->ss, &p->bs));
     p->scored = true; p->score_kmer = kmer;
     return GASM_OK;
 }

@@ -26,6 +26,6 @@ struct GuidedState {
     std::vector<u64> h_text_off;
     void release() { dp.release(); ss.release(); valid = false; }
 };
-int guided_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DevPaths& contig_paths, ScoreState& contig_scores, const ScoreTable& tb, int kmer,
+int guided_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DevPaths& contig_paths, ScoreState& contig_scores, ScoreTable& tb, int kmer,
                  GuidedState& out);
 int guided_fetch_text(gasm_ctx* ctx, GuidedState& g);

@@ -342,7 +342,7 @@ int scaffolds_as_paths(const gasm_scaffolds* sc, DevPaths& dp) {
 // ---------------------------------------------------------------------------------------------------------------
 // Row A16: breakage-score-guided traversal (kernels_asm.hip, k_guided_chain; specification in DESIGN.md §8)
 // ---------------------------------------------------------------------------------------------------------------
-int guided_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DevPaths& cp, ScoreState& cs, const ScoreTable& tb, int kmer, GuidedState& g) {
+int guided_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DevPaths& cp, ScoreState& cs, ScoreTable& tb, int kmer, GuidedState& g) {
     g.valid = false;
     if (!cs.graph || cs.graph != &bs) { gasm_set_error("guided traversal needs the batch scored through its graph in fixed point (reads of at least k bases, a finite "
                                                              "table the 64-bit fixed point can hold)"); return GASM_ERR_STATE; }
@@ -432,7 +432,8 @@ int guided_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DevPaths& cp, Scor
     GCHK(expand(ctx, csr, cp.d_words.as<u64>(), bs.d_c_off.as<u64>(), dp.d_words, tmp));
     GCHK(dp.upload_dirs(ctx));
     lap(ctx, "guided: expand + directories");
-    GCHK(pipeline_score_launch(ctx, rd, dp, kmer, tb, false, false, g.ss, nullptr));
+    ScoreTable* const tbp = &tb;
+    GCHK(pipeline_score_launch(ctx, rd, dp, kmer, &tbp, 1, false, false, g.ss, nullptr));
     lap(ctx, "guided: scoring launched");
     GCHK(pipeline_score_fetch(ctx, g.ss));
     lap(ctx, "guided: scores fetched");

@@ -181,7 +181,7 @@ void gasm_scores_free(gasm_scores* s);
  *   bp_probs: n_tables rows of n_table probabilities (row-major), all for the keys bp_kmer; n_tables in 1..GASM_MAX_TABLES,
  *   else GASM_ERR_INVALID.  out: n_tables entries; out[t] is an ordinary gasm_scores (every accessor above; free each with
  *   gasm_scores_free) holding bit for bit what gasm_calc_breakscore(..., bp_probs + t * n_table, ...) returns with the same
- *   variant and flags.  On any error every out[t] is NULL.
+ *   variant and flags (gasm_calc_breakscore is the n_tables = 1 case of the same code).  On any error every out[t] is NULL.
  * Done once per call (none of it depends on the table): read upload and index, the first occurrence of every read in every
  * path, kmer_breaks, sequence_len, lev_dist_vs_true (GPU or host, as gasm_calc_breakscore chooses), the velvet variant's
  * startpos, the genome's row histogram for the KS statistic, and the path_freq counts — count / total, one dense buffer

@@ -194,7 +194,8 @@ def test_batch_fixed_point_equals_single_table_and_exact_sums(qtable, k):
 
 def test_batch_eight_tables_lds_and_global_atomic_accumulators(qtable, monkeypatch):
     """T = 8: the LDS budget holds 6144 * 12 / 68 = 1084 paths of a segment.  GASM_DBG_SCORE_LDS_PATHS=2 leaves room for two,
-    so the segments with more contigs take the global-atomic branch; integer sums: the same bits either way"""
+    so the segments with more contigs take the global-atomic branch; integer sums: the same bits either way.  The cap
+    reaches one table (score, T = 1 of the same kernel) as well: the same statement for it, on the same segments"""
     keys, prob = qtable
     k = 21
     reads, seg_off, _ = synth.make_batch(4, 9000, 60, 15, seed0=4200, planted=True)        # (planted repeats: dozens of contigs per segment)
@@ -208,11 +209,16 @@ def test_batch_eight_tables_lds_and_global_atomic_accumulators(qtable, monkeypat
         n_contigs = [len(c) for c in b.contigs()]
         assert max(n_contigs) > 2 and sum(n > 2 for n in n_contigs) >= 2, n_contigs      # (segments beyond the budget of two)
         _assert_tables_equal_single(b, ref, k, tabs, "lds")
+        ref.build(k).score(8, tabs[0])
+        one_in_lds = _bits(ref.scores()) + (ref.score_fixed()[0].tobytes(),)
         monkeypatch.setenv("GASM_DBG_SCORE_LDS_PATHS", "2")
         b.build(k).score_tables(8, tabs)
         assert [_bits(b.scores(table=t)) + (b.score_fixed(table=t)[0].tobytes(),) for t in range(8)] == in_lds
         for t in (0, 7):
             _check_exact(b, t, segs, (1, 2), keys, tabs[t], True, ("global", t))
+        ref.build(k).score(8, tabs[0])
+        assert _bits(ref.scores()) + (ref.score_fixed()[0].tobytes(),) == one_in_lds
+        _check_exact(ref, 0, segs, (1, 2), keys, tabs[0], True, ("global", "one table"))
     finally:
         b.close()
         ref.close()
