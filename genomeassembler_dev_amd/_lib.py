@@ -37,6 +37,7 @@ SYMBOLS = {
     "gasm_ctx_stream": (_vp, [_vp]),
     "gasm_get_contigs": (_int, [_vp, _vp, _u64, _int, _int, _int, _PP]),
     "gasm_get_contigs_from_reads": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _PP]),
+    "gasm_get_contigs_from_reads_solid": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _PP]),
     "gasm_contigs_count": (_u64, [_vp]),
     "gasm_contigs_data": (_vp, [_vp]),
     "gasm_contigs_offsets": (_vp, [_vp]),
@@ -106,6 +107,10 @@ SYMBOLS = {
     "gasm_batch_free": (None, [_vp]),
     "gasm_batch_build": (_int, [_vp, _int, _u64]),
     "gasm_batch_score": (_int, [_vp, _int, _vp]),
+    "gasm_batch_build_solid": (_int, [_vp, _int, _u64, _u32]),
+    "gasm_batch_fetch_solid_stats": (_int, [_vp, _PP, _PP]),
+    "gasm_batch_kmer_spectrum": (_int, [_vp]),
+    "gasm_batch_fetch_kmer_spectrum": (_int, [_vp, _PP]),
     "gasm_batch_total_kmers": (_u64, [_vp]),
     "gasm_batch_total_reads": (_u64, [_vp]),
     "gasm_batch_fetch_distinct": (_int, [_vp, _PP, _PP, _PP, C.POINTER(_int)]),

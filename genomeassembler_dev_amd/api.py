@@ -106,14 +106,21 @@ def get_contigs(read_kmers, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_list
     return _contig_matrix(h, dbg_kmer, as_lists)
 
 
-def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False):
+def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1):
     """get_kmers_from_reads + get_contigs in one call (gasm_get_contigs_from_reads): the k-mers are taken on the GPU from the
     packed reads instead of being exploded into len(reads) * (read_len - k + 1) strings first (lib/DeNovoAssembler.R:109-130).
-    reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed)."""
+    reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed).
+    min_count > 1 (gasm_get_contigs_from_reads_solid): only k-mers seen at least min_count times become edges."""
+    if int(min_count) < 1:
+        raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
     ctx = ctx or default_context()
     buf, off = _pack(reads)
     h = C.c_void_p()
-    check(lib().gasm_get_contigs_from_reads(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows), C.byref(h)))
+    if int(min_count) == 1:
+        check(lib().gasm_get_contigs_from_reads(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows), C.byref(h)))
+    else:
+        check(lib().gasm_get_contigs_from_reads_solid(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
+                                                      int(min_count), C.byref(h)))
     return _contig_matrix(h, dbg_kmer, as_lists)
 
 

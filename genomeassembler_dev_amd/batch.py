@@ -104,10 +104,35 @@ class SegmentBatch:
         self.dropped_reads = int(dropped.value)
         return self
 
-    def build(self, k, genome_len_hint=0):
-        check(lib().gasm_batch_build(self.h, int(k), int(genome_len_hint)))
+    def build(self, k, genome_len_hint=0, min_count=1):
+        """queue a build.  min_count > 1 (gasm_batch_build_solid): only the k-mers seen at least min_count times in their segment
+        become edges — the cutoff for reads with sequencing errors; everything after the build sees the survivors only.
+        genome_len_hint then counts the distinct k-mers before the cutoff (include/gasm.h)."""
+        if int(min_count) < 1:
+            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+        if int(min_count) == 1:
+            check(lib().gasm_batch_build(self.h, int(k), int(genome_len_hint)))
+        else:
+            check(lib().gasm_batch_build_solid(self.h, int(k), int(genome_len_hint), int(min_count)))
         self.k = int(k)
         return self
+
+    def solid_stats(self):
+        """(distinct k-mers per segment before the last build's cutoff, after it): two uint64 arrays, equal at min_count = 1"""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_solid_stats(self.h, C.byref(a), C.byref(b)))
+        n = self.n_segments
+        return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint64)), shape=(n,)).copy(),
+                np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint64)), shape=(n,)).copy())
+
+    def kmer_spectrum(self):
+        """(n_segments, 256) uint64: [s, m] = distinct k-mers of segment s of the last build with multiplicity m (255: that or
+        more; column 0 is zero).  Build with min_count = 1, look for the valley, build again with the cutoff there."""
+        check(lib().gasm_batch_kmer_spectrum(self.h))
+        p = C.c_void_p()
+        check(lib().gasm_batch_fetch_kmer_spectrum(self.h, C.byref(p)))
+        n = self.n_segments * 256
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(n,)).copy().reshape(self.n_segments, 256)
 
     def build_plan(self):
         """the path the last build took (gasm_batch_build_plan; finishes a pending build first): a dict of the PLAN_FIELDS of

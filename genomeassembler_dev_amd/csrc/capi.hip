@@ -148,12 +148,12 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
 // ------------------------------------------------------------------------------------------------- get_contigs
 // reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix
 static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_off, u64 n_reads, u32 fixed_len, int dbg_kmer, int seed, int matrix_rows,
-                            gasm_contigs** out) {
+                            gasm_contigs** out, u32 min_count = 1) {
     DevReads rd;
     BuildState bs;
     const u64 seg_off[2] = {0, n_reads};
     int st = rd.upload(ctx, bases, read_off, n_reads, fixed_len, seg_off, 1);
-    if (st == GASM_OK) st = pipeline_build(ctx, rd, dbg_kmer, 0, bs);
+    if (st == GASM_OK) st = pipeline_build(ctx, rd, dbg_kmer, 0, bs, min_count);
     if (st == GASM_OK) st = pipeline_fetch_distinct(ctx, rd, bs);
     if (st == GASM_OK) st = pipeline_fetch_contigs(ctx, rd, bs);
     gasm_contigs* c = nullptr;
@@ -193,6 +193,17 @@ int gasm_get_contigs_from_reads(gasm_ctx* ctx, const char* reads, const uint64_t
     if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
     *out = nullptr;
     return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out);
+    API_GUARD_END
+}
+
+int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
+                                      int matrix_rows, uint32_t min_count, gasm_contigs** out) {
+    API_GUARD_BEGIN
+    if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("gasm_get_contigs_from_reads_solid: null argument"); return GASM_ERR_INVALID; }
+    if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
+    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
+    *out = nullptr;
+    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count);
     API_GUARD_END
 }
 
@@ -764,9 +775,10 @@ void gasm_batch_free(gasm_batch* b) {
     delete b;
 }
 
-int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint) {
-    API_GUARD_BEGIN
+// gasm_batch_build (min_count = 1) and gasm_batch_build_solid
+static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count) {
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
     b->built = false; b->scored = false;
     // consecutive steps take the slots in turn: this build does not wait for the last steps' graph and scoring, it runs
     // beside them.  A change of k rewrites the tile tables every slot reads: everything drains first.  GASM_PINGPONG=0: the
@@ -780,9 +792,52 @@ int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint) {
     }
     StepSlot& st = b->S();
     st.paths_ready = false; st.ss.valid = false; st.ss.launched = false;
-    GCHK(pipeline_build(st.cx, b->rd, k, genome_len_hint, st.bs));
+    GCHK(pipeline_build(st.cx, b->rd, k, genome_len_hint, st.bs, min_count));      // (the slot's BuildState keeps the cutoff of the build it holds)
     b->last_k = k;
     b->built = true;
+    return GASM_OK;
+}
+
+int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint) {
+    API_GUARD_BEGIN
+    return batch_build(b, k, genome_len_hint, 1);
+    API_GUARD_END
+}
+
+int gasm_batch_build_solid(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count) {
+    API_GUARD_BEGIN
+    return batch_build(b, k, genome_len_hint, min_count);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_solid_stats(gasm_batch* b, const uint64_t** distinct_before, const uint64_t** distinct_after) {
+    API_GUARD_BEGIN
+    if (!b || !distinct_before || !distinct_after) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_solid_stats before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_solid_stats(b->S().cx, b->rd, bs));
+    *distinct_before = bs.h_solid_before.data(); *distinct_after = bs.h_solid_after.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_kmer_spectrum(gasm_batch* b) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_kmer_spectrum before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    return pipeline_kmer_spectrum(b->S().cx, b->rd, b->S().bs);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist) {
+    API_GUARD_BEGIN
+    if (!b || !hist) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_kmer_spectrum before a build"); return GASM_ERR_STATE; }
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_kmer_spectrum(b->S().cx, b->rd, bs));
+    *hist = bs.h_spectrum.data();
     return GASM_OK;
     API_GUARD_END
 }

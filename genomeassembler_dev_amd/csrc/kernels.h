@@ -105,6 +105,11 @@ __global__ void k_bucket_dedup(K* keys, u32* mult, const u64* bstart, const u32*
 #define GASM_BUCKET_MAX 65535   // distinct keys of one bucket (16-bit fine directory)
 template <class K>
 __global__ void k_bucket_dedup_multi(const K* keys, K* keys_out, u32* mult, const u64* bstart, u32* bucket_d, u32* overflow, u16* fdir, int low_bits);
+// multiplicity cutoff (min_count > 1): compacts every bucket's sorted run in place, rewrites its fine-directory row
+template <class K>
+__global__ void k_bucket_solid(K* keys, u32* mult, const u64* bstart, u32* bucket_d, u16* fdir, int low_bits, int fbits, int bbits, u32 min_count,
+                               u32* removed, u32* done, u32* dstart);
+__global__ void k_kmer_spectrum(const u32* dstart, u32 nb, const u32* dk_cnt, u32 n_segments, u32 chunks, u32* hist);
 template <class K>
 __global__ void k_bucket_gather(const K* keys, const u32* mult, const u64* bstart, const u32* dstart, K* dk_key, u32* dk_cnt, u32* claim, u8* eflag,
                                 u32* flags);

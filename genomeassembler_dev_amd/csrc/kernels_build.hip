@@ -999,6 +999,112 @@ __global__ void __launch_bounds__(GASM_WG) k_bucket_dedup_multi(const K* __restr
 template __global__ void k_bucket_dedup_multi<u64>(const u64*, u64*, u32*, const u64*, u32*, u32*, u16*, int);
 template __global__ void k_bucket_dedup_multi<K128>(const K128*, K128*, u32*, const u64*, u32*, u32*, u16*, int);
 
+// ================================================================================================================
+// Multiplicity cutoff (gasm_batch_build_solid, min_count > 1 only): drop the distinct keys of a bucket that were seen fewer
+// than min_count times, in place, behind whichever de-duplication ran and in front of k_bucket_gather.  One workgroup per
+// (segment, bucket).  The run keys / mult [bstart[b], bstart[b] + bucket_d[b]) is sorted; it is compacted chunk by chunk
+// (SOLID_ITEMS consecutive entries per thread, so an exclusive scan of the threads' survivor counts keeps the order).  The
+// destination never overtakes the source: a chunk's survivors land at or in front of the chunk's own start, every load of
+// a chunk is complete before the barriers of its scan, and its stores follow them.  Runs of the multi-pass rung hold up to
+// GASM_BUCKET_MAX entries: nothing here assumes a run fits in LDS.
+// The bucket's row of the fine directory is rewritten for the survivors with dedup_order's bin function (bins are monotone
+// along a sorted run): entry `bin` = survivors in lower bins, last entry = survivors.  An empty bucket (also one the
+// de-duplication emptied after an overflow) gets an all-zero row and bucket_d = 0: still empty and searchable.
+// Thread 0 publishes the new bucket_d and adds the number of keys removed to its segment's counter; the last workgroup
+// recomputes dstart (dedup_last_scan on a done-word of its own) when the de-duplication did (dstart != nullptr).
+// The same layout as k_bucket_merge's output (kernels_pool.hip), so the pass could run on merged runs as well.
+// ================================================================================================================
+#define GASM_SOLID_ITEMS 4
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_bucket_solid(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restrict__ bstart,
+                                                          u32* __restrict__ bucket_d, u16* __restrict__ fdir, int low_bits, int fbits, int bbits,
+                                                          u32 min_count, u32* __restrict__ removed, u32* __restrict__ done, u32* __restrict__ dstart) {
+    constexpr u32 MAX_BINS = GASM_TBL / 4;
+    constexpr u32 CHUNK = GASM_WG * GASM_SOLID_ITEMS;
+    __shared__ u32 s_bin[MAX_BINS];
+    __shared__ u32 s_tmp[8];
+    const u32 bucket = blockIdx.x;
+    const u32 bins = 1u << fbits;                            // <= MAX_BINS (pipeline.hip: fbits is 9 or 10)
+    const int bshift = low_bits > fbits ? low_bits - fbits : 0;
+    const u64 beg = bstart[bucket];
+    const u32 d = bucket_d[bucket];
+    for (u32 i = threadIdx.x; i < bins; i += GASM_WG) s_bin[i] = 0;
+    __syncthreads();
+    u32 out = 0;
+    for (u32 base = 0; base < d; base += CHUNK) {
+        K rk[GASM_SOLID_ITEMS];
+        u32 rc[GASM_SOLID_ITEMS];
+        u32 n_keep = 0;
+        const u32 first = base + threadIdx.x * GASM_SOLID_ITEMS;
+#pragma unroll
+        for (int q = 0; q < GASM_SOLID_ITEMS; ++q) {
+            const bool in = first + q < d;
+            rc[q] = in ? mult[beg + first + q] : 0u;
+            rk[q] = in ? keys[beg + first + q] : key_empty<K>();
+            if (rc[q] < min_count) rc[q] = 0;                // (min_count >= 1: entries past the run drop out as well)
+            n_keep += rc[q] ? 1u : 0u;
+        }
+        u32 tot;
+        u32 pos = out + block_excl_scan<GASM_WG>(n_keep, s_tmp, &tot);     // (two barriers: every load above is behind us)
+#pragma unroll
+        for (int q = 0; q < GASM_SOLID_ITEMS; ++q) {
+            if (rc[q]) {
+                keys[beg + pos] = rk[q];
+                mult[beg + pos] = rc[q];
+                atomicAdd(&s_bin[kfield(rk[q], bshift) & (bins - 1)], 1u);
+                ++pos;
+            }
+        }
+        out += tot;
+        __syncthreads();                                     // the next chunk's loads may not pass a neighbour's stores
+    }
+    __syncthreads();
+    // bins -> exclusive offsets, written as the bucket's directory row
+    {
+        const u32 per = bins / GASM_WG;                      // 2 or 4
+        u32 c[4], sum = 0;
+#pragma unroll
+        for (u32 q = 0; q < 4; ++q) { c[q] = q < per ? s_bin[threadIdx.x * per + q] : 0u; sum += c[q]; }
+        u32 tot;
+        u32 ex = block_excl_scan<GASM_WG>(sum, s_tmp, &tot);
+        u16* const row = fdir + (u64)bucket * (bins + 1);
+#pragma unroll
+        for (u32 q = 0; q < 4; ++q)
+            if (q < per) { row[threadIdx.x * per + q] = (u16)ex; ex += c[q]; }
+        if (threadIdx.x == GASM_WG - 1) row[bins] = (u16)ex;
+    }
+    if (threadIdx.x == 0) {
+        publish_u32(&bucket_d[bucket], out);
+        if (d > out) atomicAdd(&removed[bucket >> bbits], d - out);
+    }
+    dedup_last_scan(bucket_d, dstart, gridDim.x, done, s_tmp + 7, s_tmp);
+}
+template __global__ void k_bucket_solid<u64>(u64*, u32*, const u64*, u32*, u16*, int, int, int, u32, u32*, u32*, u32*);
+template __global__ void k_bucket_solid<K128>(K128*, u32*, const u64*, u32*, u16*, int, int, int, u32, u32*, u32*, u32*);
+
+// ================================================================================================================
+// k-mer spectrum of a finished build: per segment, how many distinct k-mers of the dense arrays have multiplicity m
+// (bin min(m, 255); no k-mer has multiplicity 0).  Segment-major over dk_cnt, a 256-bin histogram per workgroup in LDS,
+// non-zero bins flushed with global atomics into a zeroed u32[S * 256]: integer additions only, so the result does not
+// depend on the order the workgroups arrive in.
+// ================================================================================================================
+__global__ void __launch_bounds__(GASM_WG) k_kmer_spectrum(const u32* __restrict__ dstart, u32 nb, const u32* __restrict__ dk_cnt, u32 n_segments,
+                                                           u32 chunks, u32* __restrict__ hist) {
+    __shared__ u32 s_h[256];
+    s_h[threadIdx.x] = 0;                                    // GASM_WG == 256
+    __syncthreads();
+    u32 seg, chunk;
+    if (!seg_chunk(n_segments, chunks, &seg, &chunk)) return;
+    for_seg_edges(dstart, nb, n_segments, chunks, [&](u32, u32, u32, u32 i) {
+        const u32 m = dk_cnt[i];
+        atomicAdd(&s_h[m < 255u ? m : 255u], 1u);
+    });
+    __syncthreads();
+    const u32 v = s_h[threadIdx.x];
+    if (v) atomicAdd(&hist[(u64)seg * 256 + threadIdx.x], v);
+}
+static_assert(GASM_WG == 256, "k_kmer_spectrum: one thread per bin");
+
 // Gather the per-bucket distinct runs into the dense per-segment arrays.
 template <class K>
 __global__ void __launch_bounds__(GASM_WG) k_bucket_gather(const K* __restrict__ keys, const u32* __restrict__ mult,

@@ -73,6 +73,8 @@ struct BuildState {
     bool ranked_in_lds = false;
     u32 tile_g = 1;                         // threads per read of the tile kernels
     u64 n_kmers = 0, hint = 0, reads_id = 0;
+    u32 min_count = 1;                      // multiplicity cutoff of this build (gasm_batch_build_solid): every attempt of the retry ladder
+                                            // filters with it (k_bucket_solid behind the de-duplication), and scores of its graph compare bases
     std::vector<u64> h_seg_nk;              // k-mers per segment
     // upper bounds the arrays are allocated at, and estimates the grids are sized from (the kernels loop beyond them)
     u64 D_cap = 0, maxD_cap = 0, bases_cap = 0;
@@ -98,11 +100,15 @@ struct BuildState {
     std::vector<u64> h_seg_bstart;          // n_segments+1
     DBuf d_keys2;                           // output of the multi-pass de-duplication (its passes re-read d_keys)
     DBuf d_keys, d_mult, d_hist, d_toff, d_tcnt, d_fdir, d_bstart, d_bucket_d, d_dstart, d_flags, d_rtab;
+    DBuf d_solid_removed;                   // min_count > 1: distinct k-mers the cutoff removed, per segment (u32, zeroed with every attempt)
+    DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_dk_key, d_dk_cnt, d_eflag, d_nxt, d_link, d_clen, d_ecid, d_ecoff;
     DBuf d_seg_cbases, d_seg_cstart, d_seg_bstart, d_c_off, d_contig_ascii;
     // host copies filled by fetch
     std::vector<u64> h_seg_doff, h_dk_key, h_c_off, h_seg_coff;
     std::vector<u32> h_dk_cnt, h_nxt;
+    std::vector<u64> h_solid_before, h_solid_after, h_spectrum;      // pipeline_fetch_solid_stats / pipeline_fetch_kmer_spectrum
+    bool spectrum_queued = false;           // k_kmer_spectrum ran on the arrays of this build
     std::vector<u8> h_eflag;
     std::vector<char> h_contigs;
     bool fetched_distinct = false, fetched_contigs = false;
@@ -148,7 +154,9 @@ struct ScoreState {
 // queues a whole build on the ctx stream and returns; pipeline_build_finish (called by every fetch) waits for its report
 // and repeats it with a larger configuration if it failed.  *rebuilt: the device arrays were produced anew (a score
 // queued behind the first attempt must be queued again).
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs);
+// min_count > 1: only the distinct k-mers seen at least min_count times in their segment enter the graph (1: all of them, and not
+// a launch more than without the argument)
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
 // one row of gasm_batch_build_plan (GASM_PLAN_FIELDS words, include/gasm.h) from a finished build's host fields
@@ -160,6 +168,12 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int launch_graph(gasm_ctx* ctx, u32 n_segments, BuildState& bs);
 int pipeline_fetch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_contigs(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// distinct k-mers per segment before and after the cutoff of the finished build (equal at min_count = 1)
+int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
+// n_segments x 256 counts
+int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_graph(gasm_ctx* ctx, DevReads& rd, BuildState& bs);    // h_eflag / h_nxt: per-edge flags and successors
 // paths of the build as a DevPaths (packs the contig text on the device; works on a queued build); the host-side numbers
 // of the same paths once the build's report has been read

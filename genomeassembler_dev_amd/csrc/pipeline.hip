@@ -433,7 +433,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_spectrum, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -644,6 +644,19 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         fprintf(stderr, "[dedup stamps, 100 MHz ticks per workgroup] init %.1f  first-iter %.1f  stream %.1f  barrier %.1f  order %.1f  writeback %.1f\n",
                 (double)h[0] / nbt, (double)h[1] / nbt, (double)h[2] / nbt, (double)h[3] / nbt, (double)h[4] / nbt, (double)h[5] / nbt);
     }
+    if (bs.min_count > 1) {
+        // the multiplicity cutoff, behind whichever de-duplication ran (every rung of pipeline_build_finish's ladder comes through
+        // here): weak keys leave the buckets' runs before anything reads them.  Its last workgroup redoes the offsets on flag word
+        // [10] (zero since the build's flags were cleared; [8] counted the de-duplication's workgroups, [9] is k_contig_scan's)
+        GCHK(bs.d_solid_removed.ensure((size_t)S * 4));
+        HIPCHK(hipMemsetAsync(bs.d_solid_removed.p, 0, (size_t)S * 4, ctx->stream));
+        if (W == 2) GLAUNCH(ctx, "k_bucket_solid", k_bucket_solid<K128>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K128>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
+                            bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.min_count, bs.d_solid_removed.as<u32>(),
+                            bs.d_flags.as<u32>() + 10, d_scan_out);
+        else GLAUNCH(ctx, "k_bucket_solid", k_bucket_solid<u64>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
+                     bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.min_count, bs.d_solid_removed.as<u32>(),
+                     bs.d_flags.as<u32>() + 10, d_scan_out);
+    }
     if (!scan_in_dedup) GLAUNCH(ctx, "k_scan_excl", k_scan_excl<u32>, dim3(1), dim3(1024), 0, bs.d_bucket_d.as<u32>(), bs.d_dstart.as<u32>(), nbt);
     return GASM_OK;
 }
@@ -849,8 +862,11 @@ static void zero_results(BuildState& bs, u32 S) {
     bs.d_total = 0; bs.n_contigs = 0; bs.contig_bases = 0;
 }
 
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs) {
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count) {
+    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
     GCHK(plan_build(ctx, rd, k, hint, bs));
+    bs.min_count = min_count;
+    bs.spectrum_queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -966,6 +982,46 @@ int pipeline_fetch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     bs.fetched_distinct = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    const u32 S = rd.n_segments;
+    std::vector<u32> removed(S, 0);
+    // (a build without k-mers launched nothing, and min_count = 1 removed nothing)
+    if (bs.min_count > 1 && bs.n_kmers) GCHK(d2h_sync(ctx, removed.data(), bs.d_solid_removed.p, (size_t)S * 4));
+    bs.h_solid_before.resize(S); bs.h_solid_after.resize(S);
+    for (u32 s = 0; s < S; ++s) {
+        bs.h_solid_after[s] = bs.h_dstart.empty() ? 0 : bs.h_dstart[s + 1] - bs.h_dstart[s];
+        bs.h_solid_before[s] = bs.h_solid_after[s] + removed[s];
+    }
+    return GASM_OK;
+}
+
+// k-mer spectrum: on the stream of the build, behind it; reads dstart and dk_cnt, writes an array of its own
+int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 S = rd.n_segments;
+    GCHK(bs.d_spectrum.ensure((size_t)S * 256 * 4));
+    HIPCHK(hipMemsetAsync(bs.d_spectrum.p, 0, (size_t)S * 256 * 4, ctx->stream));
+    if (bs.d_total) {
+        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(bs.maxD_est, GASM_WG * 8), 64u));      // a few rounds per workgroup: fewer flushes
+        GLAUNCH(ctx, "k_kmer_spectrum", k_kmer_spectrum, seg_grid(chunks, S), dim3(GASM_WG), 0, bs.d_dstart.as<u32>(), 1u << bs.bbits, bs.d_dk_cnt.as<u32>(), S, chunks,
+                bs.d_spectrum.as<u32>());
+    }
+    bs.spectrum_queued = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    if (!bs.spectrum_queued) { gasm_set_error("gasm_batch_fetch_kmer_spectrum before gasm_batch_kmer_spectrum (of the last build)"); return GASM_ERR_STATE; }
+    const size_t n = (size_t)rd.n_segments * 256;
+    std::vector<u32> h(n);
+    HIPCHK(hipMemcpyAsync(h.data(), bs.d_spectrum.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    bs.h_spectrum.assign(h.begin(), h.end());
     return GASM_OK;
 }
 
@@ -1308,8 +1364,10 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     }
     // GASM_SCORE_VERIFY=1: compare every read with the contig text where the graph says it lies (kernels_score.hip, graph_match);
     // a mismatch raises flags[2] of the build and pipeline_score_fetch refuses the scores
-    const int verify = env_int("GASM_SCORE_VERIFY", 0);
-    ss.verify = verify != 0;
+    // A graph built with a multiplicity cutoff does not hold every k-mer of every read: the comparison is then part of the match
+    // (verify = 2: a mismatch is "no match" and raises nothing)
+    const int verify = graph.min_count > 1 ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
+    ss.verify = verify == 1;
     const u32 reads_per_wg = 256;     // one read per thread: the match is a chain of dependent loads
     const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);
     // per-path accumulators kept in LDS: sized from the last build of these reads (a segment with more paths than that

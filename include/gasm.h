@@ -79,6 +79,11 @@ int gasm_get_contigs(gasm_ctx* ctx, const char* kmers, uint64_t n_kmers, int dbg
  * mattered: lib/DeNovoAssembler.cpp:91-122 counts them). */
 int gasm_get_contigs_from_reads(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                 int matrix_rows, gasm_contigs** out);
+/* The same with a multiplicity cutoff (gasm_batch_build_solid below): only k-mers seen at least min_count times become edges; the
+ * distinct k-mers handed back are the survivors, with their true multiplicities.  min_count = 1 is gasm_get_contigs_from_reads,
+ * min_count = 0 GASM_ERR_INVALID. */
+int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
+                                      int matrix_rows, uint32_t min_count, gasm_contigs** out);
 uint64_t gasm_contigs_count(const gasm_contigs* c);
 const char* gasm_contigs_data(const gasm_contigs* c);
 const uint64_t* gasm_contigs_offsets(const gasm_contigs* c);       /* count+1 */
@@ -278,6 +283,35 @@ void gasm_batch_free(gasm_batch* b);
  * 2..4 slots, default 3). */
 int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint);
 int gasm_batch_score(gasm_batch* b, int kmer, const double* table);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Solid k-mers: a build with a multiplicity cutoff.  (No counterpart in the reference, whose simulated reads are error-free;
+ * Velvet calls the knob -cov_cutoff.  min_count = 1 is the reference's graph.)
+ * One substituted base in a read makes up to k k-mers that occur once, each a spurious edge.  gasm_batch_build_solid keeps, after
+ * the de-duplication, the distinct k-mers of a segment whose multiplicity IN THAT SEGMENT is >= min_count; everything downstream
+ * — graph, contigs, scores, guided traversal, gasm_batch_fetch_distinct / _graph — sees the survivors only, with their true
+ * multiplicities.  A read scores on a contig iff it is a substring of it: a read that holds a dropped k-mer lies in no contig and
+ * adds nothing.  A segment without survivors behaves like an empty one.
+ *   gasm_batch_build(b, k, hint) is gasm_batch_build_solid(b, k, hint, 1): same results, same kernel launches.
+ *   min_count == 0: GASM_ERR_INVALID.  Each step slot remembers the cutoff of the build it holds.
+ * genome_len_hint for noisy reads: it sizes the buckets for the distinct k-mers BEFORE the cutoff, and reads with errors hold
+ * 5-10x more of them than their genome: about genome length + bases in the segment's reads x error rate x k (every wrong base
+ * makes up to k new k-mers).  A smaller hint (the genome length alone) is still correct: the tables overflow, the build repeats
+ * itself with the next larger configuration (gasm_batch_build_plan: GASM_PLAN_DISTINCT_ATTEMPTS > 1) and filters again.  0 derives
+ * the size from the k-mer count, which is usually large enough.
+ * gasm_batch_fetch_solid_stats   per segment, the distinct k-mers of the last build before and after its cutoff (n_segments entries
+ *                                each; equal when min_count was 1).  Host copies, valid until the next call or build.
+ * gasm_batch_kmer_spectrum       queues the multiplicity histogram of the last build's distinct k-mers (as the build left them: after
+ *                                its cutoff); GASM_ERR_STATE before a build.  It reads the build's arrays only and changes no build
+ *                                or score result.
+ * gasm_batch_fetch_kmer_spectrum hist[s * 256 + m] = distinct k-mers of segment s with multiplicity m; multiplicities >= 255 are
+ *                                counted in bin 255, bin 0 is always 0.  GASM_ERR_STATE without a spectrum of the last build.
+ *                                Intended use: build with min_count = 1, read the spectrum, put the cutoff into the valley between
+ *                                the error peak at 1 and the coverage peak, build again.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int gasm_batch_build_solid(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count);
+int gasm_batch_fetch_solid_stats(gasm_batch* b, const uint64_t** distinct_before, const uint64_t** distinct_after);
+int gasm_batch_kmer_spectrum(gasm_batch* b);
+int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist /* n_segments x 256 */);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
