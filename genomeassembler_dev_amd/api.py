@@ -106,17 +106,23 @@ def get_contigs(read_kmers, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_list
     return _contig_matrix(h, dbg_kmer, as_lists)
 
 
-def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1):
+def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1):
     """get_kmers_from_reads + get_contigs in one call (gasm_get_contigs_from_reads): the k-mers are taken on the GPU from the
     packed reads instead of being exploded into len(reads) * (read_len - k + 1) strings first (lib/DeNovoAssembler.R:109-130).
     reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed).
-    min_count > 1 (gasm_get_contigs_from_reads_solid): only k-mers seen at least min_count times become edges."""
+    min_count > 1 (gasm_get_contigs_from_reads_solid): only k-mers seen at least min_count times become edges.
+    strands = 2 (gasm_get_contigs_from_reads_strands): the k-mers of every read and of its reverse complement."""
     if int(min_count) < 1:
         raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+    if int(strands) not in (1, 2):
+        raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
     ctx = ctx or default_context()
     buf, off = _pack(reads)
     h = C.c_void_p()
-    if int(min_count) == 1:
+    if int(strands) == 2:
+        check(lib().gasm_get_contigs_from_reads_strands(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
+                                                        int(min_count), 2, C.byref(h)))
+    elif int(min_count) == 1:
         check(lib().gasm_get_contigs_from_reads(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows), C.byref(h)))
     else:
         check(lib().gasm_get_contigs_from_reads_solid(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),

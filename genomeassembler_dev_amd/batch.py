@@ -104,13 +104,20 @@ class SegmentBatch:
         self.dropped_reads = int(dropped.value)
         return self
 
-    def build(self, k, genome_len_hint=0, min_count=1):
+    def build(self, k, genome_len_hint=0, min_count=1, strands=1):
         """queue a build.  min_count > 1 (gasm_batch_build_solid): only the k-mers seen at least min_count times in their segment
         become edges — the cutoff for reads with sequencing errors; everything after the build sees the survivors only.
-        genome_len_hint then counts the distinct k-mers before the cutoff (include/gasm.h)."""
+        genome_len_hint then counts the distinct k-mers before the cutoff (include/gasm.h).
+        strands = 2 (gasm_batch_build_strands): the k-mers of every read and of its reverse complement — reads of both strands
+        then meet in one graph, multiplicities (and min_count) are sums over both strands, and the contigs come in
+        reverse-complement pairs (contig_twins).  Scores are over the reads as they were given, each once."""
         if int(min_count) < 1:
             raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-        if int(min_count) == 1:
+        if int(strands) not in (1, 2):
+            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+        if int(strands) == 2:
+            check(lib().gasm_batch_build_strands(self.h, int(k), int(genome_len_hint), int(min_count), 2))
+        elif int(min_count) == 1:
             check(lib().gasm_batch_build(self.h, int(k), int(genome_len_hint)))
         else:
             check(lib().gasm_batch_build_solid(self.h, int(k), int(genome_len_hint), int(min_count)))
@@ -223,11 +230,30 @@ class SegmentBatch:
         raw = C.string_at(data, int(o[-1])) if nc and o[-1] else b""
         return seg, o, raw
 
-    def contigs(self, segment=None):
+    def contigs(self, segment=None, one_per_pair=False):
+        """contig strings per segment (or of one segment).  one_per_pair (after a strands = 2 build): of every contig and its
+        reverse-complement twin only the first is kept (c <= twin[c]: self-twins stay)"""
         seg, o, raw = self.contigs_raw()
         rng = range(self.n_segments) if segment is None else [segment]
-        out = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in rng]
+        tw = self.contig_twins() if one_per_pair else None
+        out = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))
+                if tw is None or c - int(seg[s]) <= int(tw[s][c - int(seg[s])])] for s in rng]
         return out if segment is None else out[0]
+
+    def strands(self):
+        """strands of the last build (0 before the first)"""
+        return int(lib().gasm_batch_strands(self.h))
+
+    def contig_twins(self, segment=None):
+        """after a strands = 2 build: per segment a uint32 array, twin[c] = index in the segment's contig list of the contig
+        that is contig c's reverse complement (gasm_batch_fetch_contig_twins); twin[twin[c]] == c"""
+        p = C.c_void_p()
+        check(lib().gasm_batch_fetch_contig_twins(self.h, C.byref(p)))
+        seg = self.contigs_raw()[0]
+        n = int(seg[-1])
+        tw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        out = [tw[int(seg[s]):int(seg[s + 1])] for s in range(self.n_segments)]
+        return out if segment is None else out[segment]
 
     def scores(self, table=0):
         """dict of per-contig arrays, in contigs_raw() order; table: which table of the last score_tables"""

@@ -58,6 +58,11 @@ struct gasm_batch {
     u32 n_segments = 0;
     u64 n_reads = 0;
     DevReads rd;
+    // strands = 2 builds read this instead: the reads and their reverse complements (DevReads::make_both_strands), made by the first
+    // such build and shared read-only by every step slot; scoring, read k-mer counts and the guided traversal keep `rd`
+    DevReads rd2;
+    // the reads the build a slot holds was made from (whoever finishes, repeats or fetches that build hands them on)
+    DevReads& build_reads(const StepSlot& x) { return x.bs.strands == 2 ? rd2 : rd; }
     // the breakage tables of gasm_batch_score(_tables) (table 0: what gasm_batch_score, gasm_batch_guided and the plain
     // fetches use) and what each was set from (empty: never); a table stays resident until another takes its place
     ScoreTable tb[GASM_MAX_TABLES];
@@ -107,7 +112,7 @@ static int batch_queue_score(gasm_batch* b, StepSlot& x) {
 static int batch_finish(gasm_batch* b) {
     StepSlot& x = b->S();
     bool rebuilt = false;
-    GCHK(pipeline_build_finish(x.cx, b->rd, x.bs, &rebuilt));
+    GCHK(pipeline_build_finish(x.cx, b->build_reads(x), x.bs, &rebuilt));
     if (rebuilt) {
         x.paths_ready = false;
         if (b->scored) {
@@ -148,14 +153,16 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
 // ------------------------------------------------------------------------------------------------- get_contigs
 // reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix
 static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_off, u64 n_reads, u32 fixed_len, int dbg_kmer, int seed, int matrix_rows,
-                            gasm_contigs** out, u32 min_count = 1) {
-    DevReads rd;
+                            gasm_contigs** out, u32 min_count = 1, u32 strands = 1) {
+    DevReads rd, rd2;
     BuildState bs;
     const u64 seg_off[2] = {0, n_reads};
     int st = rd.upload(ctx, bases, read_off, n_reads, fixed_len, seg_off, 1);
-    if (st == GASM_OK) st = pipeline_build(ctx, rd, dbg_kmer, 0, bs, min_count);
-    if (st == GASM_OK) st = pipeline_fetch_distinct(ctx, rd, bs);
-    if (st == GASM_OK) st = pipeline_fetch_contigs(ctx, rd, bs);
+    if (st == GASM_OK && strands == 2) st = rd2.make_both_strands(ctx, rd);
+    DevReads& br = strands == 2 ? rd2 : rd;
+    if (st == GASM_OK) st = pipeline_build(ctx, br, dbg_kmer, 0, bs, min_count, strands);
+    if (st == GASM_OK) st = pipeline_fetch_distinct(ctx, br, bs);
+    if (st == GASM_OK) st = pipeline_fetch_contigs(ctx, br, bs);
     gasm_contigs* c = nullptr;
     if (st == GASM_OK) {
         c = new gasm_contigs();
@@ -168,7 +175,7 @@ static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_of
         // lib/DeNovoAssembler.cpp:195-203
         gasm_host::shuffle_perm(bs.n_contigs, seed, (u64)matrix_rows, c->perm);
     }
-    rd.release();
+    rd.release(); rd2.release();
     bs.release();
     if (st != GASM_OK) return st;
     *out = c;
@@ -204,6 +211,18 @@ int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const ui
     if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
     *out = nullptr;
     return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count);
+    API_GUARD_END
+}
+
+int gasm_get_contigs_from_reads_strands(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
+                                        int matrix_rows, uint32_t min_count, uint32_t strands, gasm_contigs** out) {
+    API_GUARD_BEGIN
+    if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("gasm_get_contigs_from_reads_strands: null argument"); return GASM_ERR_INVALID; }
+    if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
+    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
+    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
+    *out = nullptr;
+    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count, strands);
     API_GUARD_END
 }
 
@@ -770,15 +789,16 @@ void gasm_batch_free(gasm_batch* b) {
     (void)hipSetDevice(b->ctx->device);
     (void)hipStreamSynchronize(b->ctx->stream);
     for (StepSlot& x : b->slot) { if (x.cx && x.cx != b->ctx) (void)hipStreamSynchronize(x.cx->stream); x.bs.release(); x.dp.release(); x.ss.release(); }
-    b->rd.release(); b->guided.release(); b->d_rkc.release();
+    b->rd.release(); b->rd2.release(); b->guided.release(); b->d_rkc.release();
     for (ScoreTable& t : b->tb) t.release();
     delete b;
 }
 
-// gasm_batch_build (min_count = 1) and gasm_batch_build_solid
-static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count) {
+// gasm_batch_build (min_count = 1), gasm_batch_build_solid (strands = 1) and gasm_batch_build_strands
+static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands = 1) {
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
     if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
+    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
     b->built = false; b->scored = false;
     // consecutive steps take the slots in turn: this build does not wait for the last steps' graph and scoring, it runs
     // beside them.  A change of k rewrites the tile tables every slot reads: everything drains first.  GASM_PINGPONG=0: the
@@ -792,7 +812,11 @@ static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t 
     }
     StepSlot& st = b->S();
     st.paths_ready = false; st.ss.valid = false; st.ss.launched = false;
-    GCHK(pipeline_build(st.cx, b->rd, k, genome_len_hint, st.bs, min_count));      // (the slot's BuildState keeps the cutoff of the build it holds)
+    // both strands: the reverse-complemented stream is made once per upload (on this slot's stream, complete before the call
+    // returns: the other slots read it without waiting for this one)
+    if (strands == 2 && b->rd2.strands_of != b->rd.upload_id) GCHK(b->rd2.make_both_strands(st.cx, b->rd));
+    // (the slot's BuildState keeps the cutoff and the strands of the build it holds)
+    GCHK(pipeline_build(st.cx, strands == 2 ? b->rd2 : b->rd, k, genome_len_hint, st.bs, min_count, strands));
     b->last_k = k;
     b->built = true;
     return GASM_OK;
@@ -810,13 +834,33 @@ int gasm_batch_build_solid(gasm_batch* b, int k, uint64_t genome_len_hint, uint3
     API_GUARD_END
 }
 
+int gasm_batch_build_strands(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands) {
+    API_GUARD_BEGIN
+    return batch_build(b, k, genome_len_hint, min_count, strands);
+    API_GUARD_END
+}
+
+uint32_t gasm_batch_strands(const gasm_batch* b) { return b && b->built ? b->S().bs.strands : 0; }
+
+int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin) {
+    API_GUARD_BEGIN
+    if (!b || !twin) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_contig_twins before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    StepSlot& x = b->S();
+    GCHK(pipeline_fetch_contig_twins(x.cx, b->build_reads(x), x.bs));
+    *twin = x.bs.h_twin.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_batch_fetch_solid_stats(gasm_batch* b, const uint64_t** distinct_before, const uint64_t** distinct_after) {
     API_GUARD_BEGIN
     if (!b || !distinct_before || !distinct_after) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("gasm_batch_fetch_solid_stats before a build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
     BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_solid_stats(b->S().cx, b->rd, bs));
+    GCHK(pipeline_fetch_solid_stats(b->S().cx, b->build_reads(b->S()), bs));
     *distinct_before = bs.h_solid_before.data(); *distinct_after = bs.h_solid_after.data();
     return GASM_OK;
     API_GUARD_END
@@ -827,7 +871,7 @@ int gasm_batch_kmer_spectrum(gasm_batch* b) {
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("gasm_batch_kmer_spectrum before a build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    return pipeline_kmer_spectrum(b->S().cx, b->rd, b->S().bs);
+    return pipeline_kmer_spectrum(b->S().cx, b->build_reads(b->S()), b->S().bs);
     API_GUARD_END
 }
 
@@ -836,7 +880,7 @@ int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist) {
     if (!b || !hist) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("gasm_batch_fetch_kmer_spectrum before a build"); return GASM_ERR_STATE; }
     BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_kmer_spectrum(b->S().cx, b->rd, bs));
+    GCHK(pipeline_fetch_kmer_spectrum(b->S().cx, b->build_reads(b->S()), bs));
     *hist = bs.h_spectrum.data();
     return GASM_OK;
     API_GUARD_END
@@ -961,7 +1005,7 @@ int gasm_batch_build_plan(gasm_batch* b, int32_t* out, int n) {
     if (!b || n < 0 || (n > 0 && !out)) { gasm_set_error("gasm_batch_build_plan: bad argument"); return GASM_ERR_INVALID; }
     if (!b->built) { gasm_set_error("gasm_batch_build_plan before gasm_batch_build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
-    if (n >= GASM_PLAN_FIELDS) pipeline_build_plan(b->rd, b->S().bs, out);
+    if (n >= GASM_PLAN_FIELDS) pipeline_build_plan(b->rd, b->S().bs, out);      // (reads: the number of segments only)
     return 1;
     API_GUARD_END
 }
@@ -1054,7 +1098,7 @@ int gasm_batch_fetch_distinct(gasm_batch* b, const uint64_t** seg_off, const uin
     if (!b->built) { gasm_set_error("fetch before build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
     BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_distinct(b->S().cx, b->rd, bs));
+    GCHK(pipeline_fetch_distinct(b->S().cx, b->build_reads(b->S()), bs));
     *words = bs.words;
     *seg_off = bs.h_seg_doff.data(); *keys = bs.h_dk_key.data(); *mult = bs.h_dk_cnt.data();
     return GASM_OK;
@@ -1067,7 +1111,7 @@ int gasm_batch_fetch_graph(gasm_batch* b, const uint8_t** edge_flags, const uint
     if (!b->built) { gasm_set_error("fetch before build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
     BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_graph(b->S().cx, b->rd, bs));
+    GCHK(pipeline_fetch_graph(b->S().cx, b->build_reads(b->S()), bs));
     *edge_flags = bs.h_eflag.data(); *edge_next = bs.h_nxt.data();
     return GASM_OK;
     API_GUARD_END
@@ -1079,7 +1123,7 @@ int gasm_batch_fetch_contigs(gasm_batch* b, const uint64_t** seg_contig_off, con
     if (!b->built) { gasm_set_error("fetch before build"); return GASM_ERR_STATE; }
     GCHK(batch_finish(b));
     BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_contigs(b->S().cx, b->rd, bs));
+    GCHK(pipeline_fetch_contigs(b->S().cx, b->build_reads(b->S()), bs));
     *seg_contig_off = bs.h_seg_coff.data(); *off = bs.h_c_off.data(); *data = bs.h_contigs.data();
     return GASM_OK;
     API_GUARD_END

@@ -129,6 +129,13 @@ __global__ void k_contig_place(GraphView gv, const u8* eflag, const u32* seg_cst
                                u64* c_off, u32 n_segments, u32 chunks);
 template <class K>
 __global__ void k_contig_emit(GraphView gv, const u64* link, const u32* nxt, const u64* e_coff, u8* out, u32 n_segments, u32 chunks);
+// both strands (strands = 2): every segment's reads followed by their reverse complements, into a zeroed stream; g threads per read
+__global__ void k_reads_both_strands(const u64* words, const u64* read_off, const u64* seg_read_off, u32 fixed_len, u32 n_segments, u64 n_reads, u32 g,
+                                     unsigned long long* out);
+// twin[c] = index inside its segment of the contig that is contig c's reverse complement; *bad |= 1 where there is none
+template <class K>
+__global__ void k_contig_twin(GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, u32 n_segments,
+                              u32* twin, u32* bad);
 
 // ---- kernels_pool.hip
 template <class K>

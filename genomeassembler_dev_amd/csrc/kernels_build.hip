@@ -1596,3 +1596,91 @@ __global__ void __launch_bounds__(GASM_WG) k_contig_emit(GraphView gv, const u64
 }
 template __global__ void k_contig_emit<u64>(GraphView, const u64*, const u32*, const u64*, u8*, u32, u32);
 template __global__ void k_contig_emit<K128>(GraphView, const u64*, const u32*, const u64*, u8*, u32, u32);
+
+// ================================================================================================================
+// Both strands (gasm_batch_build_strands, strands = 2).  No counterpart in the reference's assembler: its simulator writes
+// read_2 as reverse complements (lib/GenerateReads.R:438) and the assembler then takes them as they are.
+//
+// k_reads_both_strands makes the build-only read stream: segment s holds its n_s reads followed by their n_s reverse
+// complements (reversed, A<->T and C<->G: 3 - x in the 2-bit code).  Read r of segment s, at base off(r) of the source,
+// goes to base off(r) + off(first read of s) and its reverse complement to base off(r) + off(first read of s + 1), where
+// off(r) = r * fixed_len or read_off[r]: the same formula for both layouts, and the reverse complements keep the order
+// of their reads.  `g` threads (a power of two) share a read and take its 32-base pieces in turn; a piece is one
+// window32 of the source, OR-ed into the one or two words it falls into (the stream was zeroed, padding words included).
+// Piece j of the reverse complement is the window that ENDS 32 j bases before the read's end: its 2-bit groups reversed
+// (__brevll reverses the bits, so the two bits of every group are swapped back), complemented, and what lies beyond the
+// read's first base masked away.
+// ================================================================================================================
+__device__ __forceinline__ void or_piece(unsigned long long* __restrict__ out, u64 d0, u64 v) {
+    const u32 sh = (u32)(d0 & 31) << 1;
+    atomicOr(&out[d0 >> 5], v >> sh);
+    if (sh && (v << (64 - sh))) atomicOr(&out[(d0 >> 5) + 1], v << (64 - sh));
+}
+
+__global__ void __launch_bounds__(GASM_WG) k_reads_both_strands(const u64* __restrict__ words, const u64* __restrict__ read_off, const u64* __restrict__ seg_read_off,
+                                                                u32 fixed_len, u32 n_segments, u64 n_reads, u32 g, unsigned long long* __restrict__ out) {
+    const u32 sub = threadIdx.x & (g - 1);
+    for (u64 r = ((u64)blockIdx.x * GASM_WG + threadIdx.x) / g; r < n_reads; r += (u64)gridDim.x * GASM_WG / g) {
+        const u32 s = upper_seg<u64>(seg_read_off, n_segments, r);        // (empty segments repeat an offset: the last of them is r's)
+        const u64 ra = seg_read_off[s], rb = seg_read_off[s + 1];
+        u64 p0, d_fwd, d_rc;
+        u32 len;
+        if (fixed_len) { p0 = r * fixed_len; len = fixed_len; d_fwd = p0 + ra * fixed_len; d_rc = p0 + rb * fixed_len; }
+        else { p0 = read_off[r]; len = (u32)(read_off[r + 1] - p0); d_fwd = p0 + read_off[ra]; d_rc = p0 + read_off[rb]; }
+        for (u32 j = sub; 32ull * j < len; j += g) {
+            const u32 at = 32u * j, nb = min(32u, len - at);
+            const u64 keep = ~0ull << (64 - 2 * nb);                      // the piece's nb bases (nb >= 1)
+            or_piece(out, d_fwd + at, window32(words, p0 + at) & keep);
+            // reverse complement: source bases [len - at - nb, len - at), last one first
+            u64 v = window32(words, p0 + (len - at - nb)) & keep;
+            v = __brevll(v);                                              // base i of the window: group 31 - i, its two bits swapped
+            v = ((v >> 1) & 0x5555555555555555ull) | ((v & 0x5555555555555555ull) << 1);
+            v <<= 64 - 2 * nb;                                            // the window's last base first
+            or_piece(out, d_rc + at, ~v & keep);
+        }
+    }
+}
+
+// ================================================================================================================
+// Twin map of a both-strand build: twin[c] = the contig of the same segment whose text is the reverse complement of
+// contig c's, as an index inside the segment.  The branching rule (lib/DeNovoAssembler.cpp:161-189) treats a node and its
+// reverse complement alike when the k-mer set is closed under reverse complement, so that contig exists, and it starts
+// with the reverse complement of c's last k bases: one k-mer -> one edge (bucket, fine bin, key, as graph_match does)
+// -> (head, distance) from the list ranking -> contig.  The distance must be 0 and the contig of the same segment; anything
+// else raises *bad (the fetch turns it into an error).  One thread per contig; the contig's last k bases come from
+// its text.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_contig_twin(GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
+                                                         const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, const u8* __restrict__ text,
+                                                         u32 n_segments, u32* __restrict__ twin, u32* __restrict__ bad) {
+    const u32 n = seg_cstart[n_segments];
+    for (u32 c = blockIdx.x * GASM_WG + threadIdx.x; c < n; c += gridDim.x * GASM_WG) {
+        const u32 seg = upper_seg<u32>(seg_cstart, n_segments, c);
+        const u64 end = c_off[c + 1];
+        K key = key_from_u64<K>(0);
+        bool ok = end - c_off[c] >= (u64)gv.k;
+        for (int i = 0; ok && i < gv.k; ++i)                              // base i of the twin's first k-mer = complement of base end - 1 - i
+            key = kor(kshl(key, 2), key_from_u64<K>(3u - base_code(text[end - 1 - i])));
+        u32 t = GASM_NONE32;
+        if (ok) {
+            u32 hi;
+            const u32 e = graph_lower_bound<K>(gv, seg, key, &hi);
+            ok = e < hi && keq(reinterpret_cast<const K*>(gv.dk_key)[e], key);
+            if (ok) {
+                const u64 l = link[e];
+                const u32 a = (u32)(l >> 32);
+                ok = a != GASM_NONE32 && (l & GASM_LINK_DONE) && ((u32)l & 0x7FFFFFFFu) == 0;
+                if (ok) {
+                    const u32 c2 = e_cid[a];
+                    ok = c2 >= seg_cstart[seg] && c2 < seg_cstart[seg + 1];
+                    if (ok) t = c2 - seg_cstart[seg];
+                }
+            }
+        }
+        twin[c] = t;
+        if (!ok) atomicOr(bad, 1u);
+    }
+}
+template __global__ void k_contig_twin<u64>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
+template __global__ void k_contig_twin<K128>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);

@@ -33,6 +33,10 @@ struct DevReads {
     int set_layout(const u64* read_off, u64 n_reads, u32 fixed_len, const u64* seg_read_off, u32 n_segments);
     int finish_upload(gasm_ctx* ctx);
     int set_tiles(gasm_ctx* ctx, u32 ipt, u32 orr);
+    // this = the both-strand form of `src` (gasm_batch_build_strands, strands = 2): every segment's reads followed by their reverse
+    // complements, same layout kind (k_reads_both_strands).  Build-only: scorers keep `src`.  Complete before it returns.
+    int make_both_strands(gasm_ctx* ctx, const DevReads& src);
+    u64 strands_of = 0;                     // upload_id of the reads this stream was made from by make_both_strands (0: none)
     ReadSet view() const;
     u64 read_len(u64 r) const { return fixed_len ? fixed_len : h_read_off[r + 1] - h_read_off[r]; }
     void release();
@@ -75,6 +79,8 @@ struct BuildState {
     u64 n_kmers = 0, hint = 0, reads_id = 0;
     u32 min_count = 1;                      // multiplicity cutoff of this build (gasm_batch_build_solid): every attempt of the retry ladder
                                             // filters with it (k_bucket_solid behind the de-duplication), and scores of its graph compare bases
+    u32 strands = 1;                        // 2: built from the reads and their reverse complements (the caller handed pipeline_build the
+                                            // both-strand DevReads); the twin map exists for such a build only
     std::vector<u64> h_seg_nk;              // k-mers per segment
     // upper bounds the arrays are allocated at, and estimates the grids are sized from (the kernels loop beyond them)
     u64 D_cap = 0, maxD_cap = 0, bases_cap = 0;
@@ -102,6 +108,9 @@ struct BuildState {
     DBuf d_keys, d_mult, d_hist, d_toff, d_tcnt, d_fdir, d_bstart, d_bucket_d, d_dstart, d_flags, d_rtab;
     DBuf d_solid_removed;                   // min_count > 1: distinct k-mers the cutoff removed, per segment (u32, zeroed with every attempt)
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
+    DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
+    std::vector<u32> h_twin;
+    bool fetched_twins = false;
     DBuf d_dk_key, d_dk_cnt, d_eflag, d_nxt, d_link, d_clen, d_ecid, d_ecoff;
     DBuf d_seg_cbases, d_seg_cstart, d_seg_bstart, d_c_off, d_contig_ascii;
     // host copies filled by fetch
@@ -156,7 +165,10 @@ struct ScoreState {
 // queued behind the first attempt must be queued again).
 // min_count > 1: only the distinct k-mers seen at least min_count times in their segment enter the graph (1: all of them, and not
 // a launch more than without the argument)
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1);
+// strands = 2: `rd` is the both-strand form of the batch's reads (DevReads::make_both_strands) and must be handed to every later
+// call that takes this build's reads (finish, fetches); genome_len_hint still means the genome: the estimate of the distinct
+// k-mers is doubled here
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1, u32 strands = 1);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
 // one row of gasm_batch_build_plan (GASM_PLAN_FIELDS words, include/gasm.h) from a finished build's host fields
@@ -174,6 +186,9 @@ int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// twin map of a finished strands = 2 build (k_contig_twin, once per build): h_twin[c] = index inside its segment of the contig that
+// is contig c's reverse complement.  GASM_ERR_STATE after a strands = 1 build, GASM_ERR_INTERNAL if a contig has no twin
+int pipeline_fetch_contig_twins(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_graph(gasm_ctx* ctx, DevReads& rd, BuildState& bs);    // h_eflag / h_nxt: per-edge flags and successors
 // paths of the build as a DevPaths (packs the contig text on the device; works on a queued build); the host-side numbers
 // of the same paths once the build's report has been read

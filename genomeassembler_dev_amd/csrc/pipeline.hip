@@ -361,6 +361,41 @@ int DevReads::set_tiles(gasm_ctx* ctx, u32 ipt, u32 orr) {
     return GASM_OK;
 }
 
+// Both strands: the reads of `src` and their reverse complements as a read set of its own, segment by segment (forward reads,
+// then their reverse complements in the same order).  Like the tile table it is shared read-only by every step slot of a
+// batch, so it is complete — stream and directories — before this returns.
+int DevReads::make_both_strands(gasm_ctx* ctx, const DevReads& src) {
+    if (src.positioned) { gasm_set_error("both-strand builds of pooled reads are not supported"); return GASM_ERR_STATE; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 S = src.n_segments;
+    const u64 n = src.n_reads;
+    std::vector<u64> seg2((size_t)S + 1), off2;
+    for (u32 s = 0; s <= S; ++s) seg2[s] = 2 * src.h_seg_read_off[s];
+    if (!src.fixed_len) {
+        off2.resize(2 * n + 1);
+        u64 at = 0, w = 0;
+        off2[0] = 0;
+        for (u32 s = 0; s < S; ++s)
+            for (int pass = 0; pass < 2; ++pass)
+                for (u64 r = src.h_seg_read_off[s]; r < src.h_seg_read_off[s + 1]; ++r) { at += src.h_read_off[r + 1] - src.h_read_off[r]; off2[++w] = at; }
+    }
+    GCHK(set_layout(src.fixed_len ? nullptr : off2.data(), 2 * n, src.fixed_len, seg2.data(), S));
+    const u64 nw = (total_bases + 31) / 32;
+    GCHK(d_words.ensure((nw + 4) * 8));
+    HIPCHK(hipMemsetAsync(d_words.p, 0, (nw + 4) * 8, ctx->stream));
+    if (n && src.total_bases) {
+        // threads per read: a power of two that covers the longest read's 32-base pieces, 64 at most (longer reads: rounds)
+        const u32 g = std::min(64u, next_pow2_u32((src.max_len + 31) / 32));
+        const u32 grid = (u32)std::min<u64>((n * g + GASM_WG - 1) / GASM_WG, (u64)ctx->n_cu * 64);
+        GLAUNCH(ctx, "k_reads_both_strands", k_reads_both_strands, dim3(std::max(1u, grid)), dim3(GASM_WG), 0, src.d_words.as<u64>(),
+                src.fixed_len ? (const u64*)nullptr : src.d_read_off.as<u64>(), src.d_seg_read_off.as<u64>(), src.fixed_len, S, n, g,
+                d_words.as<unsigned long long>());
+    }
+    GCHK(finish_upload(ctx));           // (directories up, stream drained, an upload_id of its own)
+    strands_of = src.upload_id;
+    return GASM_OK;
+}
+
 ReadSet DevReads::view() const {
     ReadSet v;
     v.words = d_words.as<u64>();
@@ -433,7 +468,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_spectrum, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -862,10 +897,15 @@ static void zero_results(BuildState& bs, u32 S) {
     bs.d_total = 0; bs.n_contigs = 0; bs.contig_bases = 0;
 }
 
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count) {
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count, u32 strands) {
     if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
-    GCHK(plan_build(ctx, rd, k, hint, bs));
+    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
+    if (strands == 2 && !rd.strands_of) { gasm_set_error("a both-strand build needs the both-strand reads"); return GASM_ERR_STATE; }
+    // (both strands: up to twice the distinct k-mers of the genome; without a hint the estimate follows the doubled k-mer count)
+    GCHK(plan_build(ctx, rd, k, strands == 2 ? 2 * hint : hint, bs));
     bs.min_count = min_count;
+    bs.strands = strands;
+    bs.fetched_twins = false;
     bs.spectrum_queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
@@ -1022,6 +1062,35 @@ int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     HIPCHK(hipMemcpyAsync(h.data(), bs.d_spectrum.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     bs.h_spectrum.assign(h.begin(), h.end());
+    return GASM_OK;
+}
+
+// twin map of a both-strand build: k_contig_twin on the build's stream behind it, once per build; reads the directory, the
+// ranking's links, the contig ids and the contig text, writes an array of its own
+int pipeline_fetch_contig_twins(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    if (bs.strands != 2) { gasm_set_error("the twin map exists after a strands = 2 build only"); return GASM_ERR_STATE; }
+    if (bs.fetched_twins) return GASM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 P = bs.n_contigs;
+    bs.h_twin.assign(P, 0);
+    if (P) {
+        GCHK(bs.d_twin.ensure(((size_t)P + 1) * 4));
+        u32* const d_bad = bs.d_twin.as<u32>() + P;
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, ctx->stream));
+        const GraphView gv = graph_view(bs);
+        const u32 grid = (u32)std::min<u64>(ceil_div_u64(P, GASM_WG), (u64)ctx->n_cu * 8);
+        if (bs.words == 1) GLAUNCH(ctx, "k_contig_twin", k_contig_twin<u64>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
+                                   bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), rd.n_segments, bs.d_twin.as<u32>(), d_bad);
+        else GLAUNCH(ctx, "k_contig_twin", k_contig_twin<K128>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
+                     bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), rd.n_segments, bs.d_twin.as<u32>(), d_bad);
+        std::vector<u32> h((size_t)P + 1);
+        HIPCHK(hipMemcpyAsync(h.data(), bs.d_twin.p, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (h[P]) { gasm_set_error("a contig of a both-strand build has no reverse-complement twin in its segment"); return GASM_ERR_INTERNAL; }
+        bs.h_twin.assign(h.begin(), h.begin() + P);
+    }
+    bs.fetched_twins = true;
     return GASM_OK;
 }
 

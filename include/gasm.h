@@ -36,7 +36,8 @@ typedef enum gasm_status {
     GASM_ERR_HIP = -4,        /* HIP runtime error during a call */
     GASM_ERR_CAPACITY = -5,   /* input exceeds a documented limit */
     GASM_ERR_RANGE = -6,      /* the reference would throw std::out_of_range here (substr past the end) */
-    GASM_ERR_STATE = -7       /* call order violated (e.g. score before build) */
+    GASM_ERR_STATE = -7,      /* call order violated (e.g. score before build) */
+    GASM_ERR_INTERNAL = -8    /* a result contradicts an invariant of the library (a bug: please report it) */
 } gasm_status;
 
 #define GASM_MAX_K 63          /* k-mer keys are 64-bit for k <= 31 and 128-bit for 32 <= k <= 63 */
@@ -84,6 +85,10 @@ int gasm_get_contigs_from_reads(gasm_ctx* ctx, const char* reads, const uint64_t
  * min_count = 0 GASM_ERR_INVALID. */
 int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                       int matrix_rows, uint32_t min_count, gasm_contigs** out);
+/* The same from both strands (gasm_batch_build_strands below): strands = 2 adds the reverse complement of every read before the
+ * k-mers are taken; strands = 1 is gasm_get_contigs_from_reads_solid, anything else GASM_ERR_INVALID. */
+int gasm_get_contigs_from_reads_strands(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
+                                        int matrix_rows, uint32_t min_count, uint32_t strands, gasm_contigs** out);
 uint64_t gasm_contigs_count(const gasm_contigs* c);
 const char* gasm_contigs_data(const gasm_contigs* c);
 const uint64_t* gasm_contigs_offsets(const gasm_contigs* c);       /* count+1 */
@@ -312,6 +317,38 @@ int gasm_batch_build_solid(gasm_batch* b, int k, uint64_t genome_len_hint, uint3
 int gasm_batch_fetch_solid_stats(gasm_batch* b, const uint64_t** distinct_before, const uint64_t** distinct_after);
 int gasm_batch_kmer_spectrum(gasm_batch* b);
 int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist /* n_segments x 256 */);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Both strands: a build from the reads and their reverse complements.  (No counterpart in the reference's assembler, which takes
+ * its k-mers forward-strand only; its simulator writes read_2 as reverse complements, lib/GenerateReads.R:438.  Velvet's "twin"
+ * nodes.  strands = 1 is the reference's graph and the default everywhere.)
+ * A sequencer reads both strands; forward-only k-mers make two unconnected half-coverage graphs of such reads.  With strands = 2
+ * a build sees, for every read r of a segment, the k-mers of r and the k-mers of rc(r) (r reversed, A<->T and C<->G swapped), and
+ * everything behind the de-duplication sees that multiset:
+ *   - the multiplicity of a k-mer x is count(x) + count(rc(x)) over the segment's reads; a k-mer that is its own reverse
+ *     complement (even k only) therefore counts TWICE per occurrence;
+ *   - min_count applies to these sums; gasm_batch_fetch_solid_stats, the k-mer spectrum, gasm_batch_fetch_distinct and
+ *     gasm_batch_fetch_graph report the both-strand set; gasm_batch_total_kmers is twice the forward count;
+ *   - the contigs of a segment are closed under reverse complement: the twin of every contig is a contig of the same segment
+ *     (the branching rule treats a node and its reverse complement alike); a contig may be its own twin (even k).
+ * Scoring is over the ORIGINAL reads only, each once: a read scores on a contig iff it is a substring of it, so a reverse-strand
+ * read scores on the twin of the contig its forward form lies in.  The fixed-point shift is unchanged (it depends on the most
+ * reads of a segment).  The guided traversal works on such a build as on any other.
+ * gasm_batch_build_strands        strands = 1 is gasm_batch_build_solid: same host path, same kernel launches; strands = 2 as above;
+ *                                 anything else GASM_ERR_INVALID.  genome_len_hint keeps meaning the genome's length (for noisy
+ *                                 reads: see above); the library doubles its own estimate of the distinct k-mers.  The
+ *                                 reverse-complemented read stream is made once per batch, by the first strands = 2 build, and
+ *                                 costs as much device memory again as the packed reads.  Each step slot remembers the strands
+ *                                 of the build it holds, as it remembers the cutoff.
+ * gasm_batch_strands              strands of the last build (0 before the first).
+ * gasm_batch_fetch_contig_twins   twin[c] = the index, INSIDE ITS SEGMENT, of the contig whose text is rc(contig c); one entry per
+ *                                 contig in the order of gasm_batch_fetch_contigs; an involution; twin[c] == c for a self-twin.
+ *                                 Host copy, valid until the next build.  GASM_ERR_STATE before a build or after a strands = 1
+ *                                 build; GASM_ERR_INTERNAL if a contig has no twin (the closure above would be broken).
+ * Pooled builds (gasm_pool_*) are forward-strand only.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int gasm_batch_build_strands(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands);
+uint32_t gasm_batch_strands(const gasm_batch* b);
+int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
@@ -365,6 +402,7 @@ int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read
  * bytes hi:lo for k <= 63, sorted inside a run) and 32-bit counts; the bucket a run belongs to follows from its place in
  * the bucket lists both sides derive from the ownership function.  Results do not depend on the number of ranks.
  *
+ *   (pooled builds take their k-mers forward-strand only: there is no strands argument here)
  *   gasm_pool_create       this rank's reads (fixed length) of ALL n_segments segments
  *   gasm_pool_local_runs   k-mers of those reads -> one sorted run of distinct (key, count) per bucket; bucket index =
  *                          segment << bbits | first bbits bits of the k-mer; run_len (host, n_segments << bbits entries)

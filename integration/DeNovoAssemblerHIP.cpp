@@ -67,11 +67,17 @@ std::vector<std::vector<std::string>> get_contigs(const std::vector<std::string>
 // get_kmers_from_reads (lib/DeNovoAssembler.R:109-130) + get_contigs in one call: the reads go down as they are and the
 // k-mers are taken on the GPU (self$read_kmers need not exist; in DeNovoAssembler.R: get_contigs_from_reads(
 // self$sequencing_reads$read_one, self$dbg_kmer, self$seed) in place of the two steps)
+// strands (optional, default 1 = the reference's forward-strand k-mers): 2 adds the reverse complement of every read before
+// the k-mers are taken (gasm_get_contigs_from_reads_strands) — for read sets that hold both strands, such as read_one and
+// read_two of lib/GenerateReads.R:438 together; the contigs then come in reverse-complement pairs
 // [[Rcpp::export]]
-std::vector<std::vector<std::string>> get_contigs_from_reads(const std::vector<std::string>& reads, const int& dbg_kmer, const int& seed) {
+std::vector<std::vector<std::string>> get_contigs_from_reads(const std::vector<std::string>& reads, const int& dbg_kmer, const int& seed,
+                                                             const int& strands = 1) {
+    if (strands != 1 && strands != 2) Rcpp::stop("strands must be 1 or 2");
     Flat f(reads);
     gasm_contigs* c = nullptr;
-    check(gasm_get_contigs_from_reads(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, &c));
+    if (strands == 2) check(gasm_get_contigs_from_reads_strands(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, 2, &c));
+    else check(gasm_get_contigs_from_reads(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, &c));
     const uint64_t n = gasm_contigs_count(c), rows = gasm_contigs_rows(c);
     std::vector<std::string> contigs = unflat(gasm_contigs_data(c), gasm_contigs_offsets(c), n);
     const uint32_t* perm = gasm_contigs_perm(c);
