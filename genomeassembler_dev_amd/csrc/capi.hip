@@ -125,22 +125,25 @@ static int batch_finish(gasm_batch* b) {
     return GASM_OK;
 }
 
-#define API_GUARD_BEGIN try {
-#define API_GUARD_END                                                          \
-    } catch (const std::bad_alloc&) {                                          \
-        gasm_set_error("out of host memory");                                  \
-        return GASM_ERR_CAPACITY;                                              \
-    } catch (const std::exception& e) {                                        \
-        gasm_set_error("internal error: %s", e.what());                        \
-        return GASM_ERR_INVALID;                                               \
-    }
-
 static void strlist_from(const std::vector<std::string>& v, std::vector<char>& data, std::vector<u64>& off) {
     off.assign(v.size() + 1, 0);
     size_t tot = 0;
     for (size_t i = 0; i < v.size(); ++i) { tot += v[i].size(); off[i + 1] = tot; }
     data.resize(tot);
     for (size_t i = 0; i < v.size(); ++i) memcpy(data.data() + off[i], v[i].data(), v[i].size());
+}
+
+// a new batch of `ctx` whose reads `fill(batch)` puts in place; handed out only if that succeeded
+template <class F>
+static int new_batch(gasm_ctx* ctx, u32 n_segments, u64 n_reads, gasm_batch** out, F&& fill) {
+    gasm_batch* b = new gasm_batch();
+    b->ctx = ctx;
+    b->n_segments = n_segments;
+    b->n_reads = n_reads;
+    const int st = fill(b);
+    if (st != GASM_OK) { gasm_batch_free(b); return st; }
+    *out = b;
+    return GASM_OK;
 }
 
 extern "C" {
@@ -182,6 +185,17 @@ static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_of
     return GASM_OK;
 }
 
+// the argument checks the gasm_get_contigs_from_reads* entries share; `entry`: the one that was called
+static int check_from_reads_args(const char* entry, const gasm_ctx* ctx, const char* reads, const u64* read_off, u64 n_reads, int matrix_rows, u32 min_count,
+                                 u32 strands, gasm_contigs** out) {
+    if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("%s: null argument", entry); return GASM_ERR_INVALID; }
+    if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
+    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
+    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
+    *out = nullptr;
+    return GASM_OK;
+}
+
 int gasm_get_contigs(gasm_ctx* ctx, const char* kmers, uint64_t n_kmers, int dbg_kmer, int seed, int matrix_rows,
                      gasm_contigs** out) {
     API_GUARD_BEGIN
@@ -196,9 +210,7 @@ int gasm_get_contigs(gasm_ctx* ctx, const char* kmers, uint64_t n_kmers, int dbg
 int gasm_get_contigs_from_reads(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                 int matrix_rows, gasm_contigs** out) {
     API_GUARD_BEGIN
-    if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("gasm_get_contigs_from_reads: null argument"); return GASM_ERR_INVALID; }
-    if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
-    *out = nullptr;
+    GCHK(check_from_reads_args("gasm_get_contigs_from_reads", ctx, reads, read_off, n_reads, matrix_rows, 1, 1, out));
     return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out);
     API_GUARD_END
 }
@@ -206,10 +218,7 @@ int gasm_get_contigs_from_reads(gasm_ctx* ctx, const char* reads, const uint64_t
 int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                       int matrix_rows, uint32_t min_count, gasm_contigs** out) {
     API_GUARD_BEGIN
-    if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("gasm_get_contigs_from_reads_solid: null argument"); return GASM_ERR_INVALID; }
-    if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
-    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
-    *out = nullptr;
+    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_solid", ctx, reads, read_off, n_reads, matrix_rows, min_count, 1, out));
     return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count);
     API_GUARD_END
 }
@@ -217,11 +226,7 @@ int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const ui
 int gasm_get_contigs_from_reads_strands(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                         int matrix_rows, uint32_t min_count, uint32_t strands, gasm_contigs** out) {
     API_GUARD_BEGIN
-    if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("gasm_get_contigs_from_reads_strands: null argument"); return GASM_ERR_INVALID; }
-    if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
-    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
-    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
-    *out = nullptr;
+    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_strands", ctx, reads, read_off, n_reads, matrix_rows, min_count, strands, out));
     return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count, strands);
     API_GUARD_END
 }
@@ -638,28 +643,14 @@ int gasm_batch_create(gasm_ctx* ctx, const char* reads, const uint64_t* read_off
     if (n_segments == 0 || !seg_read_off) { gasm_set_error("need at least one segment and seg_read_off"); return GASM_ERR_INVALID; }
     if (seg_read_off[0] != 0 || seg_read_off[n_segments] != n_reads) { gasm_set_error("seg_read_off must run from 0 to n_reads"); return GASM_ERR_INVALID; }
     for (u32 s = 0; s < n_segments; ++s) if (seg_read_off[s] > seg_read_off[s + 1]) { gasm_set_error("seg_read_off not monotone"); return GASM_ERR_INVALID; }
-    gasm_batch* b = new gasm_batch();
-    b->ctx = ctx;
-    b->n_segments = n_segments;
-    b->n_reads = n_reads;
-    const int st = b->rd.upload(ctx, reads, read_off, n_reads, fixed_len, seg_read_off, n_segments);
-    if (st != GASM_OK) { gasm_batch_free(b); return st; }
-    *out = b;
-    return GASM_OK;
+    return new_batch(ctx, n_segments, n_reads, out, [&](gasm_batch* b) { return b->rd.upload(ctx, reads, read_off, n_reads, fixed_len, seg_read_off, n_segments); });
     API_GUARD_END
 }
 
 // a batch from reads that are packed already
 static int batch_from_packed(gasm_ctx* ctx, const u64* words, const u64* read_off, u64 n_reads, u32 fixed_len, const u64* seg_read_off,
                              u32 n_segments, gasm_batch** out) {
-    gasm_batch* b = new gasm_batch();
-    b->ctx = ctx;
-    b->n_segments = n_segments;
-    b->n_reads = n_reads;
-    const int st = b->rd.upload_packed(ctx, words, read_off, n_reads, fixed_len, seg_read_off, n_segments);
-    if (st != GASM_OK) { gasm_batch_free(b); return st; }
-    *out = b;
-    return GASM_OK;
+    return new_batch(ctx, n_segments, n_reads, out, [&](gasm_batch* b) { return b->rd.upload_packed(ctx, words, read_off, n_reads, fixed_len, seg_read_off, n_segments); });
 }
 
 int gasm_batch_create_packed(gasm_ctx* ctx, const uint64_t* words, const uint64_t* read_off, uint64_t n_reads, uint32_t fixed_len,
@@ -741,14 +732,7 @@ int gasm_batch_from_files(gasm_ctx* ctx, const char* const* paths, uint32_t n_fi
     u32 flen = n ? (u32)std::min<u64>(read_off[1], 0xFFFFFFFFull) : 0;
     bool fixed = n > 0 && flen > 0;
     for (u64 r = 0; fixed && r < n; ++r) fixed = read_off[r + 1] - read_off[r] == flen;
-    gasm_batch* b = new gasm_batch();
-    b->ctx = ctx;
-    b->n_segments = n_files;
-    b->n_reads = n;
-    const int st = b->rd.adopt_packed(ctx, d_words, fixed ? nullptr : read_off.data(), n, fixed ? flen : 0, seg.data(), n_files);
-    if (st != GASM_OK) { gasm_batch_free(b); return st; }
-    *out = b;
-    return GASM_OK;
+    return new_batch(ctx, n_files, n, out, [&](gasm_batch* b) { return b->rd.adopt_packed(ctx, d_words, fixed ? nullptr : read_off.data(), n, fixed ? flen : 0, seg.data(), n_files); });
     API_GUARD_END
 }
 
@@ -757,15 +741,12 @@ int gasm_batch_simulate(gasm_ctx* ctx, const char* genomes, const uint64_t* geno
     API_GUARD_BEGIN
     if (!ctx || !out || !genomes || !genome_off) { gasm_set_error("gasm_batch_simulate: null argument"); return GASM_ERR_INVALID; }
     *out = nullptr;
-    gasm_batch* b = new gasm_batch();
-    b->ctx = ctx;
-    b->n_segments = n_segments;
-    const int st = b->rd.simulate(ctx, genomes, genome_off, n_segments, read_len, coverage, seed, kmer, table, b->d_read_start);
-    if (st != GASM_OK) { gasm_batch_free(b); return st; }
-    b->n_reads = b->rd.n_reads;
-    b->h_sim_seg_off = b->rd.h_seg_read_off;
-    *out = b;
-    return GASM_OK;
+    return new_batch(ctx, n_segments, 0, out, [&](gasm_batch* b) {
+        GCHK(b->rd.simulate(ctx, genomes, genome_off, n_segments, read_len, coverage, seed, kmer, table, b->d_read_start));
+        b->n_reads = b->rd.n_reads;
+        b->h_sim_seg_off = b->rd.h_seg_read_off;
+        return (int)GASM_OK;
+    });
     API_GUARD_END
 }
 

@@ -119,7 +119,8 @@ struct RankX {                 // exchange state of one local rank
     DBuf d_nr, d_nr_all, d_rdir, send_words, recv_words;
     DBuf d_part_saved;         // the partition's region layout (BuildState::d_bstart) while the merges use that slot
     bool part_saved = false;
-    u64* rep = nullptr;        // pinned: two reports of 2 W + 6 words
+    u64* rep = nullptr;        // pinned: the reports of the two plans (XReport), back to back
+    XReport<const u64> report(int plan, u32 W) const { return {rep + (size_t)plan * XReport<u64>::words(W), W}; }
     u64* h_base = nullptr;     // pinned: W source bases (uploaded asynchronously)
     // reads plan (exchange 3): valid for reads_id
     u64 reads_id = 0;
@@ -152,12 +153,6 @@ struct gasm_comm {
     u32 n_local() const { return rank < 0 ? (u32)world : 1u; }
     u32 global_rank(u32 li) const { return rank < 0 ? li : (u32)rank; }
 };
-
-static int upload(gasm_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
-    GCHK(b.ensure(bytes ? bytes : 8));
-    if (bytes) HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return GASM_OK;
-}
 
 // ---- transport: the three collectives, for both kinds of communicator.  Arrays are indexed by local rank.
 static int x_allgather(gasm_comm* c, const void* const* send, void* const* recv, size_t bytes) {
@@ -268,14 +263,14 @@ static int comm_plan(gasm_comm* c, u32 S, int bbits) {
     }
     std::vector<u32> iota(nbt + 1);
     for (u32 i = 0; i <= nbt; ++i) iota[i] = i;
-    GCHK(upload(ctx, c->d_own1, c->h_own1.data(), (size_t)nbt * 2));
-    GCHK(upload(ctx, c->d_order, c->h_order.data(), (size_t)nbt * 4));
-    GCHK(upload(ctx, c->d_dst_first, c->h_dst_first.data(), ((size_t)W + 1) * 4));
-    GCHK(upload(ctx, c->d_seg_first, c->h_seg_first.data(), ((size_t)W + 1) * 4));
-    GCHK(upload(ctx, c->d_iota, iota.data(), iota.size() * 4));
+    GCHK(h2d(ctx, c->d_own1, c->h_own1.data(), (size_t)nbt * 2));
+    GCHK(h2d(ctx, c->d_order, c->h_order.data(), (size_t)nbt * 4));
+    GCHK(h2d(ctx, c->d_dst_first, c->h_dst_first.data(), ((size_t)W + 1) * 4));
+    GCHK(h2d(ctx, c->d_seg_first, c->h_seg_first.data(), ((size_t)W + 1) * 4));
+    GCHK(h2d(ctx, c->d_iota, iota.data(), iota.size() * 4));
     for (u32 li = 0; li < c->n_local(); ++li) {
         const std::vector<u32>& m = c->h_mine[c->global_rank(li)];
-        GCHK(upload(ctx, c->rx[li].d_mine, m.data(), m.size() * 4));
+        GCHK(h2d(ctx, c->rx[li].d_mine, m.data(), m.size() * 4));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));      // (host vectors above go out of scope / are reused)
     c->S = S; c->bbits = bbits;
@@ -296,28 +291,12 @@ static int local_runs_queue(gasm_pool* p, RankX& x, int k, int bbits, bool small
     bs.single_pass = single_pass;
     p->graphed = false; p->paths_ready = false; p->ss.launched = false; p->ss.valid = false; p->scored = false;
     p->n_runs = S << bbits;
+    if (bs.n_kmers == 0) return pool_empty_runs(p);
     GCHK(bs.d_bucket_d.ensure(((size_t)p->n_runs + 2) * 4));       // (+ the flag word that travels with the lengths)
-    if (bs.n_kmers == 0) {
-        GCHK(bs.d_bstart.ensure(((size_t)p->n_runs + 1) * 8));
-        GCHK(bs.d_keys.ensure(64)); GCHK(bs.d_mult.ensure(64));
-        HIPCHK(hipMemsetAsync(bs.d_bucket_d.p, 0, ((size_t)p->n_runs + 2) * 4, ctx->stream));
-        bs.part_valid = false;
-        HIPCHK(hipMemsetAsync(bs.d_bstart.p, 0, ((size_t)p->n_runs + 1) * 8, ctx->stream));
-        HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, 256, ctx->stream));
-        return GASM_OK;
-    }
     distinct_caps(bs, S);
     GCHK(launch_distinct(ctx, p->rd, bs));
     hipLaunchKernelGGL(k_x_flag_word, dim3(1), dim3(64), 0, ctx->stream, bs.d_flags.as<u32>(), bs.d_bucket_d.as<u32>() + p->n_runs);
     HIPCHK(hipGetLastError());
-    return GASM_OK;
-}
-
-template <class K, int TBL>
-static int launch_merge(gasm_ctx* ctx, BuildState& bs, RankX& x, u32 n_out, u32 W) {
-    GLAUNCH(ctx, "k_bucket_merge", (k_bucket_merge<K, TBL>), dim3(n_out), dim3(GASM_WG), 0, x.recv_keys.as<K>(), x.recv_cnt.as<u32>(), x.d_run_off.as<u64>(),
-            x.d_run_len.as<u32>(), W, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(),
-            bs.d_fdir.as<u16>(), 2 * bs.k - bs.bbits, x.d_src_base.as<u64>());
     return GASM_OK;
 }
 
@@ -340,24 +319,9 @@ static int merge_received(gasm_pool* p, RankX& x, u32 n_out, u32 W, u64 cap_tota
         bs.part_valid = false;
     }
     std::swap(bs.d_bstart, x.d_bstart_new);         // the plan kernel wrote the merged runs' layout; the packed runs' layout is no longer needed
-    GCHK(bs.d_bucket_d.ensure(((size_t)n_out + 2) * 4));
-    bs.small_tbl = bs.words == 2;                   // the merge uses 4096-slot tables for 64-bit keys, 2048-slot ones for 128-bit keys
-    bs.fbits = bs.words == 1 ? 10 : 9;
-    GCHK(bs.d_fdir.ensure(((size_t)n_out + 1) * ((1u << bs.fbits) + 1) * 2));
-    HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, 256, ctx->stream));
-    if (n_out) {
-        if (bs.words == 1) GCHK((launch_merge<u64, 4096>(ctx, bs, x, n_out, W)));
-        else GCHK((launch_merge<K128, 2048>(ctx, bs, x, n_out, W)));
-    }
+    GCHK(launch_bucket_merge(p, n_out, W, x.recv_keys.p, x.recv_cnt.as<u32>(), x.d_run_off.as<u64>(), x.d_run_len.as<u32>(), x.d_src_base.as<u64>()));
     p->n_runs = n_out;
     p->graphed = false;
-    return GASM_OK;
-}
-
-template <class K>
-static int launch_pack(gasm_ctx* ctx, BuildState& bs, RankX& x, u32 n, const u32* d_list) {
-    GLAUNCH(ctx, "k_pack_runs", k_pack_runs<K>, dim3(n), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(),
-            d_list, x.d_send_off.as<u64>(), x.send_keys.as<K>(), x.send_cnt.as<u32>());
     return GASM_OK;
 }
 
@@ -375,7 +339,7 @@ static int reads_setup(gasm_comm* c, gasm_pool* const* pools) {
     for (u32 li = 0; li < nl; ++li) {
         const DevReads& rd = pools[li]->rd;
         for (u32 s = 0; s < S; ++s) nr[li][s] = rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s];
-        GCHK(upload(ctx, c->rx[li].d_nr, nr[li].data(), (size_t)S * 8));
+        GCHK(h2d(ctx, c->rx[li].d_nr, nr[li].data(), (size_t)S * 8));
         GCHK(c->rx[li].d_nr_all.ensure((size_t)W * S * 8 + 8));
         snd[li] = c->rx[li].d_nr.p; rcv[li] = c->rx[li].d_nr_all.p;
     }
@@ -402,7 +366,7 @@ static int reads_setup(gasm_comm* c, gasm_pool* const* pools) {
             }
             x.send_woff[d + 1] = woff;
         }
-        GCHK(upload(ctx, x.d_rdir, dir.data(), dir.size() * 8));
+        GCHK(h2d(ctx, x.d_rdir, dir.data(), dir.size() * 8));
         GCHK(x.send_words.ensure(std::max<u64>(woff, 1) * 8));
         // what arrives: from every source the pieces of this rank's segments, back to back
         const u32 a = c->h_seg_first[r], b = c->h_seg_first[r + 1];
@@ -471,14 +435,14 @@ static gasm_comm* comm_new(gasm_ctx* ctx, int world, int rank) {
     c->ctx = ctx; c->world = world; c->rank = rank;
     c->rx.resize(c->n_local());
     for (RankX& x : c->rx) {
-        if (hipHostMalloc((void**)&x.rep, (size_t)(2 * (2 * world + 6)) * 8, hipHostMallocCoherent) != hipSuccess ||
+        if (hipHostMalloc((void**)&x.rep, 2 * XReport<u64>::words(world) * 8, hipHostMallocCoherent) != hipSuccess ||
             hipHostMalloc((void**)&x.h_base, (size_t)(world + 1) * 8, hipHostMallocCoherent) != hipSuccess) {
             gasm_set_error("hipHostMalloc failed");
             for (RankX& y : c->rx) y.release();
             delete c;
             return nullptr;
         }
-        memset(x.rep, 0, (size_t)(2 * (2 * world + 6)) * 8);
+        memset(x.rep, 0, 2 * XReport<u64>::words(world) * 8);
     }
     return c;
 }
@@ -541,7 +505,7 @@ int gasm_pool_segment_bounds(uint32_t n_segments, uint32_t world, uint32_t* firs
 }
 
 int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_pools, int k, int bbits, int kmer, const double* table, uint64_t* stats) {
-    try {
+    API_GUARD_BEGIN
     if (!c || !pools) { gasm_set_error("gasm_pool_exchange_build: null argument"); return GASM_ERR_INVALID; }
     const u32 nl = c->n_local(), W = (u32)c->world;
     if (n_pools != nl) { gasm_set_error("gasm_pool_exchange_build: %u pools for %u local rank(s)", n_pools, nl); return GASM_ERR_INVALID; }
@@ -555,8 +519,7 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
     const u32 S = pools[0]->rd.n_segments;
     u64 st_bytes[3] = {0, 0, 0}, st_remote[3] = {0, 0, 0};
     int attempts = 0;
-    bool small_tbl = true, single_pass = true;
-    { const char* v = getenv("GASM_SINGLE_PASS"); if (v && *v && atoi(v) == 0) single_pass = false; }
+    bool small_tbl = true, single_pass = env_int("GASM_SINGLE_PASS", 1) != 0, multi_pass = false;      // (no multi-pass rung here)
     const int bb_cap = std::min(10, 2 * (k - 1));
     const int words = k <= 31 ? 1 : 2;
     const size_t KB = 8 * (size_t)words;
@@ -600,16 +563,16 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
         }
         u32 flags = 0;
         for (u32 li = 0; li < nl; ++li) {
-            GCHK(gasm_wait_word64(ctx, c->rx[li].rep + 2 * W + 5, ticket));
-            flags |= (u32)c->rx[li].rep[2 * W + 4];
+            const XReport<const u64> rep1 = c->rx[li].report(0, W);
+            GCHK(gasm_wait_word64(ctx, &rep1.ticket(), ticket));
+            flags |= (u32)rep1.flags();
         }
-        if (flags & 3u) {
-            // every rank reads the same OR of everybody's flags: the same step of the ladder everywhere
-            if ((flags & 2u) && single_pass) single_pass = false;                  // a region of the one-pass partition overflowed: exact layout
-            else if (small_tbl && words == 1) small_tbl = false;                    // larger tables
-            else if (bbits < bb_cap) bbits = std::min(bb_cap, bbits + 2);           // more buckets (changes the ownership: all ranks alike)
-            else { gasm_set_error("a k-mer bucket of some rank holds more than %u distinct k-mers even with %d bucket bits", limit, bbits); return GASM_ERR_CAPACITY; }
-            continue;
+        if (flags & (GASM_OVF_TABLE | GASM_OVF_REGION)) {
+            // every rank reads the same OR of everybody's flags: the same step of the ladder everywhere (more bucket bits change
+            // the ownership: all ranks alike)
+            if (build_next_config(flags, GASM_RUNG_EXACT | GASM_RUNG_TABLE | GASM_RUNG_BBITS, words, bb_cap, single_pass, small_tbl, bbits, multi_pass)) continue;
+            gasm_set_error("a k-mer bucket of some rank holds more than %u distinct k-mers even with %d bucket bits", limit, bbits);
+            return GASM_ERR_CAPACITY;
         }
         // ---- stage 12: all-to-all #1
         GCHK(stage_done(c, 11));
@@ -619,14 +582,12 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
         std::vector<void*> rk(nl), rc(nl);
         for (u32 li = 0; li < nl; ++li) {
             RankX& x = c->rx[li];
-            BuildState& bs = pools[li]->bs;
-            for (u32 d = 0; d < W; ++d) { soff[li][d + 1] = soff[li][d] + x.rep[d]; roff[li][d + 1] = roff[li][d] + x.rep[W + d]; }
+            const BuildState& bs = pools[li]->bs;
+            const XReport<const u64> rep1 = x.report(0, W);
+            for (u32 d = 0; d < W; ++d) { soff[li][d + 1] = soff[li][d] + rep1.send_tot(d); roff[li][d + 1] = roff[li][d] + rep1.recv_tot(d); }
             GCHK(x.send_keys.ensure(std::max<u64>(soff[li][W], 1) * KB)); GCHK(x.send_cnt.ensure(std::max<u64>(soff[li][W], 1) * 4));
             GCHK(x.recv_keys.ensure(std::max<u64>(roff[li][W], 1) * KB)); GCHK(x.recv_cnt.ensure(std::max<u64>(roff[li][W], 1) * 4));
-            if (soff[li][W]) {
-                if (words == 1) GCHK(launch_pack<u64>(ctx, bs, x, nbt, c->d_order.as<u32>()));
-                else GCHK(launch_pack<K128>(ctx, bs, x, nbt, c->d_order.as<u32>()));
-            }
+            if (soff[li][W]) GCHK(launch_pack_runs(ctx, bs, nbt, c->d_order.as<u32>(), x.d_send_off.as<u64>(), x.send_keys.p, x.send_cnt.as<u32>()));
             sk[li] = x.send_keys.p; sc[li] = x.send_cnt.p; rk[li] = x.recv_keys.p; rc[li] = x.recv_cnt.p;
         }
         {
@@ -639,7 +600,8 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
         for (u32 li = 0; li < nl; ++li) {
             RankX& x = c->rx[li];
             const u32 r = c->global_rank(li), n_mine = (u32)c->h_mine[r].size();
-            GCHK(merge_received(pools[li], x, n_mine, W, x.rep[2 * W], x.rep + W));
+            const XReport<const u64> rep1 = x.report(0, W);
+            GCHK(merge_received(pools[li], x, n_mine, W, rep1.info(0), &rep1.recv_tot(0)));
         }
         // ---- stage 21: merged lengths + flags of everybody, plan 2, report 2
         GCHK(stage_done(c, 13));
@@ -666,16 +628,16 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
                     c->d_seg_first.as<u32>(), x.d_send_off.as<u64>(), x.d_send_tot.as<u64>(), x.d_run_off.as<u64>(), x.d_run_len.as<u32>(), x.d_recv_tot.as<u64>(),
                     x.d_bstart_new.as<u64>(), x.d_info.as<u64>());
             GLAUNCH(ctx, "k_x_report", k_x_report, dim3(1), dim3(64), 0, x.d_send_tot.as<u64>(), x.d_recv_tot.as<u64>(), W, x.d_info.as<u64>(), 2u, x.d_flags_or.as<u32>(),
-                    x.rep + (2 * W + 6), ticket2);
+                    x.rep + XReport<u64>::words(W), ticket2);
         }
         flags = 0;
         for (u32 li = 0; li < nl; ++li) {
-            const u64* rep2 = c->rx[li].rep + (2 * W + 6);
-            GCHK(gasm_wait_word64(ctx, rep2 + 2 * W + 5, ticket2));
-            flags |= rep2[2 * W + 4] ? 1u : 0u;
+            const XReport<const u64> rep2 = c->rx[li].report(1, W);
+            GCHK(gasm_wait_word64(ctx, &rep2.ticket(), ticket2));
+            flags |= rep2.flags() ? GASM_OVF_TABLE : 0u;
         }
         if (flags) {
-            if (bbits < bb_cap) { bbits = std::min(bb_cap, bbits + 2); continue; }
+            if (build_next_config(flags, GASM_RUNG_BBITS, words, bb_cap, single_pass, small_tbl, bbits, multi_pass)) continue;
             gasm_set_error("a merged k-mer bucket holds more than %u distinct k-mers even with %d bucket bits", limit, bbits);
             return GASM_ERR_CAPACITY;
         }
@@ -684,16 +646,13 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
         c->stage = 22;
         for (u32 li = 0; li < nl; ++li) {
             RankX& x = c->rx[li];
-            BuildState& bs = pools[li]->bs;
-            const u64* rep2 = x.rep + (2 * W + 6);
+            const BuildState& bs = pools[li]->bs;
+            const XReport<const u64> rep2 = x.report(1, W);
             const u32 r = c->global_rank(li), n_mine = (u32)c->h_mine[r].size();
-            for (u32 d = 0; d < W; ++d) { soff[li][d + 1] = soff[li][d] + rep2[d]; roff[li][d + 1] = roff[li][d] + rep2[W + d]; }
+            for (u32 d = 0; d < W; ++d) { soff[li][d + 1] = soff[li][d] + rep2.send_tot(d); roff[li][d + 1] = roff[li][d] + rep2.recv_tot(d); }
             GCHK(x.send_keys.ensure(std::max<u64>(soff[li][W], 1) * KB)); GCHK(x.send_cnt.ensure(std::max<u64>(soff[li][W], 1) * 4));
             GCHK(x.recv_keys.ensure(std::max<u64>(roff[li][W], 1) * KB)); GCHK(x.recv_cnt.ensure(std::max<u64>(roff[li][W], 1) * 4));
-            if (soff[li][W] && n_mine) {
-                if (words == 1) GCHK(launch_pack<u64>(ctx, bs, x, n_mine, c->d_iota.as<u32>()));
-                else GCHK(launch_pack<K128>(ctx, bs, x, n_mine, c->d_iota.as<u32>()));
-            }
+            if (soff[li][W] && n_mine) GCHK(launch_pack_runs(ctx, bs, n_mine, c->d_iota.as<u32>(), x.d_send_off.as<u64>(), x.send_keys.p, x.send_cnt.as<u32>()));
             sk[li] = x.send_keys.p; sc[li] = x.send_cnt.p; rk[li] = x.recv_keys.p; rc[li] = x.recv_cnt.p;
         }
         {
@@ -705,10 +664,10 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
         c->stage = 23;
         for (u32 li = 0; li < nl; ++li) {
             RankX& x = c->rx[li];
-            const u64* rep2 = x.rep + (2 * W + 6);
+            const XReport<const u64> rep2 = x.report(1, W);
             const u32 r = c->global_rank(li), a = c->h_seg_first[r], b = c->h_seg_first[r + 1];
-            GCHK(merge_received(pools[li], x, (b - a) * nb, W, rep2[2 * W], rep2 + W));
-            GCHK(pool_graph_launch(pools[li], b - a, rep2[2 * W], rep2[2 * W + 1]));
+            GCHK(merge_received(pools[li], x, (b - a) * nb, W, rep2.info(0), &rep2.recv_tot(0)));
+            GCHK(pool_graph_launch(pools[li], b - a, rep2.info(0), rep2.info(1)));
         }
         break;
     }
@@ -750,13 +709,7 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
         stats[6] = (u64)attempts; stats[7] = (u64)bbits;
     }
     return GASM_OK;
-    } catch (const std::bad_alloc&) {
-        gasm_set_error("out of host memory");
-        return GASM_ERR_CAPACITY;
-    } catch (const std::exception& e) {
-        gasm_set_error("internal error: %s", e.what());
-        return GASM_ERR_INVALID;
-    }
+    API_GUARD_END
 }
 
 }  // extern "C"

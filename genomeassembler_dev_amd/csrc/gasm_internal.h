@@ -7,7 +7,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <map>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -41,6 +43,17 @@ struct GasmRange {
         int _s = (expr);          \
         if (_s != GASM_OK) return _s; \
     } while (0)
+
+// Body of an exported entry point: no C++ exception crosses the C boundary.
+#define API_GUARD_BEGIN try {
+#define API_GUARD_END                                                          \
+    } catch (const std::bad_alloc&) {                                          \
+        gasm_set_error("out of host memory");                                  \
+        return GASM_ERR_CAPACITY;                                              \
+    } catch (const std::exception& e) {                                        \
+        gasm_set_error("internal error: %s", e.what());                        \
+        return GASM_ERR_INVALID;                                               \
+    }
 
 // Grow-only device allocation.  Steady-state steps of the same shape never call hipMalloc.
 struct DBuf {

@@ -85,6 +85,48 @@ struct PathSet {
 #define GASM_TBL 4096       // slots of the large LDS de-duplication table (the small one has 2048)
 #define GASM_TBL_LIMIT 2816 // distinct keys one bucket may hold (11/16 of the table) before the host re-partitions
 
+// ---- the flag area of a build (BuildState::d_flags): GASM_FLAG_WORDS u32 words, behind them the one-pass partition's cursors.
+// The one definition of who writes which word, shared by the kernels and the host.
+enum : u32 {
+    GASM_FLAG_OVERFLOW = 0,         // GASM_OVF_* bits, raised by the partition, the de-duplications and the merge
+    GASM_FLAG_RANK_FAILED = 1,      // the LDS list ranking gave up (k_rank_rulers, k_rank_lds)
+    GASM_FLAG_SCORE_MISMATCH = 2,   // the graph scorer met a read that differs from its contig (GASM_SCORE_VERIFY)
+    GASM_FLAG_DEDUP_DONE = 8,       // finished workgroups of k_bucket_dedup (its last one scans the buckets' counts)
+    GASM_FLAG_CONTIG_DONE = 9,      // finished workgroups of k_contig_scan (its last one writes the report)
+    GASM_FLAG_SOLID_DONE = 10,      // finished workgroups of k_bucket_solid (its last one redoes the scan)
+    GASM_FLAG_ACTIVE = 16,          // "still active" word of every k_link_jump launch of a build ...
+    GASM_FLAG_ACTIVE_N = 40,        // ... and how many launches have one
+    GASM_FLAG_WORDS = 64,           // words the kernels below zero
+    GASM_FLAG_CURSORS = 64,         // first cursor of k_bucket_partition (one per (segment, bucket))
+    GASM_FLAG_BYTES = 256,          // size of the area without cursors
+    GASM_OVF_TABLE = 1,             // a bucket holds more distinct keys than its table (or, multi-pass, than GASM_BUCKET_MAX)
+    GASM_OVF_REGION = 2,            // a bucket outgrew its region of the one-pass partition
+};
+static_assert(GASM_FLAG_ACTIVE + GASM_FLAG_ACTIVE_N <= GASM_FLAG_WORDS && GASM_FLAG_WORDS * 4 == GASM_FLAG_BYTES, "flag area layout");
+// Zeroing contract.  Every attempt at the distinct k-mers starts with all GASM_FLAG_WORDS words zero: the one-pass partition
+// clears words and cursors with one fill on the stream, the two-pass partition has k_tile_scan clear the words, and the pooled
+// stages that produce runs without a partition (merges, a rank without k-mers) fill GASM_FLAG_BYTES.  So the done counters are
+// zero when their kernel starts, and GASM_FLAG_OVERFLOW holds what this attempt raised.  Every graph launch — the first, and a
+// repeat after a failed ranking — starts with k_bucket_gather clearing every word except GASM_FLAG_OVERFLOW, which stays for
+// the report: the ranking's flag, the scorer's flag, k_contig_scan's counter and the active words are zero again.
+
+// The pinned report of a build over S segments (BuildState::h_report, u32 words), written by k_contig_scan's last workgroup,
+// the ticket last: first distinct k-mer, first contig and first contig base (lo, hi) of every segment, each with the total in
+// entry S; then flag word GASM_FLAG_OVERFLOW, flag word GASM_FLAG_RANK_FAILED and the ticket.
+template <class W>
+struct BuildReport {
+    W* w;
+    u32 S;
+    __host__ __device__ W& dstart(u32 s) const { return w[s]; }
+    __host__ __device__ W& cstart(u32 s) const { return (w + S + 1)[s]; }
+    __host__ __device__ W& bstart_lo(u32 s) const { return (w + 2 * S + 2)[2 * s]; }
+    __host__ __device__ W& bstart_hi(u32 s) const { return (w + 2 * S + 2)[2 * s + 1]; }
+    __host__ __device__ W& flags() const { return w[4 * S + 4]; }
+    __host__ __device__ W& rank_failed() const { return w[4 * S + 5]; }
+    __host__ __device__ W& ticket() const { return w[4 * S + 6]; }
+    static size_t words(u32 S) { return 4 * (size_t)S + 8; }
+};
+
 // ---- kernels_build.hip
 __global__ void k_pack_ascii(const u8* ascii, u64 nbases_host, const u64* nbases_dev, u64* words, u32* err);
 #define GASM_TILE_WG 512     // threads of a tile workgroup (k_tile_hist, k_bucket_scatter)
@@ -218,6 +260,18 @@ __global__ void k_cover_count(const int* diff, long long seq_len, unsigned long 
 __global__ void k_prob_dist(PathSet ps, const double* dprob, int kmer, const u64* pd_off, double* out, u32 n_paths);
 
 // ---- kernels_pool.hip: exchange plans (exchange.hip)
+// the pinned report of an exchange plan among W ranks (u64 words; a rank keeps two of them back to back)
+template <class T>
+struct XReport {
+    T* w;
+    u32 W;
+    __host__ __device__ T& send_tot(u32 d) const { return w[d]; }
+    __host__ __device__ T& recv_tot(u32 d) const { return w[W + d]; }
+    __host__ __device__ T& info(u32 j) const { return w[2 * W + j]; }      // 0: records the merge will hold in all; 1 (plan 2): the most of one segment
+    __host__ __device__ T& flags() const { return w[2 * W + 4]; }          // OR of every rank's GASM_FLAG_OVERFLOW word
+    __host__ __device__ T& ticket() const { return w[2 * W + 5]; }
+    static size_t words(u32 W) { return 2 * (size_t)W + 6; }
+};
 __global__ void k_x_flag_word(const u32* flags, u32* row_tail);
 __global__ void k_x1_plan(const u32* lens_all, u64 stride, u32 nbt, const u32* order, const u32* dst_first, const u32* mine, u32 n_mine, u32 W, u32 r, u32 limit,
                           u64* send_off, u64* send_tot, u64* run_off, u32* run_len, u64* recv_tot, u64* bstart, u32* flags_or);

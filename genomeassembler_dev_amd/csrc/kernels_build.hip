@@ -174,8 +174,8 @@ __global__ void __launch_bounds__(1024) k_tile_scan(ReadSet rs, int bbits, u32 p
                                                     u32* __restrict__ toff, u32* __restrict__ hist, u32* __restrict__ flags) {
     __shared__ u32 s_part[1024];
     const u32 nb = 1u << bbits, seg = blockIdx.x;
-    // the build's 64 flag words start at zero (a fill would be a launch of its own; the first writer is k_bucket_dedup)
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) flags[threadIdx.x] = 0;
+    // the build's flag words start at zero (kernels.h; a fill would be a launch of its own)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < GASM_FLAG_WORDS) flags[threadIdx.x] = 0;
     const u32 t0 = rs.seg_tile_start[seg], t1 = rs.seg_tile_start[seg + 1];
     // a workgroup = 32 buckets (blockIdx.y) x 32 slices of the segment's tile range: slice sums first, then the offsets
     const u32 nbw = min(nb, 32u), grp = 1024u / nbw, sl = threadIdx.x / nbw, bl = threadIdx.x % nbw;
@@ -238,11 +238,7 @@ template __global__ void k_scan_excl<u32>(const u32*, u32*, u32);
 // build's REPORT: the last kernel of a build writes everything the host needs afterwards into the batch's pinned report
 // area in one go, the ticket last.  Nothing before this point makes the host wait: the build is queued in full with
 // sizes taken from upper bounds, and the host reads the report when somebody asks for results (pipeline_build_finish).
-//   report[0 .. S]            first distinct k-mer of every segment (+ the total)
-//   report[S+1 .. 2S+1]       first contig of every segment (+ the total)
-//   report[2S+2 .. 4S+3]      first contig base of every segment (+ the total), (lo, hi) pairs
-//   report[4S+4]              flags[0]: a bucket overflowed its table        report[4S+5]  flags[1]: list ranking gave up
-//   report[4S+6]              ticket
+// The layout is BuildReport (kernels.h).
 // (body: one wave; `seg_ncontig` / `seg_cbases` are read with agent-scope loads — in k_contig_scan's last workgroup they come
 // from workgroups of other XCDs, whose L2 this one does not share)
 __device__ __forceinline__ void seg_offsets_wave(const u32* __restrict__ seg_ncontig, const u64* __restrict__ seg_cbases, u32 S,
@@ -253,8 +249,9 @@ __device__ __forceinline__ void seg_offsets_wave(const u32* __restrict__ seg_nco
     const u32 ln = threadIdx.x & 63;
     u32 ccarry = 0;
     u64 bcarry = 0;
-    u32* const rc = report + S + 1;
-    u32* const rb = report + 2 * S + 2;
+    const BuildReport<u32> rep{report, S};
+    u32* const rc = &rep.cstart(0);
+    u32* const rb = &rep.bstart_lo(0);      // (lo, hi) pairs
     for (u32 base = 0; base < S; base += 64) {
         const u32 i = base + ln;
         const u32 c = i < S ? __hip_atomic_load(&seg_ncontig[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -272,7 +269,7 @@ __device__ __forceinline__ void seg_offsets_wave(const u32* __restrict__ seg_nco
             seg_cstart[i] = cs; seg_bstart[i] = bs;
             rc[i] = cs;
             rb[2 * i] = (u32)bs; rb[2 * i + 1] = (u32)(bs >> 32);
-            report[i] = dstart[(u64)i * nb];
+            rep.dstart(i) = dstart[(u64)i * nb];
         }
         ccarry += wave_last(cinc);
         bcarry += __shfl(binc, 63, 64);
@@ -281,12 +278,12 @@ __device__ __forceinline__ void seg_offsets_wave(const u32* __restrict__ seg_nco
         seg_cstart[S] = ccarry; seg_bstart[S] = bcarry;
         rc[S] = ccarry;
         rb[2 * S] = (u32)bcarry; rb[2 * S + 1] = (u32)(bcarry >> 32);
-        report[S] = dstart[(u64)S * nb];
-        report[4 * S + 4] = flags[0];
-        report[4 * S + 5] = flags[1];
+        rep.dstart(S) = dstart[(u64)S * nb];
+        rep.flags() = flags[GASM_FLAG_OVERFLOW];
+        rep.rank_failed() = flags[GASM_FLAG_RANK_FAILED];
     }
     __threadfence_system();                    // (one wave: every lane's report words are out before lane 0's ticket)
-    if (ln == 0) report[4 * S + 6] = ticket;
+    if (ln == 0) rep.ticket() = ticket;
 }
 
 // ================================================================================================================
@@ -451,7 +448,7 @@ template __global__ void k_bucket_scatter<K128>(ReadSet, const uint4*, int, int,
 // in its (bucket, sub-counter) — then reserves its line-padded runs with one global atomic per bucket and flushes whole
 // lines as before.  Runs of a bucket therefore lie in the order the tiles got there, which the de-duplication does not
 // care about (its result is ordered and counted).  cursor[gb] ends up as the bucket's padded length (what `hist` is in the
-// two-pass form).  A run that does not fit its region goes to the scratch line, bit 1 of flags[0] is raised, the
+// two-pass form).  A run that does not fit its region goes to the scratch line, GASM_OVF_REGION is raised, the
 // de-duplication leaves such a bucket empty, and pipeline_build_finish repeats the build with the two-pass kernels.
 // Memory operations of a wave: [next tile's words, region bounds] [cursor atomic: wave(s) of the bucket threads]
 // [NFL stores]; the atomic's value is used before the flush, so the wait at the top stays "all but the NFL stores".
@@ -556,7 +553,7 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
         if (t < nb) {
             const bool fits = (u64)run + padc <= end - beg;
             s_comb[t] = fits ? beg + run - soff : ~0ull;        // staging index i goes to keys[s_comb[bucket] + i]
-            if (!fits) atomicOr(flags, 2u);
+            if (!fits) atomicOr(flags + GASM_FLAG_OVERFLOW, GASM_OVF_REGION);
         }
         __syncthreads();
         // (one 16-byte slot per wave, shared by its lanes past the end: 128 KB in all, resident in L2 — a slot per lane was an
@@ -768,12 +765,12 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
     u64 n = end - beg;
     if (blen) {
         // single-pass partition (k_bucket_partition): the bucket's region is [beg, end), its keys the first blen[bucket] of it.
-        // A bucket that outgrew its region lost runs (bit 1 of *overflow is up, the build will be repeated): empty and searchable
+        // A bucket that outgrew its region lost runs (GASM_OVF_REGION is up, the build will be repeated): empty and searchable
         const u64 len = blen[bucket];
         if (len > n) {
             for (u32 i = threadIdx.x; i <= (u32)BINS; i += GASM_WG) fdir[(u64)bucket * (BINS + 1) + i] = 0;
             if (threadIdx.x == 0) publish_u32(&bucket_d[bucket], 0u);
-            dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + 8, s_tmp + 7, s_tmp);
+            dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + GASM_FLAG_DEDUP_DONE, s_tmp + 7, s_tmp);
             return;
         }
         n = len;
@@ -907,19 +904,19 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
         // kernels of THIS attempt run (pipeline_build_finish), so the bucket must be left empty AND searchable: an all-zero
         // fine directory (graph_lower_bound would otherwise bisect between whatever the allocation held)
         for (u32 i = threadIdx.x; i <= (u32)BINS; i += GASM_WG) fdir[(u64)bucket * (BINS + 1) + i] = 0;
-        if (threadIdx.x == 0) { atomicOr(overflow, 1u); publish_u32(&bucket_d[bucket], 0u); }
-        dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + 8, s_tmp + 7, s_tmp);
+        if (threadIdx.x == 0) { atomicOr(overflow + GASM_FLAG_OVERFLOW, GASM_OVF_TABLE); publish_u32(&bucket_d[bucket], 0u); }
+        dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + GASM_FLAG_DEDUP_DONE, s_tmp + 7, s_tmp);
         return;
     }
     const u32 d = *w_distinct;
-    if ((dbg & 3) == 1 || (dbg & 3) == 2) { if (threadIdx.x == 0) publish_u32(&bucket_d[bucket], d); dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + 8, s_tmp + 7, s_tmp); return; }
+    if ((dbg & 3) == 1 || (dbg & 3) == 2) { if (threadIdx.x == 0) publish_u32(&bucket_d[bucket], d); dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + GASM_FLAG_DEDUP_DONE, s_tmp + 7, s_tmp); return; }
     dedup_order<K, TBL, true>(t_key, t_cnt, s_start, s_cur, s_tmp, fdir, bucket, low_bits, d);
     phase(4);
     for (u32 i = threadIdx.x; i < d; i += GASM_WG) { keys[beg + i] = t_key[i]; mult[beg + i] = t_cnt[i]; }
     if (threadIdx.x == 0) publish_u32(&bucket_d[bucket], d);
     phase(5);
     if (stamps && threadIdx.x == 0) stamps[8 + 3 * (u64)blockIdx.x + 1] = wall_clock64();
-    dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + 8, s_tmp + 7, s_tmp);
+    dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + GASM_FLAG_DEDUP_DONE, s_tmp + 7, s_tmp);
 }
 template __global__ void k_bucket_dedup<u64, 4096>(u64*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, int, unsigned long long*, u32*);
 template __global__ void k_bucket_dedup<u64, 2048>(u64*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, int, unsigned long long*, u32*);
@@ -953,7 +950,7 @@ __global__ void __launch_bounds__(GASM_WG) k_bucket_dedup_multi(const K* __restr
     u16* const fd = fdir + (u64)bucket * (BINS + 1);
     auto give_up = [&]() {                                      // (an empty, searchable bucket: see k_bucket_dedup)
         for (u32 i = threadIdx.x; i <= (u32)BINS; i += GASM_WG) fd[i] = 0;
-        if (threadIdx.x == 0) { atomicOr(overflow, 1u); bucket_d[bucket] = 0; }
+        if (threadIdx.x == 0) { atomicOr(overflow + GASM_FLAG_OVERFLOW, GASM_OVF_TABLE); bucket_d[bucket] = 0; }
     };
     for (int r = 0;; ++r) {
         if (r > r_max) { give_up(); return; }
@@ -1112,9 +1109,8 @@ __global__ void __launch_bounds__(GASM_WG) k_bucket_gather(const K* __restrict__
                                                            K* __restrict__ dk_key, u32* __restrict__ dk_cnt, u32* __restrict__ claim,
                                                            u8* __restrict__ eflag, u32* __restrict__ flags) {
     const u32 bucket = blockIdx.x;
-    // the graph kernels' flags — [1] ranking gave up, [16..] "still active" words of the k_link_jump launches — start at
-    // zero; [0], the de-duplication's overflow flag, stays
-    if (bucket == 0 && threadIdx.x >= 1 && threadIdx.x < 64) flags[threadIdx.x] = 0;
+    // the graph kernels' flag words start at zero; the de-duplication's overflow word stays (kernels.h)
+    if (bucket == 0 && threadIdx.x != GASM_FLAG_OVERFLOW && threadIdx.x < GASM_FLAG_WORDS) flags[threadIdx.x] = 0;
     const u64 src = bstart[bucket];
     const u32 dst = dstart[bucket], d = dstart[bucket + 1] - dst;
     for (u32 i = threadIdx.x; i < d; i += GASM_WG) {
@@ -1229,7 +1225,7 @@ __global__ void __launch_bounds__(GASM_WG) k_edge_next(GraphView gv, u32 n_segme
 // be in step; what is guaranteed per launch is that every link's span grows by the factor jumps + 1 (each step adds at
 // least the span its ancestor had before the launch).  Whole-GPU launches beat one workgroup per segment: a CU resolves about one scattered address per clock,
 // and a segment's ~15 rounds of gathers through a single CU took 0.28 ms against 5 launches of ~10 us here.
-// `active` (one word per launch, zeroed by the host): set when some link is still short of its head; a launch returns
+// `active` (one of the GASM_FLAG_ACTIVE words per launch, kernels.h): set when some link is still short of its head; a launch returns
 // at once when the previous one left it clear.  Members of isolated cycles never finish: the number of launches bounds them.
 #define GASM_JUMP_ILP 4      // links per thread, advanced together: the steps are dependent gathers, so the kernel lives on loads in flight
 // nxt / clen (optional): the launch also does k_chain_len's work for the links it sees final — a chain's last edge publishes
@@ -1342,7 +1338,7 @@ __global__ void __launch_bounds__(GASM_WG) k_rank_rulers(GraphView gv, u32 n_seg
         }
         // 4096 edges in a row without a ruler: the host repeats the ranking with whole-GPU pointer doubling instead of
         // handing out a contig that silently lost edges
-        if (step == 4096) flags[1] = 1u;
+        if (step == 4096) flags[GASM_FLAG_RANK_FAILED] = 1u;
         rtab[(lo >> rshift) + seg + r] = e;     // segment s owns entries [(lo >> shift) + s, ...): room for the ragged ends
     }
 }
@@ -1370,7 +1366,7 @@ __global__ void __launch_bounds__(1024) k_rank_lds(GraphView gv, const u32* __re
     const u32 nb = 1u << gv.bbits;
     const u32 lo = gv.dstart[seg * nb], hi = gv.dstart[(seg + 1) * nb];
     const u32 nr = (hi - lo + rmask) >> rshift;
-    if (nr > lds_entries || hi - lo > 65534u) { if (threadIdx.x == 0) flags[1] = 1u; return; }
+    if (nr > lds_entries || hi - lo > 65534u) { if (threadIdx.x == 0) flags[GASM_FLAG_RANK_FAILED] = 1u; return; }
     const u32* src = rtab + (lo >> rshift) + seg;
     u32 mine[32];
     u32 live = 0;                                     // bit q: entry q of this thread is still hopping

@@ -108,7 +108,7 @@ k_bucket_merge(const K* __restrict__ in_keys, const u32* __restrict__ in_cnt, co
             const u64 off = n_nonempty ? run_off[(u64)j * n_src + only] + (src_base ? src_base[only] : 0ull) : 0ull;
             if (len > (u32)LIMIT) {
                 for (u32 i = threadIdx.x; i <= (u32)BINS; i += GASM_WG) fdir[(u64)j * (BINS + 1) + i] = 0;
-                if (threadIdx.x == 0) { atomicOr(overflow, 1u); bucket_d[j] = 0; }
+                if (threadIdx.x == 0) { atomicOr(overflow + GASM_FLAG_OVERFLOW, GASM_OVF_TABLE); bucket_d[j] = 0; }
                 return;
             }
             const u64 beg = bstart[j];
@@ -147,7 +147,7 @@ k_bucket_merge(const K* __restrict__ in_keys, const u32* __restrict__ in_cnt, co
     __syncthreads();
     if (s_tmp[5] || s_tmp[4] > (u32)LIMIT) {
         for (u32 i = threadIdx.x; i <= (u32)BINS; i += GASM_WG) fdir[(u64)j * (BINS + 1) + i] = 0;      // empty and searchable
-        if (threadIdx.x == 0) { atomicOr(overflow, 1u); bucket_d[j] = 0; }
+        if (threadIdx.x == 0) { atomicOr(overflow + GASM_FLAG_OVERFLOW, GASM_OVF_TABLE); bucket_d[j] = 0; }
         return;
     }
     const u32 d = s_tmp[4];
@@ -232,7 +232,7 @@ __device__ __forceinline__ u64 wg_scan_seq(u32 n, u64* s_wave, G&& get, P&& put)
 }
 
 // the row a rank contributes to the all-gather of exchange 1: its NBT run lengths (already in place) + its flag word
-__global__ void k_x_flag_word(const u32* __restrict__ flags, u32* __restrict__ row_tail) { if (threadIdx.x == 0) *row_tail = flags[0]; }
+__global__ void k_x_flag_word(const u32* __restrict__ flags, u32* __restrict__ row_tail) { if (threadIdx.x == 0) *row_tail = flags[GASM_FLAG_OVERFLOW]; }
 
 // Exchange 1 (every bucket's runs to the bucket's owner), rank r of W.  lens_all[s * stride + gb] = rank s's run length of
 // bucket gb, [.. + nbt] = rank s's flag word.  order[0..nbt) = the buckets sorted by owner (dst_first[d] .. dst_first[d+1]:
@@ -281,7 +281,7 @@ __global__ void __launch_bounds__(GASM_WG) k_x2_fill(u32* __restrict__ G, u32 nb
                                                      const u32* __restrict__ bucket_d, const u32* __restrict__ flags) {
     const u32 j = blockIdx.x * GASM_WG + threadIdx.x;
     if (j < n_mine) G[mine[j]] = bucket_d[j];
-    if (j == 0) G[nbt] = flags[0];
+    if (j == 0) G[nbt] = flags[GASM_FLAG_OVERFLOW];
 }
 
 // Exchange 2 (the merged runs to their segment's owner), rank r of W.  G[gb] = merged length of bucket gb (all-reduced),
@@ -325,14 +325,15 @@ __global__ void __launch_bounds__(1024) k_x2_plan(const u32* __restrict__ G, con
     }
 }
 
-// The report of an exchange plan: W send totals, W receive totals, up to four more words, then the ticket (pinned memory).
+// The report of an exchange plan (XReport, kernels.h; pinned memory), the ticket last.
 __global__ void __launch_bounds__(64) k_x_report(const u64* __restrict__ send_tot, const u64* __restrict__ recv_tot, u32 W, const u64* __restrict__ info, u32 n_info,
                                                  const u32* __restrict__ flags_or, u64* __restrict__ report, u64 ticket) {
-    for (u32 i = threadIdx.x; i < W; i += 64) { report[i] = send_tot[i]; report[W + i] = recv_tot[i]; }
-    if (threadIdx.x < n_info) report[2 * W + threadIdx.x] = info[threadIdx.x];
-    if (threadIdx.x == 0) report[2 * W + 4] = flags_or ? (u64)*flags_or : 0ull;
+    const XReport<u64> rep{report, W};
+    for (u32 i = threadIdx.x; i < W; i += 64) { rep.send_tot(i) = send_tot[i]; rep.recv_tot(i) = recv_tot[i]; }
+    if (threadIdx.x < n_info) rep.info(threadIdx.x) = info[threadIdx.x];
+    if (threadIdx.x == 0) rep.flags() = flags_or ? (u64)*flags_or : 0ull;
     __threadfence_system();
-    if (threadIdx.x == 0) report[2 * W + 5] = ticket;
+    if (threadIdx.x == 0) rep.ticket() = ticket;
 }
 
 // sum of n u32 arrays, element by element (the all-reduce of the virtual communicator)

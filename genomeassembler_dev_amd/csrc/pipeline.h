@@ -3,6 +3,17 @@
 #include "gasm_internal.h"
 #include "kernels.h"
 
+// ---- one launch site for both key widths: f(KeyTag<u64>) for one key word, f(KeyTag<K128>) for two.  GLAUNCH_K wraps a
+// GLAUNCH whose kernel and arguments name the key type as K
+template <class K> struct KeyTag { using type = K; };
+template <class F> static inline int with_key(int words, F&& f) { return words == 1 ? f(KeyTag<u64>{}) : f(KeyTag<K128>{}); }
+#define GLAUNCH_K(ctx, words, name, kern, grid, block, shmem, ...)          \
+    GCHK(with_key(words, [&](auto _tag) -> int {                            \
+        using K = typename decltype(_tag)::type;                            \
+        GLAUNCH(ctx, name, kern, grid, block, shmem, __VA_ARGS__);          \
+        return GASM_OK;                                                     \
+    }))
+
 // Reads of one or more segments, resident in HBM as one packed base stream.
 struct DevReads {
     u32 n_segments = 0;
@@ -171,6 +182,11 @@ struct ScoreState {
 int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1, u32 strands = 1);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
+// The overflow retry ladder of every build path: after an attempt raised the GASM_OVF_* bits `ovf`, advance the configuration by
+// the first rung that applies among those the caller permits — a region overflowed: exact partition; small tables: large ones
+// (64-bit keys only); two more bucket bits up to bb_cap; multi-pass de-duplication — or return false: none is left
+enum : u32 { GASM_RUNG_EXACT = 1, GASM_RUNG_TABLE = 2, GASM_RUNG_BBITS = 4, GASM_RUNG_MULTI = 8, GASM_RUNG_ALL = 15 };
+bool build_next_config(u32 ovf, u32 rungs, int words, int bb_cap, bool& single_pass, bool& small_tbl, int& bbits, bool& multi_pass);
 // one row of gasm_batch_build_plan (GASM_PLAN_FIELDS words, include/gasm.h) from a finished build's host fields
 void pipeline_build_plan(const DevReads& rd, const BuildState& bs, int32_t* row);
 // building blocks shared with the pooled build (pool.hip)
@@ -225,6 +241,8 @@ int read_kmer_windows_check(const DevReads& rd);
 int launch_read_kmer_count(gasm_ctx* ctx, const DevReads& rd, u32* d_out);
 int read_kmer_split();
 
+// grow `b` to `bytes` and queue the copy of `src` into it on the ctx stream (the caller keeps `src` alive until the stream got there)
+int h2d(gasm_ctx* ctx, DBuf& b, const void* src, size_t bytes);
 // wait for `ticket` to appear at `word` (pinned memory written last by a kernel of the ctx stream); spin, then poll with a deadline
 int gasm_wait_word32(gasm_ctx* ctx, const volatile u32* word, u32 ticket);
 int gasm_wait_word64(gasm_ctx* ctx, const volatile u64* word, u64 ticket);

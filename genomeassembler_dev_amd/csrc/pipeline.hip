@@ -95,7 +95,7 @@ static u32 next_ticket() { static std::atomic<u32> t{1}; u32 v = t.fetch_add(1);
 // grid of the segment-major kernels (seg_chunk, device_utils.h): 8 x chunks x ceil(S / 8) workgroups
 static dim3 seg_grid(u32 chunks, u32 S) { return dim3(8u * chunks * ((S + 7u) / 8u)); }
 
-static int h2d(gasm_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
+int h2d(gasm_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
     GCHK(b.ensure(bytes ? bytes : 8));
     if (bytes) HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return GASM_OK;
@@ -491,18 +491,18 @@ void ScoreState::release() {
 // ---------------------------------------------------------------------------------------------------------------
 static int ensure_lds_attrs(gasm_ctx* ctx) {
     if (ctx->lds_attrs_set) return GASM_OK;         // per context = per device: the attribute is a property of the device's code object
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_scatter<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_scatter<K128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_partition<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_partition<K128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_hist<K128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-#define GASM_SCORE_LDS_ATTR(T)                                                                                                                                        \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<u64, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));  \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_reads_graph<K128, T>), hipFuncAttributeMaxDynamicSharedMemorySize, GASM_SCORE_PATH_CAP * 12));
-    GASM_SCORE_LDS_ATTR(1) GASM_SCORE_LDS_ATTR(2) GASM_SCORE_LDS_ATTR(3) GASM_SCORE_LDS_ATTR(4) GASM_SCORE_LDS_ATTR(5) GASM_SCORE_LDS_ATTR(6) GASM_SCORE_LDS_ATTR(7) GASM_SCORE_LDS_ATTR(8)
+#define GASM_LDS_ATTR(kern, bytes) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+#define GASM_SCORE_LDS_ATTR(T) GASM_LDS_ATTR((k_score_reads_graph<K, T>), GASM_SCORE_PATH_CAP * 12)
+    for (int words = 1; words <= 2; ++words)
+        GCHK(with_key(words, [&](auto tag) -> int {
+            using K = typename decltype(tag)::type;
+            GASM_LDS_ATTR(k_bucket_scatter<K>, 160 * 1024) GASM_LDS_ATTR(k_bucket_partition<K>, 160 * 1024) GASM_LDS_ATTR(k_tile_hist<K>, 160 * 1024)
+            GASM_SCORE_LDS_ATTR(1) GASM_SCORE_LDS_ATTR(2) GASM_SCORE_LDS_ATTR(3) GASM_SCORE_LDS_ATTR(4) GASM_SCORE_LDS_ATTR(5) GASM_SCORE_LDS_ATTR(6) GASM_SCORE_LDS_ATTR(7) GASM_SCORE_LDS_ATTR(8)
+            return GASM_OK;
+        }));
+    GASM_LDS_ATTR(k_rank_lds, 160 * 1024 - 64)
 #undef GASM_SCORE_LDS_ATTR
+#undef GASM_LDS_ATTR
     ctx->lds_attrs_set = true;
     return GASM_OK;
 }
@@ -533,6 +533,19 @@ static GraphView graph_view(const BuildState& bs) {
     return gv;
 }
 
+// k_bucket_dedup over the key width and the table size of `bs`: 64-bit keys have both tables, 128-bit keys the small one
+template <class K, int TBL>
+static int launch_bucket_dedup_as(gasm_ctx* ctx, BuildState& bs, u32 nbt, const u32* d_blen, int dbg_d, unsigned long long* d_stamps, u32* d_scan_out) {
+    GLAUNCH(ctx, "k_bucket_dedup", (k_bucket_dedup<K, TBL>), dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), d_blen,
+            bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * bs.k - bs.bbits, dbg_d, d_stamps, d_scan_out);
+    return GASM_OK;
+}
+static int launch_bucket_dedup(gasm_ctx* ctx, BuildState& bs, u32 nbt, const u32* d_blen, int dbg_d, unsigned long long* d_stamps, u32* d_scan_out) {
+    if (bs.words == 2) return launch_bucket_dedup_as<K128, 2048>(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out);
+    if (bs.small_tbl) return launch_bucket_dedup_as<u64, 2048>(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out);
+    return launch_bucket_dedup_as<u64, 4096>(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out);
+}
+
 // ---- reads -> per-(segment, bucket) distinct k-mers with multiplicities (in place in d_keys / d_mult) + dstart
 int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     GasmRange range("gasm:distinct (partition + de-duplication)");
@@ -560,7 +573,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     if (single) {
         // ---- one pass (k_bucket_partition): a region of fixed capacity per (segment, bucket) — the segment's k-mers per
         // bucket with `part_slack` percent to spare, room for Poisson noise and for the padding of its tiles' runs, in whole
-        // lines — and a cursor per region; cursors and the build's flag words are one allocation, zeroed by one fill
+        // lines — and a cursor per region behind the build's flag words
         const int slack = env_int("GASM_PART_SLACK", 100), forced = env_int("GASM_DBG_PART_CAP", 0);
         const bool same_layout = bs.part_valid && bs.part_reads_id == rd.upload_id && bs.part_k == k && bs.part_bbits == bbits && bs.part_padm == padm &&
                                  bs.part_g == g && bs.part_slack == slack && bs.part_forced == forced;
@@ -584,19 +597,14 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         n_alloc = bs.part_alloc;
         GCHK(bs.d_keys.ensure((n_alloc + SCRATCH_KEYS) * KB));
         GCHK(bs.d_mult.ensure(n_alloc * 4));
-        GCHK(bs.d_flags.ensure(256 + (size_t)nbt * 4));
-        HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, 256 + (size_t)nbt * 4, ctx->stream));
-        u32* const d_cursor = bs.d_flags.as<u32>() + 64;
+        GCHK(bs.d_flags.ensure(GASM_FLAG_BYTES + (size_t)nbt * 4));
+        HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, GASM_FLAG_BYTES + (size_t)nbt * 4, ctx->stream));
+        u32* const d_cursor = bs.d_flags.as<u32>() + GASM_FLAG_CURSORS;
         d_blen = d_cursor;
         const size_t lds = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB + (size_t)((nb + 1) & ~1u) * 8 + (size_t)(4 * nb + 4) * 8 + 48 + (size_t)nb * 4;
         const u32 grid_part = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().scatter_wgs);
-        if (W == 1) {
-            GLAUNCH(ctx, "k_bucket_partition", k_bucket_partition<u64>, dim3(grid_part), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
-                    bs.d_bstart.as<u64>(), d_cursor, bs.d_keys.as<u64>(), n_alloc, bs.d_flags.as<u32>());
-        } else {
-            GLAUNCH(ctx, "k_bucket_partition", k_bucket_partition<K128>, dim3(grid_part), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
-                    bs.d_bstart.as<u64>(), d_cursor, bs.d_keys.as<K128>(), n_alloc, bs.d_flags.as<u32>());
-        }
+        GLAUNCH_K(ctx, W, "k_bucket_partition", k_bucket_partition<K>, dim3(grid_part), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
+                  bs.d_bstart.as<u64>(), d_cursor, bs.d_keys.as<K>(), n_alloc, bs.d_flags.as<u32>());
     } else {
         // ---- two passes: count, scan, scatter (exact layout; the retry path of the single pass, > 512 buckets, multi-pass builds)
         bs.part_valid = false;                // (k_scan_excl overwrites d_bstart)
@@ -606,27 +614,16 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         GCHK(bs.d_keys.ensure((n_alloc + SCRATCH_KEYS) * KB));
         GCHK(bs.d_mult.ensure(n_alloc * 4));
         GCHK(bs.d_tcnt.ensure((size_t)rd.n_tiles * nb * 8 + 64));      // four 16-bit sub-counts per (tile, bucket)
-        // (d_flags is zeroed by k_tile_scan)
-        if (W == 1) {
-            GLAUNCH(ctx, "k_tile_hist", k_tile_hist<u64>, dim3(grid_tiles), dim3(GASM_TILE_WG), (size_t)nb * 16, rs, rs.tile_info, k, bbits, g, rd.n_tiles,
-                    bs.d_tcnt.as<ushort4>());
-        } else {
-            GLAUNCH(ctx, "k_tile_hist", k_tile_hist<K128>, dim3(grid_tiles), dim3(GASM_TILE_WG), (size_t)nb * 16, rs, rs.tile_info, k, bbits, g, rd.n_tiles,
-                    bs.d_tcnt.as<ushort4>());
-        }
+        GLAUNCH_K(ctx, W, "k_tile_hist", k_tile_hist<K>, dim3(grid_tiles), dim3(GASM_TILE_WG), (size_t)nb * 16, rs, rs.tile_info, k, bbits, g, rd.n_tiles,
+                  bs.d_tcnt.as<ushort4>());
         GLAUNCH(ctx, "k_tile_scan", k_tile_scan, dim3(S, std::max(1u, nb / 32u)), dim3(1024), 0, rs, bbits, padm, bs.d_tcnt.as<ushort4>(),
                 bs.d_toff.as<u32>(), bs.d_hist.as<u32>(), bs.d_flags.as<u32>());
         GLAUNCH(ctx, "k_scan_excl", k_scan_excl<u64>, dim3(1), dim3(1024), 0, bs.d_hist.as<u32>(), bs.d_bstart.as<u64>(), nbt);
         const size_t lds = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB + (size_t)nb * 24 + 96;   // KeyTraits<K>::NFL passes + trash slots + cursors
         // two workgroups per CU fit (LDS); a few tiles per workgroup so that the prefetch of the next tile pays
         const u32 grid_scatter = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().scatter_wgs);
-        if (W == 1) {
-            GLAUNCH(ctx, "k_bucket_scatter", k_bucket_scatter<u64>, dim3(grid_scatter), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
-                    bs.d_bstart.as<u64>(), bs.d_toff.as<u32>(), bs.d_tcnt.as<ushort4>(), bs.d_keys.as<u64>(), n_alloc);
-        } else {
-            GLAUNCH(ctx, "k_bucket_scatter", k_bucket_scatter<K128>, dim3(grid_scatter), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
-                    bs.d_bstart.as<u64>(), bs.d_toff.as<u32>(), bs.d_tcnt.as<ushort4>(), bs.d_keys.as<K128>(), n_alloc);
-        }
+        GLAUNCH_K(ctx, W, "k_bucket_scatter", k_bucket_scatter<K>, dim3(grid_scatter), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
+                  bs.d_bstart.as<u64>(), bs.d_toff.as<u32>(), bs.d_tcnt.as<ushort4>(), bs.d_keys.as<K>(), n_alloc);
     }
     unsigned long long* d_stamps = nullptr;
     static DBuf stamp_buf;
@@ -643,8 +640,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         d_stamps = stamp_buf.as<unsigned long long>();
     }
     const int dbg_d = knobs().dbg_dedup | (knobs().dedup_warm << 2);
-    // the buckets' distinct counts -> dstart by the de-duplication's last workgroup (a word of the build's zeroed flags counts
-    // the finished ones); beyond 16 384 buckets one workgroup of 256 is too slow a scanner: k_scan_excl in a launch of its own
+    // the buckets' distinct counts -> dstart by the de-duplication's last workgroup; beyond 16 384 buckets one workgroup of 256 is too slow a scanner: k_scan_excl in a launch of its own
     const bool scan_in_dedup = !bs.multi_pass && nbt <= 16384 && env_int("GASM_SCAN_IN_DEDUP", 1) != 0;
     bs.scan_in_dedup = scan_in_dedup;
     u32* const d_scan_out = scan_in_dedup ? bs.d_dstart.as<u32>() : nullptr;
@@ -655,20 +651,11 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         // passes over key sub-ranges, for buckets no table can hold; they re-read the bucket, so the result goes to a second
         // array and is copied back
         GCHK(bs.d_keys2.ensure(n_alloc * KB));
-        if (W == 2) GLAUNCH(ctx, "k_bucket_dedup_multi", k_bucket_dedup_multi<K128>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K128>(), bs.d_keys2.as<K128>(),
-                            bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits);
-        else GLAUNCH(ctx, "k_bucket_dedup_multi", k_bucket_dedup_multi<u64>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_keys2.as<u64>(),
-                     bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits);
+        GLAUNCH_K(ctx, W, "k_bucket_dedup_multi", k_bucket_dedup_multi<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_keys2.as<K>(),
+                  bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits);
         HIPCHK(hipMemcpyAsync(bs.d_keys.p, bs.d_keys2.p, n_alloc * KB, hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (W == 2) {
-        GLAUNCH(ctx, "k_bucket_dedup", (k_bucket_dedup<K128, 2048>), dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K128>(), bs.d_mult.as<u32>(),
-                bs.d_bstart.as<u64>(), d_blen, bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, dbg_d, d_stamps, d_scan_out);
-    } else if (bs.small_tbl) {
-        GLAUNCH(ctx, "k_bucket_dedup", (k_bucket_dedup<u64, 2048>), dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(),
-                bs.d_bstart.as<u64>(), d_blen, bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, dbg_d, d_stamps, d_scan_out);
     } else {
-        GLAUNCH(ctx, "k_bucket_dedup", (k_bucket_dedup<u64, 4096>), dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(),
-                bs.d_bstart.as<u64>(), d_blen, bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, dbg_d, d_stamps, d_scan_out);
+        GCHK(launch_bucket_dedup(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out));
     }
     if (d_stamps) {
         std::vector<unsigned long long> hv(8 + (size_t)nbt * 3);
@@ -681,16 +668,13 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     }
     if (bs.min_count > 1) {
         // the multiplicity cutoff, behind whichever de-duplication ran (every rung of pipeline_build_finish's ladder comes through
-        // here): weak keys leave the buckets' runs before anything reads them.  Its last workgroup redoes the offsets on flag word
-        // [10] (zero since the build's flags were cleared; [8] counted the de-duplication's workgroups, [9] is k_contig_scan's)
+        // here): weak keys leave the buckets' runs before anything reads them.  Its last workgroup redoes the offsets, counting on
+        // a flag word of its own
         GCHK(bs.d_solid_removed.ensure((size_t)S * 4));
         HIPCHK(hipMemsetAsync(bs.d_solid_removed.p, 0, (size_t)S * 4, ctx->stream));
-        if (W == 2) GLAUNCH(ctx, "k_bucket_solid", k_bucket_solid<K128>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K128>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
-                            bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.min_count, bs.d_solid_removed.as<u32>(),
-                            bs.d_flags.as<u32>() + 10, d_scan_out);
-        else GLAUNCH(ctx, "k_bucket_solid", k_bucket_solid<u64>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
-                     bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.min_count, bs.d_solid_removed.as<u32>(),
-                     bs.d_flags.as<u32>() + 10, d_scan_out);
+        GLAUNCH_K(ctx, W, "k_bucket_solid", k_bucket_solid<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
+                  bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.min_count, bs.d_solid_removed.as<u32>(),
+                  bs.d_flags.as<u32>() + GASM_FLAG_SOLID_DONE, d_scan_out);
     }
     if (!scan_in_dedup) GLAUNCH(ctx, "k_scan_excl", k_scan_excl<u32>, dim3(1), dim3(1024), 0, bs.d_bucket_d.as<u32>(), bs.d_dstart.as<u32>(), nbt);
     return GASM_OK;
@@ -727,16 +711,9 @@ int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
     const int W = bs.words, bbits = bs.bbits;
     const u32 nb = 1u << bbits, nbt = S * nb;
     GCHK(alloc_graph(bs, S));
-    // (k_bucket_gather zeroes the ranking's failure flag and the "still active" words of the k_link_jump launches; the
-    // overflow flag [0] stays)
     u32* const d_claim = bs.d_nxt.as<u32>();      // claim words of the degree kernels live in nxt until k_edge_next overwrites them
-    if (W == 1) {
-        GLAUNCH(ctx, "k_bucket_gather", k_bucket_gather<u64>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(),
-                bs.d_bstart.as<u64>(), bs.d_dstart.as<u32>(), bs.d_dk_key.as<u64>(), bs.d_dk_cnt.as<u32>(), d_claim, bs.d_eflag.as<u8>(), bs.d_flags.as<u32>());
-    } else {
-        GLAUNCH(ctx, "k_bucket_gather", k_bucket_gather<K128>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K128>(), bs.d_mult.as<u32>(),
-                bs.d_bstart.as<u64>(), bs.d_dstart.as<u32>(), bs.d_dk_key.as<K128>(), bs.d_dk_cnt.as<u32>(), d_claim, bs.d_eflag.as<u8>(), bs.d_flags.as<u32>());
-    }
+    GLAUNCH_K(ctx, W, "k_bucket_gather", k_bucket_gather<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(),
+              bs.d_bstart.as<u64>(), bs.d_dstart.as<u32>(), bs.d_dk_key.as<K>(), bs.d_dk_cnt.as<u32>(), d_claim, bs.d_eflag.as<u8>(), bs.d_flags.as<u32>());
     return launch_graph_dense(ctx, S, bs);
 }
 
@@ -754,14 +731,12 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
     const u32 gchunks = (u32)ceil_div_u64(est, GASM_WG * GASM_EDGE_ILP);     // the kernels that take GASM_EDGE_ILP edges per thread and round
     const dim3 grid_grp = seg_grid(gchunks, S);
     u32* const d_tgt = bs.d_ecid.as<u32>();        // first out-edge of every edge's target node; e_cid is written later (k_contig_scan)
-    if (W == 1) GLAUNCH(ctx, "k_edge_target", k_edge_target<u64>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_tgt, d_claim);
-    else GLAUNCH(ctx, "k_edge_target", k_edge_target<K128>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_tgt, d_claim);
+    GLAUNCH_K(ctx, W, "k_edge_target", k_edge_target<K>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_tgt, d_claim);
     GLAUNCH(ctx, "k_edge_multi", k_edge_multi, grid_grp, dim3(GASM_WG), 0, gv, S, gchunks, d_tgt, d_claim, bs.d_eflag.as<u8>());
     // (links: k_edge_next is their only writer — every edge's — before the ranking reads them; chain lengths: k_link_jump / k_chain_len)
-    if (W == 1) GLAUNCH(ctx, "k_node_flags", k_node_flags<u64>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_claim, bs.d_eflag.as<u8>(), bs.d_link.as<u64>(), bs.d_clen.as<u32>());
-    else GLAUNCH(ctx, "k_node_flags", k_node_flags<K128>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_claim, bs.d_eflag.as<u8>(), bs.d_link.as<u64>(), bs.d_clen.as<u32>());
+    GLAUNCH_K(ctx, W, "k_node_flags", k_node_flags<K>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_claim, bs.d_eflag.as<u8>(), bs.d_link.as<u64>(), bs.d_clen.as<u32>());
     GLAUNCH(ctx, "k_edge_next", k_edge_next, grid_grp, dim3(GASM_WG), 0, gv, S, gchunks, d_tgt, bs.d_eflag.as<u8>(), bs.d_nxt.as<u32>(), bs.d_link.as<u64>());
-    u32* const act = d_fl + 16;     // "still active" words of the k_link_jump launches
+    u32* const act = d_fl + GASM_FLAG_ACTIVE;     // "still active" words of the k_link_jump launches
     const u32 jchunks = (u32)ceil_div_u64(est, GASM_WG * 4);      // GASM_JUMP_ILP links per thread
     bs.ranked_in_lds = est <= 65534 && !bs.rank_global && !knobs().rank_global;
     bs.ruler_shift = 0;
@@ -772,7 +747,7 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
         bs.ruler_shift = rshift;
         const u32 rchunks = (u32)ceil_div_u64((est + (1u << rshift) - 1) >> rshift, GASM_WG);
         // LDS list of a segment: everything a workgroup can have while a CU only ever holds one of them, else the
-        // estimate with a quarter to spare (a segment that does not fit raises flags[1]: pipeline_build_finish)
+        // estimate with a quarter to spare (a segment that does not fit raises GASM_FLAG_RANK_FAILED: pipeline_build_finish)
         u32 lds_entries = 32767;
         if (S > (u32)ctx->n_cu) lds_entries = std::min<u32>(32767, (((est + est / 4) >> rshift) + 1024) & ~1023u);
         GLAUNCH(ctx, "k_rank_rulers", k_rank_rulers, seg_grid(rchunks, S), dim3(GASM_WG), 0, gv, S, rchunks, bs.d_link.as<u64>(), bs.d_rtab.as<u32>(), rshift, d_fl);
@@ -782,6 +757,7 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
         // (a thread stops as soon as its link is final; spans grow by a factor of jumps + 1 per launch at the very
         // least, so two launches cover any segment of this size, and the second normally returns at once)
         const int jumps = 255, launches = 2;
+        static_assert(launches <= GASM_FLAG_ACTIVE_N, "an active word per launch");
         for (int r = 0; r < launches; ++r)
             GLAUNCH(ctx, "k_link_jump", k_link_jump, seg_grid(jchunks, S), dim3(GASM_WG), 0, gv, S, jchunks, bs.d_link.as<u64>(), r ? act + r - 1 : nullptr, act + r, jumps,
                     bs.d_nxt.as<u32>(), bs.d_clen.as<u32>());         // (+ the chains' lengths: k_chain_len's work)
@@ -792,7 +768,7 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
         while ((1ull << rounds) < bs.maxD_cap) ++rounds;
         rounds += 1;
         const int jumps = 4, launches = (rounds * 10 + 22) / 23 + 1;
-        if (launches > 40) { gasm_set_error("segment too large for the list-ranking flags"); return GASM_ERR_CAPACITY; }
+        if (launches > (int)GASM_FLAG_ACTIVE_N) { gasm_set_error("segment too large for the list-ranking flags"); return GASM_ERR_CAPACITY; }
         for (int r = 0; r < launches; ++r)
             GLAUNCH(ctx, "k_link_jump", k_link_jump, seg_grid(jchunks, S), dim3(GASM_WG), 0, gv, S, jchunks, bs.d_link.as<u64>(), r ? act + r - 1 : nullptr, act + r, jumps,
                     (const u32*)nullptr, (u32*)nullptr);
@@ -802,7 +778,7 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
         GLAUNCH(ctx, "k_chain_len", k_chain_len, dim3(std::max(1u, grid_all)), dim3(GASM_WG), 0, bs.d_nxt.as<u32>(), bs.d_link.as<u64>(),
                 bs.d_clen.as<u32>(), gv.dstart + (size_t)S * nb);
     // segment directories of the contigs + the report (ticket last): written by the last workgroup of k_contig_scan to finish
-    const size_t words = 4 * (size_t)S + 8;
+    const size_t words = BuildReport<u32>::words(S);
     if (bs.h_report_words < words) {
         if (bs.h_report) (void)hipHostFree(bs.h_report);
         bs.h_report = nullptr; bs.h_report_words = 0;
@@ -810,19 +786,14 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs) {
         bs.h_report_words = words;
     }
     bs.ticket = next_ticket();
-    reinterpret_cast<volatile u32*>(bs.h_report)[4 * (size_t)S + 6] = 0;     // (the report of the previous build has been read or is void)
+    BuildReport<volatile u32>{bs.h_report, S}.ticket() = 0;     // (the report of the previous build has been read or is void)
     GLAUNCH(ctx, "k_contig_scan", k_contig_scan, dim3(S), dim3(1024), 0, gv, bs.d_eflag.as<u8>(), bs.d_clen.as<u32>(),
-            bs.d_ecid.as<u32>(), bs.d_ecoff.as<u64>(), d_seg_ncontig, bs.d_seg_cbases.as<u64>(), d_fl + 9, bs.d_seg_cstart.as<u32>(),
+            bs.d_ecid.as<u32>(), bs.d_ecoff.as<u64>(), d_seg_ncontig, bs.d_seg_cbases.as<u64>(), d_fl + GASM_FLAG_CONTIG_DONE, bs.d_seg_cstart.as<u32>(),
             bs.d_seg_bstart.as<u64>(), d_fl, bs.h_report, bs.ticket);
     GLAUNCH(ctx, "k_contig_place", k_contig_place, grid_seg, dim3(GASM_WG), 0, gv, bs.d_eflag.as<u8>(),
             bs.d_seg_cstart.as<u32>(), bs.d_seg_bstart.as<u64>(), bs.d_ecid.as<u32>(), bs.d_ecoff.as<u64>(), bs.d_c_off.as<u64>(), S, dchunks);
-    if (W == 1) {
-        GLAUNCH(ctx, "k_contig_emit", k_contig_emit<u64>, grid_grp, dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_nxt.as<u32>(),
-                bs.d_ecoff.as<u64>(), bs.d_contig_ascii.as<u8>(), S, gchunks);
-    } else {
-        GLAUNCH(ctx, "k_contig_emit", k_contig_emit<K128>, grid_grp, dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_nxt.as<u32>(),
-                bs.d_ecoff.as<u64>(), bs.d_contig_ascii.as<u8>(), S, gchunks);
-    }
+    GLAUNCH_K(ctx, W, "k_contig_emit", k_contig_emit<K>, grid_grp, dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_nxt.as<u32>(),
+              bs.d_ecoff.as<u64>(), bs.d_contig_ascii.as<u8>(), S, gchunks);
     bs.pending = true;
     return GASM_OK;
 }
@@ -885,7 +856,7 @@ int plan_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs) {
         bs.multi_pass = false;
         bs.single_pass = env_int("GASM_SINGLE_PASS", 1) != 0;
     }   // else: the same reads again — the partition that worked and the sizes the last build reported
-    GCHK(bs.d_flags.ensure(256));      // [0] bucket overflow, [1] list ranking gave up, [16..] the list-ranking launches' "still active" words
+    GCHK(bs.d_flags.ensure(GASM_FLAG_BYTES));
     bs.d_total = 0; bs.n_contigs = 0; bs.contig_bases = 0;
     return GASM_OK;
 }
@@ -932,6 +903,15 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs,
     return GASM_OK;
 }
 
+bool build_next_config(u32 ovf, u32 rungs, int words, int bb_cap, bool& single_pass, bool& small_tbl, int& bbits, bool& multi_pass) {
+    if ((rungs & GASM_RUNG_EXACT) && (ovf & GASM_OVF_REGION) && single_pass) single_pass = false;   // same partition, exact layout (count, scan, scatter)
+    else if ((rungs & GASM_RUNG_TABLE) && small_tbl && words == 1) small_tbl = false;               // same partition, larger tables
+    else if ((rungs & GASM_RUNG_BBITS) && bbits < bb_cap) bbits = std::min(bb_cap, bbits + 2);      // more buckets
+    else if ((rungs & GASM_RUNG_MULTI) && !multi_pass) multi_pass = true;                           // all bucket bits used: key sub-ranges, pass by pass
+    else return false;
+    return true;
+}
+
 // Read the report of a queued build; repeat the build with the next larger configuration while it reports a failure.
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt) {
     return pipeline_build_finish_n(ctx, &rd, rd.n_segments, bs, rebuilt);
@@ -943,21 +923,15 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
     if (!bs.pending) return GASM_OK;
     HIPCHK(hipSetDevice(ctx->device));
     for (;;) {
-        const u32* const rep = bs.h_report;
-        GCHK(wait_report(ctx, rep + 4 * (size_t)S + 6, bs.ticket));
+        const BuildReport<const u32> rep{bs.h_report, S};
+        GCHK(wait_report(ctx, &rep.ticket(), bs.ticket));
         bs.pending = false;
-        // flags[0]: bit 0 = a bucket overflowed its table, bit 1 = a bucket outgrew its region (single-pass partition)
-        const bool part_overflow = (rep[4 * (size_t)S + 4] & 2u) != 0;
-        const bool overflow = (rep[4 * (size_t)S + 4] & 1u) != 0 || part_overflow, rank_failed = rep[4 * (size_t)S + 5] != 0;
-        if (!overflow && !rank_failed) break;
+        const u32 overflow = rep.flags() & (GASM_OVF_TABLE | GASM_OVF_REGION);
+        if (!overflow && !rep.rank_failed()) break;
         if (rebuilt) *rebuilt = true;
         if (overflow) {
             if (!rd) { gasm_set_error("a merged k-mer bucket overflowed its table: the pooled build needs more bucket bits"); return GASM_ERR_CAPACITY; }
-            if (part_overflow && bs.single_pass) bs.single_pass = false;  // same partition, exact layout (count, scan, scatter)
-            else if (bs.small_tbl && bs.words == 1) bs.small_tbl = false;      // same partition, larger tables
-            else if (bs.bbits < bs.bb_cap) bs.bbits = std::min(bs.bb_cap, bs.bbits + 2);
-            else if (!bs.multi_pass) bs.multi_pass = true;                // all bucket bits used: key sub-ranges, pass by pass
-            else {
+            if (!build_next_config(overflow, GASM_RUNG_ALL, bs.words, bs.bb_cap, bs.single_pass, bs.small_tbl, bs.bbits, bs.multi_pass)) {
                 gasm_set_error("a k-mer bucket holds more than %d distinct k-mers even with %d bucket bits", GASM_BUCKET_MAX, bs.bbits);
                 return GASM_ERR_CAPACITY;
             }
@@ -970,13 +944,13 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
         }
         GCHK(launch_graph(ctx, S, bs));
     }
-    const u32* const rep = bs.h_report;
-    bs.h_dstart.assign(rep, rep + S + 1);
+    const BuildReport<const u32> rep{bs.h_report, S};
+    bs.h_dstart.assign(&rep.dstart(0), &rep.dstart(S) + 1);
     u32 maxD = 0;
     for (u32 s = 0; s <= S; ++s) {
-        bs.h_seg_cstart[s] = rep[S + 1 + s];
-        bs.h_seg_bstart[s] = (u64)rep[2 * S + 2 + 2 * s] | ((u64)rep[2 * S + 3 + 2 * s] << 32);
-        if (s < S) maxD = std::max(maxD, rep[s + 1] - rep[s]);
+        bs.h_seg_cstart[s] = rep.cstart(s);
+        bs.h_seg_bstart[s] = (u64)rep.bstart_lo(s) | ((u64)rep.bstart_hi(s) << 32);
+        if (s < S) maxD = std::max(maxD, rep.dstart(s + 1) - rep.dstart(s));
     }
     bs.d_total = bs.h_dstart[S];
     bs.n_contigs = bs.h_seg_cstart[S];
@@ -1080,10 +1054,8 @@ int pipeline_fetch_contig_twins(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         HIPCHK(hipMemsetAsync(d_bad, 0, 4, ctx->stream));
         const GraphView gv = graph_view(bs);
         const u32 grid = (u32)std::min<u64>(ceil_div_u64(P, GASM_WG), (u64)ctx->n_cu * 8);
-        if (bs.words == 1) GLAUNCH(ctx, "k_contig_twin", k_contig_twin<u64>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
-                                   bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), rd.n_segments, bs.d_twin.as<u32>(), d_bad);
-        else GLAUNCH(ctx, "k_contig_twin", k_contig_twin<K128>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
-                     bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), rd.n_segments, bs.d_twin.as<u32>(), d_bad);
+        GLAUNCH_K(ctx, bs.words, "k_contig_twin", k_contig_twin<K>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
+                  bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), rd.n_segments, bs.d_twin.as<u32>(), d_bad);
         std::vector<u32> h((size_t)P + 1);
         HIPCHK(hipMemcpyAsync(h.data(), bs.d_twin.p, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1432,7 +1404,7 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
         ft.p[t] = tbs[t]->d_fix.as<long long>();
     }
     // GASM_SCORE_VERIFY=1: compare every read with the contig text where the graph says it lies (kernels_score.hip, graph_match);
-    // a mismatch raises flags[2] of the build and pipeline_score_fetch refuses the scores
+    // a mismatch raises GASM_FLAG_SCORE_MISMATCH of the build and pipeline_score_fetch refuses the scores
     // A graph built with a multiplicity cutoff does not hold every k-mer of every read: the comparison is then part of the match
     // (verify = 2: a mismatch is "no match" and raises nothing)
     const int verify = graph.min_count > 1 ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
@@ -1444,13 +1416,10 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     u32 lds_paths = std::min<u32>(std::max<u32>(graph.have_actual ? graph.paths_est : 1024u, 1u), (u32)(GASM_SCORE_PATH_CAP * 12 / (4 + 8 * T)));
     if (const int cap = env_int("GASM_DBG_SCORE_LDS_PATHS", 0)) lds_paths = std::min<u32>(lds_paths, (u32)std::max(1, cap));
     const size_t lds_bytes = (size_t)lds_paths * (4 + 8 * (size_t)T);
-#define GASM_LAUNCH_SCORE(TT)                                                                                                                 \
-    do {                                                                                                                                      \
-        const auto kern = graph.words == 1 ? k_score_reads_graph<u64, TT> : k_score_reads_graph<K128, TT>;                                    \
-        GLAUNCH(ctx, "k_score_reads_graph", kern, seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), gv, graph.d_link.as<u64>(),      \
-                graph.d_ecid.as<u32>(), ps, ft, kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(), d_fx, (u64)PC, verify,          \
-                graph.d_flags.as<u32>() + 2);                                                                                                 \
-    } while (0)
+#define GASM_LAUNCH_SCORE(TT)                                                                                                                       \
+    GLAUNCH_K(ctx, graph.words, "k_score_reads_graph", (k_score_reads_graph<K, TT>), seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), gv, \
+              graph.d_link.as<u64>(), graph.d_ecid.as<u32>(), ps, ft, kmer, reads_per_wg, rchunks, lds_paths, ss.d_total.as<u32>(), d_fx, (u64)PC,  \
+              verify, graph.d_flags.as<u32>() + GASM_FLAG_SCORE_MISMATCH)
     GASM_TABLES_SWITCH(T, GASM_LAUNCH_SCORE)
 #undef GASM_LAUNCH_SCORE
     int32_t* o_br = ss.d_out_i32.as<int32_t>();
@@ -1637,7 +1606,7 @@ int pipeline_score_fetch(gasm_ctx* ctx, ScoreState& ss) {
         ss.n_paths = ss.graph->n_contigs;
         if (ss.verify) {
             u32 bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, ss.graph->d_flags.as<u32>() + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(&bad, ss.graph->d_flags.as<u32>() + GASM_FLAG_SCORE_MISMATCH, 4, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
             if (bad) { gasm_set_error("GASM_SCORE_VERIFY: a read that fits its contig by the graph differs from the contig's text"); return GASM_ERR_STATE; }
         }

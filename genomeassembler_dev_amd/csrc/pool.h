@@ -29,3 +29,13 @@ int pool_graph_launch(gasm_pool* p, u32 n_local_segments, u64 D, u64 maxD);
 int pool_score_launch(gasm_pool* p, int kmer, const double* table, bool wait_for_build);
 // read the graph's report (every fetch does); a graph that had to be repeated takes its scoring with it
 int pool_finish(gasm_pool* p);
+// ---- stages shared by the stage-by-stage entry points (pool.hip) and the exchange (exchange.hip); all queue on the pool's stream
+// and wait for nothing.  A rank without k-mers: empty runs everywhere (the arrays the later stages read still have to exist)
+int pool_empty_runs(gasm_pool* p);
+// k_pack_runs: the runs of the n buckets in d_list, back to back at records d_off[i] of keys_out / cnt_out
+int launch_pack_runs(gasm_ctx* ctx, const BuildState& bs, u32 n, const u32* d_list, const u64* d_off, void* keys_out, u32* cnt_out);
+// k_bucket_merge into the pool's runs (layout already in bs.d_bstart): n_out runs, each from n_src input runs (run_off / run_len,
+// offsets relative to src_base[source] where given).  Chooses the table (4096 slots for 64-bit keys, 2048 for 128-bit keys) and
+// the fine directory's width, sizes the outputs' directories and clears the build's flag words
+int launch_bucket_merge(gasm_pool* p, u32 n_out, u32 n_src, const void* keys_in, const u32* cnt_in, const u64* run_off, const u32* run_len,
+                        const u64* src_base);

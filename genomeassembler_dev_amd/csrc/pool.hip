@@ -19,29 +19,55 @@
 
 #include "pool.h"
 
-#define POOL_GUARD_BEGIN try {
-#define POOL_GUARD_END                                                         \
-    } catch (const std::bad_alloc&) {                                          \
-        gasm_set_error("out of host memory");                                  \
-        return GASM_ERR_CAPACITY;                                              \
-    } catch (const std::exception& e) {                                        \
-        gasm_set_error("internal error: %s", e.what());                        \
-        return GASM_ERR_INVALID;                                               \
-    }
-
-static int up(gasm_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
-    GCHK(b.ensure(bytes ? bytes : 8));
-    if (bytes) HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return GASM_OK;
-}
-
 static int read_lens(gasm_pool* p, u32 n) {
     p->h_len.assign(n, 0);
     if (n) HIPCHK(hipMemcpyAsync(p->h_len.data(), p->bs.d_bucket_d.p, (size_t)n * 4, hipMemcpyDeviceToHost, p->ctx->stream));
-    u32 fl[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(fl, p->bs.d_flags.p, 8, hipMemcpyDeviceToHost, p->ctx->stream));
+    u32 ovf = 0;
+    HIPCHK(hipMemcpyAsync(&ovf, p->bs.d_flags.as<u32>() + GASM_FLAG_OVERFLOW, 4, hipMemcpyDeviceToHost, p->ctx->stream));
     HIPCHK(hipStreamSynchronize(p->ctx->stream));
-    return (int)(fl[0] & 3u);   // bit 0 = a bucket overflowed its table, bit 1 = a bucket outgrew its region (single-pass partition)
+    return (int)(ovf & (GASM_OVF_TABLE | GASM_OVF_REGION));
+}
+
+int pool_empty_runs(gasm_pool* p) {
+    gasm_ctx* ctx = p->ctx;
+    BuildState& bs = p->bs;
+    GCHK(bs.d_bucket_d.ensure(((size_t)p->n_runs + 2) * 4));       // (+ the flag word that travels with the lengths in an exchange)
+    GCHK(bs.d_bstart.ensure(((size_t)p->n_runs + 1) * 8));
+    GCHK(bs.d_keys.ensure(64)); GCHK(bs.d_mult.ensure(64));
+    HIPCHK(hipMemsetAsync(bs.d_bucket_d.p, 0, ((size_t)p->n_runs + 2) * 4, ctx->stream));
+    bs.part_valid = false;
+    HIPCHK(hipMemsetAsync(bs.d_bstart.p, 0, ((size_t)p->n_runs + 1) * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, GASM_FLAG_BYTES, ctx->stream));
+    return GASM_OK;
+}
+
+int launch_pack_runs(gasm_ctx* ctx, const BuildState& bs, u32 n, const u32* d_list, const u64* d_off, void* keys_out, u32* cnt_out) {
+    GLAUNCH_K(ctx, bs.words, "k_pack_runs", k_pack_runs<K>, dim3(n), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
+              bs.d_bucket_d.as<u32>(), d_list, d_off, static_cast<K*>(keys_out), cnt_out);
+    return GASM_OK;
+}
+
+template <class K, int TBL>
+static int launch_bucket_merge_as(gasm_pool* p, u32 n_out, u32 n_src, const void* keys_in, const u32* cnt_in, const u64* run_off, const u32* run_len,
+                                  const u64* src_base) {
+    BuildState& bs = p->bs;
+    GLAUNCH(p->ctx, "k_bucket_merge", (k_bucket_merge<K, TBL>), dim3(n_out), dim3(GASM_WG), 0, static_cast<const K*>(keys_in), cnt_in, run_off, run_len, n_src,
+            bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(),
+            2 * bs.k - bs.bbits, src_base);
+    return GASM_OK;
+}
+
+int launch_bucket_merge(gasm_pool* p, u32 n_out, u32 n_src, const void* keys_in, const u32* cnt_in, const u64* run_off, const u32* run_len,
+                        const u64* src_base) {
+    BuildState& bs = p->bs;
+    GCHK(bs.d_bucket_d.ensure(((size_t)n_out + 2) * 4));
+    bs.small_tbl = bs.words == 2;
+    bs.fbits = bs.small_tbl ? 9 : 10;
+    GCHK(bs.d_fdir.ensure(((size_t)n_out + 1) * ((1u << bs.fbits) + 1) * 2));
+    HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, GASM_FLAG_BYTES, p->ctx->stream));
+    if (!n_out) return GASM_OK;
+    if (bs.small_tbl) return launch_bucket_merge_as<K128, 2048>(p, n_out, n_src, keys_in, cnt_in, run_off, run_len, src_base);
+    return launch_bucket_merge_as<u64, 4096>(p, n_out, n_src, keys_in, cnt_in, run_off, run_len, src_base);
 }
 
 int pool_graph_launch(gasm_pool* p, u32 S, u64 D, u64 maxD) {
@@ -106,7 +132,7 @@ extern "C" {
 
 int gasm_pool_create(gasm_ctx* ctx, const char* reads, uint64_t n_reads, uint32_t fixed_len, const uint64_t* seg_read_off,
                      uint32_t n_segments, gasm_pool** out) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!ctx || !out) { gasm_set_error("gasm_pool_create: null argument"); return GASM_ERR_INVALID; }
     *out = nullptr;
     if (fixed_len == 0) { gasm_set_error("pooled builds take fixed-length reads"); return GASM_ERR_INVALID; }
@@ -116,7 +142,7 @@ int gasm_pool_create(gasm_ctx* ctx, const char* reads, uint64_t n_reads, uint32_
     if (st != GASM_OK) { gasm_pool_free(p); return st; }
     *out = p;
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 void gasm_pool_free(gasm_pool* p) {
@@ -130,7 +156,7 @@ void gasm_pool_free(gasm_pool* p) {
 int gasm_pool_key_words(const gasm_pool* p) { return p ? p->bs.words : 0; }
 
 int gasm_pool_local_runs(gasm_pool* p, int k, int bbits, const uint32_t** run_len) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || !run_len) { gasm_set_error("gasm_pool_local_runs: null argument"); return GASM_ERR_INVALID; }
     gasm_ctx* ctx = p->ctx;
     BuildState& bs = p->bs;
@@ -142,14 +168,7 @@ int gasm_pool_local_runs(gasm_pool* p, int k, int bbits, const uint32_t** run_le
     p->graphed = false; p->paths_ready = false; p->ss.launched = false; p->ss.valid = false;
     p->n_runs = S << bbits;
     if (bs.n_kmers == 0) {
-        // this rank holds no k-mer: empty runs everywhere (the arrays the later stages read still have to exist)
-        GCHK(bs.d_bucket_d.ensure((size_t)p->n_runs * 4 + 8));
-        GCHK(bs.d_bstart.ensure(((size_t)p->n_runs + 1) * 8));
-        GCHK(bs.d_keys.ensure(64)); GCHK(bs.d_mult.ensure(64));
-        HIPCHK(hipMemsetAsync(bs.d_bucket_d.p, 0, (size_t)p->n_runs * 4 + 8, ctx->stream));
-        bs.part_valid = false;
-        HIPCHK(hipMemsetAsync(bs.d_bstart.p, 0, ((size_t)p->n_runs + 1) * 8, ctx->stream));
-        HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, 256, ctx->stream));
+        GCHK(pool_empty_runs(p));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         p->h_len.assign(p->n_runs, 0);
         *run_len = p->h_len.data();
@@ -162,18 +181,17 @@ int gasm_pool_local_runs(gasm_pool* p, int k, int bbits, const uint32_t** run_le
         const int ov = read_lens(p, p->n_runs);
         if (ov < 0) return ov;
         if (!ov) break;
-        if ((ov & 2) && bs.single_pass) { bs.single_pass = false; continue; }
-        if (bs.small_tbl && bs.words == 1) { bs.small_tbl = false; continue; }
+        if (build_next_config((u32)ov, GASM_RUNG_EXACT | GASM_RUNG_TABLE, bs.words, bs.bb_cap, bs.single_pass, bs.small_tbl, bs.bbits, bs.multi_pass)) continue;
         gasm_set_error("a k-mer bucket of this rank holds more than %d distinct k-mers with %d bucket bits", GASM_TBL_LIMIT, bbits);
         return GASM_ERR_CAPACITY;
     }
     *run_len = p->h_len.data();
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_pack_runs(gasm_pool* p, const uint32_t* bucket_ix, uint64_t n, void* d_keys_out, void* d_counts_out) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || (n && !bucket_ix)) { gasm_set_error("gasm_pool_pack_runs: null argument"); return GASM_ERR_INVALID; }
     if (n == 0) return GASM_OK;
     gasm_ctx* ctx = p->ctx;
@@ -187,24 +205,17 @@ int gasm_pool_pack_runs(gasm_pool* p, const uint32_t* bucket_ix, uint64_t n, voi
     }
     if (run == 0) return GASM_OK;                 // every listed run is empty: nothing to write (the buffers may be null)
     if (!d_keys_out || !d_counts_out) { gasm_set_error("gasm_pool_pack_runs: null output buffer"); return GASM_ERR_INVALID; }
-    GCHK(up(ctx, p->d_list, bucket_ix, n * 4));
-    GCHK(up(ctx, p->d_off, off.data(), n * 8));
-    const BuildState& bs = p->bs;
-    if (bs.words == 1) {
-        GLAUNCH(ctx, "k_pack_runs", k_pack_runs<u64>, dim3((u32)n), dim3(GASM_WG), 0, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
-                bs.d_bucket_d.as<u32>(), p->d_list.as<u32>(), p->d_off.as<u64>(), static_cast<u64*>(d_keys_out), static_cast<u32*>(d_counts_out));
-    } else {
-        GLAUNCH(ctx, "k_pack_runs", k_pack_runs<K128>, dim3((u32)n), dim3(GASM_WG), 0, bs.d_keys.as<K128>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
-                bs.d_bucket_d.as<u32>(), p->d_list.as<u32>(), p->d_off.as<u64>(), static_cast<K128*>(d_keys_out), static_cast<u32*>(d_counts_out));
-    }
+    GCHK(h2d(ctx, p->d_list, bucket_ix, n * 4));
+    GCHK(h2d(ctx, p->d_off, off.data(), n * 8));
+    GCHK(launch_pack_runs(ctx, p->bs, (u32)n, p->d_list.as<u32>(), p->d_off.as<u64>(), d_keys_out, static_cast<u32*>(d_counts_out)));
     HIPCHK(hipStreamSynchronize(ctx->stream));     // the buffers belong to the caller's streams from here on
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_merge_runs(gasm_pool* p, uint32_t n_out, uint32_t n_src, const uint64_t* run_off, const uint32_t* run_len, const void* d_keys_in,
                          const void* d_counts_in, const uint32_t** merged_len) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || !merged_len || (n_out && n_src && (!run_off || !run_len))) { gasm_set_error("gasm_pool_merge_runs: null argument"); return GASM_ERR_INVALID; }
     if (p->bs.k == 0) { gasm_set_error("gasm_pool_merge_runs before gasm_pool_local_runs"); return GASM_ERR_STATE; }
     gasm_ctx* ctx = p->ctx;
@@ -223,25 +234,10 @@ int gasm_pool_merge_runs(gasm_pool* p, uint32_t n_out, uint32_t n_src, const uin
     GCHK(bs.d_keys.ensure(std::max<u64>(bstart[n_out], 1) * KB));
     GCHK(bs.d_mult.ensure(std::max<u64>(bstart[n_out], 1) * 4));
     bs.part_valid = false;                      // (d_bstart no longer holds the partition's region layout)
-    GCHK(up(ctx, bs.d_bstart, bstart.data(), bstart.size() * 8));
-    GCHK(bs.d_bucket_d.ensure((size_t)n_out * 4 + 8));
-    bs.small_tbl = bs.words == 2;               // the merge uses 4096-slot tables for 64-bit keys, 2048-slot ones for 128-bit keys
-    bs.fbits = bs.words == 1 ? 10 : 9;
-    GCHK(bs.d_fdir.ensure(((size_t)n_out + 1) * ((1u << bs.fbits) + 1) * 2));
-    GCHK(up(ctx, p->d_roff, run_off, (size_t)n_out * n_src * 8));
-    GCHK(up(ctx, p->d_rlen, run_len, (size_t)n_out * n_src * 4));
-    HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, 256, ctx->stream));
-    if (n_out) {
-        if (bs.words == 1) {
-            GLAUNCH(ctx, "k_bucket_merge", (k_bucket_merge<u64, 4096>), dim3(n_out), dim3(GASM_WG), 0, static_cast<const u64*>(d_keys_in),
-                    static_cast<const u32*>(d_counts_in), p->d_roff.as<u64>(), p->d_rlen.as<u32>(), n_src, bs.d_keys.as<u64>(), bs.d_mult.as<u32>(),
-                    bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * bs.k - bs.bbits, (const u64*)nullptr);
-        } else {
-            GLAUNCH(ctx, "k_bucket_merge", (k_bucket_merge<K128, 2048>), dim3(n_out), dim3(GASM_WG), 0, static_cast<const K128*>(d_keys_in),
-                    static_cast<const u32*>(d_counts_in), p->d_roff.as<u64>(), p->d_rlen.as<u32>(), n_src, bs.d_keys.as<K128>(), bs.d_mult.as<u32>(),
-                    bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * bs.k - bs.bbits, (const u64*)nullptr);
-        }
-    }
+    GCHK(h2d(ctx, bs.d_bstart, bstart.data(), bstart.size() * 8));
+    GCHK(h2d(ctx, p->d_roff, run_off, (size_t)n_out * n_src * 8));
+    GCHK(h2d(ctx, p->d_rlen, run_len, (size_t)n_out * n_src * 4));
+    GCHK(launch_bucket_merge(p, n_out, n_src, d_keys_in, static_cast<const u32*>(d_counts_in), p->d_roff.as<u64>(), p->d_rlen.as<u32>(), nullptr));
     p->n_runs = n_out;
     const int ov = read_lens(p, n_out);
     if (ov < 0) return ov;
@@ -252,11 +248,11 @@ int gasm_pool_merge_runs(gasm_pool* p, uint32_t n_out, uint32_t n_src, const uin
     p->graphed = false;
     *merged_len = p->h_len.data();
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_graph(gasm_pool* p, uint32_t n_local_segments) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p) { gasm_set_error("pool is null"); return GASM_ERR_INVALID; }
     const u32 S = n_local_segments, nb = 1u << p->bs.bbits;
     if ((u64)S * nb != p->n_runs) { gasm_set_error("the current runs cover %u buckets, %u segments need %llu", p->n_runs, S, (unsigned long long)S * nb); return GASM_ERR_STATE; }
@@ -268,7 +264,7 @@ int gasm_pool_graph(gasm_pool* p, uint32_t n_local_segments) {
         D += d; maxD = std::max(maxD, d);
     }
     return pool_graph_launch(p, S, D, maxD);
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 // ---- reads to their segment's owner ------------------------------------------------------------------------------
@@ -282,7 +278,7 @@ int gasm_pool_piece_words(gasm_pool* p, uint32_t seg_lo, uint32_t seg_hi, uint64
 }
 
 int gasm_pool_pack_reads(gasm_pool* p, uint32_t seg_lo, uint32_t seg_hi, void* d_words_out) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || seg_lo > seg_hi || seg_hi > p->rd.n_segments) { gasm_set_error("gasm_pool_pack_reads: bad argument"); return GASM_ERR_INVALID; }
     gasm_ctx* ctx = p->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -300,17 +296,17 @@ int gasm_pool_pack_reads(gasm_pool* p, uint32_t seg_lo, uint32_t seg_hi, void* d
     if (woff == 0) return GASM_OK;
     if (!d_words_out) { gasm_set_error("gasm_pool_pack_reads: null buffer"); return GASM_ERR_INVALID; }
     if (np > 65535) { gasm_set_error("at most 65535 pieces per call"); return GASM_ERR_CAPACITY; }
-    GCHK(up(ctx, p->d_off, dir.data(), dir.size() * 8));
+    GCHK(h2d(ctx, p->d_off, dir.data(), dir.size() * 8));
     GLAUNCH(ctx, "k_repack_reads", k_repack_reads, dim3(std::max(1u, std::min<u32>(ceil_div_u64(max_words, GASM_WG), 64u)), np), dim3(GASM_WG), 0,
             p->rd.d_words.as<u64>(), p->d_off.as<u64>(), static_cast<u64*>(d_words_out));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_set_reads(gasm_pool* p, const void* d_words, uint64_t n_words, uint32_t n_pieces, const uint32_t* piece_seg, const uint64_t* piece_reads,
                         const uint64_t* piece_word_off) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || (n_pieces && (!piece_seg || !piece_reads || !piece_word_off)) || (n_words && !d_words)) { gasm_set_error("gasm_pool_set_reads: null argument"); return GASM_ERR_INVALID; }
     if (!p->graphed) { gasm_set_error("gasm_pool_set_reads before gasm_pool_graph"); return GASM_ERR_STATE; }
     gasm_ctx* ctx = p->ctx;
@@ -340,58 +336,58 @@ int gasm_pool_set_reads(gasm_pool* p, const void* d_words, uint64_t n_words, uin
     HIPCHK(hipMemsetAsync(static_cast<char*>(o.d_words.p) + n_words * 8, 0, 32, ctx->stream));
     GCHK(o.d_read_off.ensure(std::max<u64>(o.n_reads, 1) * 8));
     if (o.n_reads) {
-        GCHK(up(ctx, p->d_roff, pfirst.data(), pfirst.size() * 8));
-        GCHK(up(ctx, p->d_off, pword.data(), pword.size() * 8));
+        GCHK(h2d(ctx, p->d_roff, pfirst.data(), pfirst.size() * 8));
+        GCHK(h2d(ctx, p->d_off, pword.data(), pword.size() * 8));
         GLAUNCH(ctx, "k_piece_positions", k_piece_positions, dim3(std::min<u32>(ceil_div_u64(o.n_reads, GASM_WG), (u32)ctx->n_cu * 8u)), dim3(GASM_WG), 0,
                 p->d_roff.as<u64>(), p->d_off.as<u64>(), (u32)pfirst.size(), o.n_reads, flen, o.d_read_off.as<u64>());
     }
-    GCHK(up(ctx, o.d_seg_read_off, o.h_seg_read_off.data(), ((size_t)S + 1) * 8));
+    GCHK(h2d(ctx, o.d_seg_read_off, o.h_seg_read_off.data(), ((size_t)S + 1) * 8));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     p->reads_set = true;
     p->ss.launched = false; p->ss.valid = false;
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_score(gasm_pool* p, int kmer, const double* table) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || !table) { gasm_set_error("gasm_pool_score: null argument"); return GASM_ERR_INVALID; }
     return pool_score_launch(p, kmer, table, true);
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_fetch_distinct(gasm_pool* p, const uint64_t** seg_off, const uint64_t** keys, const uint32_t** mult, int* words) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || !seg_off || !keys || !mult || !words) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!p->graphed) { gasm_set_error("fetch before gasm_pool_graph"); return GASM_ERR_STATE; }
     GCHK(pool_finish(p));
     GCHK(pipeline_fetch_distinct(p->ctx, p->own, p->bs));
     *seg_off = p->bs.h_seg_doff.data(); *keys = p->bs.h_dk_key.data(); *mult = p->bs.h_dk_cnt.data(); *words = p->bs.words;
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_fetch_contigs(gasm_pool* p, const uint64_t** seg_contig_off, const uint64_t** off, const char** data) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || !seg_contig_off || !off || !data) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     if (!p->graphed) { gasm_set_error("fetch before gasm_pool_graph"); return GASM_ERR_STATE; }
     GCHK(pool_finish(p));
     GCHK(pipeline_fetch_contigs(p->ctx, p->own, p->bs));
     *seg_contig_off = p->bs.h_seg_coff.data(); *off = p->bs.h_c_off.data(); *data = p->bs.h_contigs.data();
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 int gasm_pool_fetch_scores(gasm_pool* p, const double** bp_score, const double** norm_by_break_freqs, const double** norm_by_len,
                            const int32_t** kmer_breaks, const int32_t** sequence_len) {
-    POOL_GUARD_BEGIN
+    API_GUARD_BEGIN
     if (!p || !bp_score || !norm_by_break_freqs || !norm_by_len || !kmer_breaks || !sequence_len) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
     GCHK(pool_finish(p));
     GCHK(pipeline_score_fetch(p->ctx, p->ss));
     *bp_score = p->ss.h_bp.data(); *norm_by_break_freqs = p->ss.h_nf.data(); *norm_by_len = p->ss.h_nl.data();
     *kmer_breaks = p->ss.h_breaks.data(); *sequence_len = p->ss.h_len.data();
     return GASM_OK;
-    POOL_GUARD_END
+    API_GUARD_END
 }
 
 }  // extern "C"
