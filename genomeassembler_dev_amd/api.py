@@ -106,20 +106,34 @@ def get_contigs(read_kmers, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_list
     return _contig_matrix(h, dbg_kmer, as_lists)
 
 
-def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1):
+def _check_tips(tip_len, tip_rounds):
+    """the argument rule of every tip-clipping entry: tip_len >= 0, and 1.._lib.MAX_TIP_ROUNDS rounds when it is on"""
+    if int(tip_len) < 0 or int(tip_len) > 0xFFFFFFFF:
+        raise ValueError("tip_len must be >= 0 (0: no tip clipping)")
+    if int(tip_len) > 0 and not 1 <= int(tip_rounds) <= _lib.MAX_TIP_ROUNDS:
+        raise ValueError(f"tip_rounds must be 1..{_lib.MAX_TIP_ROUNDS} when tip_len > 0")
+
+
+def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
+                           tip_rounds=1):
     """get_kmers_from_reads + get_contigs in one call (gasm_get_contigs_from_reads): the k-mers are taken on the GPU from the
     packed reads instead of being exploded into len(reads) * (read_len - k + 1) strings first (lib/DeNovoAssembler.R:109-130).
     reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed).
     min_count > 1 (gasm_get_contigs_from_reads_solid): only k-mers seen at least min_count times become edges.
-    strands = 2 (gasm_get_contigs_from_reads_strands): the k-mers of every read and of its reverse complement."""
+    strands = 2 (gasm_get_contigs_from_reads_strands): the k-mers of every read and of its reverse complement.
+    tip_len > 0 (gasm_get_contigs_from_reads_tips): tip_rounds rounds of tip clipping before the contigs are cut (include/gasm.h)."""
     if int(min_count) < 1:
         raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
     if int(strands) not in (1, 2):
         raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+    _check_tips(tip_len, tip_rounds)
     ctx = ctx or default_context()
     buf, off = _pack(reads)
     h = C.c_void_p()
-    if int(strands) == 2:
+    if int(tip_len) > 0:
+        check(lib().gasm_get_contigs_from_reads_tips(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
+                                                     int(min_count), int(strands), int(tip_len), int(tip_rounds), C.byref(h)))
+    elif int(strands) == 2:
         check(lib().gasm_get_contigs_from_reads_strands(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
                                                         int(min_count), 2, C.byref(h)))
     elif int(min_count) == 1:

@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import PLAN_FIELDS, check, default_context, lib
-from .api import unpack_kmers
+from ._lib import MAX_TIP_ROUNDS, PLAN_FIELDS, check, default_context, lib
+from .api import _check_tips, unpack_kmers
 
 
 class SegmentBatch:
@@ -110,7 +110,8 @@ class SegmentBatch:
         genome_len_hint then counts the distinct k-mers before the cutoff (include/gasm.h).
         strands = 2 (gasm_batch_build_strands): the k-mers of every read and of its reverse complement — reads of both strands
         then meet in one graph, multiplicities (and min_count) are sums over both strands, and the contigs come in
-        reverse-complement pairs (contig_twins).  Scores are over the reads as they were given, each once."""
+        reverse-complement pairs (contig_twins).  Scores are over the reads as they were given, each once.
+        Tip clipping: build_tips()."""
         if int(min_count) < 1:
             raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
         if int(strands) not in (1, 2):
@@ -124,6 +125,23 @@ class SegmentBatch:
         self.k = int(k)
         return self
 
+    def build_tips(self, k, genome_len_hint=0, min_count=1, strands=1, tip_len=0, tip_rounds=1):
+        """build() with tip clipping (gasm_batch_build_tips): exactly tip_rounds rounds (1.._lib.MAX_TIP_ROUNDS) behind the cutoff
+        — a contig of at most tip_len bases that dead-ends on one side and hangs, on the other, on a node with a strictly
+        stronger sibling edge leaves the k-mer set with all its k-mers (the rule: include/gasm.h); 2k - 1 is the intended
+        length.  tip_stats() tells what each round removed.  tip_len = 0 is build(k, genome_len_hint, min_count, strands):
+        the same call into the library, and tip_rounds is not read."""
+        if int(tip_len) == 0:
+            return self.build(k, genome_len_hint, min_count, strands)
+        if int(min_count) < 1:
+            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+        if int(strands) not in (1, 2):
+            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+        _check_tips(tip_len, tip_rounds)
+        check(lib().gasm_batch_build_tips(self.h, int(k), int(genome_len_hint), int(min_count), int(strands), int(tip_len), int(tip_rounds)))
+        self.k = int(k)
+        return self
+
     def solid_stats(self):
         """(distinct k-mers per segment before the last build's cutoff, after it): two uint64 arrays, equal at min_count = 1"""
         a, b = C.c_void_p(), C.c_void_p()
@@ -131,6 +149,18 @@ class SegmentBatch:
         n = self.n_segments
         return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint64)), shape=(n,)).copy(),
                 np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint64)), shape=(n,)).copy())
+
+    def tip_stats(self):
+        """(contigs clipped, k-mers clipped) by the last build's tip clipping: two (n_segments, MAX_TIP_ROUNDS) uint32 arrays,
+        column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would clip more."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_tip_stats(self.h, C.byref(a), C.byref(b)))
+        n = self.n_segments * MAX_TIP_ROUNDS
+        shape = (self.n_segments, MAX_TIP_ROUNDS)
+        if not n:
+            return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
+                np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
 
     def kmer_spectrum(self):
         """(n_segments, 256) uint64: [s, m] = distinct k-mers of segment s of the last build with multiplicity m (255: that or

@@ -101,6 +101,7 @@ enum : u32 {
     GASM_FLAG_BYTES = 256,          // size of the area without cursors
     GASM_OVF_TABLE = 1,             // a bucket holds more distinct keys than its table (or, multi-pass, than GASM_BUCKET_MAX)
     GASM_OVF_REGION = 2,            // a bucket outgrew its region of the one-pass partition
+    GASM_OVF_TIP_RANK = 4,          // the LDS list ranking gave up in a tip-clipping round before the last graph pass (k_tip_mark)
 };
 static_assert(GASM_FLAG_ACTIVE + GASM_FLAG_ACTIVE_N <= GASM_FLAG_WORDS && GASM_FLAG_WORDS * 4 == GASM_FLAG_BYTES, "flag area layout");
 // Zeroing contract.  Every attempt at the distinct k-mers starts with all GASM_FLAG_WORDS words zero: the one-pass partition
@@ -108,7 +109,9 @@ static_assert(GASM_FLAG_ACTIVE + GASM_FLAG_ACTIVE_N <= GASM_FLAG_WORDS && GASM_F
 // stages that produce runs without a partition (merges, a rank without k-mers) fill GASM_FLAG_BYTES.  So the done counters are
 // zero when their kernel starts, and GASM_FLAG_OVERFLOW holds what this attempt raised.  Every graph launch — the first, and a
 // repeat after a failed ranking — starts with k_bucket_gather clearing every word except GASM_FLAG_OVERFLOW, which stays for
-// the report: the ranking's flag, the scorer's flag, k_contig_scan's counter and the active words are zero again.
+// the report: the ranking's flag, the scorer's flag, k_contig_scan's counter and the active words are zero again.  A build
+// with tip clipping runs a graph pass per round: the gather of each pass also clears the done counter of the compaction
+// (GASM_FLAG_SOLID_DONE) that ran in front of it, and k_tip_mark saves a ranking failure of its pass into the overflow word.
 
 // The pinned report of a build over S segments (BuildState::h_report, u32 words), written by k_contig_scan's last workgroup,
 // the ticket last: first distinct k-mer, first contig and first contig base (lo, hi) of every segment, each with the total in
@@ -151,6 +154,10 @@ __global__ void k_bucket_dedup_multi(const K* keys, K* keys_out, u32* mult, cons
 template <class K>
 __global__ void k_bucket_solid(K* keys, u32* mult, const u64* bstart, u32* bucket_d, u16* fdir, int low_bits, int fbits, int bbits, u32 min_count,
                                u32* removed, u32* done, u32* dstart);
+// tip clipping (tip_len > 0): zeroes, in the bucket runs, the multiplicities of the edges of every tip of the ranked graph
+template <class K>
+__global__ void k_tip_mark(GraphView gv, u32 n_segments, u32 chunks, const u8* eflag, const u32* clen, const u32* nxt, const u32* dk_cnt, const u64* bstart,
+                           u32* mult, u32 tip_len, u32* flags, u32* tips);
 __global__ void k_kmer_spectrum(const u32* dstart, u32 nb, const u32* dk_cnt, u32 n_segments, u32 chunks, u32* hist);
 template <class K>
 __global__ void k_bucket_gather(const K* keys, const u32* mult, const u64* bstart, const u32* dstart, K* dk_key, u32* dk_cnt, u32* claim, u8* eflag,

@@ -1680,3 +1680,84 @@ __global__ void __launch_bounds__(GASM_WG) k_contig_twin(GraphView gv, const u64
 }
 template __global__ void k_contig_twin<u64>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
 template __global__ void k_contig_twin<K128>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
+
+// ================================================================================================================
+// Tip clipping (gasm_batch_build_tips, tip_len > 0 only).  No counterpart in the reference, whose walk ends contigs at every
+// branching node and never simplifies the graph; Velvet clips tips right behind its coverage cutoff.  A tip is a short
+// contig that hangs on the graph at one end only and whose attaching edge is strictly weaker than a sibling's:
+//   forward tip   the target of its last edge has no out-edge, and the source of its first edge has another out-edge of
+//                 strictly higher multiplicity than the first edge;
+//   backward tip  the source of its first edge has no in-edge, and the target of its last edge has another in-edge of
+//                 strictly higher multiplicity than the last edge.
+// k_tip_mark runs on a ranked graph (eflag bit 0 = head of a contig, clen = edges of the head's chain, nxt = the walk): one
+// thread per head whose contig has at most tip_len bases (clen + k - 1) walks its at most tip_len - k + 1 edges to the last
+// one, tests both rules and, for a tip, walks again and zeroes the multiplicity of every edge IN THE BUCKET RUNS (dense
+// edge e of bucket b sits at bstart[b] + (e - dstart[b])).  It reads the dense arrays only and writes the runs only, so all
+// tips of a round are found on the same graph.  k_bucket_solid with min_count = 1 then compacts the runs (a multiplicity of
+// 0 is below any cutoff), rewrites the directory rows and the offsets, and counts the k-mers that left.
+// Out-edges of a node are neighbours in the sorted list; the in-edges of a node are the four keys x·node, one directory
+// lookup each.  The comparison is strict and has no tie-break by key: that keeps the rule symmetric under reverse
+// complement (a forward tip's twin is a backward tip with the same multiplicities, clipped in the same round).
+// A ranking that gave up leaves chain lengths that mean nothing: every walk is bounded by tip_len and stays inside the
+// segment's edges, every store is checked against its bucket's run, and the ranking's flag is copied into the overflow word
+// (GASM_OVF_TIP_RANK), which the next round's k_bucket_gather keeps, so the host repeats the build.
+// tips[seg] += contigs clipped.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_tip_mark(GraphView gv, u32 n_segments, u32 chunks, const u8* __restrict__ eflag,
+                                                      const u32* __restrict__ clen, const u32* __restrict__ nxt, const u32* __restrict__ dk_cnt,
+                                                      const u64* __restrict__ bstart, u32* __restrict__ mult, u32 tip_len, u32* __restrict__ flags,
+                                                      u32* __restrict__ tips) {
+    const K* dk = reinterpret_cast<const K*>(gv.dk_key);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && flags[GASM_FLAG_RANK_FAILED]) atomicOr(&flags[GASM_FLAG_OVERFLOW], (u32)GASM_OVF_TIP_RANK);
+    const u32 nb = 1u << gv.bbits;
+    const int node_bits = 2 * (gv.k - 1);
+    for_seg_edges(gv.dstart, nb, n_segments, chunks, [&](u32 seg, u32 lo, u32 hi, u32 i) {
+        if (!(eflag[i] & 1)) return;
+        const u32 len = clen[i];
+        if (len == 0 || (u64)len + (u32)(gv.k - 1) > tip_len) return;
+        u32 t = i;
+        for (u32 s = 1; s < len; ++s) {
+            const u32 n = nxt[t];
+            if (n < lo || n >= hi) return;                    // (also GASM_NONE32: a chain shorter than its length says)
+            t = n;
+        }
+        if (nxt[t] != GASM_NONE32) return;
+        const K u = kshr(dk[i], 2), v = klowbits(dk[t], node_bits);
+        const u32 m_first = dk_cnt[i], m_last = dk_cnt[t];
+        bool tip = false;
+        {   // forward: nothing leaves v, and a stronger edge leaves u
+            u32 bhi;
+            const u32 j = graph_lower_bound<K>(gv, seg, kshl(v, 2), &bhi);
+            if (!(j < bhi && keq(kshr(dk[j], 2), v))) {
+                for (u32 r = i; r > lo && keq(kshr(dk[r - 1], 2), u); --r) tip = tip || dk_cnt[r - 1] > m_first;
+                for (u32 e = i + 1; e < hi && keq(kshr(dk[e], 2), u); ++e) tip = tip || dk_cnt[e] > m_first;
+            }
+        }
+        if (!tip) {   // backward: nothing enters u, and a stronger edge enters v
+            bool in_u = false, stronger = false;
+            for (u32 x = 0; x < 4; ++x) {
+                u32 bhi;
+                const K a = kor(kshl(key_from_u64<K>(x), node_bits), u);
+                const u32 ja = graph_lower_bound<K>(gv, seg, a, &bhi);
+                in_u = in_u || (ja < bhi && keq(dk[ja], a));
+                const K b = kor(kshl(key_from_u64<K>(x), node_bits), v);
+                const u32 jb = graph_lower_bound<K>(gv, seg, b, &bhi);
+                stronger = stronger || (jb < bhi && jb != t && keq(dk[jb], b) && dk_cnt[jb] > m_last);
+            }
+            tip = !in_u && stronger;
+        }
+        if (!tip) return;
+        atomicAdd(&tips[seg], 1u);
+        const int low = 2 * gv.k - gv.bbits;
+        u32 e = i;
+        for (u32 s = 0; s < len; ++s) {
+            const u32 gb = seg * nb + (gv.bbits ? kfield(dk[e], low) & (nb - 1) : 0u);
+            const u32 d0 = gv.dstart[gb], d1 = gv.dstart[gb + 1];
+            if (e >= d0 && e < d1) mult[bstart[gb] + (e - d0)] = 0;
+            if (s + 1 < len) e = nxt[e];
+        }
+    });
+}
+template __global__ void k_tip_mark<u64>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);
+template __global__ void k_tip_mark<K128>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);

@@ -89,6 +89,11 @@ int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const ui
  * k-mers are taken; strands = 1 is gasm_get_contigs_from_reads_solid, anything else GASM_ERR_INVALID. */
 int gasm_get_contigs_from_reads_strands(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                         int matrix_rows, uint32_t min_count, uint32_t strands, gasm_contigs** out);
+/* The same with tip clipping (gasm_batch_build_tips below): tip_len > 0 removes, for tip_rounds rounds, the short dead-end contigs
+ * of the graph before the contigs are cut; tip_len = 0 is gasm_get_contigs_from_reads_strands and tip_rounds is not read. */
+int gasm_get_contigs_from_reads_tips(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
+                                     int matrix_rows, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
+                                     gasm_contigs** out);
 uint64_t gasm_contigs_count(const gasm_contigs* c);
 const char* gasm_contigs_data(const gasm_contigs* c);
 const uint64_t* gasm_contigs_offsets(const gasm_contigs* c);       /* count+1 */
@@ -298,6 +303,8 @@ int gasm_batch_score(gasm_batch* b, int kmer, const double* table);
  * adds nothing.  A segment without survivors behaves like an empty one.
  *   gasm_batch_build(b, k, hint) is gasm_batch_build_solid(b, k, hint, 1): same results, same kernel launches.
  *   min_count == 0: GASM_ERR_INVALID.  Each step slot remembers the cutoff of the build it holds.
+ * (after a build with tip clipping, below, distinct_after still counts the survivors of the CUTOFF: the k-mers of
+ * gasm_batch_fetch_distinct are distinct_after minus the segment's clipped k-mers of gasm_batch_fetch_tip_stats)
  * genome_len_hint for noisy reads: it sizes the buckets for the distinct k-mers BEFORE the cutoff, and reads with errors hold
  * 5-10x more of them than their genome: about genome length + bases in the segment's reads x error rate x k (every wrong base
  * makes up to k new k-mers).  A smaller hint (the genome length alone) is still correct: the tables overflow, the build repeats
@@ -344,11 +351,56 @@ int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist /* n_seg
  *                                 contig in the order of gasm_batch_fetch_contigs; an involution; twin[c] == c for a self-twin.
  *                                 Host copy, valid until the next build.  GASM_ERR_STATE before a build or after a strands = 1
  *                                 build; GASM_ERR_INTERNAL if a contig has no twin (the closure above would be broken).
- * Pooled builds (gasm_pool_*) are forward-strand only.
+ * Pooled builds (gasm_pool_*) are forward-strand only and clip no tips (below).
  * ---------------------------------------------------------------------------------------------------------------- */
 int gasm_batch_build_strands(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands);
 uint32_t gasm_batch_strands(const gasm_batch* b);
 int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Tip clipping: short dead-end branches leave the k-mer set before the contigs are cut.  (No counterpart in the reference, which
+ * never simplifies its graph; Velvet clips tips right behind its coverage cutoff.  tip_len = 0 is the reference's graph and the
+ * default everywhere.)
+ * A substitution near the end of a read makes fewer than k wrong k-mers: a short branch that leaves the true path and ends
+ * nowhere.  A cutoff removes most of them, but a tip seen min_count times survives, and every surviving tip makes its junction a
+ * branching node, which cuts the true contig in two.  gasm_batch_build_tips removes tips from the k-mer set that survived the
+ * cutoff, for exactly tip_rounds rounds; graph, contigs, scores and every by-product are made from what is left.
+ * The rule, on the graph of a segment as everywhere here (edges = distinct k-mers with their multiplicities, nodes = (k-1)-mers,
+ * degrees count distinct edges, contigs = the paths from branching node to branching node).  One round, on the current set:
+ *   for a contig c let u = its first k-1 bases, v = its last k-1 bases, e_first = its first k-mer, e_last = its last k-mer;
+ *   c is a FORWARD tip  if out(v) == 0 and u has another out-edge f != e_first with mult(f) > mult(e_first);
+ *   c is a BACKWARD tip if in(u) == 0  and v has another in-edge  f != e_last  with mult(f) > mult(e_last);
+ *   c is clipped if len(c) <= tip_len (bases) and it is a forward or a backward tip.
+ *   The comparison is strict: among siblings of equal multiplicity nobody is clipped, and there is no tie-break by key (a key
+ *   order is not symmetric under reverse complement).  A contig with nothing attached at either end is not a tip and stays.
+ *   All tips of a round are found on the same graph and leave together, with all their k-mers (a k-mer lies in at most one
+ *   contig); the next round starts from the remaining set.
+ * A build runs exactly tip_rounds rounds — a round that finds nothing changes nothing —, so it stays queued as a whole: the host
+ * does not wait between rounds.  gasm_batch_fetch_tip_stats tells whether the last round still found something.
+ * With strands = 2 the multiplicities are symmetric under reverse complement: a forward tip's twin is a backward tip and is
+ * clipped in the same round, the contigs stay closed under reverse complement and gasm_batch_fetch_contig_twins keeps working.
+ * The intended setting is tip_len = 2k - 1 (Velvet: "shorter than 2k"); tip_len < k can match no contig and is allowed.
+ * tip_len has no upper limit, but its cost has: in every round one GPU thread per contig of at most tip_len bases walks that
+ * contig edge by edge (tip_len - k + 1 dependent loads at most).  That is nothing at 2k - 1; with a tip_len of thousands a
+ * long unbranched contig is one thread's walk in every round — still correct and bounded by the segment, only slow.
+ * Everything behind the build — contigs, gasm_batch_fetch_distinct / _graph, the k-mer spectrum, twins, scores under one or
+ * several tables, the guided traversal — sees the clipped set with its true multiplicities.  A read scores on a contig iff it is
+ * a substring of it: a read that holds a clipped k-mer adds nothing.
+ * gasm_batch_build_tips         tip_len == 0 is gasm_batch_build_strands: same host path, same kernel launches, tip_rounds is
+ *                               not read.  tip_len > 0 needs tip_rounds in 1..GASM_MAX_TIP_ROUNDS, else GASM_ERR_INVALID.  Each
+ *                               step slot remembers tip_len and tip_rounds of the build it holds, as it remembers the cutoff
+ *                               and the strands.
+ * gasm_batch_tip_len / _tip_rounds   of the last build (0: no clipping, or no build yet).
+ * gasm_batch_fetch_tip_stats    tips[s * GASM_MAX_TIP_ROUNDS + r] = contigs clipped in segment s, round r; kmers[...] = k-mers
+ *                               clipped, same index; rounds not run are 0.  Host copies, valid until the next call or build.
+ *                               GASM_ERR_STATE before a build or after a build with tip_len == 0.
+ * Pooled builds (gasm_pool_*) do not clip.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAX_TIP_ROUNDS 8
+int gasm_batch_build_tips(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands,
+                          uint32_t tip_len, uint32_t tip_rounds);
+uint32_t gasm_batch_tip_len(const gasm_batch* b);      /* of the last build; 0: none */
+uint32_t gasm_batch_tip_rounds(const gasm_batch* b);
+int gasm_batch_fetch_tip_stats(gasm_batch* b, const uint32_t** tips, const uint32_t** kmers);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
@@ -402,7 +454,8 @@ int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read
  * bytes hi:lo for k <= 63, sorted inside a run) and 32-bit counts; the bucket a run belongs to follows from its place in
  * the bucket lists both sides derive from the ownership function.  Results do not depend on the number of ranks.
  *
- *   (pooled builds take their k-mers forward-strand only: there is no strands argument here)
+ *   (pooled builds take their k-mers forward-strand only: there is no strands argument here; they do not clip tips either:
+ *   there is no tip_len argument)
  *   gasm_pool_create       this rank's reads (fixed length) of ALL n_segments segments
  *   gasm_pool_local_runs   k-mers of those reads -> one sorted run of distinct (key, count) per bucket; bucket index =
  *                          segment << bbits | first bbits bits of the k-mer; run_len (host, n_segments << bbits entries)

@@ -70,13 +70,21 @@ std::vector<std::vector<std::string>> get_contigs(const std::vector<std::string>
 // strands (optional, default 1 = the reference's forward-strand k-mers): 2 adds the reverse complement of every read before
 // the k-mers are taken (gasm_get_contigs_from_reads_strands) — for read sets that hold both strands, such as read_one and
 // read_two of lib/GenerateReads.R:438 together; the contigs then come in reverse-complement pairs
+// tip_len, tip_rounds (optional, default 0 = no clipping): tip_rounds rounds (1..GASM_MAX_TIP_ROUNDS) of tip clipping before the
+// contigs are cut (gasm_get_contigs_from_reads_tips; the rule is in include/gasm.h) — for reads with sequencing errors; 2 * dbg_kmer - 1
+// is the intended tip_len
 // [[Rcpp::export]]
 std::vector<std::vector<std::string>> get_contigs_from_reads(const std::vector<std::string>& reads, const int& dbg_kmer, const int& seed,
-                                                             const int& strands = 1) {
+                                                             const int& strands = 1, const int& tip_len = 0, const int& tip_rounds = 1) {
     if (strands != 1 && strands != 2) Rcpp::stop("strands must be 1 or 2");
+    if (tip_len < 0) Rcpp::stop("tip_len must be >= 0");
+    if (tip_len > 0 && (tip_rounds < 1 || tip_rounds > GASM_MAX_TIP_ROUNDS)) Rcpp::stop("tip_rounds must be 1..%d when tip_len > 0", GASM_MAX_TIP_ROUNDS);
     Flat f(reads);
     gasm_contigs* c = nullptr;
-    if (strands == 2) check(gasm_get_contigs_from_reads_strands(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, 2, &c));
+    if (tip_len > 0)
+        check(gasm_get_contigs_from_reads_tips(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, (uint32_t)strands,
+                                               (uint32_t)tip_len, (uint32_t)tip_rounds, &c));
+    else if (strands == 2) check(gasm_get_contigs_from_reads_strands(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, 2, &c));
     else check(gasm_get_contigs_from_reads(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, &c));
     const uint64_t n = gasm_contigs_count(c), rows = gasm_contigs_rows(c);
     std::vector<std::string> contigs = unflat(gasm_contigs_data(c), gasm_contigs_offsets(c), n);
