@@ -136,6 +136,7 @@ SYMBOLS = {
     "gasm_pool_local_runs": (_int, [_vp, _int, _int, _PP]),
     "gasm_pool_pack_runs": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "gasm_pool_merge_runs": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _PP]),
+    "gasm_pool_fetch_fine_directory": (_int, [_vp, _PP, C.POINTER(_int)]),
     "gasm_pool_graph": (_int, [_vp, _u32]),
     "gasm_pool_piece_words": (_int, [_vp, _u32, _u32, _vp]),
     "gasm_pool_pack_reads": (_int, [_vp, _u32, _u32, _vp]),
@@ -151,6 +152,8 @@ SYMBOLS = {
     "gasm_comm_world": (_int, [_vp]),
     "gasm_comm_rank": (_int, [_vp]),
     "gasm_comm_stage": (_int, [_vp]),
+    "gasm_comm_keep_plans": (_int, [_vp, _int]),
+    "gasm_comm_fetch_plan": (_int, [_vp, _int, _u32, _vp, _PP, _PP, _PP, _PP, _PP, _PP, _PP]),
     "gasm_pool_bucket_owner": (_int, [_u32, _int, _u32, _vp]),
     "gasm_pool_segment_bounds": (_int, [_u32, _u32, _vp]),
     "gasm_pool_exchange_build": (_int, [_vp, _vp, _u32, _int, _int, _int, _vp, _vp]),

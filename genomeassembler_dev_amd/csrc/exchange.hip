@@ -127,7 +127,11 @@ struct RankX {                 // exchange state of one local rank
     bool reads_ready = false;
     std::vector<u64> send_woff, recv_woff;     // W + 1 word offsets
     u32 max_piece_words = 0;
+    // gasm_comm_keep_plans: copies of the arrays the two plan kernels wrote (both plans share their buffers, and the merges take
+    // the capacity layout), as u64 words: send_off | send_tot | run_off | recv_tot | bstart | info[2] | flag word | run_len (u32)
+    struct PlanKeep { DBuf d; u64 n_send_off = 0, n_run = 0, n_bstart = 0; bool valid = false; std::vector<u64> h; } keep[2];
     void release() {
+        for (PlanKeep& k : keep) { k.d.release(); k.valid = false; }
         for (DBuf* b : {&d_mine, &d_lens_all, &d_send_off, &d_send_tot, &d_recv_tot, &d_run_off, &d_run_len, &d_bstart_new, &d_flags_or, &d_info, &d_src_base, &d_G,
                         &send_keys, &send_cnt, &recv_keys, &recv_cnt, &d_nr, &d_nr_all, &d_rdir, &send_words, &recv_words, &d_part_saved})
             b->release();
@@ -149,6 +153,7 @@ struct gasm_comm {
     std::vector<std::vector<u32>> h_mine;
     DBuf d_own1, d_order, d_dst_first, d_seg_first, d_iota, d_tmp;
     std::vector<RankX> rx;             // one per local rank
+    bool keep_plans = false;           // gasm_comm_keep_plans (a debugging aid: off unless a caller asks)
     u64 ticket = 1;
     u32 n_local() const { return rank < 0 ? (u32)world : 1u; }
     u32 global_rank(u32 li) const { return rank < 0 ? li : (u32)rank; }
@@ -201,17 +206,24 @@ static int x_alltoallv(gasm_comm* c, const XStream* st, int n_streams, const std
             if (bytes_total) *bytes_total += n * st[t].elem;
         }
         NCHK(api->GroupStart());
-        for (int p = 0; p < W; ++p) {
+        // A failure inside the group does not return at once: the group is closed first (a return between ncclGroupStart and
+        // ncclGroupEnd leaves the group open, and every later RCCL call of this thread is queued into it), then the first
+        // failure is reported.
+        ncclResult_t bad = ncclSuccess;
+        const char* what = "";
+        for (int p = 0; p < W && bad == ncclSuccess; ++p) {
             if (p == me) continue;
-            for (int t = 0; t < n_streams; ++t) {
+            for (int t = 0; t < n_streams && bad == ncclSuccess; ++t) {
                 const u64 ns = soff[0][p + 1] - soff[0][p], nr = roff[0][p + 1] - roff[0][p];
-                if (ns) NCHK(api->Send(static_cast<const char*>(st[t].send[0]) + soff[0][p] * st[t].elem, ns * st[t].elem, ncclUint8, p, c->nccl, ctx->stream));
-                if (nr) NCHK(api->Recv(static_cast<char*>(st[t].recv[0]) + roff[0][p] * st[t].elem, nr * st[t].elem, ncclUint8, p, c->nccl, ctx->stream));
+                if (ns) { bad = api->Send(static_cast<const char*>(st[t].send[0]) + soff[0][p] * st[t].elem, ns * st[t].elem, ncclUint8, p, c->nccl, ctx->stream); what = "ncclSend"; }
+                if (nr && bad == ncclSuccess) { bad = api->Recv(static_cast<char*>(st[t].recv[0]) + roff[0][p] * st[t].elem, nr * st[t].elem, ncclUint8, p, c->nccl, ctx->stream); what = "ncclRecv"; }
                 if (bytes_total) *bytes_total += ns * st[t].elem;
                 if (bytes_remote) *bytes_remote += ns * st[t].elem;
             }
         }
-        NCHK(api->GroupEnd());
+        const ncclResult_t end = api->GroupEnd();
+        if (bad != ncclSuccess) { gasm_set_error("%s:%d: %s failed inside the all-to-all's group: %s", __FILE__, __LINE__, what, api->GetErrorString(bad)); return GASM_ERR_HIP; }
+        NCHK(end);
         return GASM_OK;
     }
     for (int s = 0; s < W; ++s)
@@ -225,6 +237,30 @@ static int x_alltoallv(gasm_comm* c, const XStream* st, int n_streams, const std
                 if (s == 0) { if (bytes_total) *bytes_total += n * st[t].elem; if (bytes_remote && d != 0) *bytes_remote += n * st[t].elem; }
             }
         }
+    return GASM_OK;
+}
+
+// gasm_comm_keep_plans: set the arrays of plan `which` (0, 1) aside, by copies on the stream behind the plan kernel (no launch)
+static int plan_keep(gasm_comm* c, RankX& x, int which, u64 n_send_off, u64 n_run, u64 n_bstart, const u64* d_info, u32 n_info) {
+    gasm_ctx* ctx = c->ctx;
+    const u64 W = (u64)c->world;
+    RankX::PlanKeep& k = x.keep[which];
+    k.n_send_off = n_send_off; k.n_run = n_run; k.n_bstart = n_bstart;
+    const u64 words = n_send_off + W + n_run + W + n_bstart + 3 + (n_run + 1) / 2;
+    GCHK(k.d.ensure(words * 8));
+    u64* o = k.d.as<u64>();
+    auto put = [&](const void* src, u64 bytes) { return bytes ? hipMemcpyAsync(o, src, bytes, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess; };
+    HIPCHK(put(x.d_send_off.p, n_send_off * 8)); o += n_send_off;
+    HIPCHK(put(x.d_send_tot.p, W * 8)); o += W;
+    HIPCHK(put(x.d_run_off.p, n_run * 8)); o += n_run;
+    HIPCHK(put(x.d_recv_tot.p, W * 8)); o += W;
+    HIPCHK(put(x.d_bstart_new.p, n_bstart * 8)); o += n_bstart;
+    HIPCHK(hipMemsetAsync(o, 0, 24, ctx->stream));
+    HIPCHK(put(d_info, (u64)n_info * 8));
+    o += 2;
+    HIPCHK(put(x.d_flags_or.p, 4)); o += 1;
+    HIPCHK(put(x.d_run_len.p, n_run * 4));
+    k.valid = true;
     return GASM_OK;
 }
 
@@ -489,6 +525,40 @@ int gasm_comm_world(const gasm_comm* c) { return c ? c->world : 0; }
 int gasm_comm_rank(const gasm_comm* c) { return c ? c->rank : -1; }
 int gasm_comm_stage(const gasm_comm* c) { return c ? c->stage.load() : 0; }
 
+int gasm_comm_keep_plans(gasm_comm* c, int on) {
+    if (!c) { gasm_set_error("gasm_comm_keep_plans: null argument"); return GASM_ERR_INVALID; }
+    c->keep_plans = on != 0;
+    if (!on) for (RankX& x : c->rx) for (RankX::PlanKeep& k : x.keep) k.valid = false;
+    return GASM_OK;
+}
+
+int gasm_comm_fetch_plan(gasm_comm* c, int which, uint32_t local_rank, uint64_t* sizes, const uint64_t** send_off, const uint64_t** send_tot,
+                         const uint64_t** run_off, const uint32_t** run_len, const uint64_t** recv_tot, const uint64_t** bstart, const uint64_t** info) {
+    API_GUARD_BEGIN
+    if (!c || !sizes || !send_off || !send_tot || !run_off || !run_len || !recv_tot || !bstart || !info) { gasm_set_error("gasm_comm_fetch_plan: null argument"); return GASM_ERR_INVALID; }
+    if ((which != 1 && which != 2) || local_rank >= c->n_local()) { gasm_set_error("gasm_comm_fetch_plan: plan %d of local rank %u", which, local_rank); return GASM_ERR_INVALID; }
+    RankX::PlanKeep& k = c->rx[local_rank].keep[which - 1];
+    if (!k.valid) { gasm_set_error("gasm_comm_fetch_plan: no plan kept (gasm_comm_keep_plans before the exchange)"); return GASM_ERR_STATE; }
+    gasm_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const u64 W = (u64)c->world;
+    const u64 words = k.n_send_off + W + k.n_run + W + k.n_bstart + 3 + (k.n_run + 1) / 2;
+    k.h.assign(words, 0);
+    HIPCHK(hipMemcpyAsync(k.h.data(), k.d.p, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const u64* o = k.h.data();
+    sizes[0] = k.n_send_off; sizes[1] = k.n_run; sizes[2] = k.n_bstart; sizes[3] = W;
+    *send_off = o; o += k.n_send_off;
+    *send_tot = o; o += W;
+    *run_off = o; o += k.n_run;
+    *recv_tot = o; o += W;
+    *bstart = o; o += k.n_bstart;
+    *info = o; o += 3;
+    *run_len = reinterpret_cast<const u32*>(o);
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_pool_bucket_owner(uint32_t n_segments, int bbits, uint32_t world, uint32_t* owner) {
     if (!owner || world == 0 || bbits < 0 || bbits > 10) { gasm_set_error("gasm_pool_bucket_owner: bad argument"); return GASM_ERR_INVALID; }
     const u64 nbt = (u64)n_segments << bbits;
@@ -560,6 +630,7 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
                     x.d_recv_tot.as<u64>(), x.d_bstart_new.as<u64>(), x.d_flags_or.as<u32>());
             GLAUNCH(ctx, "k_x_report", k_x_report, dim3(1), dim3(64), 0, x.d_send_tot.as<u64>(), x.d_recv_tot.as<u64>(), W, x.d_bstart_new.as<u64>() + n_mine, 1u,
                     x.d_flags_or.as<u32>(), x.rep, ticket);
+            if (c->keep_plans) GCHK(plan_keep(c, x, 0, (u64)nbt + 1, (u64)n_mine * W, (u64)n_mine + 1, x.d_bstart_new.as<u64>() + n_mine, 1u));
         }
         u32 flags = 0;
         for (u32 li = 0; li < nl; ++li) {
@@ -629,6 +700,7 @@ int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_p
                     x.d_bstart_new.as<u64>(), x.d_info.as<u64>());
             GLAUNCH(ctx, "k_x_report", k_x_report, dim3(1), dim3(64), 0, x.d_send_tot.as<u64>(), x.d_recv_tot.as<u64>(), W, x.d_info.as<u64>(), 2u, x.d_flags_or.as<u32>(),
                     x.rep + XReport<u64>::words(W), ticket2);
+            if (c->keep_plans) GCHK(plan_keep(c, x, 1, (u64)n_mine + 1, (u64)(b - a) * nb * W, (u64)(b - a) * nb + 1, x.d_info.as<u64>(), 2u));
         }
         flags = 0;
         for (u32 li = 0; li < nl; ++li) {

@@ -9,6 +9,7 @@ struct gasm_pool {
     BuildState bs;          // current runs (d_keys / d_mult / d_bstart / d_bucket_d), later the rank's graph
     u32 n_runs = 0;         // buckets the current runs cover
     std::vector<u32> h_len; // their lengths
+    std::vector<u16> h_fdir; // gasm_pool_fetch_fine_directory's copy
     DevReads own;           // the reads of the rank's own segments (gasm_pool_set_reads)
     u32 n_local = 0;
     bool graphed = false, reads_set = false;

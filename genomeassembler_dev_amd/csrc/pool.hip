@@ -251,6 +251,22 @@ int gasm_pool_merge_runs(gasm_pool* p, uint32_t n_out, uint32_t n_src, const uin
     API_GUARD_END
 }
 
+int gasm_pool_fetch_fine_directory(gasm_pool* p, const uint16_t** fdir, int* fbits) {
+    API_GUARD_BEGIN
+    if (!p || !fdir || !fbits) { gasm_set_error("gasm_pool_fetch_fine_directory: null argument"); return GASM_ERR_INVALID; }
+    if (p->bs.k == 0 || p->graphed) { gasm_set_error("gasm_pool_fetch_fine_directory: the pool holds no merged runs"); return GASM_ERR_STATE; }
+    gasm_ctx* ctx = p->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)p->n_runs * ((1u << p->bs.fbits) + 1);
+    if (n * 2 > p->bs.d_fdir.cap) { gasm_set_error("gasm_pool_fetch_fine_directory: no directory of %u runs", p->n_runs); return GASM_ERR_STATE; }
+    p->h_fdir.assign(n, 0);
+    if (n) HIPCHK(hipMemcpyAsync(p->h_fdir.data(), p->bs.d_fdir.p, n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *fdir = p->h_fdir.data(); *fbits = p->bs.fbits;
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_pool_graph(gasm_pool* p, uint32_t n_local_segments) {
     API_GUARD_BEGIN
     if (!p) { gasm_set_error("pool is null"); return GASM_ERR_INVALID; }

@@ -163,6 +163,15 @@ class GasmBackend:
                                                  self.C.c_void_p(keys.data_ptr()), self.C.c_void_p(counts.data_ptr()), self.C.byref(p)))
         return self._u32(p, n_out)
 
+    def fine_directory(self, n_runs):
+        """(rows [n_runs, 2^fbits + 1] of the runs the last merge_runs wrote, fbits): a debugging aid"""
+        p, fb = self.C.c_void_p(), self.C.c_int()
+        self.check(self.lib.gasm_pool_fetch_fine_directory(self.h, self.C.byref(p), self.C.byref(fb)))
+        w = (1 << fb.value) + 1
+        if not n_runs:
+            return np.zeros((0, w), np.uint16), fb.value
+        return np.ctypeslib.as_array(self.C.cast(p, self.C.POINTER(self.C.c_uint16)), shape=(n_runs, w)).copy(), fb.value
+
     def graph(self, n_local):
         self.n_local = int(n_local)
         self.check(self.lib.gasm_pool_graph(self.h, self.n_local))
@@ -276,6 +285,28 @@ class Comm:
     def stage(self):
         from ._lib import lib
         return lib().gasm_comm_stage(self.h)
+
+    def keep_plans(self, on=True):
+        """a debugging aid: later exchanges set their plans' arrays aside for `fetch_plan`"""
+        from ._lib import check, lib
+        check(lib().gasm_comm_keep_plans(self.h, int(on)))
+
+    def fetch_plan(self, which, local_rank=0):
+        """plan `which` (1, 2) of the last exchange for one local rank, as a dict of numpy arrays (gasm_comm_fetch_plan)"""
+        import ctypes as C
+
+        from ._lib import check, lib
+        sizes = (C.c_uint64 * 4)()
+        ps = [C.c_void_p() for _ in range(7)]
+        check(lib().gasm_comm_fetch_plan(self.h, int(which), int(local_rank), sizes, *[C.byref(p) for p in ps]))
+        n_so, n_run, n_bs, W = (int(v) for v in sizes)
+
+        def arr(p, n, ct):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
+        info = arr(ps[6], 3, C.c_uint64)
+        return dict(send_off=arr(ps[0], n_so, C.c_uint64), send_tot=arr(ps[1], W, C.c_uint64), run_off=arr(ps[2], n_run, C.c_uint64).reshape(-1, W),
+                    run_len=arr(ps[3], n_run, C.c_uint32).reshape(-1, W), recv_tot=arr(ps[4], W, C.c_uint64), bstart=arr(ps[5], n_bs, C.c_uint64),
+                    info=info[:2], flags=int(info[2]))
 
     def close(self):
         from ._lib import lib

@@ -483,6 +483,9 @@ int gasm_pool_local_runs(gasm_pool* p, int k, int bbits, const uint32_t** run_le
 int gasm_pool_pack_runs(gasm_pool* p, const uint32_t* bucket_ix, uint64_t n, void* d_keys_out, void* d_counts_out);
 int gasm_pool_merge_runs(gasm_pool* p, uint32_t n_out, uint32_t n_src, const uint64_t* run_off, const uint32_t* run_len,
                          const void* d_keys_in, const void* d_counts_in, const uint32_t** merged_len);
+/* Debugging aid (tests): the fine directories gasm_pool_merge_runs wrote, one row of 2^fbits + 1 offsets per merged run
+ * (offsets, relative to the run, of the key bins below the bucket prefix).  Host memory of the pool, valid until the next call. */
+int gasm_pool_fetch_fine_directory(gasm_pool* p, const uint16_t** fdir, int* fbits);
 int gasm_pool_graph(gasm_pool* p, uint32_t n_local_segments);
 int gasm_pool_piece_words(gasm_pool* p, uint32_t seg_lo, uint32_t seg_hi, uint64_t* n_words /* seg_hi - seg_lo */);
 int gasm_pool_pack_reads(gasm_pool* p, uint32_t seg_lo, uint32_t seg_hi, void* d_words_out);
@@ -527,6 +530,18 @@ void gasm_comm_destroy(gasm_comm* c);
 int gasm_comm_world(const gasm_comm* c);
 int gasm_comm_rank(const gasm_comm* c);      /* -1: virtual */
 int gasm_comm_stage(const gasm_comm* c);
+/* Debugging aid (tests): read-only access to the exchange plans.  After gasm_comm_keep_plans(c, 1) every
+ * gasm_pool_exchange_build sets the arrays its plan kernels wrote aside (device copies behind each plan; no kernel launch, and
+ * nothing at all while keeping is off, the default).  gasm_comm_fetch_plan copies out plan `which` (1: every bucket's runs to
+ * the bucket's owner, 2: the merged runs to the segment's owner) of the last attempt of the last exchange for one local rank
+ * (virtual communicator: the rank; RCCL: 0).  sizes = {entries of send_off, of run_off / run_len (rows x world), of bstart,
+ * world}; send_tot and recv_tot have `world` entries; info = {info[0], info[1], the OR-ed flag word} (plan 1: info[0] = the
+ * merged runs' capacity, info[1] = 0; plan 2: the rank's distinct k-mers in all and of its largest segment).  The arrays are
+ * host memory of the communicator, valid until the next fetch of the same plan and rank. */
+int gasm_comm_keep_plans(gasm_comm* c, int on);
+int gasm_comm_fetch_plan(gasm_comm* c, int which, uint32_t local_rank, uint64_t* sizes /* 4 */, const uint64_t** send_off,
+                         const uint64_t** send_tot, const uint64_t** run_off, const uint32_t** run_len, const uint64_t** recv_tot,
+                         const uint64_t** bstart, const uint64_t** info /* 3 */);
 int gasm_pool_bucket_owner(uint32_t n_segments, int bbits, uint32_t world, uint32_t* owner /* n_segments << bbits */);
 int gasm_pool_segment_bounds(uint32_t n_segments, uint32_t world, uint32_t* first /* world + 1 */);
 int gasm_pool_exchange_build(gasm_comm* c, gasm_pool* const* pools, uint32_t n_pools, int k, int bbits, int kmer,
