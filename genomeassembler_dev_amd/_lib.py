@@ -11,6 +11,8 @@ STATUS = {0: "GASM_OK", -1: "GASM_ERR_INVALID", -2: "GASM_ERR_NON_ACGT", -3: "GA
           -5: "GASM_ERR_CAPACITY", -6: "GASM_ERR_RANGE", -7: "GASM_ERR_STATE", -8: "GASM_ERR_INTERNAL"}
 TABLE_ROWS = 69904
 MAX_TIP_ROUNDS = 8      # GASM_MAX_TIP_ROUNDS: rounds of tip clipping one build takes
+MAX_BUBBLE_ROUNDS = 8   # GASM_MAX_BUBBLE_ROUNDS: rounds of bubble popping one build takes
+MAX_BUBBLE_LEN = 65535  # GASM_MAX_BUBBLE_LEN: longest contig (bases) bubble popping looks at
 MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
@@ -41,6 +43,7 @@ SYMBOLS = {
     "gasm_get_contigs_from_reads_solid": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _PP]),
     "gasm_get_contigs_from_reads_strands": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _u32, _PP]),
     "gasm_get_contigs_from_reads_tips": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _u32, _u32, _u32, _PP]),
+    "gasm_get_contigs_from_reads_bubbles": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _u32, _u32, _u32, _u32, _u32, _PP]),
     "gasm_contigs_count": (_u64, [_vp]),
     "gasm_contigs_data": (_vp, [_vp]),
     "gasm_contigs_offsets": (_vp, [_vp]),
@@ -117,6 +120,10 @@ SYMBOLS = {
     "gasm_batch_tip_len": (_u32, [_vp]),
     "gasm_batch_tip_rounds": (_u32, [_vp]),
     "gasm_batch_fetch_tip_stats": (_int, [_vp, _PP, _PP]),
+    "gasm_batch_build_bubbles": (_int, [_vp, _int, _u64, _u32, _u32, _u32, _u32, _u32, _u32]),
+    "gasm_batch_bubble_len": (_u32, [_vp]),
+    "gasm_batch_bubble_rounds": (_u32, [_vp]),
+    "gasm_batch_fetch_bubble_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_fetch_contig_twins": (_int, [_vp, _PP]),
     "gasm_batch_fetch_solid_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_kmer_spectrum": (_int, [_vp]),

@@ -114,6 +114,15 @@ def _check_tips(tip_len, tip_rounds):
         raise ValueError(f"tip_rounds must be 1..{_lib.MAX_TIP_ROUNDS} when tip_len > 0")
 
 
+def _check_bubbles(bubble_len, bubble_rounds):
+    """the argument rule of every bubble-popping entry: 0 <= bubble_len <= _lib.MAX_BUBBLE_LEN, and 1.._lib.MAX_BUBBLE_ROUNDS rounds
+    when it is on"""
+    if not 0 <= int(bubble_len) <= _lib.MAX_BUBBLE_LEN:
+        raise ValueError(f"bubble_len must be 0..{_lib.MAX_BUBBLE_LEN} (0: no bubble popping)")
+    if int(bubble_len) > 0 and not 1 <= int(bubble_rounds) <= _lib.MAX_BUBBLE_ROUNDS:
+        raise ValueError(f"bubble_rounds must be 1..{_lib.MAX_BUBBLE_ROUNDS} when bubble_len > 0")
+
+
 def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
                            tip_rounds=1):
     """get_kmers_from_reads + get_contigs in one call (gasm_get_contigs_from_reads): the k-mers are taken on the GPU from the
@@ -121,7 +130,8 @@ def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, a
     reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed).
     min_count > 1 (gasm_get_contigs_from_reads_solid): only k-mers seen at least min_count times become edges.
     strands = 2 (gasm_get_contigs_from_reads_strands): the k-mers of every read and of its reverse complement.
-    tip_len > 0 (gasm_get_contigs_from_reads_tips): tip_rounds rounds of tip clipping before the contigs are cut (include/gasm.h)."""
+    tip_len > 0 (gasm_get_contigs_from_reads_tips): tip_rounds rounds of tip clipping before the contigs are cut (include/gasm.h).
+    Bubble popping behind the tips: get_contigs_from_reads_bubbles()."""
     if int(min_count) < 1:
         raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
     if int(strands) not in (1, 2):
@@ -141,6 +151,30 @@ def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, a
     else:
         check(lib().gasm_get_contigs_from_reads_solid(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
                                                       int(min_count), C.byref(h)))
+    return _contig_matrix(h, dbg_kmer, as_lists)
+
+
+def get_contigs_from_reads_bubbles(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
+                                   tip_rounds=1, bubble_len=0, bubble_rounds=1):
+    """get_contigs_from_reads with bubble popping (gasm_get_contigs_from_reads_bubbles): after the tip rounds, bubble_rounds rounds
+    (1.._lib.MAX_BUBBLE_ROUNDS) in which every contig of at most bubble_len bases (<= _lib.MAX_BUBBLE_LEN) beside which a parallel
+    one of strictly higher mean multiplicity runs leaves the k-mer set (the rule: include/gasm.h).  bubble_len = 0 is
+    get_contigs_from_reads(..., tip_len, tip_rounds), and bubble_rounds is not read.  (An entry of its own, as build_bubbles() is
+    beside build_tips(): get_contigs_from_reads keeps its parameter list.)"""
+    _check_bubbles(bubble_len, bubble_rounds)
+    if int(bubble_len) == 0:
+        return get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count, strands, tip_len, tip_rounds)
+    if int(min_count) < 1:
+        raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+    if int(strands) not in (1, 2):
+        raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+    _check_tips(tip_len, tip_rounds)
+    ctx = ctx or default_context()
+    buf, off = _pack(reads)
+    h = C.c_void_p()
+    check(lib().gasm_get_contigs_from_reads_bubbles(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
+                                                    int(min_count), int(strands), int(tip_len), int(tip_rounds) if int(tip_len) else 0,
+                                                    int(bubble_len), int(bubble_rounds), C.byref(h)))
     return _contig_matrix(h, dbg_kmer, as_lists)
 
 

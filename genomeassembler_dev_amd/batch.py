@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import MAX_TIP_ROUNDS, PLAN_FIELDS, check, default_context, lib
-from .api import _check_tips, unpack_kmers
+from ._lib import MAX_BUBBLE_ROUNDS, MAX_TIP_ROUNDS, PLAN_FIELDS, check, default_context, lib
+from .api import _check_bubbles, _check_tips, unpack_kmers
 
 
 class SegmentBatch:
@@ -111,7 +111,7 @@ class SegmentBatch:
         strands = 2 (gasm_batch_build_strands): the k-mers of every read and of its reverse complement — reads of both strands
         then meet in one graph, multiplicities (and min_count) are sums over both strands, and the contigs come in
         reverse-complement pairs (contig_twins).  Scores are over the reads as they were given, each once.
-        Tip clipping: build_tips()."""
+        Tip clipping: build_tips().  Bubble popping: build_bubbles()."""
         if int(min_count) < 1:
             raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
         if int(strands) not in (1, 2):
@@ -142,6 +142,25 @@ class SegmentBatch:
         self.k = int(k)
         return self
 
+    def build_bubbles(self, k, genome_len_hint=0, min_count=1, strands=1, tip_len=0, tip_rounds=1, bubble_len=0, bubble_rounds=1):
+        """build_tips() with bubble popping (gasm_batch_build_bubbles): exactly bubble_rounds rounds (1.._lib.MAX_BUBBLE_ROUNDS)
+        behind the tip rounds — a contig of at most bubble_len bases (<= _lib.MAX_BUBBLE_LEN) beside which a parallel one (same
+        first and last node, at most bubble_len bases too) of strictly higher mean multiplicity runs leaves the k-mer set with
+        all its k-mers (the rule: include/gasm.h); 2k - 1 is the intended length.  bubble_stats() tells what each round removed.
+        bubble_len = 0 is build_tips(k, genome_len_hint, min_count, strands, tip_len, tip_rounds), and bubble_rounds is not read."""
+        if int(bubble_len) == 0:
+            return self.build_tips(k, genome_len_hint, min_count, strands, tip_len, tip_rounds)
+        if int(min_count) < 1:
+            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+        if int(strands) not in (1, 2):
+            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+        _check_tips(tip_len, tip_rounds)
+        _check_bubbles(bubble_len, bubble_rounds)
+        check(lib().gasm_batch_build_bubbles(self.h, int(k), int(genome_len_hint), int(min_count), int(strands), int(tip_len),
+                                             int(tip_rounds) if int(tip_len) else 0, int(bubble_len), int(bubble_rounds)))
+        self.k = int(k)
+        return self
+
     def solid_stats(self):
         """(distinct k-mers per segment before the last build's cutoff, after it): two uint64 arrays, equal at min_count = 1"""
         a, b = C.c_void_p(), C.c_void_p()
@@ -157,6 +176,18 @@ class SegmentBatch:
         check(lib().gasm_batch_fetch_tip_stats(self.h, C.byref(a), C.byref(b)))
         n = self.n_segments * MAX_TIP_ROUNDS
         shape = (self.n_segments, MAX_TIP_ROUNDS)
+        if not n:
+            return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
+                np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
+
+    def bubble_stats(self):
+        """(contigs popped, k-mers popped) by the last build's bubble popping: two (n_segments, MAX_BUBBLE_ROUNDS) uint32 arrays,
+        column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would pop more."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_bubble_stats(self.h, C.byref(a), C.byref(b)))
+        n = self.n_segments * MAX_BUBBLE_ROUNDS
+        shape = (self.n_segments, MAX_BUBBLE_ROUNDS)
         if not n:
             return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
         return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),

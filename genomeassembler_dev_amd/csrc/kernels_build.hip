@@ -1761,3 +1761,85 @@ __global__ void __launch_bounds__(GASM_WG) k_tip_mark(GraphView gv, u32 n_segmen
 }
 template __global__ void k_tip_mark<u64>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);
 template __global__ void k_tip_mark<K128>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);
+
+// ================================================================================================================
+// Bubble popping (gasm_batch_build_bubbles, bubble_len > 0 only; the rule: include/gasm.h).  No counterpart in the reference;
+// Velvet (Tour Bus) and SPAdes pop bubbles behind their tip clipping.  A bubble is a short contig c beside which a PARALLEL
+// short contig d runs — same first node u, same last node v — with a strictly higher mean multiplicity:
+//   m(d) * n(c) > m(c) * n(d)     (n = edges, m = sum of the edges' multiplicities; exact in 64 bits: n <= 65535, mult < 2^32)
+// k_bubble_mark runs on a ranked graph as k_tip_mark does: one thread per head whose contig has at most bubble_len bases.  It
+// looks at its neighbours in the sorted list first — the out-edges of u are neighbours there, and with a single one there is
+// nothing parallel: most threads of a wave end here, before any walk.  Otherwise every out-edge of u is a head (u branches);
+// the thread walks its own chain (sum of dk_cnt, last edge), then the chain of every sibling that is a head and short enough,
+// and compares the last edge's target node with v and the means.  For a bubble it walks its own chain again and zeroes the
+// multiplicities IN THE BUCKET RUNS, as k_tip_mark does; k_bucket_solid with min_count = 1 compacts behind it.  It reads the
+// dense arrays only and writes the runs only, so all bubbles of a round are found on the same graph; of three parallel paths
+// the two weaker see a stronger one each and go together; equal means pop nobody (no tie-break by key: twins tie).
+// The guards are k_tip_mark's: a ranking that gave up leaves chain lengths that mean nothing, so every walk is bounded by
+// bubble_len (<= GASM_MAX_BUBBLE_LEN) and stays inside the segment's edges, every store is checked against its bucket's run,
+// and the ranking's flag is copied into the overflow word (GASM_OVF_TIP_RANK).
+// bubbles[seg] += contigs popped.
+// ================================================================================================================
+// the chain of head h with n edges: sum of its multiplicities and its last edge; false if the walk leaves [lo, hi) or the chain
+// does not end where its length says
+__device__ __forceinline__ bool bubble_walk(const u32* __restrict__ nxt, const u32* __restrict__ dk_cnt, u32 lo, u32 hi, u32 h, u32 n, u64* m, u32* last) {
+    u64 sum = dk_cnt[h];
+    u32 t = h;
+    for (u32 s = 1; s < n; ++s) {
+        const u32 x = nxt[t];
+        if (x < lo || x >= hi) return false;              // (also GASM_NONE32)
+        t = x;
+        sum += dk_cnt[t];
+    }
+    *m = sum; *last = t;
+    return nxt[t] == GASM_NONE32;
+}
+
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_bubble_mark(GraphView gv, u32 n_segments, u32 chunks, const u8* __restrict__ eflag,
+                                                         const u32* __restrict__ clen, const u32* __restrict__ nxt, const u32* __restrict__ dk_cnt,
+                                                         const u64* __restrict__ bstart, u32* __restrict__ mult, u32 bubble_len, u32* __restrict__ flags,
+                                                         u32* __restrict__ bubbles) {
+    const K* dk = reinterpret_cast<const K*>(gv.dk_key);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && flags[GASM_FLAG_RANK_FAILED]) atomicOr(&flags[GASM_FLAG_OVERFLOW], (u32)GASM_OVF_TIP_RANK);
+    const u32 nb = 1u << gv.bbits;
+    const int node_bits = 2 * (gv.k - 1);
+    const u32 kk = (u32)(gv.k - 1);
+    for_seg_edges(gv.dstart, nb, n_segments, chunks, [&](u32 seg, u32 lo, u32 hi, u32 i) {
+        if (!(eflag[i] & 1)) return;
+        const u32 len = clen[i];
+        if (len == 0 || (u64)len + kk > bubble_len) return;
+        // the out-edges of u: at most four neighbours in the sorted list
+        const K u = kshr(dk[i], 2);
+        u32 r = i, e = i + 1;
+        while (r > lo && i - r < 3 && keq(kshr(dk[r - 1], 2), u)) --r;
+        while (e < hi && e - r < 4 && keq(kshr(dk[e], 2), u)) ++e;
+        if (e - r < 2) return;
+        u64 m;
+        u32 t;
+        if (!bubble_walk(nxt, dk_cnt, lo, hi, i, len, &m, &t)) return;
+        const K v = klowbits(dk[t], node_bits);
+        bool popped = false;
+        for (u32 j = r; j < e && !popped; ++j) {
+            if (j == i || !(eflag[j] & 1)) continue;
+            const u32 lj = clen[j];
+            if (lj == 0 || (u64)lj + kk > bubble_len) continue;
+            u64 mj;
+            u32 tj;
+            if (!bubble_walk(nxt, dk_cnt, lo, hi, j, lj, &mj, &tj)) continue;
+            popped = keq(klowbits(dk[tj], node_bits), v) && mj * (u64)len > m * (u64)lj;
+        }
+        if (!popped) return;
+        atomicAdd(&bubbles[seg], 1u);
+        const int low = 2 * gv.k - gv.bbits;
+        u32 x = i;
+        for (u32 s = 0; s < len; ++s) {
+            const u32 gb = seg * nb + (gv.bbits ? kfield(dk[x], low) & (nb - 1) : 0u);
+            const u32 d0 = gv.dstart[gb], d1 = gv.dstart[gb + 1];
+            if (x >= d0 && x < d1) mult[bstart[gb] + (x - d0)] = 0;
+            if (s + 1 < len) x = nxt[x];
+        }
+    });
+}
+template __global__ void k_bubble_mark<u64>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);
+template __global__ void k_bubble_mark<K128>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);

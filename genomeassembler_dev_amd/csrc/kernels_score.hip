@@ -181,7 +181,7 @@ __device__ __forceinline__ u64 graph_match(const ReadSet& rs, const GraphView& g
         // (128 bases per round, aligned in registers: word-by-word with an early exit was a chain of dependent round trips)
         // verify == 2: a build with a multiplicity cutoff (min_count > 1).  A read whose first k-mer survived may hold a dropped
         // k-mer further on, the argument above does not hold, and the comparison decides: a mismatch is "no match", no flag
-        // (the same after tip clipping, tip_len > 0: a read may hold a clipped k-mer)
+        // (the same after tip clipping, tip_len > 0, and bubble popping, bubble_len > 0: a read may hold a clipped or popped k-mer)
         if (!bases_equal(rs.words, p0, ps.words, g, len)) { if (verify == 1) atomicOr(verify_flag, 1u); return ~0ull; }
     }
     return g;

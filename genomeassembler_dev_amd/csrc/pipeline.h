@@ -95,6 +95,8 @@ struct BuildState {
     u32 tip_len = 0, tip_rounds = 0;        // tip clipping of this build (gasm_batch_build_tips): contigs of at most tip_len bases, for
                                             // exactly tip_rounds rounds behind the cutoff; 0: none.  Every attempt of the retry ladder
                                             // clips again, and scores of its graph compare bases
+    u32 bubble_len = 0, bubble_rounds = 0;  // bubble popping of this build (gasm_batch_build_bubbles): contigs of at most bubble_len bases,
+                                            // for exactly bubble_rounds rounds behind the tip rounds; 0: none.  Kept and repeated like tip_len
     std::vector<u64> h_seg_nk;              // k-mers per segment
     // upper bounds the arrays are allocated at, and estimates the grids are sized from (the kernels loop beyond them)
     u64 D_cap = 0, maxD_cap = 0, bases_cap = 0;
@@ -123,6 +125,8 @@ struct BuildState {
     DBuf d_solid_removed;                   // min_count > 1: distinct k-mers the cutoff removed, per segment (u32, zeroed with every attempt)
     DBuf d_tip_stats;                       // tip_len > 0: u32[2][GASM_MAX_TIP_ROUNDS][S], contigs then k-mers clipped per round and segment
     std::vector<u32> h_tip_tips, h_tip_kmers;      // pipeline_fetch_tip_stats: [s * GASM_MAX_TIP_ROUNDS + r]
+    DBuf d_bubble_stats;                    // bubble_len > 0: u32[2][GASM_MAX_BUBBLE_ROUNDS][S], contigs then k-mers popped per round and segment
+    std::vector<u32> h_bubble_bubbles, h_bubble_kmers;   // pipeline_fetch_bubble_stats: [s * GASM_MAX_BUBBLE_ROUNDS + r]
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -186,8 +190,10 @@ struct ScoreState {
 // k-mers is doubled here
 // tip_len > 0: tip_rounds (1 .. GASM_MAX_TIP_ROUNDS) rounds of tip clipping behind the cutoff, each a graph pass up to the chain
 // lengths, k_tip_mark and a compaction of the buckets' runs; the last graph pass alone writes the report.  0: not a launch more
+// bubble_len > 0 (<= GASM_MAX_BUBBLE_LEN): bubble_rounds (1 .. GASM_MAX_BUBBLE_ROUNDS) rounds of bubble popping behind the tip rounds,
+// the same passes with k_bubble_mark as the marking kernel.  0: not a launch more
 int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1, u32 strands = 1, u32 tip_len = 0,
-                   u32 tip_rounds = 0);
+                   u32 tip_rounds = 0, u32 bubble_len = 0, u32 bubble_rounds = 0);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
 // The overflow retry ladder of every build path: after an attempt raised the GASM_OVF_* bits `ovf`, advance the configuration by
@@ -208,6 +214,8 @@ int pipeline_fetch_contigs(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // contigs and k-mers clipped per segment and round of the finished build (zero for rounds not run and for tip_len = 0)
 int pipeline_fetch_tip_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// contigs and k-mers popped per segment and round of the finished build (zero for rounds not run and for bubble_len = 0)
+int pipeline_fetch_bubble_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

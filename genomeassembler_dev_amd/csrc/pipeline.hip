@@ -468,7 +468,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_bubble_stats, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -712,28 +712,46 @@ static int alloc_graph(BuildState& bs, u32 S) {
 // k_bucket_solid with a cutoff of 1, which compacts the runs in place, rewrites the directory rows and redoes the offsets as it
 // does behind the de-duplication; then the next pass gathers what is left.  All of it is queued: the host waits for nothing
 // between rounds, and only the last pass's k_contig_scan publishes the report.
+// Bubble popping (bs.bubble_len > 0) adds bubble_rounds such rounds behind the tip rounds, with k_bubble_mark as the marking
+// kernel: tip_rounds + bubble_rounds + 1 passes in all.  (Tips first: a tip that hangs on a bubble's branch splits it.)
 int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
     const int W = bs.words, bbits = bs.bbits;
     const u32 nb = 1u << bbits, nbt = S * nb;
     GCHK(alloc_graph(bs, S));
     u32* const d_claim = bs.d_nxt.as<u32>();      // claim words of the degree kernels live in nxt until k_edge_next overwrites them
-    const u32 rounds = bs.tip_len ? bs.tip_rounds : 0;
-    if (rounds) {
+    const u32 tip_rounds = bs.tip_len ? bs.tip_rounds : 0;
+    const u32 rounds = tip_rounds + (bs.bubble_len ? bs.bubble_rounds : 0);
+    if (tip_rounds) {
         GCHK(bs.d_tip_stats.ensure((size_t)2 * GASM_MAX_TIP_ROUNDS * S * 4));
         HIPCHK(hipMemsetAsync(bs.d_tip_stats.p, 0, (size_t)2 * GASM_MAX_TIP_ROUNDS * S * 4, ctx->stream));
+    }
+    if (rounds > tip_rounds) {
+        GCHK(bs.d_bubble_stats.ensure((size_t)2 * GASM_MAX_BUBBLE_ROUNDS * S * 4));
+        HIPCHK(hipMemsetAsync(bs.d_bubble_stats.p, 0, (size_t)2 * GASM_MAX_BUBBLE_ROUNDS * S * 4, ctx->stream));
     }
     for (u32 r = 0; r <= rounds; ++r) {
         GLAUNCH_K(ctx, W, "k_bucket_gather", k_bucket_gather<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(),
                   bs.d_bstart.as<u64>(), bs.d_dstart.as<u32>(), bs.d_dk_key.as<K>(), bs.d_dk_cnt.as<u32>(), d_claim, bs.d_eflag.as<u8>(), bs.d_flags.as<u32>());
         GCHK(launch_graph_dense(ctx, S, bs, r == rounds));
         if (r == rounds) break;
-        GasmRange range("gasm:tips (mark, compact)");
+        const bool tips = r < tip_rounds;
+        GasmRange range(tips ? "gasm:tips (mark, compact)" : "gasm:bubbles (mark, compact)");
         const u32 est = std::max<u32>(1, (u32)std::min<u64>(bs.maxD_est, bs.maxD_cap));
         const u32 dchunks = (u32)ceil_div_u64(est, GASM_WG);
-        u32* const d_tips = bs.d_tip_stats.as<u32>() + (size_t)r * S;
-        u32* const d_kmers = bs.d_tip_stats.as<u32>() + ((size_t)GASM_MAX_TIP_ROUNDS + r) * S;
-        GLAUNCH_K(ctx, W, "k_tip_mark", k_tip_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(), bs.d_clen.as<u32>(),
-                  bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.tip_len, bs.d_flags.as<u32>(), d_tips);
+        u32* d_kmers;
+        if (tips) {
+            u32* const d_tips = bs.d_tip_stats.as<u32>() + (size_t)r * S;
+            d_kmers = bs.d_tip_stats.as<u32>() + ((size_t)GASM_MAX_TIP_ROUNDS + r) * S;
+            GLAUNCH_K(ctx, W, "k_tip_mark", k_tip_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(), bs.d_clen.as<u32>(),
+                      bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.tip_len, bs.d_flags.as<u32>(), d_tips);
+        } else {
+            const u32 br = r - tip_rounds;
+            u32* const d_bubbles = bs.d_bubble_stats.as<u32>() + (size_t)br * S;
+            d_kmers = bs.d_bubble_stats.as<u32>() + ((size_t)GASM_MAX_BUBBLE_ROUNDS + br) * S;
+            GLAUNCH_K(ctx, W, "k_bubble_mark", k_bubble_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(),
+                      bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.bubble_len,
+                      bs.d_flags.as<u32>(), d_bubbles);
+        }
         // (the done word is zero: the gather of this pass cleared it behind the cutoff's or the last round's compaction)
         u32* const d_scan_out = bs.scan_in_dedup ? bs.d_dstart.as<u32>() : nullptr;
         GLAUNCH_K(ctx, W, "k_bucket_solid", k_bucket_solid<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
@@ -743,7 +761,8 @@ int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
     return GASM_OK;
 }
 
-// last_pass = false (a tip-clipping round): stops behind the chains' lengths — eflag, nxt and clen are what k_tip_mark reads
+// last_pass = false (a tip-clipping or bubble-popping round): stops behind the chains' lengths — eflag, nxt and clen are what
+// k_tip_mark and k_bubble_mark read
 static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs, bool last_pass) {
     GasmRange range("gasm:graph (degrees, list ranking, contigs)");
     const int W = bs.words;
@@ -896,16 +915,21 @@ static void zero_results(BuildState& bs, u32 S) {
     bs.d_total = 0; bs.n_contigs = 0; bs.contig_bases = 0;
 }
 
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count, u32 strands, u32 tip_len, u32 tip_rounds) {
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count, u32 strands, u32 tip_len, u32 tip_rounds, u32 bubble_len,
+                   u32 bubble_rounds) {
     if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
     if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
     if (strands == 2 && !rd.strands_of) { gasm_set_error("a both-strand build needs the both-strand reads"); return GASM_ERR_STATE; }
+    // (the bound of every walk of k_bubble_mark, and what keeps its products inside 64 bits)
+    if (bubble_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("bubble_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, bubble_len); return GASM_ERR_INVALID; }
     // (both strands: up to twice the distinct k-mers of the genome; without a hint the estimate follows the doubled k-mer count)
     GCHK(plan_build(ctx, rd, k, strands == 2 ? 2 * hint : hint, bs));
     bs.min_count = min_count;
     bs.strands = strands;
     bs.tip_len = tip_len;
     bs.tip_rounds = tip_len ? tip_rounds : 0;
+    bs.bubble_len = bubble_len;
+    bs.bubble_rounds = bubble_len ? bubble_rounds : 0;
     bs.fetched_twins = false;
     bs.spectrum_queued = false;
     const u32 S = rd.n_segments;
@@ -971,9 +995,9 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
         } else {
             bs.rank_global = true;        // whole-GPU pointer doubling instead of the LDS ranking
             ++bs.attempts_graph;
-            // a clipped build has compacted its runs round by round: a repeat of the graph alone would start from what the rounds
+            // a clipped or popped build has compacted its runs round by round: a repeat of the graph alone would start from what the rounds
             // so far left and count them twice.  It starts over from the reads (same configuration, so the same k-mer set)
-            if (bs.tip_len && rd) { ++bs.attempts_distinct; GCHK(launch_distinct(ctx, *rd, bs)); }
+            if ((bs.tip_len || bs.bubble_len) && rd) { ++bs.attempts_distinct; GCHK(launch_distinct(ctx, *rd, bs)); }
         }
         GCHK(launch_graph(ctx, S, bs));
     }
@@ -1044,6 +1068,18 @@ int pipeline_fetch_tip_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     return GASM_OK;
 }
 
+int pipeline_fetch_bubble_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    const u32 S = rd.n_segments, R = GASM_MAX_BUBBLE_ROUNDS;
+    bs.h_bubble_bubbles.assign((size_t)S * R, 0); bs.h_bubble_kmers.assign((size_t)S * R, 0);
+    if (!bs.bubble_len || !bs.n_kmers) return GASM_OK;       // (a build without k-mers launched nothing)
+    std::vector<u32> h((size_t)2 * R * S);
+    GCHK(d2h_sync(ctx, h.data(), bs.d_bubble_stats.p, h.size() * 4));
+    for (u32 s = 0; s < S; ++s)
+        for (u32 r = 0; r < R; ++r) { bs.h_bubble_bubbles[(size_t)s * R + r] = h[(size_t)r * S + s]; bs.h_bubble_kmers[(size_t)s * R + r] = h[((size_t)R + r) * S + s]; }
+    return GASM_OK;
+}
+
 int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
     const u32 S = rd.n_segments;
@@ -1051,11 +1087,13 @@ int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     // (a build without k-mers launched nothing, and min_count = 1 removed nothing)
     if (bs.min_count > 1 && bs.n_kmers) GCHK(d2h_sync(ctx, removed.data(), bs.d_solid_removed.p, (size_t)S * 4));
     bs.h_solid_before.resize(S); bs.h_solid_after.resize(S);
-    // (the tips clipped behind the cutoff are not the cutoff's: they count as survivors here)
+    // (the tips clipped and the bubbles popped behind the cutoff are not the cutoff's: they count as survivors here)
     if (bs.tip_len) GCHK(pipeline_fetch_tip_stats(ctx, rd, bs));
+    if (bs.bubble_len) GCHK(pipeline_fetch_bubble_stats(ctx, rd, bs));
     for (u32 s = 0; s < S; ++s) {
         bs.h_solid_after[s] = bs.h_dstart.empty() ? 0 : bs.h_dstart[s + 1] - bs.h_dstart[s];
         if (bs.tip_len) for (u32 r = 0; r < GASM_MAX_TIP_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_tip_kmers[(size_t)s * GASM_MAX_TIP_ROUNDS + r];
+        if (bs.bubble_len) for (u32 r = 0; r < GASM_MAX_BUBBLE_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_bubble_kmers[(size_t)s * GASM_MAX_BUBBLE_ROUNDS + r];
         bs.h_solid_before[s] = bs.h_solid_after[s] + removed[s];
     }
     return GASM_OK;
@@ -1455,7 +1493,7 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     // a mismatch raises GASM_FLAG_SCORE_MISMATCH of the build and pipeline_score_fetch refuses the scores
     // A graph built with a multiplicity cutoff does not hold every k-mer of every read: the comparison is then part of the match
     // (verify = 2: a mismatch is "no match" and raises nothing)
-    const int verify = (graph.min_count > 1 || graph.tip_len) ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
+    const int verify = (graph.min_count > 1 || graph.tip_len || graph.bubble_len) ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
     ss.verify = verify == 1;
     const u32 reads_per_wg = 256;     // one read per thread: the match is a chain of dependent loads
     const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);

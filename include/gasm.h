@@ -94,6 +94,11 @@ int gasm_get_contigs_from_reads_strands(gasm_ctx* ctx, const char* reads, const 
 int gasm_get_contigs_from_reads_tips(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                      int matrix_rows, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
                                      gasm_contigs** out);
+/* The same with bubble popping (gasm_batch_build_bubbles below): bubble_len > 0 removes, for bubble_rounds rounds behind the tip
+ * rounds, the weaker of parallel short contigs; bubble_len = 0 is gasm_get_contigs_from_reads_tips and bubble_rounds is not read. */
+int gasm_get_contigs_from_reads_bubbles(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
+                                        int matrix_rows, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
+                                        uint32_t bubble_len, uint32_t bubble_rounds, gasm_contigs** out);
 uint64_t gasm_contigs_count(const gasm_contigs* c);
 const char* gasm_contigs_data(const gasm_contigs* c);
 const uint64_t* gasm_contigs_offsets(const gasm_contigs* c);       /* count+1 */
@@ -305,6 +310,8 @@ int gasm_batch_score(gasm_batch* b, int kmer, const double* table);
  *   min_count == 0: GASM_ERR_INVALID.  Each step slot remembers the cutoff of the build it holds.
  * (after a build with tip clipping, below, distinct_after still counts the survivors of the CUTOFF: the k-mers of
  * gasm_batch_fetch_distinct are distinct_after minus the segment's clipped k-mers of gasm_batch_fetch_tip_stats)
+ * (the same after a build with bubble popping, further below: distinct_after adds back the popped k-mers of
+ * gasm_batch_fetch_bubble_stats as it adds back the clipped ones)
  * genome_len_hint for noisy reads: it sizes the buckets for the distinct k-mers BEFORE the cutoff, and reads with errors hold
  * 5-10x more of them than their genome: about genome length + bases in the segment's reads x error rate x k (every wrong base
  * makes up to k new k-mers).  A smaller hint (the genome length alone) is still correct: the tables overflow, the build repeats
@@ -351,7 +358,7 @@ int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist /* n_seg
  *                                 contig in the order of gasm_batch_fetch_contigs; an involution; twin[c] == c for a self-twin.
  *                                 Host copy, valid until the next build.  GASM_ERR_STATE before a build or after a strands = 1
  *                                 build; GASM_ERR_INTERNAL if a contig has no twin (the closure above would be broken).
- * Pooled builds (gasm_pool_*) are forward-strand only and clip no tips (below).
+ * Pooled builds (gasm_pool_*) are forward-strand only and clip no tips (below).  They pop no bubbles either (further below).
  * ---------------------------------------------------------------------------------------------------------------- */
 int gasm_batch_build_strands(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands);
 uint32_t gasm_batch_strands(const gasm_batch* b);
@@ -401,6 +408,57 @@ int gasm_batch_build_tips(gasm_batch* b, int k, uint64_t genome_len_hint, uint32
 uint32_t gasm_batch_tip_len(const gasm_batch* b);      /* of the last build; 0: none */
 uint32_t gasm_batch_tip_rounds(const gasm_batch* b);
 int gasm_batch_fetch_tip_stats(gasm_batch* b, const uint32_t** tips, const uint32_t** kmers);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Bubble popping: of two parallel short paths the weaker leaves the k-mer set before the contigs are cut.  (No counterpart in the
+ * reference; Velvet (Tour Bus) and SPAdes pop bubbles after they clip tips.  bubble_len = 0 is the default everywhere.)
+ * A substitution in the middle of a read makes k wrong k-mers: a second path of k edges that leaves the true path at one node and
+ * rejoins it k edges later.  Both ends stay attached, so it is no tip; seen min_count times it survives the cutoff; and each such
+ * bubble cuts the true contig in three and adds a fourth, false one.  gasm_batch_build_bubbles removes bubbles from the k-mer set
+ * that the cutoff and the tip rounds left, for exactly bubble_rounds rounds; everything else is made from what is left.
+ * The rule, on the same graph as the tip rule (edges = distinct k-mers with their multiplicities, nodes = (k-1)-mers, contigs =
+ * what the build would cut).  For a contig c let u(c) = its first node, v(c) = its last node, n(c) = its edges, m(c) = the sum of
+ * its edges' multiplicities, len(c) = n(c) + k - 1 bases.  One round, on the current set:
+ *   c and d are PARALLEL if d != c, u(d) == u(c) and v(d) == v(c).  (d starts with a sibling out-edge of c's first edge: every
+ *   out-edge of a node with two or more is the head of a contig.)
+ *   c is POPPED if len(c) <= bubble_len and a parallel d exists with len(d) <= bubble_len and STRICTLY higher mean multiplicity:
+ *   m(d) * n(c) > m(c) * n(d), compared exactly in 64-bit integers.
+ *   The two paths need not be equally long (an indel makes them differ).  The comparison is strict, with no tie-break by key:
+ *   among parallel paths of equal mean multiplicity nobody is popped, for the reason given for tips (a key order is not symmetric
+ *   under reverse complement).  With strands = 2 the twin of a popped contig is popped in the same round, and two paths that are
+ *   each other's twin tie and both stay.  Of three parallel paths the two weaker go in the same round.  u == v (two parallel
+ *   loops) gets no special case.
+ *   All bubbles of a round are found on the same graph and leave together, with all their k-mers (a k-mer lies in at most one
+ *   contig); the next round starts from the remaining set.
+ * A build runs exactly bubble_rounds rounds, queued as a whole, AFTER all tip rounds: a tip that hangs on a bubble's branch splits
+ * that branch, so the bubble is only seen once the tip is gone.  A nested bubble — a bubble inside one branch of a larger one —
+ * takes two rounds: the inner one goes first, then the re-joined branch.
+ * STATED LIMIT: two bubbles that OVERLAP are not popped by this rule — two errors less than k apart in different reads, say, each
+ * branching off inside the other's span: neither has a parallel contig, because the true path between their ends is itself cut.
+ * Tour Bus handles that case; this rule does not try to.
+ * bubble_len <= GASM_MAX_BUBBLE_LEN keeps m * n inside 64 bits for any 32-bit multiplicities and bounds a GPU thread's walk: in
+ * every round one thread per short contig that has siblings walks its own chain and those of at most three siblings, edge by edge.
+ * The intended setting is 2k - 1, the exact length of a single-substitution bubble; bubble_len < k can match no contig and is
+ * allowed.  As for tip_len, a bubble_len of thousands is paid for in dependent loads: still correct, only slow.
+ * Everything behind the build — contigs, gasm_batch_fetch_distinct / _graph, the k-mer spectrum, twins, scores under one or
+ * several tables, the guided traversal — sees the popped set with its true multiplicities.  A read scores on a contig iff it is a
+ * substring of it: a read that holds a popped k-mer adds nothing.
+ * gasm_batch_build_bubbles      bubble_len == 0 is gasm_batch_build_tips: same host path, same kernel launches, bubble_rounds is
+ *                               not read.  bubble_len > 0 needs bubble_len <= GASM_MAX_BUBBLE_LEN and bubble_rounds in
+ *                               1..GASM_MAX_BUBBLE_ROUNDS, else GASM_ERR_INVALID.  Each step slot remembers both of the build it
+ *                               holds, as it remembers tip_len and tip_rounds.
+ * gasm_batch_bubble_len / _bubble_rounds   of the last build (0: no popping, or no build yet).
+ * gasm_batch_fetch_bubble_stats bubbles[s * GASM_MAX_BUBBLE_ROUNDS + r] = contigs popped in segment s, round r; kmers[...] =
+ *                               k-mers popped, same index; rounds not run are 0.  Host copies, valid until the next call or
+ *                               build.  GASM_ERR_STATE before a build or after a build with bubble_len == 0.
+ * Pooled builds (gasm_pool_*) pop no bubbles.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAX_BUBBLE_ROUNDS 8
+#define GASM_MAX_BUBBLE_LEN 65535
+int gasm_batch_build_bubbles(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands,
+                             uint32_t tip_len, uint32_t tip_rounds, uint32_t bubble_len, uint32_t bubble_rounds);
+uint32_t gasm_batch_bubble_len(const gasm_batch* b);   /* of the last build; 0: none */
+uint32_t gasm_batch_bubble_rounds(const gasm_batch* b);
+int gasm_batch_fetch_bubble_stats(gasm_batch* b, const uint32_t** bubbles, const uint32_t** kmers);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
@@ -455,7 +513,7 @@ int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read
  * the bucket lists both sides derive from the ownership function.  Results do not depend on the number of ranks.
  *
  *   (pooled builds take their k-mers forward-strand only: there is no strands argument here; they do not clip tips either:
- *   there is no tip_len argument)
+ *   there is no tip_len argument; and they pop no bubbles: there is no bubble_len argument)
  *   gasm_pool_create       this rank's reads (fixed length) of ALL n_segments segments
  *   gasm_pool_local_runs   k-mers of those reads -> one sorted run of distinct (key, count) per bucket; bucket index =
  *                          segment << bbits | first bbits bits of the k-mer; run_len (host, n_segments << bbits entries)

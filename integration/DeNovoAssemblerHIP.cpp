@@ -73,15 +73,26 @@ std::vector<std::vector<std::string>> get_contigs(const std::vector<std::string>
 // tip_len, tip_rounds (optional, default 0 = no clipping): tip_rounds rounds (1..GASM_MAX_TIP_ROUNDS) of tip clipping before the
 // contigs are cut (gasm_get_contigs_from_reads_tips; the rule is in include/gasm.h) — for reads with sequencing errors; 2 * dbg_kmer - 1
 // is the intended tip_len
+// bubble_len, bubble_rounds (optional, default 0 = no popping): then bubble_rounds rounds (1..GASM_MAX_BUBBLE_ROUNDS) of bubble popping
+// (gasm_get_contigs_from_reads_bubbles; the rule is in include/gasm.h) — the weaker of two parallel short paths, the mark a
+// substitution in the middle of a read leaves; 2 * dbg_kmer - 1 is the intended bubble_len, GASM_MAX_BUBBLE_LEN the largest
 // [[Rcpp::export]]
 std::vector<std::vector<std::string>> get_contigs_from_reads(const std::vector<std::string>& reads, const int& dbg_kmer, const int& seed,
-                                                             const int& strands = 1, const int& tip_len = 0, const int& tip_rounds = 1) {
+                                                             const int& strands = 1, const int& tip_len = 0, const int& tip_rounds = 1,
+                                                             const int& bubble_len = 0, const int& bubble_rounds = 1) {
     if (strands != 1 && strands != 2) Rcpp::stop("strands must be 1 or 2");
     if (tip_len < 0) Rcpp::stop("tip_len must be >= 0");
     if (tip_len > 0 && (tip_rounds < 1 || tip_rounds > GASM_MAX_TIP_ROUNDS)) Rcpp::stop("tip_rounds must be 1..%d when tip_len > 0", GASM_MAX_TIP_ROUNDS);
+    if (bubble_len < 0 || bubble_len > GASM_MAX_BUBBLE_LEN) Rcpp::stop("bubble_len must be 0..%d", GASM_MAX_BUBBLE_LEN);
+    if (bubble_len > 0 && (bubble_rounds < 1 || bubble_rounds > GASM_MAX_BUBBLE_ROUNDS))
+        Rcpp::stop("bubble_rounds must be 1..%d when bubble_len > 0", GASM_MAX_BUBBLE_ROUNDS);
     Flat f(reads);
     gasm_contigs* c = nullptr;
-    if (tip_len > 0)
+    if (bubble_len > 0)
+        check(gasm_get_contigs_from_reads_bubbles(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, (uint32_t)strands,
+                                                  (uint32_t)tip_len, tip_len > 0 ? (uint32_t)tip_rounds : 0u, (uint32_t)bubble_len,
+                                                  (uint32_t)bubble_rounds, &c));
+    else if (tip_len > 0)
         check(gasm_get_contigs_from_reads_tips(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, (uint32_t)strands,
                                                (uint32_t)tip_len, (uint32_t)tip_rounds, &c));
     else if (strands == 2) check(gasm_get_contigs_from_reads_strands(the_ctx(), f.data.data(), f.off.data(), reads.size(), dbg_kmer, seed, 10000, 1, 2, &c));
