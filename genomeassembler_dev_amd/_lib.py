@@ -13,6 +13,7 @@ TABLE_ROWS = 69904
 MAX_TIP_ROUNDS = 8      # GASM_MAX_TIP_ROUNDS: rounds of tip clipping one build takes
 MAX_BUBBLE_ROUNDS = 8   # GASM_MAX_BUBBLE_ROUNDS: rounds of bubble popping one build takes
 MAX_BUBBLE_LEN = 65535  # GASM_MAX_BUBBLE_LEN: longest contig (bases) bubble popping looks at
+MAX_COV_ROUNDS = 8      # GASM_MAX_COV_ROUNDS: rounds of low-coverage removal one build takes
 MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
@@ -30,6 +31,20 @@ class GasmError(RuntimeError):
 _vp, _u64, _u32, _i32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_int
 _PP = C.POINTER(C.c_void_p)
 
+
+class BuildParams(C.Structure):
+    """gasm_build_params (include/gasm.h): every knob of a build; make() fills `size`"""
+    _fields_ = [("size", _u32), ("k", _i32), ("genome_len_hint", _u64), ("min_count", _u32), ("strands", _u32), ("tip_len", _u32),
+                ("tip_rounds", _u32), ("bubble_len", _u32), ("bubble_rounds", _u32), ("cov_cutoff", _u32), ("cov_len", _u32), ("cov_rounds", _u32)]
+
+    @classmethod
+    def make(cls, k, **fields):
+        p = cls(size=C.sizeof(cls), k=int(k))
+        for name, v in fields.items():
+            setattr(p, name, int(v))
+        return p
+
+
 # every symbol include/gasm.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "gasm_last_error": (C.c_char_p, []),
@@ -44,6 +59,7 @@ SYMBOLS = {
     "gasm_get_contigs_from_reads_strands": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _u32, _PP]),
     "gasm_get_contigs_from_reads_tips": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _u32, _u32, _u32, _PP]),
     "gasm_get_contigs_from_reads_bubbles": (_int, [_vp, _vp, _vp, _u64, _int, _int, _int, _u32, _u32, _u32, _u32, _u32, _u32, _PP]),
+    "gasm_get_contigs_from_reads_params": (_int, [_vp, _vp, _vp, _u64, _int, _int, C.POINTER(BuildParams), _PP]),
     "gasm_contigs_count": (_u64, [_vp]),
     "gasm_contigs_data": (_vp, [_vp]),
     "gasm_contigs_offsets": (_vp, [_vp]),
@@ -124,6 +140,13 @@ SYMBOLS = {
     "gasm_batch_bubble_len": (_u32, [_vp]),
     "gasm_batch_bubble_rounds": (_u32, [_vp]),
     "gasm_batch_fetch_bubble_stats": (_int, [_vp, _PP, _PP]),
+    "gasm_batch_build_params": (_int, [_vp, C.POINTER(BuildParams)]),
+    "gasm_batch_cov_cutoff": (_u32, [_vp]),
+    "gasm_batch_cov_len": (_u32, [_vp]),
+    "gasm_batch_cov_rounds": (_u32, [_vp]),
+    "gasm_batch_fetch_lowcov_stats": (_int, [_vp, _PP, _PP]),
+    "gasm_batch_contig_coverage": (_int, [_vp]),
+    "gasm_batch_fetch_contig_coverage": (_int, [_vp, _PP, _PP]),
     "gasm_batch_fetch_contig_twins": (_int, [_vp, _PP]),
     "gasm_batch_fetch_solid_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_kmer_spectrum": (_int, [_vp]),

@@ -123,6 +123,17 @@ def _check_bubbles(bubble_len, bubble_rounds):
         raise ValueError(f"bubble_rounds must be 1..{_lib.MAX_BUBBLE_ROUNDS} when bubble_len > 0")
 
 
+def _check_lowcov(cov_cutoff, cov_len, cov_rounds):
+    """the argument rule of every low-coverage entry: cov_cutoff >= 0, 0 <= cov_len <= _lib.MAX_BUBBLE_LEN, and 1.._lib.MAX_COV_ROUNDS
+    rounds when both are positive (either 0: the feature is off and cov_rounds is not read)"""
+    if not 0 <= int(cov_cutoff) <= 0xFFFFFFFF:
+        raise ValueError("cov_cutoff must be >= 0 (0: no low-coverage removal)")
+    if not 0 <= int(cov_len) <= _lib.MAX_BUBBLE_LEN:
+        raise ValueError(f"cov_len must be 0..{_lib.MAX_BUBBLE_LEN} (0: no low-coverage removal)")
+    if int(cov_cutoff) > 0 and int(cov_len) > 0 and not 1 <= int(cov_rounds) <= _lib.MAX_COV_ROUNDS:
+        raise ValueError(f"cov_rounds must be 1..{_lib.MAX_COV_ROUNDS} when cov_cutoff > 0 and cov_len > 0")
+
+
 def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
                            tip_rounds=1):
     """get_kmers_from_reads + get_contigs in one call (gasm_get_contigs_from_reads): the k-mers are taken on the GPU from the
@@ -175,6 +186,33 @@ def get_contigs_from_reads_bubbles(reads, dbg_kmer, seed, matrix_rows=10000, ctx
     check(lib().gasm_get_contigs_from_reads_bubbles(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
                                                     int(min_count), int(strands), int(tip_len), int(tip_rounds) if int(tip_len) else 0,
                                                     int(bubble_len), int(bubble_rounds), C.byref(h)))
+    return _contig_matrix(h, dbg_kmer, as_lists)
+
+
+def get_contigs_from_reads_simplified(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, *, min_count=1, strands=1, tip_len=0,
+                                      tip_rounds=1, bubble_len=0, bubble_rounds=1, cov_cutoff=0, cov_len=0, cov_rounds=1):
+    """get_contigs_from_reads_bubbles with low-coverage removal (gasm_get_contigs_from_reads_params): after the tip and the bubble
+    rounds, cov_rounds rounds (1.._lib.MAX_COV_ROUNDS) in which every contig of at most cov_len bases (<= _lib.MAX_BUBBLE_LEN) whose mean
+    multiplicity is strictly below cov_cutoff leaves the k-mer set, attached or not (the rule: include/gasm.h).  cov_cutoff = 0 or
+    cov_len = 0 is get_contigs_from_reads_bubbles with the other arguments, and cov_rounds is not read.  The knobs are keyword-only:
+    the positional chain ends with get_contigs_from_reads_bubbles."""
+    _check_lowcov(cov_cutoff, cov_len, cov_rounds)
+    if int(cov_cutoff) == 0 or int(cov_len) == 0:
+        return get_contigs_from_reads_bubbles(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count, strands, tip_len, tip_rounds, bubble_len,
+                                              bubble_rounds)
+    if int(min_count) < 1:
+        raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+    if int(strands) not in (1, 2):
+        raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+    _check_tips(tip_len, tip_rounds)
+    _check_bubbles(bubble_len, bubble_rounds)
+    ctx = ctx or default_context()
+    buf, off = _pack(reads)
+    h = C.c_void_p()
+    p = _lib.BuildParams.make(dbg_kmer, min_count=min_count, strands=strands, tip_len=tip_len, tip_rounds=tip_rounds if int(tip_len) else 0,
+                              bubble_len=bubble_len, bubble_rounds=bubble_rounds if int(bubble_len) else 0, cov_cutoff=cov_cutoff, cov_len=cov_len,
+                              cov_rounds=cov_rounds)
+    check(lib().gasm_get_contigs_from_reads_params(ctx.h, buf, _ptr(off), len(reads), int(seed), int(matrix_rows), C.byref(p), C.byref(h)))
     return _contig_matrix(h, dbg_kmer, as_lists)
 
 

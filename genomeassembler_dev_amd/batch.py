@@ -2,12 +2,26 @@
 between the calls (gasm_batch_* in include/gasm.h).  This is the reads-level surface the reference only has in R
 (lib/DeNovoAssembler.R:58-68: get_reads -> get_kmers_from_reads -> get_contigs -> calc_breakscore)."""
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import MAX_BUBBLE_ROUNDS, MAX_TIP_ROUNDS, PLAN_FIELDS, check, default_context, lib
-from .api import _check_bubbles, _check_tips, unpack_kmers
+from ._lib import MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from .api import _check_bubbles, _check_lowcov, _check_tips, unpack_kmers
+
+
+def weighted_median_half(mult_sum, n_edges):
+    """floor(median / 2) of the contigs' mean multiplicities mult_sum / n_edges, each weighted by n_edges: the median is the mean of
+    the first contig, in ascending order of mean, at which the running weight reaches half the total.  Exact integers."""
+    ms, ns = [int(x) for x in mult_sum], [int(x) for x in n_edges]
+    order = sorted(range(len(ns)), key=lambda i: Fraction(ms[i], ns[i]))
+    total, run = sum(ns), 0
+    for i in order:
+        run += ns[i]
+        if 2 * run >= total:
+            return ms[i] // (2 * ns[i])
+    return 0
 
 
 class SegmentBatch:
@@ -111,7 +125,7 @@ class SegmentBatch:
         strands = 2 (gasm_batch_build_strands): the k-mers of every read and of its reverse complement — reads of both strands
         then meet in one graph, multiplicities (and min_count) are sums over both strands, and the contigs come in
         reverse-complement pairs (contig_twins).  Scores are over the reads as they were given, each once.
-        Tip clipping: build_tips().  Bubble popping: build_bubbles()."""
+        Tip clipping: build_tips().  Bubble popping: build_bubbles().  Low-coverage removal: build_simplified()."""
         if int(min_count) < 1:
             raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
         if int(strands) not in (1, 2):
@@ -122,7 +136,7 @@ class SegmentBatch:
             check(lib().gasm_batch_build(self.h, int(k), int(genome_len_hint)))
         else:
             check(lib().gasm_batch_build_solid(self.h, int(k), int(genome_len_hint), int(min_count)))
-        self.k = int(k)
+        self.k, self._min_count = int(k), int(min_count)
         return self
 
     def build_tips(self, k, genome_len_hint=0, min_count=1, strands=1, tip_len=0, tip_rounds=1):
@@ -139,7 +153,7 @@ class SegmentBatch:
             raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
         _check_tips(tip_len, tip_rounds)
         check(lib().gasm_batch_build_tips(self.h, int(k), int(genome_len_hint), int(min_count), int(strands), int(tip_len), int(tip_rounds)))
-        self.k = int(k)
+        self.k, self._min_count = int(k), int(min_count)
         return self
 
     def build_bubbles(self, k, genome_len_hint=0, min_count=1, strands=1, tip_len=0, tip_rounds=1, bubble_len=0, bubble_rounds=1):
@@ -158,7 +172,31 @@ class SegmentBatch:
         _check_bubbles(bubble_len, bubble_rounds)
         check(lib().gasm_batch_build_bubbles(self.h, int(k), int(genome_len_hint), int(min_count), int(strands), int(tip_len),
                                              int(tip_rounds) if int(tip_len) else 0, int(bubble_len), int(bubble_rounds)))
-        self.k = int(k)
+        self.k, self._min_count = int(k), int(min_count)
+        return self
+
+    def build_simplified(self, k, genome_len_hint=0, *, min_count=1, strands=1, tip_len=0, tip_rounds=1, bubble_len=0, bubble_rounds=1, cov_cutoff=0,
+                         cov_len=0, cov_rounds=1):
+        """build_bubbles() with low-coverage removal (gasm_batch_build_params): exactly cov_rounds rounds (1.._lib.MAX_COV_ROUNDS) behind
+        the tip and the bubble rounds — a contig of at most cov_len bases (<= _lib.MAX_BUBBLE_LEN) whose mean multiplicity is strictly
+        below cov_cutoff leaves the k-mer set with all its k-mers, whatever is attached to it (the rule: include/gasm.h).  The intended
+        setting is cov_len = 2k - 1, cov_cutoff = min_count + 1, one round; suggest_cov_cutoff() derives a cutoff from a build's own
+        contigs.  lowcov_stats() tells what each round removed.  cov_cutoff = 0 or cov_len = 0 is build_bubbles() with the other
+        arguments, and cov_rounds is not read.  The knobs are keyword-only: the positional chain ends with build_bubbles()."""
+        _check_lowcov(cov_cutoff, cov_len, cov_rounds)
+        if int(cov_cutoff) == 0 or int(cov_len) == 0:
+            return self.build_bubbles(k, genome_len_hint, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds)
+        if int(min_count) < 1:
+            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
+        if int(strands) not in (1, 2):
+            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
+        _check_tips(tip_len, tip_rounds)
+        _check_bubbles(bubble_len, bubble_rounds)
+        p = BuildParams.make(k, genome_len_hint=genome_len_hint, min_count=min_count, strands=strands, tip_len=tip_len,
+                             tip_rounds=tip_rounds if int(tip_len) else 0, bubble_len=bubble_len, bubble_rounds=bubble_rounds if int(bubble_len) else 0,
+                             cov_cutoff=cov_cutoff, cov_len=cov_len, cov_rounds=cov_rounds)
+        check(lib().gasm_batch_build_params(self.h, C.byref(p)))
+        self.k, self._min_count = int(k), int(min_count)
         return self
 
     def solid_stats(self):
@@ -192,6 +230,46 @@ class SegmentBatch:
             return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
         return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
                 np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
+
+    def lowcov_stats(self):
+        """(contigs removed, k-mers removed) by the last build's low-coverage removal: two (n_segments, MAX_COV_ROUNDS) uint32 arrays,
+        column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would remove more."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_lowcov_stats(self.h, C.byref(a), C.byref(b)))
+        n = self.n_segments * MAX_COV_ROUNDS
+        shape = (self.n_segments, MAX_COV_ROUNDS)
+        if not n:
+            return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
+                np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
+
+    def contig_coverage(self, segment=None):
+        """(mult_sum uint64, n_edges uint32) of the last build's contigs (gasm_batch_contig_coverage), one entry per contig in the
+        order of contigs(): the sum of the contig's k-mer multiplicities and the number of its k-mers; mult_sum / n_edges is its
+        mean multiplicity.  segment = None: the whole batch, segment after segment; else that segment's contigs only."""
+        check(lib().gasm_batch_contig_coverage(self.h))
+        m, n = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_contig_coverage(self.h, C.byref(m), C.byref(n)))
+        so, _, _ = self.contigs_raw()
+        total = int(so[-1])
+        if not total:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+        ms = np.ctypeslib.as_array(C.cast(m, C.POINTER(C.c_uint64)), shape=(total,)).copy()
+        ns = np.ctypeslib.as_array(C.cast(n, C.POINTER(C.c_uint32)), shape=(total,)).copy()
+        if segment is None:
+            return ms, ns
+        a, z = int(so[int(segment)]), int(so[int(segment) + 1])
+        return ms[a:z], ns[a:z]
+
+    def suggest_cov_cutoff(self, segment):
+        """a cov_cutoff for build_simplified() from the last build's own contigs of `segment`: half the length-weighted median of the
+        contigs' mean multiplicities (Velvet's -cov_cutoff auto), floored, and at least min_count + 1 of that build (below that the
+        rule can match nothing).  The weight of a contig is its number of k-mers.  Host arithmetic over contig_coverage()."""
+        floor = getattr(self, "_min_count", 1) + 1
+        ms, ns = self.contig_coverage(segment)
+        if not len(ns):
+            return floor
+        return max(floor, weighted_median_half(ms, ns))
 
     def kmer_spectrum(self):
         """(n_segments, 256) uint64: [s, m] = distinct k-mers of segment s of the last build with multiplicity m (255: that or

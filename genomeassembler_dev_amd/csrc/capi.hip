@@ -157,14 +157,15 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
 // reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix
 static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_off, u64 n_reads, u32 fixed_len, int dbg_kmer, int seed, int matrix_rows,
                             gasm_contigs** out, u32 min_count = 1, u32 strands = 1, u32 tip_len = 0, u32 tip_rounds = 0, u32 bubble_len = 0,
-                            u32 bubble_rounds = 0) {
+                            u32 bubble_rounds = 0, u32 cov_cutoff = 0, u32 cov_len = 0, u32 cov_rounds = 0) {
     DevReads rd, rd2;
     BuildState bs;
     const u64 seg_off[2] = {0, n_reads};
     int st = rd.upload(ctx, bases, read_off, n_reads, fixed_len, seg_off, 1);
     if (st == GASM_OK && strands == 2) st = rd2.make_both_strands(ctx, rd);
     DevReads& br = strands == 2 ? rd2 : rd;
-    if (st == GASM_OK) st = pipeline_build(ctx, br, dbg_kmer, 0, bs, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds);
+    if (st == GASM_OK) st = pipeline_build(ctx, br, dbg_kmer, 0, bs, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds, cov_cutoff, cov_len,
+                                            cov_rounds);
     if (st == GASM_OK) st = pipeline_fetch_distinct(ctx, br, bs);
     if (st == GASM_OK) st = pipeline_fetch_contigs(ctx, br, bs);
     gasm_contigs* c = nullptr;
@@ -214,6 +215,30 @@ static int check_bubble_args(u32 bubble_len, u32 bubble_rounds) {
     }
     if (bubble_len && (bubble_rounds < 1 || bubble_rounds > GASM_MAX_BUBBLE_ROUNDS)) {
         gasm_set_error("bubble_rounds must be 1..%d when bubble_len > 0 (got %u)", GASM_MAX_BUBBLE_ROUNDS, bubble_rounds);
+        return GASM_ERR_INVALID;
+    }
+    return GASM_OK;
+}
+
+// cov_cutoff == 0 or cov_len == 0: no low-coverage removal, cov_rounds is not read
+static int check_cov_args(u32 cov_cutoff, u32 cov_len, u32 cov_rounds) {
+    if (!cov_cutoff || !cov_len) return GASM_OK;
+    if (cov_len > GASM_MAX_BUBBLE_LEN) {
+        gasm_set_error("cov_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, cov_len);
+        return GASM_ERR_INVALID;
+    }
+    if (cov_rounds < 1 || cov_rounds > GASM_MAX_COV_ROUNDS) {
+        gasm_set_error("cov_rounds must be 1..%d when cov_cutoff > 0 and cov_len > 0 (got %u)", GASM_MAX_COV_ROUNDS, cov_rounds);
+        return GASM_ERR_INVALID;
+    }
+    return GASM_OK;
+}
+
+// the struct form's own checks; the fields' are those of the positional entries
+static int check_build_params(const char* entry, const gasm_build_params* p) {
+    if (!p) { gasm_set_error("%s: params is null", entry); return GASM_ERR_INVALID; }
+    if (p->size != sizeof(gasm_build_params)) {
+        gasm_set_error("%s: params->size is %u, this library's gasm_build_params has %zu bytes", entry, p->size, sizeof(gasm_build_params));
         return GASM_ERR_INVALID;
     }
     return GASM_OK;
@@ -273,6 +298,21 @@ int gasm_get_contigs_from_reads_bubbles(gasm_ctx* ctx, const char* reads, const 
     GCHK(check_bubble_args(bubble_len, bubble_rounds));
     return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count, strands, tip_len, tip_len ? tip_rounds : 0,
                             bubble_len, bubble_len ? bubble_rounds : 0);
+    API_GUARD_END
+}
+
+int gasm_get_contigs_from_reads_params(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int seed, int matrix_rows,
+                                       const gasm_build_params* params, gasm_contigs** out) {
+    API_GUARD_BEGIN
+    GCHK(check_build_params("gasm_get_contigs_from_reads_params", params));
+    const gasm_build_params& p = *params;
+    const u32 min_count = p.min_count ? p.min_count : 1, strands = p.strands ? p.strands : 1;
+    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_params", ctx, reads, read_off, n_reads, matrix_rows, min_count, strands, out));
+    GCHK(check_tip_args(p.tip_len, p.tip_rounds));
+    GCHK(check_bubble_args(p.bubble_len, p.bubble_rounds));
+    GCHK(check_cov_args(p.cov_cutoff, p.cov_len, p.cov_rounds));
+    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, p.k, seed, matrix_rows, out, min_count, strands, p.tip_len, p.tip_len ? p.tip_rounds : 0,
+                            p.bubble_len, p.bubble_len ? p.bubble_rounds : 0, p.cov_cutoff, p.cov_len, p.cov_cutoff && p.cov_len ? p.cov_rounds : 0);
     API_GUARD_END
 }
 
@@ -821,14 +861,16 @@ void gasm_batch_free(gasm_batch* b) {
 }
 
 // gasm_batch_build (min_count = 1), gasm_batch_build_solid (strands = 1), gasm_batch_build_strands (tip_len = 0), gasm_batch_build_tips
-// (bubble_len = 0) and gasm_batch_build_bubbles
+// (bubble_len = 0), gasm_batch_build_bubbles (cov_cutoff = 0) and gasm_batch_build_params
 static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands = 1, uint32_t tip_len = 0,
-                       uint32_t tip_rounds = 0, uint32_t bubble_len = 0, uint32_t bubble_rounds = 0) {
+                       uint32_t tip_rounds = 0, uint32_t bubble_len = 0, uint32_t bubble_rounds = 0, uint32_t cov_cutoff = 0, uint32_t cov_len = 0,
+                       uint32_t cov_rounds = 0) {
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
     if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
     if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
     GCHK(check_tip_args(tip_len, tip_rounds));
     GCHK(check_bubble_args(bubble_len, bubble_rounds));
+    GCHK(check_cov_args(cov_cutoff, cov_len, cov_rounds));
     b->built = false; b->scored = false;
     // consecutive steps take the slots in turn: this build does not wait for the last steps' graph and scoring, it runs
     // beside them.  A change of k rewrites the tile tables every slot reads: everything drains first.  GASM_PINGPONG=0: the
@@ -845,8 +887,10 @@ static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t 
     // both strands: the reverse-complemented stream is made once per upload (on this slot's stream, complete before the call
     // returns: the other slots read it without waiting for this one)
     if (strands == 2 && b->rd2.strands_of != b->rd.upload_id) GCHK(b->rd2.make_both_strands(st.cx, b->rd));
-    // (the slot's BuildState keeps the cutoff, the strands, the tip clipping and the bubble popping of the build it holds)
-    GCHK(pipeline_build(st.cx, strands == 2 ? b->rd2 : b->rd, k, genome_len_hint, st.bs, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds));
+    // (the slot's BuildState keeps the cutoff, the strands, the tip clipping, the bubble popping and the low-coverage removal of the
+    // build it holds)
+    GCHK(pipeline_build(st.cx, strands == 2 ? b->rd2 : b->rd, k, genome_len_hint, st.bs, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds,
+                        cov_cutoff, cov_len, cov_rounds));
     b->last_k = k;
     b->built = true;
     return GASM_OK;
@@ -913,6 +957,52 @@ int gasm_batch_fetch_bubble_stats(gasm_batch* b, const uint32_t** bubbles, const
     BuildState& bs = b->S().bs;
     GCHK(pipeline_fetch_bubble_stats(b->S().cx, b->build_reads(b->S()), bs));
     *bubbles = bs.h_bubble_bubbles.data(); *kmers = bs.h_bubble_kmers.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_build_params(gasm_batch* b, const gasm_build_params* params) {
+    API_GUARD_BEGIN
+    GCHK(check_build_params("gasm_batch_build_params", params));
+    const gasm_build_params& p = *params;
+    return batch_build(b, p.k, p.genome_len_hint, p.min_count ? p.min_count : 1, p.strands ? p.strands : 1, p.tip_len, p.tip_len ? p.tip_rounds : 0,
+                       p.bubble_len, p.bubble_len ? p.bubble_rounds : 0, p.cov_cutoff, p.cov_len, p.cov_cutoff && p.cov_len ? p.cov_rounds : 0);
+    API_GUARD_END
+}
+
+uint32_t gasm_batch_cov_cutoff(const gasm_batch* b) { return b && b->built ? b->S().bs.cov_cutoff : 0; }
+uint32_t gasm_batch_cov_len(const gasm_batch* b) { return b && b->built ? b->S().bs.cov_len : 0; }
+uint32_t gasm_batch_cov_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.cov_rounds : 0; }
+
+int gasm_batch_fetch_lowcov_stats(gasm_batch* b, const uint32_t** contigs, const uint32_t** kmers) {
+    API_GUARD_BEGIN
+    if (!b || !contigs || !kmers) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_lowcov_stats before a build"); return GASM_ERR_STATE; }
+    if (!b->S().bs.lowcov()) { gasm_set_error("the last build removed no low-coverage contigs (cov_cutoff = 0 or cov_len = 0)"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_lowcov_stats(b->S().cx, b->build_reads(b->S()), bs));
+    *contigs = bs.h_cov_contigs.data(); *kmers = bs.h_cov_kmers.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_contig_coverage(gasm_batch* b) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_contig_coverage before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    return pipeline_contig_coverage(b->S().cx, b->build_reads(b->S()), b->S().bs);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, const uint32_t** n_edges) {
+    API_GUARD_BEGIN
+    if (!b || !mult_sum || !n_edges) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_contig_coverage before a build"); return GASM_ERR_STATE; }
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_contig_coverage(b->S().cx, b->build_reads(b->S()), bs));
+    *mult_sum = bs.h_ccov_m.data(); *n_edges = bs.h_ccov_n.data();
     return GASM_OK;
     API_GUARD_END
 }

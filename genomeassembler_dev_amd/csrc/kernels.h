@@ -101,8 +101,8 @@ enum : u32 {
     GASM_FLAG_BYTES = 256,          // size of the area without cursors
     GASM_OVF_TABLE = 1,             // a bucket holds more distinct keys than its table (or, multi-pass, than GASM_BUCKET_MAX)
     GASM_OVF_REGION = 2,            // a bucket outgrew its region of the one-pass partition
-    GASM_OVF_TIP_RANK = 4,          // the LDS list ranking gave up in a tip-clipping or bubble-popping round before the last graph
-                                    // pass (k_tip_mark, k_bubble_mark)
+    GASM_OVF_TIP_RANK = 4,          // the LDS list ranking gave up in a tip-clipping, bubble-popping or low-coverage round before the
+                                    // last graph pass (k_tip_mark, k_bubble_mark, k_lowcov_mark)
 };
 static_assert(GASM_FLAG_ACTIVE + GASM_FLAG_ACTIVE_N <= GASM_FLAG_WORDS && GASM_FLAG_WORDS * 4 == GASM_FLAG_BYTES, "flag area layout");
 // Zeroing contract.  Every attempt at the distinct k-mers starts with all GASM_FLAG_WORDS words zero: the one-pass partition
@@ -113,7 +113,8 @@ static_assert(GASM_FLAG_ACTIVE + GASM_FLAG_ACTIVE_N <= GASM_FLAG_WORDS && GASM_F
 // the report: the ranking's flag, the scorer's flag, k_contig_scan's counter and the active words are zero again.  A build
 // with tip clipping runs a graph pass per round: the gather of each pass also clears the done counter of the compaction
 // (GASM_FLAG_SOLID_DONE) that ran in front of it, and k_tip_mark saves a ranking failure of its pass into the overflow word.
-// The rounds of bubble popping behind them are the same passes with k_bubble_mark in k_tip_mark's place.
+// The rounds of bubble popping behind them are the same passes with k_bubble_mark in k_tip_mark's place, and the low-coverage
+// rounds behind those with k_lowcov_mark.
 
 // The pinned report of a build over S segments (BuildState::h_report, u32 words), written by k_contig_scan's last workgroup,
 // the ticket last: first distinct k-mer, first contig and first contig base (lo, hi) of every segment, each with the total in
@@ -165,6 +166,13 @@ template <class K>
 __global__ void k_bubble_mark(GraphView gv, u32 n_segments, u32 chunks, const u8* eflag, const u32* clen, const u32* nxt, const u32* dk_cnt, const u64* bstart,
                               u32* mult, u32 bubble_len, u32* flags, u32* bubbles);
 __global__ void k_kmer_spectrum(const u32* dstart, u32 nb, const u32* dk_cnt, u32 n_segments, u32 chunks, u32* hist);
+// low-coverage removal (cov_cutoff > 0, cov_len > 0): the same for every short contig whose mean multiplicity is strictly below cov_cutoff
+template <class K>
+__global__ void k_lowcov_mark(GraphView gv, u32 n_segments, u32 chunks, const u8* eflag, const u32* clen, const u32* nxt, const u32* dk_cnt, const u64* bstart,
+                              u32* mult, u32 cov_len, u32 cov_cutoff, u32* flags, u32* removed);
+// per-contig coverage of a finished build: msum[c] += multiplicities, nedges[c] += 1 for every edge of contig c (both zeroed by the caller)
+__global__ void k_contig_cov(const u32* dstart, u32 nb, u32 n_segments, u32 chunks, const u64* link, const u32* e_cid, const u32* dk_cnt,
+                             const u32* seg_cstart, unsigned long long* msum, u32* nedges);
 template <class K>
 __global__ void k_bucket_gather(const K* keys, const u32* mult, const u64* bstart, const u32* dstart, K* dk_key, u32* dk_cnt, u32* claim, u8* eflag,
                                 u32* flags);

@@ -1843,3 +1843,108 @@ __global__ void __launch_bounds__(GASM_WG) k_bubble_mark(GraphView gv, u32 n_seg
 }
 template __global__ void k_bubble_mark<u64>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);
 template __global__ void k_bubble_mark<K128>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32*, u32*);
+
+// ================================================================================================================
+// Low-coverage removal (gasm_batch_build_params, cov_cutoff > 0 and cov_len > 0 only; the rule: include/gasm.h).  No counterpart
+// in the reference; Velvet removes nodes below its -cov_cutoff behind Tour Bus, SPAdes removes low-coverage and isolated edges.
+// What the tip and bubble rounds leave of sequencing errors is short and sits at the multiplicity cutoff: islands, links attached
+// at both ends, the remains of overlapping bubbles.  A contig c of at most cov_len bases goes if its mean multiplicity is
+// strictly below cov_cutoff:
+//   m(c) < cov_cutoff * n(c)      (n = edges, m = sum of the edges' multiplicities; exact in 64 bits: n <= 65535, cutoff < 2^32)
+// with NO test of what is attached to it.  k_lowcov_mark runs on a ranked graph as k_tip_mark and k_bubble_mark do: one thread
+// per head whose contig has at most cov_len bases walks its own chain once (bubble_walk: the sum and the last edge), applies the
+// rule and, for a contig that goes, walks again and zeroes the multiplicities IN THE BUCKET RUNS; k_bucket_solid with
+// min_count = 1 compacts behind it.  It reads the dense arrays only and writes the runs only, so all contigs of a round are found
+// on the same graph.  A contig and its twin have equal n and m: they go in the same round.
+// The guards are k_tip_mark's: a ranking that gave up leaves chain lengths that mean nothing, so every walk is bounded by
+// cov_len (<= GASM_MAX_BUBBLE_LEN) and stays inside the segment's edges, every store is checked against its bucket's run, and
+// the ranking's flag is copied into the overflow word (GASM_OVF_TIP_RANK).
+// removed[seg] += contigs removed.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_lowcov_mark(GraphView gv, u32 n_segments, u32 chunks, const u8* __restrict__ eflag,
+                                                         const u32* __restrict__ clen, const u32* __restrict__ nxt, const u32* __restrict__ dk_cnt,
+                                                         const u64* __restrict__ bstart, u32* __restrict__ mult, u32 cov_len, u32 cov_cutoff,
+                                                         u32* __restrict__ flags, u32* __restrict__ removed) {
+    const K* dk = reinterpret_cast<const K*>(gv.dk_key);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && flags[GASM_FLAG_RANK_FAILED]) atomicOr(&flags[GASM_FLAG_OVERFLOW], (u32)GASM_OVF_TIP_RANK);
+    const u32 nb = 1u << gv.bbits;
+    const u32 kk = (u32)(gv.k - 1);
+    for_seg_edges(gv.dstart, nb, n_segments, chunks, [&](u32 seg, u32 lo, u32 hi, u32 i) {
+        if (!(eflag[i] & 1)) return;
+        const u32 len = clen[i];
+        if (len == 0 || (u64)len + kk > cov_len) return;
+        u64 m;
+        u32 t;
+        if (!bubble_walk(nxt, dk_cnt, lo, hi, i, len, &m, &t)) return;
+        if (m >= (u64)cov_cutoff * (u64)len) return;      // (strict: a mean equal to the cutoff stays)
+        atomicAdd(&removed[seg], 1u);
+        const int low = 2 * gv.k - gv.bbits;
+        u32 x = i;
+        for (u32 s = 0; s < len; ++s) {
+            const u32 gb = seg * nb + (gv.bbits ? kfield(dk[x], low) & (nb - 1) : 0u);
+            const u32 d0 = gv.dstart[gb], d1 = gv.dstart[gb + 1];
+            if (x >= d0 && x < d1) mult[bstart[gb] + (x - d0)] = 0;
+            if (s + 1 < len) x = nxt[x];
+        }
+    });
+}
+template __global__ void k_lowcov_mark<u64>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32, u32*, u32*);
+template __global__ void k_lowcov_mark<K128>(GraphView, u32, u32, const u8*, const u32*, const u32*, const u32*, const u64*, u32*, u32, u32, u32*, u32*);
+
+// ================================================================================================================
+// Per-contig coverage of a finished build (gasm_batch_contig_coverage): for every contig, in the order of the contig list,
+// m = the sum of its edges' multiplicities (u64) and n = its edges (u32).  It reads the build's arrays only.
+// No thread walks a contig: one thread per edge.  link[e] = (head, distance) from the list ranking, e_cid[head] = the contig,
+// and the edge adds dk_cnt[e] to that contig's sum.  An unbranched genome is ONE contig per segment, so one address would take
+// an atomic per edge; the lanes of a wave that hit the same contig are summed first: the first lane still to do names its
+// contig, the lanes with the same contig add up through six xor-shuffles, and the named lane alone issues the two atomics.
+// After GASM_COV_COMBINE such rounds (clean reads need one) whoever is left adds for itself: those are the waves of noisy
+// graphs, whose lanes spread over many short contigs and therefore over many addresses.
+// The trip count of the loop is the workgroup's, so every lane reaches every shuffle.  Edges of isolated cycles (no head)
+// lie in no contig and add nothing.  A head outside the segment's edges or a contig outside the segment's contigs (a
+// build that failed: the host repeats it before this kernel runs) is skipped: every index is checked before it is used.
+// Integer sums into zeroed arrays: exact and independent of the order the waves arrive in.
+// ================================================================================================================
+#define GASM_COV_COMBINE 4
+__global__ void __launch_bounds__(GASM_WG) k_contig_cov(const u32* __restrict__ dstart, u32 nb, u32 n_segments, u32 chunks, const u64* __restrict__ link,
+                                                        const u32* __restrict__ e_cid, const u32* __restrict__ dk_cnt, const u32* __restrict__ seg_cstart,
+                                                        unsigned long long* __restrict__ msum, u32* __restrict__ nedges) {
+    u32 seg, chunk;
+    if (!seg_chunk(n_segments, chunks, &seg, &chunk)) return;
+    const u32 lo = dstart[seg * nb], hi = dstart[(seg + 1) * nb];
+    const u32 c_lo = seg_cstart[seg], c_hi = seg_cstart[seg + 1];
+    const u32 lane = threadIdx.x & 63u;
+    for (u32 base = chunk * GASM_WG; base < hi - lo; base += chunks * GASM_WG) {
+        const u32 i = lo + base + threadIdx.x;
+        u32 c = GASM_NONE32;
+        u64 m = 0;
+        if (i < hi) {
+            const u64 l = link[i];
+            const u32 a = (u32)(l >> 32);
+            if (a != GASM_NONE32 && (l & GASM_LINK_DONE) && a >= lo && a < hi) {
+                const u32 cid = e_cid[a];
+                if (cid >= c_lo && cid < c_hi) { c = cid; m = dk_cnt[i]; }
+            }
+        }
+        u64 todo = __ballot(c != GASM_NONE32);
+        for (int r = 0; r < GASM_COV_COMBINE && todo; ++r) {
+            const u32 leader = (u32)__ffsll((unsigned long long)todo) - 1u;
+            const u32 lc = __shfl(c, leader, 64);
+            const bool mine = c == lc;
+            const u64 same = __ballot(mine);
+            u64 v = mine ? m : 0ull;
+            for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+            if (lane == leader) {
+                atomicAdd(&msum[lc], (unsigned long long)v);
+                atomicAdd(&nedges[lc], (u32)__popcll(same));
+            }
+            if (mine) c = GASM_NONE32;
+            todo &= ~same;
+        }
+        if (c != GASM_NONE32) {
+            atomicAdd(&msum[c], (unsigned long long)m);
+            atomicAdd(&nedges[c], 1u);
+        }
+    }
+}

@@ -97,6 +97,11 @@ struct BuildState {
                                             // clips again, and scores of its graph compare bases
     u32 bubble_len = 0, bubble_rounds = 0;  // bubble popping of this build (gasm_batch_build_bubbles): contigs of at most bubble_len bases,
                                             // for exactly bubble_rounds rounds behind the tip rounds; 0: none.  Kept and repeated like tip_len
+    u32 cov_cutoff = 0, cov_len = 0, cov_rounds = 0;   // low-coverage removal of this build (gasm_batch_build_params): contigs of at most
+                                            // cov_len bases whose mean multiplicity is below cov_cutoff, for exactly cov_rounds rounds behind
+                                            // the bubble rounds; cov_cutoff = 0 or cov_len = 0: none (cov_rounds is 0 then).  Kept and
+                                            // repeated like tip_len
+    bool lowcov() const { return cov_cutoff != 0 && cov_len != 0; }
     std::vector<u64> h_seg_nk;              // k-mers per segment
     // upper bounds the arrays are allocated at, and estimates the grids are sized from (the kernels loop beyond them)
     u64 D_cap = 0, maxD_cap = 0, bases_cap = 0;
@@ -127,6 +132,12 @@ struct BuildState {
     std::vector<u32> h_tip_tips, h_tip_kmers;      // pipeline_fetch_tip_stats: [s * GASM_MAX_TIP_ROUNDS + r]
     DBuf d_bubble_stats;                    // bubble_len > 0: u32[2][GASM_MAX_BUBBLE_ROUNDS][S], contigs then k-mers popped per round and segment
     std::vector<u32> h_bubble_bubbles, h_bubble_kmers;   // pipeline_fetch_bubble_stats: [s * GASM_MAX_BUBBLE_ROUNDS + r]
+    DBuf d_cov_stats;                       // lowcov(): u32[2][GASM_MAX_COV_ROUNDS][S], contigs then k-mers removed per round and segment
+    std::vector<u32> h_cov_contigs, h_cov_kmers;         // pipeline_fetch_lowcov_stats: [s * GASM_MAX_COV_ROUNDS + r]
+    DBuf d_ccov;                            // per-contig coverage of the last build (u64 sums[P], then u32 edges[P]: pipeline_contig_coverage)
+    std::vector<u64> h_ccov_m;
+    std::vector<u32> h_ccov_n;
+    bool coverage_queued = false;           // k_contig_cov ran on the arrays of this build
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -192,8 +203,10 @@ struct ScoreState {
 // lengths, k_tip_mark and a compaction of the buckets' runs; the last graph pass alone writes the report.  0: not a launch more
 // bubble_len > 0 (<= GASM_MAX_BUBBLE_LEN): bubble_rounds (1 .. GASM_MAX_BUBBLE_ROUNDS) rounds of bubble popping behind the tip rounds,
 // the same passes with k_bubble_mark as the marking kernel.  0: not a launch more
+// cov_cutoff > 0 and cov_len > 0 (<= GASM_MAX_BUBBLE_LEN): cov_rounds (1 .. GASM_MAX_COV_ROUNDS) rounds of low-coverage removal behind the
+// bubble rounds, the same passes with k_lowcov_mark as the marking kernel.  Either 0: not a launch more
 int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1, u32 strands = 1, u32 tip_len = 0,
-                   u32 tip_rounds = 0, u32 bubble_len = 0, u32 bubble_rounds = 0);
+                   u32 tip_rounds = 0, u32 bubble_len = 0, u32 bubble_rounds = 0, u32 cov_cutoff = 0, u32 cov_len = 0, u32 cov_rounds = 0);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
 // The overflow retry ladder of every build path: after an attempt raised the GASM_OVF_* bits `ovf`, advance the configuration by
@@ -216,6 +229,12 @@ int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_tip_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // contigs and k-mers popped per segment and round of the finished build (zero for rounds not run and for bubble_len = 0)
 int pipeline_fetch_bubble_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// contigs and k-mers removed for low coverage per segment and round of the finished build (zero for rounds not run and with the feature off)
+int pipeline_fetch_lowcov_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// per-contig sum of multiplicities and number of edges of the finished build: queue (k_contig_cov, reads the build's arrays only), then
+// fetch h_ccov_m / h_ccov_n, one entry per contig in the order of the contig list
+int pipeline_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

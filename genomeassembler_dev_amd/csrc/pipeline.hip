@@ -468,7 +468,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_bubble_stats, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_bubble_stats, &d_cov_stats, &d_ccov, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -714,20 +714,27 @@ static int alloc_graph(BuildState& bs, u32 S) {
 // between rounds, and only the last pass's k_contig_scan publishes the report.
 // Bubble popping (bs.bubble_len > 0) adds bubble_rounds such rounds behind the tip rounds, with k_bubble_mark as the marking
 // kernel: tip_rounds + bubble_rounds + 1 passes in all.  (Tips first: a tip that hangs on a bubble's branch splits it.)
+// Low-coverage removal (bs.lowcov()) adds cov_rounds such rounds behind all of those, with k_lowcov_mark as the marking kernel:
+// tip_rounds + bubble_rounds + cov_rounds + 1 passes in all.
 int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
     const int W = bs.words, bbits = bs.bbits;
     const u32 nb = 1u << bbits, nbt = S * nb;
     GCHK(alloc_graph(bs, S));
     u32* const d_claim = bs.d_nxt.as<u32>();      // claim words of the degree kernels live in nxt until k_edge_next overwrites them
     const u32 tip_rounds = bs.tip_len ? bs.tip_rounds : 0;
-    const u32 rounds = tip_rounds + (bs.bubble_len ? bs.bubble_rounds : 0);
+    const u32 pop_rounds = tip_rounds + (bs.bubble_len ? bs.bubble_rounds : 0);
+    const u32 rounds = pop_rounds + (bs.lowcov() ? bs.cov_rounds : 0);
     if (tip_rounds) {
         GCHK(bs.d_tip_stats.ensure((size_t)2 * GASM_MAX_TIP_ROUNDS * S * 4));
         HIPCHK(hipMemsetAsync(bs.d_tip_stats.p, 0, (size_t)2 * GASM_MAX_TIP_ROUNDS * S * 4, ctx->stream));
     }
-    if (rounds > tip_rounds) {
+    if (pop_rounds > tip_rounds) {
         GCHK(bs.d_bubble_stats.ensure((size_t)2 * GASM_MAX_BUBBLE_ROUNDS * S * 4));
         HIPCHK(hipMemsetAsync(bs.d_bubble_stats.p, 0, (size_t)2 * GASM_MAX_BUBBLE_ROUNDS * S * 4, ctx->stream));
+    }
+    if (rounds > pop_rounds) {
+        GCHK(bs.d_cov_stats.ensure((size_t)2 * GASM_MAX_COV_ROUNDS * S * 4));
+        HIPCHK(hipMemsetAsync(bs.d_cov_stats.p, 0, (size_t)2 * GASM_MAX_COV_ROUNDS * S * 4, ctx->stream));
     }
     for (u32 r = 0; r <= rounds; ++r) {
         GLAUNCH_K(ctx, W, "k_bucket_gather", k_bucket_gather<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(),
@@ -735,7 +742,7 @@ int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
         GCHK(launch_graph_dense(ctx, S, bs, r == rounds));
         if (r == rounds) break;
         const bool tips = r < tip_rounds;
-        GasmRange range(tips ? "gasm:tips (mark, compact)" : "gasm:bubbles (mark, compact)");
+        GasmRange range(tips ? "gasm:tips (mark, compact)" : r < pop_rounds ? "gasm:bubbles (mark, compact)" : "gasm:lowcov (mark, compact)");
         const u32 est = std::max<u32>(1, (u32)std::min<u64>(bs.maxD_est, bs.maxD_cap));
         const u32 dchunks = (u32)ceil_div_u64(est, GASM_WG);
         u32* d_kmers;
@@ -744,13 +751,20 @@ int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
             d_kmers = bs.d_tip_stats.as<u32>() + ((size_t)GASM_MAX_TIP_ROUNDS + r) * S;
             GLAUNCH_K(ctx, W, "k_tip_mark", k_tip_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(), bs.d_clen.as<u32>(),
                       bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.tip_len, bs.d_flags.as<u32>(), d_tips);
-        } else {
+        } else if (r < pop_rounds) {
             const u32 br = r - tip_rounds;
             u32* const d_bubbles = bs.d_bubble_stats.as<u32>() + (size_t)br * S;
             d_kmers = bs.d_bubble_stats.as<u32>() + ((size_t)GASM_MAX_BUBBLE_ROUNDS + br) * S;
             GLAUNCH_K(ctx, W, "k_bubble_mark", k_bubble_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(),
                       bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.bubble_len,
                       bs.d_flags.as<u32>(), d_bubbles);
+        } else {
+            const u32 cr = r - pop_rounds;
+            u32* const d_removed = bs.d_cov_stats.as<u32>() + (size_t)cr * S;
+            d_kmers = bs.d_cov_stats.as<u32>() + ((size_t)GASM_MAX_COV_ROUNDS + cr) * S;
+            GLAUNCH_K(ctx, W, "k_lowcov_mark", k_lowcov_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(),
+                      bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.cov_len, bs.cov_cutoff,
+                      bs.d_flags.as<u32>(), d_removed);
         }
         // (the done word is zero: the gather of this pass cleared it behind the cutoff's or the last round's compaction)
         u32* const d_scan_out = bs.scan_in_dedup ? bs.d_dstart.as<u32>() : nullptr;
@@ -761,8 +775,8 @@ int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
     return GASM_OK;
 }
 
-// last_pass = false (a tip-clipping or bubble-popping round): stops behind the chains' lengths — eflag, nxt and clen are what
-// k_tip_mark and k_bubble_mark read
+// last_pass = false (a tip-clipping, bubble-popping or low-coverage round): stops behind the chains' lengths — eflag, nxt and clen
+// are what k_tip_mark, k_bubble_mark and k_lowcov_mark read
 static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs, bool last_pass) {
     GasmRange range("gasm:graph (degrees, list ranking, contigs)");
     const int W = bs.words;
@@ -916,12 +930,14 @@ static void zero_results(BuildState& bs, u32 S) {
 }
 
 int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count, u32 strands, u32 tip_len, u32 tip_rounds, u32 bubble_len,
-                   u32 bubble_rounds) {
+                   u32 bubble_rounds, u32 cov_cutoff, u32 cov_len, u32 cov_rounds) {
     if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
     if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
     if (strands == 2 && !rd.strands_of) { gasm_set_error("a both-strand build needs the both-strand reads"); return GASM_ERR_STATE; }
     // (the bound of every walk of k_bubble_mark, and what keeps its products inside 64 bits)
     if (bubble_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("bubble_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, bubble_len); return GASM_ERR_INVALID; }
+    // (the same bound and the same two reasons for k_lowcov_mark)
+    if (cov_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("cov_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, cov_len); return GASM_ERR_INVALID; }
     // (both strands: up to twice the distinct k-mers of the genome; without a hint the estimate follows the doubled k-mer count)
     GCHK(plan_build(ctx, rd, k, strands == 2 ? 2 * hint : hint, bs));
     bs.min_count = min_count;
@@ -930,8 +946,12 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs,
     bs.tip_rounds = tip_len ? tip_rounds : 0;
     bs.bubble_len = bubble_len;
     bs.bubble_rounds = bubble_len ? bubble_rounds : 0;
+    bs.cov_cutoff = cov_cutoff;
+    bs.cov_len = cov_len;
+    bs.cov_rounds = cov_cutoff && cov_len ? cov_rounds : 0;
     bs.fetched_twins = false;
     bs.spectrum_queued = false;
+    bs.coverage_queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -995,9 +1015,9 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
         } else {
             bs.rank_global = true;        // whole-GPU pointer doubling instead of the LDS ranking
             ++bs.attempts_graph;
-            // a clipped or popped build has compacted its runs round by round: a repeat of the graph alone would start from what the rounds
+            // a clipped, popped or low-coverage-filtered build has compacted its runs round by round: a repeat of the graph alone would start from what the rounds
             // so far left and count them twice.  It starts over from the reads (same configuration, so the same k-mer set)
-            if ((bs.tip_len || bs.bubble_len) && rd) { ++bs.attempts_distinct; GCHK(launch_distinct(ctx, *rd, bs)); }
+            if ((bs.tip_len || bs.bubble_len || bs.lowcov()) && rd) { ++bs.attempts_distinct; GCHK(launch_distinct(ctx, *rd, bs)); }
         }
         GCHK(launch_graph(ctx, S, bs));
     }
@@ -1080,6 +1100,18 @@ int pipeline_fetch_bubble_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     return GASM_OK;
 }
 
+int pipeline_fetch_lowcov_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    const u32 S = rd.n_segments, R = GASM_MAX_COV_ROUNDS;
+    bs.h_cov_contigs.assign((size_t)S * R, 0); bs.h_cov_kmers.assign((size_t)S * R, 0);
+    if (!bs.lowcov() || !bs.n_kmers) return GASM_OK;         // (a build without k-mers launched nothing)
+    std::vector<u32> h((size_t)2 * R * S);
+    GCHK(d2h_sync(ctx, h.data(), bs.d_cov_stats.p, h.size() * 4));
+    for (u32 s = 0; s < S; ++s)
+        for (u32 r = 0; r < R; ++r) { bs.h_cov_contigs[(size_t)s * R + r] = h[(size_t)r * S + s]; bs.h_cov_kmers[(size_t)s * R + r] = h[((size_t)R + r) * S + s]; }
+    return GASM_OK;
+}
+
 int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
     const u32 S = rd.n_segments;
@@ -1087,13 +1119,16 @@ int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     // (a build without k-mers launched nothing, and min_count = 1 removed nothing)
     if (bs.min_count > 1 && bs.n_kmers) GCHK(d2h_sync(ctx, removed.data(), bs.d_solid_removed.p, (size_t)S * 4));
     bs.h_solid_before.resize(S); bs.h_solid_after.resize(S);
-    // (the tips clipped and the bubbles popped behind the cutoff are not the cutoff's: they count as survivors here)
+    // (the tips clipped, the bubbles popped and the low-coverage contigs removed behind the cutoff are not the cutoff's: they count as
+    // survivors here)
     if (bs.tip_len) GCHK(pipeline_fetch_tip_stats(ctx, rd, bs));
     if (bs.bubble_len) GCHK(pipeline_fetch_bubble_stats(ctx, rd, bs));
+    if (bs.lowcov()) GCHK(pipeline_fetch_lowcov_stats(ctx, rd, bs));
     for (u32 s = 0; s < S; ++s) {
         bs.h_solid_after[s] = bs.h_dstart.empty() ? 0 : bs.h_dstart[s + 1] - bs.h_dstart[s];
         if (bs.tip_len) for (u32 r = 0; r < GASM_MAX_TIP_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_tip_kmers[(size_t)s * GASM_MAX_TIP_ROUNDS + r];
         if (bs.bubble_len) for (u32 r = 0; r < GASM_MAX_BUBBLE_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_bubble_kmers[(size_t)s * GASM_MAX_BUBBLE_ROUNDS + r];
+        if (bs.lowcov()) for (u32 r = 0; r < GASM_MAX_COV_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_cov_kmers[(size_t)s * GASM_MAX_COV_ROUNDS + r];
         bs.h_solid_before[s] = bs.h_solid_after[s] + removed[s];
     }
     return GASM_OK;
@@ -1112,6 +1147,36 @@ int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
                 bs.d_spectrum.as<u32>());
     }
     bs.spectrum_queued = true;
+    return GASM_OK;
+}
+
+// per-contig coverage: on the stream of the build, behind it; reads dstart, the ranking's links, the contig ids and dk_cnt, writes an
+// array of its own (u64 sums[P], then u32 edges[P])
+int pipeline_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 S = rd.n_segments, P = bs.n_contigs;
+    if (P && bs.d_total) {
+        GCHK(bs.d_ccov.ensure((size_t)P * 12));
+        HIPCHK(hipMemsetAsync(bs.d_ccov.p, 0, (size_t)P * 12, ctx->stream));
+        const u32 chunks = std::max(1u, (u32)ceil_div_u64(bs.maxD_est, GASM_WG));
+        GLAUNCH(ctx, "k_contig_cov", k_contig_cov, seg_grid(chunks, S), dim3(GASM_WG), 0, bs.d_dstart.as<u32>(), 1u << bs.bbits, S, chunks, bs.d_link.as<u64>(),
+                bs.d_ecid.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_seg_cstart.as<u32>(), reinterpret_cast<unsigned long long*>(bs.d_ccov.as<u64>()),
+                reinterpret_cast<u32*>(bs.d_ccov.as<u64>() + P));
+    }
+    bs.coverage_queued = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    if (!bs.coverage_queued) { gasm_set_error("gasm_batch_fetch_contig_coverage before gasm_batch_contig_coverage (of the last build)"); return GASM_ERR_STATE; }
+    const u32 P = bs.n_contigs;
+    bs.h_ccov_m.assign(P, 0); bs.h_ccov_n.assign(P, 0);
+    if (P && bs.d_total) {
+        HIPCHK(hipMemcpyAsync(bs.h_ccov_m.data(), bs.d_ccov.p, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_ccov_n.data(), bs.d_ccov.as<u64>() + P, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return GASM_OK;
 }
 
@@ -1493,7 +1558,7 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     // a mismatch raises GASM_FLAG_SCORE_MISMATCH of the build and pipeline_score_fetch refuses the scores
     // A graph built with a multiplicity cutoff does not hold every k-mer of every read: the comparison is then part of the match
     // (verify = 2: a mismatch is "no match" and raises nothing)
-    const int verify = (graph.min_count > 1 || graph.tip_len || graph.bubble_len) ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
+    const int verify = (graph.min_count > 1 || graph.tip_len || graph.bubble_len || graph.lowcov()) ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
     ss.verify = verify == 1;
     const u32 reads_per_wg = 256;     // one read per thread: the match is a chain of dependent loads
     const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);

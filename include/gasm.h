@@ -99,6 +99,24 @@ int gasm_get_contigs_from_reads_tips(gasm_ctx* ctx, const char* reads, const uin
 int gasm_get_contigs_from_reads_bubbles(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                         int matrix_rows, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
                                         uint32_t bubble_len, uint32_t bubble_rounds, gasm_contigs** out);
+/* The positional chain build -> _solid -> _strands -> _tips -> _bubbles ends here: every knob of a build in one struct, for this entry and
+ * for gasm_batch_build_params below.  size must be sizeof(gasm_build_params), else GASM_ERR_INVALID (a caller compiled against another
+ * header).  Zeroed optional fields mean the defaults of the positional entries: min_count 0 -> 1, strands 0 -> 1, tip_len = 0 no
+ * clipping, bubble_len = 0 no popping, cov_cutoff = 0 or cov_len = 0 no low-coverage removal (the rounds of a feature that is off
+ * are not read).  genome_len_hint is read by gasm_batch_build_params only. */
+typedef struct gasm_build_params {
+    uint32_t size;
+    int32_t  k;
+    uint64_t genome_len_hint;
+    uint32_t min_count, strands;
+    uint32_t tip_len, tip_rounds;
+    uint32_t bubble_len, bubble_rounds;
+    uint32_t cov_cutoff, cov_len, cov_rounds;
+} gasm_build_params;
+/* The same with everything gasm_build_params holds (gasm_batch_build_params below): with cov_cutoff = 0 or cov_len = 0 it is
+ * gasm_get_contigs_from_reads_bubbles with the struct's other fields; params->k is the dbg_kmer of the other entries. */
+int gasm_get_contigs_from_reads_params(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int seed, int matrix_rows,
+                                       const gasm_build_params* params, gasm_contigs** out);
 uint64_t gasm_contigs_count(const gasm_contigs* c);
 const char* gasm_contigs_data(const gasm_contigs* c);
 const uint64_t* gasm_contigs_offsets(const gasm_contigs* c);       /* count+1 */
@@ -311,7 +329,8 @@ int gasm_batch_score(gasm_batch* b, int kmer, const double* table);
  * (after a build with tip clipping, below, distinct_after still counts the survivors of the CUTOFF: the k-mers of
  * gasm_batch_fetch_distinct are distinct_after minus the segment's clipped k-mers of gasm_batch_fetch_tip_stats)
  * (the same after a build with bubble popping, further below: distinct_after adds back the popped k-mers of
- * gasm_batch_fetch_bubble_stats as it adds back the clipped ones)
+ * gasm_batch_fetch_bubble_stats as it adds back the clipped ones; and after a build with low-coverage removal, below that: the removed
+ * k-mers of gasm_batch_fetch_lowcov_stats)
  * genome_len_hint for noisy reads: it sizes the buckets for the distinct k-mers BEFORE the cutoff, and reads with errors hold
  * 5-10x more of them than their genome: about genome length + bases in the segment's reads x error rate x k (every wrong base
  * makes up to k new k-mers).  A smaller hint (the genome length alone) is still correct: the tables overflow, the build repeats
@@ -359,6 +378,7 @@ int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist /* n_seg
  *                                 Host copy, valid until the next build.  GASM_ERR_STATE before a build or after a strands = 1
  *                                 build; GASM_ERR_INTERNAL if a contig has no twin (the closure above would be broken).
  * Pooled builds (gasm_pool_*) are forward-strand only and clip no tips (below).  They pop no bubbles either (further below).
+ * They remove no low-coverage contigs (below that).
  * ---------------------------------------------------------------------------------------------------------------- */
 int gasm_batch_build_strands(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands);
 uint32_t gasm_batch_strands(const gasm_batch* b);
@@ -400,7 +420,7 @@ int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin);
  * gasm_batch_fetch_tip_stats    tips[s * GASM_MAX_TIP_ROUNDS + r] = contigs clipped in segment s, round r; kmers[...] = k-mers
  *                               clipped, same index; rounds not run are 0.  Host copies, valid until the next call or build.
  *                               GASM_ERR_STATE before a build or after a build with tip_len == 0.
- * Pooled builds (gasm_pool_*) do not clip.
+ * Pooled builds (gasm_pool_*) do not clip.  They do not remove low-coverage contigs either.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define GASM_MAX_TIP_ROUNDS 8
 int gasm_batch_build_tips(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands,
@@ -450,7 +470,7 @@ int gasm_batch_fetch_tip_stats(gasm_batch* b, const uint32_t** tips, const uint3
  * gasm_batch_fetch_bubble_stats bubbles[s * GASM_MAX_BUBBLE_ROUNDS + r] = contigs popped in segment s, round r; kmers[...] =
  *                               k-mers popped, same index; rounds not run are 0.  Host copies, valid until the next call or
  *                               build.  GASM_ERR_STATE before a build or after a build with bubble_len == 0.
- * Pooled builds (gasm_pool_*) pop no bubbles.
+ * Pooled builds (gasm_pool_*) pop no bubbles.  They remove no low-coverage contigs either.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define GASM_MAX_BUBBLE_ROUNDS 8
 #define GASM_MAX_BUBBLE_LEN 65535
@@ -459,6 +479,63 @@ int gasm_batch_build_bubbles(gasm_batch* b, int k, uint64_t genome_len_hint, uin
 uint32_t gasm_batch_bubble_len(const gasm_batch* b);   /* of the last build; 0: none */
 uint32_t gasm_batch_bubble_rounds(const gasm_batch* b);
 int gasm_batch_fetch_bubble_stats(gasm_batch* b, const uint32_t** bubbles, const uint32_t** kmers);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Low-coverage removal: short contigs of low mean multiplicity leave the k-mer set before the contigs are cut; and the per-contig
+ * coverage such a cutoff is chosen from.  (No counterpart in the reference; Velvet removes nodes below its per-node -cov_cutoff behind
+ * Tour Bus and prints every contig's coverage in its name, SPAdes removes low-coverage and isolated edges.  cov_cutoff = 0 is the
+ * default everywhere.)
+ * What the cutoff, the tip rounds and the bubble rounds leave of sequencing errors is short and sits at the cutoff: ISLANDS (short false
+ * contigs seen exactly min_count times with nothing attached at either end: "not a tip and stays", above), the remains of OVERLAPPING
+ * BUBBLES (the bubble rule's stated limit) and of tied tips, and chimeric links attached at both ends.  Each one that hangs on the true
+ * path makes its junction a branching node and cuts the true contig there.  True contigs sit at the coverage of the reads, far above.
+ * gasm_batch_build_params removes such contigs from the k-mer set that the cutoff, the tip rounds and the bubble rounds left, for exactly
+ * cov_rounds rounds; everything else is made from what is left.
+ * The rule, on the same graph as the tip and the bubble rule (edges = distinct k-mers with their multiplicities, nodes = (k-1)-mers,
+ * contigs = what the build would cut).  For a contig c let n(c) = its edges, m(c) = the sum of its edges' multiplicities,
+ * len(c) = n(c) + k - 1 bases.  One round, on the current set:
+ *   c is REMOVED if len(c) <= cov_len and m(c) < cov_cutoff * n(c), compared exactly in 64-bit integers: a mean multiplicity STRICTLY
+ *   below cov_cutoff.  A mean equal to cov_cutoff stays.
+ *   There is NO attachment test: islands, links attached at both ends and the remains of overlapping bubbles all go.
+ *   All contigs of a round are found on the same graph and leave together, with all their k-mers (a k-mer lies in at most one
+ *   contig); the next round starts from the remaining set.
+ * A build runs exactly cov_rounds rounds, queued as a whole with no host wait, AFTER all tip rounds and all bubble rounds.
+ * With strands = 2 a contig and its twin have equal n and m: they go in the same round, the contigs stay closed under reverse
+ * complement and gasm_batch_fetch_contig_twins keeps working.
+ * cov_cutoff = 0 or cov_len = 0 switches the feature off.  cov_cutoff <= min_count can match nothing and is allowed (every multiplicity
+ * is at least min_count).  cov_len <= GASM_MAX_BUBBLE_LEN for the two reasons given for bubble_len: it keeps cov_cutoff * n inside 64 bits
+ * and bounds a GPU thread's walk (in every round one thread per short contig walks its own chain, edge by edge).  The intended setting
+ * is cov_len = 2k - 1, cov_cutoff = min_count + 1, one round.
+ * STATED LIMITS: a TRUE stretch that is short and thinly covered goes too — the rule cannot tell it from an error.  And once the junk is
+ * gone new tips can appear (a tip that was tied with a junk contig, say); this build does not clip again: a second pass of tip and
+ * bubble rounds behind the low-coverage rounds is not made.
+ * Everything behind the build — contigs, gasm_batch_fetch_distinct / _graph, the k-mer spectrum, twins, scores under one or several
+ * tables, the guided traversal — sees what is left with its true multiplicities.  A read scores on a contig iff it is a substring of
+ * it: a read that holds a removed k-mer adds nothing.
+ * gasm_batch_build_params       the struct form of gasm_batch_build_bubbles plus cov_cutoff, cov_len, cov_rounds (gasm_build_params, above).
+ *                               With cov_cutoff == 0 or cov_len == 0 it is gasm_batch_build_bubbles with the struct's other fields: same
+ *                               host path, same kernel launches, cov_rounds is not read.  Otherwise cov_len <= GASM_MAX_BUBBLE_LEN and
+ *                               cov_rounds in 1..GASM_MAX_COV_ROUNDS, else GASM_ERR_INVALID.  Each step slot remembers the three values
+ *                               of the build it holds.
+ * gasm_batch_cov_cutoff / _cov_len / _cov_rounds   of the last build (cov_rounds 0: no removal, or no build yet).
+ * gasm_batch_fetch_lowcov_stats contigs[s * GASM_MAX_COV_ROUNDS + r] = contigs removed in segment s, round r; kmers[...] = k-mers
+ *                               removed, same index; rounds not run are 0.  Host copies, valid until the next call or build.
+ *                               GASM_ERR_STATE before a build or after a build with the feature off.
+ * gasm_batch_contig_coverage    queues the per-contig coverage of the last build's contigs (as the build left them, whatever it removed);
+ *                               GASM_ERR_STATE before a build.  It reads the build's arrays only and changes no build or score result.
+ * gasm_batch_fetch_contig_coverage   mult_sum[c] = m(c), n_edges[c] = n(c), one entry per contig in the order of
+ *                               gasm_batch_fetch_contigs; m(c) / n(c) is the contig's mean multiplicity (Velvet's "cov").  Integer sums:
+ *                               exact.  Host copies, valid until the next call or build.  GASM_ERR_STATE before a build or without a
+ *                               coverage pass over the last build.
+ * Pooled builds (gasm_pool_*) remove no low-coverage contigs.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAX_COV_ROUNDS 8
+int gasm_batch_build_params(gasm_batch* b, const gasm_build_params* params);
+uint32_t gasm_batch_cov_cutoff(const gasm_batch* b);   /* of the last build */
+uint32_t gasm_batch_cov_len(const gasm_batch* b);
+uint32_t gasm_batch_cov_rounds(const gasm_batch* b);   /* 0: none */
+int gasm_batch_fetch_lowcov_stats(gasm_batch* b, const uint32_t** contigs, const uint32_t** kmers);
+int gasm_batch_contig_coverage(gasm_batch* b);
+int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, const uint32_t** n_edges);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
@@ -513,7 +590,8 @@ int gasm_count_read_kmers(gasm_ctx* ctx, const char* reads, const uint64_t* read
  * the bucket lists both sides derive from the ownership function.  Results do not depend on the number of ranks.
  *
  *   (pooled builds take their k-mers forward-strand only: there is no strands argument here; they do not clip tips either:
- *   there is no tip_len argument; and they pop no bubbles: there is no bubble_len argument)
+ *   there is no tip_len argument; and they pop no bubbles: there is no bubble_len argument; and they remove no low-coverage contigs:
+ *   there is no cov_cutoff argument)
  *   gasm_pool_create       this rank's reads (fixed length) of ALL n_segments segments
  *   gasm_pool_local_runs   k-mers of those reads -> one sorted run of distinct (key, count) per bucket; bucket index =
  *                          segment << bbits | first bbits bits of the k-mer; run_len (host, n_segments << bbits entries)
