@@ -451,3 +451,19 @@ def coverage_percent(starts, lens, seq_len, ctx=None):
     out = C.c_double()
     check(lib().gasm_coverage_percent(ctx.h, _ptr(a), _ptr(b), len(a), int(seq_len), C.byref(out)))
     return out.value
+
+
+def correct_reads(reads, k, min_count=2, strands=1, ctx=None):
+    """the reads (a list of str: one segment) with their substitution errors repaired against their own solid k-mers: build(k,
+    min_count, strands), SegmentBatch.correct_reads(), fetch.  Returns a list of str of the same lengths in the same order; a read the
+    rule cannot repair comes back as it was (the rule and its limits: include/gasm.h "Read correction")."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        c = b.build(int(k), min_count=min_count, strands=strands).correct_reads()
+        try:
+            return c.read_strings()
+        finally:
+            c.close()
+    finally:
+        b.close()

@@ -7,7 +7,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_bubbles, _check_lowcov, _check_tips, unpack_kmers
 
 
@@ -327,6 +327,42 @@ class SegmentBatch:
         if getattr(self, "_rkc", None) is None:
             self.count_read_kmers()
         return self._rkc[segment, readkmers.table_slice(kmer)]
+
+    def correct_reads(self):
+        """a new SegmentBatch of the same context and layout whose reads are this batch's reads with their substitution errors repaired
+        against the distinct k-mers of the last build (gasm_batch_correct_reads; the rule: include/gasm.h "Read correction"): a run of
+        weak k-mers that one changed base explains in exactly one way is fixed, everything else is copied.  This batch, its build and
+        its scores are untouched; the new batch has no build yet.  correction_stats() of the NEW batch tells what happened."""
+        h = C.c_void_p()
+        check(lib().gasm_batch_correct_reads(self.h, C.byref(h)))
+        new = SegmentBatch.__new__(SegmentBatch)
+        new.ctx, new.h, new.k, new._table = self.ctx, h, None, None
+        new.n_segments, new.n_reads = self.n_segments, int(lib().gasm_batch_total_reads(h))
+        return new
+
+    def correction_stats(self, as_dict=False):
+        """of a batch that correct_reads() returned: (n_segments, 6) uint32, the columns in the order of _lib.CORRECT_FIELDS (reads
+        without a k-mer, clean, corrected, partly corrected, left; bases changed); as_dict: a dict of the columns by those names"""
+        p = C.c_void_p()
+        check(lib().gasm_batch_fetch_correct_stats(self.h, C.byref(p)))
+        n = self.n_segments * len(CORRECT_FIELDS)
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(self.n_segments, len(CORRECT_FIELDS))
+        return {name: a[:, i] for i, name in enumerate(CORRECT_FIELDS)} if as_dict else a
+
+    def reads(self):
+        """(uint8 array of the batch's reads as ASCII, back to back; read_off uint64[n_reads + 1]) (gasm_batch_fetch_reads)"""
+        d, o = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_reads(self.h, C.byref(d), C.byref(o)))
+        off = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(self.n_reads + 1,)).copy()
+        total = int(off[-1])
+        data = np.frombuffer(C.string_at(d, total), dtype=np.uint8).copy() if total else np.zeros(0, np.uint8)
+        return data, off
+
+    def read_strings(self):
+        """the reads as one list of str, in the batch's order (segment after segment)"""
+        data, off = self.reads()
+        raw = data.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])].decode() for i in range(self.n_reads)]
 
     def total_kmers(self):
         return int(lib().gasm_batch_total_kmers(self.h))

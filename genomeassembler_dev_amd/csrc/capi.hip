@@ -99,6 +99,13 @@ struct gasm_batch {
     bool rkc_checked = false;               // read_kmer_windows_check passed (the reads never change)
     bool rkc_counted = false;
     std::vector<u32> h_rkc;
+    // a batch made by gasm_batch_correct_reads: the correction's counters, GASM_CORRECT_FIELDS per segment
+    DBuf d_correct;
+    bool corrected = false;
+    std::vector<u32> h_correct;
+    // gasm_batch_fetch_reads: the reads as ASCII and their offsets
+    std::vector<char> h_reads_ascii;
+    std::vector<u64> h_reads_off;
 };
 
 // the last gasm_batch_score or gasm_batch_score_tables on slot x
@@ -855,7 +862,7 @@ void gasm_batch_free(gasm_batch* b) {
     (void)hipSetDevice(b->ctx->device);
     (void)hipStreamSynchronize(b->ctx->stream);
     for (StepSlot& x : b->slot) { if (x.cx && x.cx != b->ctx) (void)hipStreamSynchronize(x.cx->stream); x.bs.release(); x.dp.release(); x.ss.release(); }
-    b->rd.release(); b->rd2.release(); b->guided.release(); b->d_rkc.release();
+    b->rd.release(); b->rd2.release(); b->guided.release(); b->d_rkc.release(); b->d_correct.release();
     for (ScoreTable& t : b->tb) t.release();
     delete b;
 }
@@ -1200,6 +1207,53 @@ int gasm_batch_fetch_read_kmer_counts(gasm_batch* b, const uint32_t** counts) {
     HIPCHK(hipMemcpyAsync(b->h_rkc.data(), b->d_rkc.p, b->h_rkc.size() * 4, hipMemcpyDeviceToHost, b->ctx->stream));
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
     *counts = b->h_rkc.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+// ---- read correction (kernels_correct.hip; the rule: include/gasm.h "Read correction")
+int gasm_batch_correct_reads(gasm_batch* b, gasm_batch** out) {
+    API_GUARD_BEGIN
+    if (!b || !out) { gasm_set_error("gasm_batch_correct_reads: null argument"); return GASM_ERR_INVALID; }
+    *out = nullptr;
+    if (!b->built) { gasm_set_error("gasm_batch_correct_reads before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    StepSlot& x = b->S();
+    // on the stream of the slot that holds the build, behind it; always the batch's own reads (a strands = 2 build's k-mer set holds
+    // both orientations already)
+    DBuf words, stats;
+    struct Rel { DBuf &a, &b; ~Rel() { a.release(); b.release(); } } rel{words, stats};
+    GCHK(pipeline_correct_reads(x.cx, b->rd, x.bs, words, stats));
+    HIPCHK(hipStreamSynchronize(x.cx->stream));
+    const DevReads& rd = b->rd;
+    return new_batch(b->ctx, b->n_segments, rd.n_reads, out, [&](gasm_batch* nb) {
+        GCHK(nb->rd.adopt_packed(b->ctx, words, rd.fixed_len ? nullptr : rd.h_read_off.data(), rd.n_reads, rd.fixed_len, rd.h_seg_read_off.data(), rd.n_segments));
+        std::swap(nb->d_correct, stats);
+        nb->corrected = true;
+        return (int)GASM_OK;
+    });
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_correct_stats(gasm_batch* b, const uint32_t** stats) {
+    API_GUARD_BEGIN
+    if (!b || !stats) { gasm_set_error("gasm_batch_fetch_correct_stats: null argument"); return GASM_ERR_INVALID; }
+    if (!b->corrected) { gasm_set_error("gasm_batch_fetch_correct_stats: not a batch made by gasm_batch_correct_reads"); return GASM_ERR_STATE; }
+    b->h_correct.resize((size_t)b->n_segments * GASM_CORRECT_FIELDS);
+    HIPCHK(hipSetDevice(b->ctx->device));
+    HIPCHK(hipMemcpyAsync(b->h_correct.data(), b->d_correct.p, b->h_correct.size() * 4, hipMemcpyDeviceToHost, b->ctx->stream));
+    HIPCHK(hipStreamSynchronize(b->ctx->stream));
+    *stats = b->h_correct.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_reads(gasm_batch* b, const char** ascii, const uint64_t** read_off) {
+    API_GUARD_BEGIN
+    if (!b || !ascii || !read_off) { gasm_set_error("gasm_batch_fetch_reads: null argument"); return GASM_ERR_INVALID; }
+    GCHK(pipeline_fetch_reads(b->ctx, b->rd, b->h_reads_ascii, b->h_reads_off));
+    *ascii = b->h_reads_ascii.data();
+    *read_off = b->h_reads_off.data();
     return GASM_OK;
     API_GUARD_END
 }

@@ -240,6 +240,13 @@ __global__ void k_sim_extract(const u64* gwords, const u64* gbase, const u64* se
 template <int LS>
 __global__ void k_read_kmer_count(const u64* words, const u64* read_off, const u64* seg_read_off, u32 fixed_len, u32 n_segments, u32* out);
 
+// ---- kernels_correct.hip: read correction against the distinct k-mers of a finished build (include/gasm.h, "Read correction")
+#define GASM_CORRECT_STATS 6          // = GASM_CORRECT_FIELDS of include/gasm.h (checked in pipeline.hip)
+#define GASM_CORRECT_KMER_CAP 4096    // = GASM_CORRECT_MAX_KMERS: k-mers of a read whose weak bits one wave keeps (64 lanes x 64 bits)
+// out_words: a copy of rs.words that receives the fixes; stats: GASM_CORRECT_STATS zeroed counters per segment
+template <class K>
+__global__ void k_read_correct(ReadSet rs, GraphView gv, int have_graph, u32 reads_per_wg, u32 chunks, unsigned long long* out_words, u32* stats);
+
 // ---- kernels_score.hip
 struct SeedTable {
     u64* seed;            // slot -> seed value

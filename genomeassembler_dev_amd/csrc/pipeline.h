@@ -242,6 +242,15 @@ int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // twin map of a finished strands = 2 build (k_contig_twin, once per build): h_twin[c] = index inside its segment of the contig that
 // is contig c's reverse complement.  GASM_ERR_STATE after a strands = 1 build, GASM_ERR_INTERNAL if a contig has no twin
 int pipeline_fetch_contig_twins(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// Read correction (k_read_correct; the rule: include/gasm.h) of the reads `rd` against the distinct k-mers of the FINISHED build `bs` (the
+// caller has read its report: a retry cannot swap the arrays underneath; a pending build is GASM_ERR_STATE).  out_words: a copy of
+// rd's packed stream, padding words included, with the fixes applied; d_stats: GASM_CORRECT_FIELDS u32 counters per segment.  Both are
+// (re)allocated here; everything is queued on the ctx stream, behind the build, and the caller waits.  `rd` is always the batch's own
+// reads, never the both-strand stream of a strands = 2 build (whose k-mer set holds both orientations already).  Positioned reads
+// (pooled builds): GASM_ERR_STATE.  Reads only the build's arrays and the reads: no build or score result changes.
+int pipeline_correct_reads(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DBuf& out_words, DBuf& d_stats);
+// the packed reads of `rd` as ASCII in h_ascii (k_unpack_ascii; GASM_ERR_STATE for positioned reads) and their n_reads + 1 offsets
+int pipeline_fetch_reads(gasm_ctx* ctx, DevReads& rd, std::vector<char>& h_ascii, std::vector<u64>& h_read_off);
 int pipeline_fetch_graph(gasm_ctx* ctx, DevReads& rd, BuildState& bs);    // h_eflag / h_nxt: per-edge flags and successors
 // paths of the build as a DevPaths (packs the contig text on the device; works on a queued build); the host-side numbers
 // of the same paths once the build's report has been read

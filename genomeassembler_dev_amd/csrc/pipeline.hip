@@ -1180,6 +1180,55 @@ int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs) 
     return GASM_OK;
 }
 
+static_assert(GASM_CORRECT_STATS == GASM_CORRECT_FIELDS && GASM_CORRECT_KMER_CAP == GASM_CORRECT_MAX_KMERS, "kernels.h and gasm.h disagree on read correction");
+
+// read correction: on the stream of the build, behind it; reads the packed reads, dstart, the fine directory and the dense keys, writes a
+// copy of the reads and a stats array, both the caller's
+int pipeline_correct_reads(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DBuf& out_words, DBuf& d_stats) {
+    if (rd.positioned) { gasm_set_error("read correction needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
+    if (bs.pending || bs.k == 0) { gasm_set_error("read correction needs a finished build"); return GASM_ERR_STATE; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 S = rd.n_segments;
+    const size_t bytes = ((rd.total_bases + 31) / 32 + 4) * 8;              // the stream and its four padding words
+    GCHK(out_words.ensure(bytes));
+    const size_t have = rd.d_words.p ? std::min(bytes, rd.d_words.cap) : 0;
+    if (have) HIPCHK(hipMemcpyAsync(out_words.p, rd.d_words.p, have, hipMemcpyDeviceToDevice, ctx->stream));
+    if (have < bytes) HIPCHK(hipMemsetAsync(static_cast<char*>(out_words.p) + have, 0, bytes - have, ctx->stream));
+    GCHK(d_stats.ensure((size_t)S * GASM_CORRECT_FIELDS * 4));
+    HIPCHK(hipMemsetAsync(d_stats.p, 0, (size_t)S * GASM_CORRECT_FIELDS * 4, ctx->stream));
+    if (!rd.n_reads) return GASM_OK;
+    u64 most = 1;
+    for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
+    // 64 reads per workgroup and round, 16 per wave: enough to amortise the workgroup's six atomics; the kernel loops where a segment
+    // holds more reads than the grid covers at once
+    const u32 reads_per_wg = 64;
+    const u32 groups = (S + 7u) / 8u;
+    const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
+    const int have_graph = bs.n_kmers && bs.d_total ? 1 : 0;
+    GLAUNCH_K(ctx, bs.words, "k_read_correct", k_read_correct<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), have_graph, reads_per_wg,
+              chunks, reinterpret_cast<unsigned long long*>(out_words.p), d_stats.as<u32>());
+    return GASM_OK;
+}
+
+int pipeline_fetch_reads(gasm_ctx* ctx, DevReads& rd, std::vector<char>& h_ascii, std::vector<u64>& h_read_off) {
+    if (rd.positioned) { gasm_set_error("the reads of a pooled build lie at positions, not back to back: nothing to fetch"); return GASM_ERR_STATE; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const u64 T = rd.total_bases;
+    h_read_off.resize(rd.n_reads + 1);
+    for (u64 r = 0; r <= rd.n_reads; ++r) h_read_off[r] = rd.fixed_len ? r * (u64)rd.fixed_len : rd.h_read_off[r];
+    h_ascii.assign(T + 1, 0);                   // (one byte more: a pointer to hand out for no bases at all)
+    if (T) {
+        DBuf d;
+        struct Rel { DBuf& b; ~Rel() { b.release(); } } rel{d};
+        GCHK(d.ensure(T));
+        GLAUNCH(ctx, "k_unpack_ascii", k_unpack_ascii, dim3(std::min<u32>(ceil_div_u64(T, GASM_WG), (u32)ctx->n_cu * 32u)), dim3(GASM_WG), 0, rd.d_words.as<u64>(), T,
+                d.as<u8>());
+        HIPCHK(hipMemcpyAsync(h_ascii.data(), d.p, T, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return GASM_OK;
+}
+
 int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     if (!bs.spectrum_queued) { gasm_set_error("gasm_batch_fetch_kmer_spectrum before gasm_batch_kmer_spectrum (of the last build)"); return GASM_ERR_STATE; }
     const size_t n = (size_t)rd.n_segments * 256;

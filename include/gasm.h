@@ -536,6 +536,51 @@ uint32_t gasm_batch_cov_rounds(const gasm_batch* b);   /* 0: none */
 int gasm_batch_fetch_lowcov_stats(gasm_batch* b, const uint32_t** contigs, const uint32_t** kmers);
 int gasm_batch_contig_coverage(gasm_batch* b);
 int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, const uint32_t** n_edges);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Read correction: substituted bases of the reads are repaired against the k-mer set of a build.  (No counterpart in the reference,
+ * whose simulated reads are error-free; spectral correction is the first stage of Quake, BFC, Musket and the SPAdes hammer.)
+ * The cutoff, both strands, the tip, bubble and low-coverage rounds all make the GRAPH tolerate sequencing errors by throwing k-mers
+ * away; none of them repairs a READ.  Scoring is an exact match of a read against the contigs: a read with one wrong base scores
+ * nothing, although its start — the breakpoint — is good.  And at low coverage a cutoff removes true k-mers with the wrong ones; a
+ * corrected read gives its coverage back to the true path.
+ * The rule.  The TRUSTED SET of a segment is the distinct k-mers of that segment in the batch's last finished build, whatever options
+ * that build had (min_count, strands, tips, bubbles, low coverage): what gasm_batch_fetch_distinct returns.  A k-mer of a read is WEAK
+ * if it is not in the trusted set of the read's segment.  For a read of len bases let n = len - k + 1; its k-mer starts are 0 .. n-1.
+ *   n <= 0: the read is copied and counted as no_kmer.
+ *   No weak k-mer: copied and counted as clean.
+ *   Otherwise every maximal run [a, b] of weak k-mer starts is judged ON THE READ AS GIVEN.  Runs do not interact: no k-mer of one run
+ *   contains another run's candidate position, so the order of evaluation cannot matter.
+ *     a == 0 and b == n-1 (the whole read is weak): left.
+ *     Interior (a > 0, b < n-1): only a run of exactly k k-mers is tried, at position p = b.  Any other length is left.
+ *     Touching the start (a == 0, b < n-1): p = b.  (A single substitution makes such a run at most k long; a longer one holds k-mers
+ *     without position b, which stay weak whatever stands there: no candidate fits.)
+ *     Touching the end (a > 0, b == n-1): a run longer than k is left; otherwise p = a + k - 1.
+ *     At p each of the three other bases is tried.  A candidate FITS if all k-mers a .. b of the read with that base at p are in the
+ *     trusted set.  The run is FIXED, and the base is written, only if EXACTLY ONE candidate fits; zero, or two or more, leave the run.
+ *   Read counters: corrected (it had weak runs, all fixed), partial (some fixed), left (none fixed); bases_changed counts written bases.
+ * STATED LIMITS: two errors closer than k merge into one long run and stay; a read whose every k-mer contains the error stays (a read
+ * of fewer than 2k - 1 bases with an error in its middle, or of exactly k bases); substitutions only, no insertions or deletions; a read
+ * of more than GASM_CORRECT_MAX_KMERS k-mers is copied and counted as left.  Against the same trusted set the rule is idempotent:
+ * correcting the corrected reads changes nothing.
+ * gasm_batch_correct_reads        GASM_ERR_STATE before any build.  Finishes the pending build, corrects on the stream of the step slot
+ *                                 that holds it and is complete before it returns.  *out is a new batch of the same context with the
+ *                                 same layout (fixed_len / read_off / seg_read_off) whose reads are the corrected ones; the packed bases
+ *                                 never leave the device.  It always corrects the batch's own reads, each once, also after a strands = 2
+ *                                 build, whose trusted set holds both orientations.  The source batch, its reads, its build and its
+ *                                 scores are untouched; the new batch has no build yet.  Free it with gasm_batch_free.
+ * gasm_batch_fetch_correct_stats  of a batch gasm_batch_correct_reads made: n_segments x GASM_CORRECT_FIELDS counters, per segment in
+ *                                 the order no_kmer, clean, corrected, partial, left, bases_changed (the first five sum to the
+ *                                 segment's reads).  Host copy, valid until the next call or free.  GASM_ERR_STATE on any other batch.
+ * gasm_batch_fetch_reads          the reads of a batch as ASCII, back to back, with n_reads + 1 offsets: of any batch, before or after
+ *                                 a build (the corrected reads, for the FASTQ a user wants to keep).  Host copies, valid until the next
+ *                                 call or free.
+ * Pooled builds (gasm_pool_*) have no read correction.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_CORRECT_FIELDS 6
+#define GASM_CORRECT_MAX_KMERS 4096
+int gasm_batch_correct_reads(gasm_batch* b, gasm_batch** out);
+int gasm_batch_fetch_correct_stats(gasm_batch* b, const uint32_t** stats);
+int gasm_batch_fetch_reads(gasm_batch* b, const char** ascii, const uint64_t** read_off);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 

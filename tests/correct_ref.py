@@ -1,0 +1,203 @@
+"""CPU restatement of the read-correction rule (include/gasm.h, "Read correction") on strings, by composition with
+tests/lowcov_ref.py (TEST INFRASTRUCTURE: imported by the correction tests only).  Per segment:
+    trusted = the distinct k-mers lowcov_ref.expected(...) leaves (cutoff, strands, tips, bubbles, low coverage: whatever the build had)
+    a k-mer of a read is weak if it is not in `trusted`; every maximal run [a, b] of weak k-mer starts is judged on the read as given:
+        whole read weak: left.  Interior: only a run of exactly k, at p = b.  Touching the start: p = b.  Touching the end: longer than
+        k left, else p = a + k - 1.  At p the three other bases are tried; a candidate fits if all k-mers a .. b with that base at p are
+        trusted; exactly one fitting candidate is written.
+    categories: no_kmer, clean, corrected (every run fixed), partial (some), left (none)
+and the hand-built cases the host and the GPU tests share.
+"""
+import numpy as np
+
+import bubbles_ref as br
+import lowcov_ref as lr
+import tips_ref as tr
+
+FIELDS = ("no_kmer", "clean", "corrected", "partial", "left", "bases_changed")
+
+
+def weak_runs(read, trusted, k):
+    """the maximal runs [a, b] of k-mer starts whose k-mer is not in `trusted`"""
+    n = len(read) - k + 1
+    runs, a = [], None
+    for j in range(n):
+        if read[j:j + k] not in trusted:
+            if a is None:
+                a = j
+        elif a is not None:
+            runs.append((a, j - 1))
+            a = None
+    if a is not None:
+        runs.append((a, n - 1))
+    return runs
+
+
+def correct(read, trusted, k):
+    """the rule on one read: (the read afterwards, bases changed, category)"""
+    n = len(read) - k + 1
+    if n <= 0:
+        return read, 0, "no_kmer"
+    runs = weak_runs(read, trusted, k)
+    if not runs:
+        return read, 0, "clean"
+    out, fixed = list(read), 0
+    for a, b in runs:
+        if a == 0 and b == n - 1:
+            continue
+        if a > 0 and b < n - 1:
+            if b - a + 1 != k:
+                continue
+            p = b
+        elif a == 0:
+            p = b
+        else:
+            if b - a + 1 > k:
+                continue
+            p = a + k - 1
+        fits = []
+        for x in "ACGT":
+            if x == read[p]:
+                continue
+            cand = read[:p] + x + read[p + 1:]                  # (the read as given: other runs' fixes are not in it)
+            if all(cand[j:j + k] in trusted for j in range(a, b + 1)):
+                fits.append(x)
+        if len(fits) == 1:
+            out[p] = fits[0]
+            fixed += 1
+    return "".join(out), fixed, "corrected" if fixed == len(runs) else "partial" if fixed else "left"
+
+
+def correct_all(rs, trusted, k):
+    """(corrected reads, [no_kmer, clean, corrected, partial, left, bases_changed]) of one segment"""
+    out, stats = [], dict.fromkeys(FIELDS, 0)
+    for r in rs:
+        c, nb, cat = correct(r, trusted, k)
+        out.append(c)
+        stats[cat] += 1
+        stats["bases_changed"] += nb
+    return out, [stats[f] for f in FIELDS]
+
+
+_CACHE = {}
+
+
+def expected(rs, k, **build):
+    """one segment: dict(reads = the corrected reads, stats = the six counters, trusted = the set) with the trusted set that
+    lowcov_ref.expected(rs, k, **build) leaves (min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds, cov_cutoff, cov_len,
+    cov_rounds).  Computed once per process for the same reads and options; read-only."""
+    key = (len(rs), hash(tuple(rs)), k, tuple(sorted(build.items())))
+    if key not in _CACHE:
+        trusted = set(lr.expected_cached(rs, k, **build)["ref"]["distinct"])
+        reads, stats = correct_all(rs, trusted, k)
+        _CACHE[key] = dict(reads=reads, stats=stats, trusted=trusted)
+    return _CACHE[key]
+
+
+def readme_options(k):
+    """the README's build_simplified options for noisy reads, as the low-coverage tests use them (their references are shared)"""
+    return dict(min_count=2, tip_len=2 * k - 1, tip_rounds=2, bubble_len=2 * k - 1, bubble_rounds=2, cov_cutoff=3, cov_len=2 * k - 1, cov_rounds=2)
+
+
+def noisy_and_clean(L, rl, cov, seed, strands):
+    """bubbles_ref.noisy_segments' one segment and the same reads before the substitutions (same strand flips): (noisy, clean)"""
+    from genomeassembler_dev_amd import synth
+    noisy = br.noisy_segments(L, rl, cov, seed, strands)[2][0]
+    reads, _, _ = synth.make_batch(1, L, rl, cov, seed0=seed)
+    if strands == 2:
+        reads = tr.flip_half(reads, seed)
+    return noisy, tr.strs(reads)
+
+
+def table_row(L, rl, cov, k, seed, strands, min_count=2):
+    """a row of the issue's table under build(k, min_count, strands): (reads, clean, corrected, partial, left, bases changed, changed to a
+    wrong base, error-free reads before, after)"""
+    noisy, clean = noisy_and_clean(L, rl, cov, seed, strands)
+    e = expected(noisy, k, min_count=min_count, strands=strands)
+    wrong = sum(1 for a, b, c in zip(noisy, e["reads"], clean) for x, y, z in zip(a, b, c) if x != y and y != z)
+    s = e["stats"]
+    assert s[0] == 0
+    return (len(noisy), s[1], s[2], s[3], s[4], s[5], wrong, sum(a == c for a, c in zip(noisy, clean)), sum(b == c for b, c in zip(e["reads"], clean)))
+
+
+# ---- hand-built cases
+def _sub(read, *positions):
+    """the read with the base at every given position cycled A -> C -> G -> T -> A"""
+    r = list(read)
+    for p in positions:
+        r[p] = "ACGTA"["ACGT".index(r[p]) + 1]
+    return "".join(r)
+
+
+def backbone(rng, k):
+    """k = 21: lowcov_ref._backbone (300 random bases, their 60-base windows, each four times); larger k: the same with 100-base windows"""
+    if k <= 21:
+        G, reads = lr._backbone(rng)
+        return G, reads, 60
+    G = br._rnd(rng, 300)
+    return G, [G[i:i + 100] for i in range(300 - 100 + 1)] * 4, 100
+
+
+def hand_cases(k, seed=7):
+    """two segments for build(k, min_count = 2) and what the rule makes of every added read.
+    Segment 0: a backbone G covered four times, plus one read per case, each a W-base window of G (another window for every case, so no
+    two cases share a wrong k-mer) with substitutions:
+        middle          at W // 2: an interior run of exactly k                                           -> corrected, the window
+        pos0            at 0: a start-touching run of length 1                                            -> corrected
+        pos_k-2         at k - 2: a start-touching run of length k - 1                                    -> corrected
+        pos_k-1         at k - 1: a start-touching run of length k                                        -> corrected
+        last            at the last base: an end-touching run of length 1                                 -> corrected
+        k-1_from_end    at W - k: an end-touching run of length k                                         -> corrected
+        two_apart_k+1   at 10 and 10 + k + 1: two runs with one trusted k-mer between them                -> corrected, 2 bases
+        two_apart_k-1   at 5 and 5 + k - 1: one run of k + 5 from the start                               -> left
+        short           k - 1 bases                                                                       -> no_kmer
+        empty           no bases                                                                          -> no_kmer
+        random          W random bases: the whole read is weak                                            -> left
+        one_kmer        k bases with an error: one k-mer, the whole read weak                             -> left
+        clean           a window as it is                                                                 -> clean
+    Segment 1: G and H = G with base 150 cycled once, both covered four times, and one read: a window of G with base 150 cycled twice
+        ambiguous       two candidates fit (G's base and H's)                                             -> left
+    Returns (segments, cases): cases = [(name, segment, index of the read in its segment, the read afterwards, bases changed, category)]"""
+    rng = np.random.default_rng(seed)
+    G, reads, W = backbone(rng, k)
+    subs_of = [(W // 2,), (0,), (k - 2,), (k - 1,), (W - 1,), (W - k,), (10, 10 + k + 1), (5, 5 + k - 1), (), (), (), (k // 2,), ()]
+    # window i starts at i * step: the largest step that keeps every window inside G and with which no two cases substitute the same base of G
+    step = next(st for st in range((len(G) - W) // 12, 0, -1) if len({i * st + p for i, ps in enumerate(subs_of) for p in ps}) == sum(map(len, subs_of)))
+    win = lambda i: G[i * step:i * step + W]
+    names = ["middle", "pos0", "pos_k-2", "pos_k-1", "last", "k-1_from_end", "two_apart_k+1", "two_apart_k-1", "short", "empty", "random", "one_kmer", "clean"]
+    cats = ["corrected"] * 7 + ["left", "no_kmer", "no_kmer", "left", "left", "clean"]
+    srcs = [win(i) for i in range(13)]
+    srcs[8], srcs[9], srcs[10], srcs[11] = win(8)[:k - 1], "", br._rnd(rng, W), win(11)[:k]
+    spec = list(zip(names, srcs, subs_of, cats))
+    seg0, cases = list(reads), []
+    for name, src, subs, cat in spec:
+        fixed = cat == "corrected"
+        cases.append((name, 0, len(seg0), src if fixed else _sub(src, *subs), len(subs) if fixed else 0, cat))
+        seg0.append(_sub(src, *subs))
+    H = _sub(G, 150)
+    seg1 = reads + [H[i:i + W] for i in range(len(H) - W + 1)] * 4
+    lo = 150 - W // 2
+    amb = _sub(G[lo:lo + W], W // 2, W // 2)
+    cases.append(("ambiguous", 1, len(seg1), amb, 0, "left"))
+    seg1.append(amb)
+    return [seg0, seg1], cases
+
+
+def long_read_cases(seed=8):
+    """k = 21, more than 64 k-mers per read: a backbone G (300 bases, 60-base windows four times) plus 150-base windows of G (130 k-mers:
+    three 64-bit words of weak bits) and one of 148 bases (128 k-mers: the last word is full):
+        at_70       a substitution at 70: its run [50, 70] straddles k-mer starts 63 / 64                  -> corrected
+        at_128      at 128: the run [108, 128] straddles starts 127 / 128, interior by one start          -> corrected
+        at_135      at 135: the run [115, 129] straddles 127 / 128 and touches the end                    -> corrected
+        clean_150   a window as it is                                                                      -> clean
+        last_of_148 148 bases, the last one substituted: the run [127, 127] is the last bit of a full word -> corrected
+    Returns (the segment, cases) as hand_cases does"""
+    rng = np.random.default_rng(seed)
+    G, reads = lr._backbone(rng)
+    spec = [("at_70", G[0:150], (70,), "corrected"), ("at_128", G[30:180], (128,), "corrected"), ("at_135", G[60:210], (135,), "corrected"),
+            ("clean_150", G[90:240], (), "clean"), ("last_of_148", G[120:268], (147,), "corrected")]
+    seg, cases = list(reads), []
+    for name, src, subs, cat in spec:
+        cases.append((name, 0, len(seg), src, len(subs), cat))
+        seg.append(_sub(src, *subs))
+    return seg, cases

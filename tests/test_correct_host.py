@@ -1,0 +1,134 @@
+"""Read correction without a GPU: libgasm.so exports the new entries, include/gasm.h declares them and states the rule, the ctypes mirror
+and the Python surface know them, and the CPU restatement of the rule (tests/correct_ref.py) reproduces the table of noisy reads that
+pins it, is idempotent, and gives on the hand-built cases what their docstrings say."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import pytest
+
+import correct_ref as cr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "genomeassembler_dev_amd", "libgasm.so")
+HEADER = os.path.join(ROOT, "include", "gasm.h")
+
+SIGNATURES = {
+    "gasm_batch_correct_reads": "int gasm_batch_correct_reads(gasm_batch* b, gasm_batch** out);",
+    "gasm_batch_fetch_correct_stats": "int gasm_batch_fetch_correct_stats(gasm_batch* b, const uint32_t** stats);",
+    "gasm_batch_fetch_reads": "int gasm_batch_fetch_reads(gasm_batch* b, const char** ascii, const uint64_t** read_off);",
+}
+
+# L, read length, coverage, k, seed, strands, min_count: reads, clean, corrected, partial, left, bases changed, changed to a wrong base,
+# error-free reads before, after (plain Python on a Counter of k-mers: the trusted set is the k-mers seen at least min_count times)
+TABLE = [((4000, 80, 20, 21, 5, 1, 2), (980, 433, 419, 25, 103, 518, 0, 423, 842)),
+         ((4000, 80, 20, 21, 5, 2, 2), (980, 433, 419, 25, 103, 518, 0, 423, 842)),
+         ((4000, 80, 40, 21, 5, 1, 2), (1959, 908, 775, 64, 212, 961, 0, 860, 1618)),
+         ((8000, 100, 40, 41, 11, 2, 2), (3168, 1381, 1015, 100, 672, 1234, 0, 1157, 2116)),
+         ((600, 50, 12, 15, 3, 1, 2), (133, 74, 49, 2, 8, 60, 0, 75, 124)),
+         ((400, 40, 15, 11, 9, 1, 2), (131, 80, 40, 1, 10, 46, 0, 81, 120)),
+         ((4000, 80, 20, 21, 5, 1, 3), (980, 421, 439, 26, 94, 542, 0, 423, 863))]
+
+
+def _flat(text):
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"\s+", " ", text).replace("( ", "(").replace(" )", ")")
+
+
+def test_header_declares_the_entries_and_the_rule():
+    with open(HEADER) as f:
+        raw = f.read()
+    flat = _flat(raw)
+    for name, sig in SIGNATURES.items():
+        assert _flat(sig) in flat, name
+    assert "#define GASM_CORRECT_FIELDS 6" in raw and "#define GASM_CORRECT_MAX_KMERS 4096" in raw
+    words = " ".join(re.sub(r"(?m)^ \* ?", " ", raw).split())             # (the comment's text, whatever its line breaks)
+    assert "Read correction" in raw and "TRUSTED SET" in raw and "WEAK" in raw and "FITS" in raw and "FIXED" in raw
+    assert "distinct k-mers of that segment in the batch's last finished build" in words
+    assert "ON THE READ AS GIVEN" in words and "Runs do not interact" in words
+    assert "a == 0 and b == n-1 (the whole read is weak): left" in words
+    assert "only a run of exactly k k-mers is tried, at position p = b" in words
+    assert "Touching the start (a == 0, b < n-1): p = b" in words
+    assert "a run longer than k is left; otherwise p = a + k - 1" in words
+    assert "only if EXACTLY ONE candidate fits" in words
+    assert "no_kmer, clean, corrected, partial, left, bases_changed" in words
+    # the stated limits
+    assert "STATED LIMITS" in raw and "two errors closer than k merge into one long run and stay" in words
+    assert "a read whose every k-mer contains the error stays" in words and "substitutions only, no insertions or deletions" in words
+    assert "the rule is idempotent" in words and "GASM_CORRECT_MAX_KMERS k-mers is copied and counted as left" in words
+    assert "GASM_ERR_STATE before any build" in words and "The source batch, its reads, its build and its scores are untouched" in words
+
+
+def test_library_exports_the_entries():
+    # (symbol table only: nothing here calls into the library)
+    lib = C.CDLL(LIB)
+    for name in SIGNATURES:
+        assert hasattr(lib, name), name
+
+
+def test_ctypes_mirror_and_python_wrappers():
+    from genomeassembler_dev_amd import _lib, api, batch
+    import genomeassembler_dev_amd as ga
+    i, vp, pp = C.c_int, C.c_void_p, C.POINTER(C.c_void_p)
+    want = {"gasm_batch_correct_reads": (i, [vp, pp]), "gasm_batch_fetch_correct_stats": (i, [vp, pp]), "gasm_batch_fetch_reads": (i, [vp, pp, pp])}
+    for name, (res, args) in want.items():
+        assert name in _lib.SYMBOLS, name
+        assert _lib.SYMBOLS[name][0] is res and list(_lib.SYMBOLS[name][1]) == args, name
+    assert _lib.CORRECT_FIELDS == cr.FIELDS and len(_lib.CORRECT_FIELDS) == 6 and _lib.CORRECT_MAX_KMERS == 4096
+    for name in ("correct_reads", "correction_stats", "reads", "read_strings"):
+        assert callable(getattr(batch.SegmentBatch, name)), name
+    assert ga.correct_reads is api.correct_reads
+    q = inspect.signature(api.correct_reads).parameters
+    assert list(q)[:4] == ["reads", "k", "min_count", "strands"] and (q["min_count"].default, q["strands"].default) == (2, 1)
+
+
+@pytest.mark.parametrize("row,want", TABLE)
+def test_the_restatement_reproduces_the_table(row, want):
+    """the numbers were computed with the rule as written, and nothing is changed to a wrong base: judged against the reads before
+    the substitutions"""
+    got = cr.table_row(*row)
+    print(row, got)
+    assert got == want
+    assert got[6] == 0 and sum(got[1:5]) == got[0]
+
+
+@pytest.mark.parametrize("row", [TABLE[0][0], TABLE[1][0], TABLE[4][0], TABLE[5][0]])
+def test_idempotent(row):
+    """correcting the corrected reads against the same set changes nothing: no read is corrected or partly corrected any more"""
+    L, rl, cov, k, seed, strands, c = row
+    noisy, _ = cr.noisy_and_clean(L, rl, cov, seed, strands)
+    e = cr.expected(noisy, k, min_count=c, strands=strands)
+    again, stats = cr.correct_all(e["reads"], e["trusted"], k)
+    assert again == e["reads"] and stats[2] == stats[3] == stats[5] == 0
+    assert stats[1] == e["stats"][1] + e["stats"][2] and stats[4] == e["stats"][3] + e["stats"][4]
+
+
+@pytest.mark.parametrize("k", [21, 41])
+def test_hand_built_cases(k):
+    segs, cases = cr.hand_cases(k)
+    assert {len(r) for r in segs[0][:4]} == {60 if k == 21 else 100}
+    for name, s, i, want, changed, cat in cases:
+        e = cr.expected(segs[s], k, min_count=2)
+        assert cr.correct(segs[s][i], e["trusted"], k) == (want, changed, cat), name
+        assert e["reads"][i] == want, name
+    assert cr.expected(segs[0], k, min_count=2)["stats"][0::2] == [2, 7, 3] and cr.expected(segs[0], k, min_count=2)["stats"][5] == 8
+    assert cr.expected(segs[1], k, min_count=2)["stats"][2:] == [0, 0, 1, 0]
+    # what the docstring says about the runs
+    t = cr.expected(segs[0], k, min_count=2)["trusted"]
+    runs = {name: cr.weak_runs(segs[s][i], t, k) for name, s, i, _, _, _ in cases if s == 0}
+    W = len(segs[0][0])
+    n = W - k + 1
+    assert runs["middle"] == [(W // 2 - k + 1, W // 2)] and runs["pos0"] == [(0, 0)] and runs["pos_k-2"] == [(0, k - 2)] and runs["pos_k-1"] == [(0, k - 1)]
+    assert runs["last"] == [(n - 1, n - 1)] and runs["k-1_from_end"] == [(n - k, n - 1)]
+    assert runs["two_apart_k+1"] == [(0, 10), (12, 10 + k + 1)] and runs["two_apart_k-1"] == [(0, 5 + k - 1)]
+    assert runs["random"] == [(0, n - 1)] and runs["one_kmer"] == [(0, 0)] and runs["clean"] == runs["short"] == runs["empty"] == []
+
+
+def test_long_read_cases():
+    seg, cases = cr.long_read_cases()
+    e = cr.expected(seg, 21, min_count=2)
+    for name, _, i, want, changed, cat in cases:
+        assert cr.correct(seg[i], e["trusted"], 21) == (want, changed, cat), name
+    runs = {name: cr.weak_runs(seg[i], e["trusted"], 21) for name, _, i, _, _, _ in cases}
+    assert runs["at_70"] == [(50, 70)] and runs["at_128"] == [(108, 128)] and runs["at_135"] == [(115, 129)] and runs["last_of_148"] == [(127, 127)]
