@@ -16,6 +16,8 @@ MAX_BUBBLE_LEN = 65535  # GASM_MAX_BUBBLE_LEN: longest contig (bases) bubble pop
 MAX_COV_ROUNDS = 8      # GASM_MAX_COV_ROUNDS: rounds of low-coverage removal one build takes
 CORRECT_FIELDS = ("no_kmer", "clean", "corrected", "partial", "left", "bases_changed")   # GASM_CORRECT_FIELDS counters, in the header's order
 CORRECT_MAX_KMERS = 4096   # GASM_CORRECT_MAX_KMERS: k-mers of the longest read that read correction looks at
+THREAD_MAX_KMERS = 4096    # GASM_THREAD_MAX_KMERS: k-mers of the longest read that contig_links() threads
+MAX_SPAN_LEN = 65535       # GASM_MAX_SPAN_LEN: longest contig (bases) that span support looks at
 MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
@@ -150,6 +152,8 @@ SYMBOLS = {
     "gasm_batch_contig_coverage": (_int, [_vp]),
     "gasm_batch_fetch_contig_coverage": (_int, [_vp, _PP, _PP]),
     "gasm_batch_fetch_contig_twins": (_int, [_vp, _PP]),
+    "gasm_batch_contig_links": (_int, [_vp, _u32]),
+    "gasm_batch_fetch_contig_links": (_int, [_vp, _PP, _PP, _PP, _PP, _PP]),
     "gasm_batch_fetch_solid_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_kmer_spectrum": (_int, [_vp]),
     "gasm_batch_fetch_kmer_spectrum": (_int, [_vp, _PP]),

@@ -467,3 +467,24 @@ def correct_reads(reads, k, min_count=2, strands=1, ctx=None):
             c.close()
     finally:
         b.close()
+
+
+def contig_graph(reads, k, span_len=None, ctx=None, **build):
+    """the contigs of one segment's reads (a list of str) and the graph between them: (contigs, links.ContigLinks).  build: the keyword
+    set of SegmentBatch.build_simplified (min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds, cov_cutoff, cov_len,
+    cov_rounds, genome_len_hint).  The ContigLinks speaks of segment 0: links(0), to_gfa(0), resolve_repeats(0).  span_len = None: the
+    longest read."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        cl = b.build_simplified(int(k), **build).contig_links(span_len)
+        return cl.contigs(0), cl
+    finally:
+        b.close()
+
+
+def resolve_repeats(reads, k, min_support=2, ctx=None, **build):
+    """the contigs of one segment's reads with the repeats shorter than a read put back into their flanks, where the reads that run
+    through a repeat say so unambiguously (links.ContigLinks.resolve_repeats: the rule and its limits); a sorted list of str.
+    build: as for contig_graph."""
+    return contig_graph(reads, k, None, ctx, **build)[1].resolve_repeats(0, min_support)

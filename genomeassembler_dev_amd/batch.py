@@ -7,8 +7,9 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_bubbles, _check_lowcov, _check_tips, unpack_kmers
+from .links import ContigLinks
 
 
 def weighted_median_half(mult_sum, n_edges):
@@ -260,6 +261,34 @@ class SegmentBatch:
             return ms, ns
         a, z = int(so[int(segment)]), int(so[int(segment) + 1])
         return ms[a:z], ns[a:z]
+
+    def contig_links(self, span_len=None):
+        """the links between the last build's contigs and the reads' support for them (gasm_batch_contig_links; the rule: include/gasm.h
+        "Contig links") as a links.ContigLinks: per segment succ / pred (which contig follows / precedes which over which base), link
+        support (crossings of every link in the reads), span support (reads that run through a contig of at most span_len bases from an
+        in-edge to an out-edge) and the reads too long to thread.  span_len = None: the longest read of the batch (a longer contig cannot
+        be spanned), at most _lib.MAX_SPAN_LEN; 0: no span work.  After a strands = 2 build every read and its reverse complement are
+        threaded.  Reads the build only: contigs, scores, coverage and twins are what they were."""
+        if span_len is None:
+            if getattr(self, "_max_read_len", None) is None:
+                off = self.reads()[1]
+                self._max_read_len = int(np.diff(off).max()) if len(off) > 1 else 0
+            span_len = min(self._max_read_len, MAX_SPAN_LEN)
+        if not 0 <= int(span_len) <= MAX_SPAN_LEN:
+            raise ValueError(f"span_len must be 0..{MAX_SPAN_LEN} (0: no span support)")
+        seg, o, raw = self.contigs_raw()
+        total = int(seg[-1])
+        check(lib().gasm_batch_contig_links(self.h, int(span_len)))
+        ps = [C.c_void_p() for _ in range(5)]
+        check(lib().gasm_batch_fetch_contig_links(self.h, *[C.byref(p) for p in ps]))
+
+        def arr(p, ct, n):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
+        succ, pred, lsup = (arr(p, C.c_uint32, 4 * total) for p in ps[:3])
+        ssup, skipped = arr(ps[3], C.c_uint32, 16 * total), arr(ps[4], C.c_uint64, self.n_segments)
+        contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+        ms, _ = self.contig_coverage()
+        return ContigLinks(self.k, int(span_len), self.strands(), seg, contigs, succ, pred, lsup, ssup, skipped, ms)
 
     def suggest_cov_cutoff(self, segment):
         """a cov_cutoff for build_simplified() from the last build's own contigs of `segment`: half the length-weighted median of the

@@ -1014,6 +1014,29 @@ int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, c
     API_GUARD_END
 }
 
+int gasm_batch_contig_links(gasm_batch* b, uint32_t span_len) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (span_len > GASM_MAX_SPAN_LEN) { gasm_set_error("span_len must be <= %d (got %u)", GASM_MAX_SPAN_LEN, span_len); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_contig_links before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    return pipeline_contig_links(b->S().cx, b->build_reads(b->S()), b->S().bs, span_len);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const uint32_t** pred, const uint32_t** link_support, const uint32_t** span_support,
+                                  const uint64_t** skipped) {
+    API_GUARD_BEGIN
+    if (!b || !succ || !pred || !link_support || !span_support || !skipped) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_contig_links before a build"); return GASM_ERR_STATE; }
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_contig_links(b->S().cx, b->build_reads(b->S()), bs));
+    *succ = bs.h_succ.data(); *pred = bs.h_pred.data(); *link_support = bs.h_link_support.data(); *span_support = bs.h_span_support.data();
+    *skipped = bs.h_links_skipped.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin) {
     API_GUARD_BEGIN
     if (!b || !twin) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }

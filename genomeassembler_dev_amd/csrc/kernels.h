@@ -247,6 +247,17 @@ __global__ void k_read_kmer_count(const u64* words, const u64* read_off, const u
 template <class K>
 __global__ void k_read_correct(ReadSet rs, GraphView gv, int have_graph, u32 reads_per_wg, u32 chunks, unsigned long long* out_words, u32* stats);
 
+// ---- kernels_links.hip: the links between the contigs of a finished build and the reads' support for them (include/gasm.h, "Contig links")
+#define GASM_THREAD_KMER_CAP 4096     // = GASM_THREAD_MAX_KMERS: k-mers of a read whose in-set bits one wave keeps (64 words of 64 bits in LDS)
+// succ / pred: 4 entries per contig, filled with GASM_NONE32 by the caller; text: the contigs' ASCII
+template <class K>
+__global__ void k_contig_links(GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, u32 n_segments, u32* succ,
+                               u32* pred);
+// text: the contigs' ASCII; link_support: 4 per contig, span_support: 16 per contig, skipped: one per segment, all zeroed by the caller
+template <class K>
+__global__ void k_read_thread(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph, u32 span_len,
+                              u32 reads_per_wg, u32 chunks, u32* link_support, u32* span_support, unsigned long long* skipped);
+
 // ---- kernels_score.hip
 struct SeedTable {
     u64* seed;            // slot -> seed value

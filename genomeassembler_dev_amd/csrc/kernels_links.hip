@@ -1,0 +1,202 @@
+// kernels_links.hip — the graph between the contigs of a finished build and the reads' evidence on it (include/gasm.h, "Contig links"):
+//   k_contig_links    one thread per contig: the contigs its last node leads to (succ) and the ones that lead to its first node (pred)
+//   k_read_thread     one wave per read: every k-mer's contig and offset, the crossings from contig to contig (link support) and the
+//                     short contigs a read passes through from an in-edge to an out-edge (span support)
+// Both read the build's arrays only.  Where an edge lies: list ranking left (head, distance) on every edge (link), the head carries the
+// contig's id (e_cid), the contig's bases start at c_off[id] — what k_score_reads_graph and k_contig_cov go by.  An edge of an isolated
+// cycle has no head and lies in no contig: for both kernels it is not there.
+#include "kernels.h"
+
+#define GASM_THREAD_WAVES (GASM_WG / 64)
+
+// what the kernels need of a finished build beside the k-mer directory
+struct ContigIndex {
+    const u64* link;       // per edge: head << 32 | done << 31 | distance
+    const u32* e_cid;      // at a head: its contig
+    const u64* c_off;      // per contig: its first base in the batch's contig text (+ the end of the last)
+    const u32* seg_cstart; // n_segments + 1 contig indices
+};
+
+// the contig (index in the batch) and the offset in it of the k-mer `key` of segment `seg`, whose edges are [elo, ehi) and whose contigs
+// are [c_lo, c_hi): false if the k-mer is not in the build's set or lies in no contig.  Every index is checked before it is used.
+template <class K>
+__device__ __forceinline__ bool kmer_contig(const GraphView& gv, const ContigIndex& ci, u32 seg, u32 elo, u32 ehi, u32 c_lo, u32 c_hi, const K& key, u32* cid,
+                                            u32* off) {
+    u32 hi;
+    const u32 e = graph_lower_bound<K>(gv, seg, key, &hi);
+    if (e >= hi || e >= ehi || !keq(reinterpret_cast<const K*>(gv.dk_key)[e], key)) return false;
+    const u64 l = ci.link[e];
+    const u32 a = (u32)(l >> 32);
+    if (a == GASM_NONE32 || !(l & GASM_LINK_DONE) || a < elo || a >= ehi) return false;
+    const u32 c = ci.e_cid[a];
+    if (c < c_lo || c >= c_hi) return false;
+    *cid = c;
+    *off = (u32)l & 0x7FFFFFFFu;
+    return true;
+}
+
+// ================================================================================================================
+// succ / pred.  Contig c ends at node v(c) = its last k-1 bases and starts at node u(c) = its first k-1 bases (from the contig text, as
+// k_contig_twin takes its k-mer).  The four candidate out-edges of v are v followed by A, C, G, T, the four candidate in-edges of u are
+// A, C, G, T followed by u: eight independent look-ups, each the bucket pair, the bin pair and a key of graph_lower_bound, then the
+// edge's link and its head's contig.  A contig ends at a branching node or at a dead end, so an out-edge of v(c) that exists is the
+// FIRST edge of its contig (distance 0) and an in-edge of u(c) the LAST of its (distance = edges - 1): anything else is left as "none".
+//   succ[4 c + x] = index inside the segment of the contig whose first k-mer is v(c) + x, pred[4 c + x] the one whose last k-mer is
+//   x + u(c); 0xFFFFFFFF (the caller filled both arrays with it) where there is none.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_contig_links(GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid, const u64* __restrict__ c_off,
+                                                          const u32* __restrict__ seg_cstart, const u8* __restrict__ text, u32 n_segments,
+                                                          u32* __restrict__ succ, u32* __restrict__ pred) {
+    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
+    const u32 n = seg_cstart[n_segments];
+    const u32 nb = 1u << gv.bbits;
+    const int k = gv.k;
+    for (u32 c = blockIdx.x * GASM_WG + threadIdx.x; c < n; c += gridDim.x * GASM_WG) {
+        const u32 seg = upper_seg<u32>(seg_cstart, n_segments, c);
+        const u32 elo = gv.dstart[seg * nb], ehi = gv.dstart[(seg + 1) * nb];
+        const u32 c_lo = seg_cstart[seg], c_hi = seg_cstart[seg + 1];
+        const u64 beg = c_off[c], end = c_off[c + 1];
+        if (end - beg < (u64)k) continue;                                     // (no contig is shorter than one k-mer)
+        K u = key_from_u64<K>(0), v = key_from_u64<K>(0);
+        for (int i = 0; i < k - 1; ++i) {
+            u = kor(kshl(u, 2), key_from_u64<K>(base_code(text[beg + i])));
+            v = kor(kshl(v, 2), key_from_u64<K>(base_code(text[end - (u64)(k - 1) + i])));
+        }
+        u32 cid[8], off[8];
+        bool ok[8];
+#pragma unroll
+        for (u32 x = 0; x < 4; ++x) {
+            ok[x] = kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kor(kshl(v, 2), key_from_u64<K>(x)), &cid[x], &off[x]);
+            ok[4 + x] = kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kor(kshl(key_from_u64<K>(x), 2 * (k - 1)), u), &cid[4 + x], &off[4 + x]);
+        }
+#pragma unroll
+        for (u32 x = 0; x < 4; ++x) {
+            if (ok[x] && off[x] == 0) succ[4 * (size_t)c + x] = cid[x] - c_lo;
+            if (ok[4 + x]) {
+                const u64 edges = c_off[cid[4 + x] + 1] - c_off[cid[4 + x]] - (u64)(k - 1);
+                if ((u64)off[4 + x] + 1 == edges) pred[4 * (size_t)c + x] = cid[4 + x] - c_lo;
+            }
+        }
+    }
+}
+template __global__ void k_contig_links<u64>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
+template __global__ void k_contig_links<K128>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
+
+// base p of a packed stream
+__device__ __forceinline__ u32 base_at(const u64* __restrict__ w, u64 p) { return (u32)(w[p >> 5] >> (62 - 2 * (u32)(p & 31))) & 3u; }
+
+// are the bits lo .. hi (inclusive) of the in-set words all set?  Word `w_now` is `m_now` (this chunk's ballot), the words behind it are
+// in LDS; lo >> 6 >= w_now
+__device__ __forceinline__ bool run_in_set(const u64* in, u32 lo, u32 hi, u32 w_now, u64 m_now) {
+    for (u32 q = lo >> 6; q <= (hi >> 6); ++q) {
+        const u64 word = q == w_now ? m_now : in[q];
+        u64 need = ~0ull;
+        if (q == (lo >> 6)) need &= ~0ull << (lo & 63u);
+        if (q == (hi >> 6)) need &= ~0ull >> (63u - (hi & 63u));
+        if ((word & need) != need) return false;
+    }
+    return true;
+}
+
+// ================================================================================================================
+// Threading.  One wave per read, GASM_THREAD_WAVES reads of one segment per workgroup and round (seg_chunk: a segment's k-mers and
+// directories stay in one XCD's L2), chunks of 64 k-mer positions, as k_read_correct.  A gather like it: a look-up costs the three
+// dependent requests of graph_lower_bound + the key, then the edge's link and the head's contig id — but only the first position of a
+// chunk and the positions behind a place where the read leaves its contig's text make one (below): the kernel is bound by the requests
+// it sends to L2, and most positions of a read follow their predecessor inside one contig.
+// The chunks are taken LAST FIRST.  Position j asks two things of the positions behind it: where position j + 1 lies (a crossing of link
+// (a, b): both in the set, and another contig or an offset that does not advance by one), and, once it crossed into a contig r of at
+// most span_len bases, whether the n(r) + 1 positions j + 1 .. j + 1 + n(r) are all in the set.  Going backwards both are known when j's
+// turn comes: the neighbour inside the chunk is a cross-lane move, across the 63|64 seam it is lane 0 of the chunk before (v_readlane,
+// carried in a scalar), and "in the set" is one ballot per chunk, kept in LDS (64 words per wave for GASM_THREAD_KMER_CAP positions — the
+// only thing a later position needs of an earlier chunk, so contig and offset never leave the registers).
+// r is unbranched inside: after a crossing into r, a run of n(r) + 1 further positions in the set is r followed by one of its
+// out-edges (include/gasm.h), so the run of bits is the whole test.  x = first base of k-mer j, y = last base of k-mer j + 1 + n(r).
+//   link_support[4 a + last base of k-mer j + 1] += 1 per crossing, span_support[16 r + 4 x + y] += 1 per span (a, r: indices in the
+//   batch); skipped[seg] += 1 per read of more than GASM_THREAD_KMER_CAP k-mers.  All zeroed by the caller; integer atomics: exact.
+// text: the contigs' ASCII, as the build emitted it.  have_graph = 0: the build holds no contig at all (its arrays may not exist): only `skipped` is counted.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_read_thread(ReadSet rs, GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
+                                                         const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, const u8* __restrict__ text,
+                                                         int have_graph, u32 span_len, u32 reads_per_wg, u32 chunks, u32* __restrict__ link_support,
+                                                         u32* __restrict__ span_support, unsigned long long* __restrict__ skipped) {
+    __shared__ u64 s_in[GASM_THREAD_WAVES][GASM_THREAD_KMER_CAP / 64];
+    __shared__ u32 s_skip;
+    u32 seg, chunk;
+    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
+    if (threadIdx.x == 0) s_skip = 0;
+    __syncthreads();
+    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    u64* const in = s_in[wv];
+    const int k = gv.k;
+    u32 elo = 0, ehi = 0, c_lo = 0, c_hi = 0;
+    if (have_graph) {
+        const u32 nb = 1u << gv.bbits;
+        elo = gv.dstart[seg * nb]; ehi = gv.dstart[(seg + 1) * nb];
+        c_lo = seg_cstart[seg]; c_hi = seg_cstart[seg + 1];
+    }
+    const bool graph = elo < ehi && c_lo < c_hi;
+    const u64 rbeg = rs.seg_read_off[seg], rend = rs.seg_read_off[seg + 1];
+    u32 c_skip = 0;                                                           // of this wave's reads (wave-uniform)
+    for (u64 base = rbeg + (u64)chunk * reads_per_wg; base < rend; base += (u64)chunks * reads_per_wg) {
+        const u64 end = base + reads_per_wg < rend ? base + reads_per_wg : rend;
+        for (u64 r = base + wv; r < end; r += GASM_THREAD_WAVES) {
+            u64 p0;
+            u32 len;
+            read_span(rs, r, &p0, &len);
+            if (len < (u32)k) continue;
+            const u32 n = len - (u32)k + 1;
+            if (n > GASM_THREAD_KMER_CAP) { ++c_skip; continue; }
+            if (!graph) continue;
+            u32 nx_cid = GASM_NONE32, nx_off = 0;                             // position 64 (w + 1): lane 0 of the chunk before (none yet)
+            // the first position of every chunk, looked up by lane w for chunk w: one round of dependent requests for the whole read
+            const u32 nw = (n + 63u) >> 6;
+            u32 f_cid = GASM_NONE32, f_off = 0;
+            if (lane < nw && !kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kmer_key_at<K>(rs.words, p0 + (lane << 6), k), &f_cid, &f_off)) f_cid = GASM_NONE32;
+            for (u32 w = nw; w-- > 0;) {
+                const u32 j = (w << 6) + lane;
+                u32 cid = GASM_NONE32, off = 0;
+                // ---- the chunk's first position was looked up ahead of the loop.  Where it lies in a contig, the positions behind it that
+                // read on as the contig's text does lie in the same contig at the next offsets (k-mer j + 1 is k-mer j without its first
+                // base plus one more): one compare of the read's bases with the contig's text tells how far, and only the lanes behind
+                // the first difference, or behind the contig's end, look up for themselves
+                const u32 s_cid = (u32)__builtin_amdgcn_readlane((int)f_cid, (int)w), s_off = (u32)__builtin_amdgcn_readlane((int)f_off, (int)w);
+                bool known = lane == 0;
+                if (known) { cid = s_cid; off = s_off; }
+                if (s_cid != GASM_NONE32) {
+                    const u64 cb = c_off[s_cid], edges = c_off[s_cid + 1] - cb - (u64)(k - 1);
+                    const bool same = lane == 0 || (j < n && (u64)s_off + lane < edges &&
+                                                    base_at(rs.words, p0 + j + (u32)k - 1) == base_code(text[cb + s_off + lane + (u32)k - 1]));
+                    const u64 differ = ~__ballot(same);
+                    if (lane < (differ ? (u32)__builtin_ctzll(differ) : 64u)) { cid = s_cid; off = s_off + lane; known = true; }
+                }
+                if (!known && j < n && !kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kmer_key_at<K>(rs.words, p0 + j, k), &cid, &off)) cid = GASM_NONE32;
+                const u64 m = __ballot(cid != GASM_NONE32);
+                if (lane == 0) in[w] = m;
+                __builtin_amdgcn_wave_barrier();
+                u32 ncid = (u32)__shfl_down((int)cid, 1, 64), noff = (u32)__shfl_down((int)off, 1, 64);
+                if (lane == 63) { ncid = nx_cid; noff = nx_off; }
+                nx_cid = (u32)__builtin_amdgcn_readfirstlane((int)cid);
+                nx_off = (u32)__builtin_amdgcn_readfirstlane((int)off);
+                if (cid == GASM_NONE32 || ncid == GASM_NONE32 || (ncid == cid && noff == off + 1)) continue;
+                // ---- a crossing of (cid, ncid) between positions j and j + 1
+                atomicAdd(&link_support[4 * (size_t)cid + base_at(rs.words, p0 + j + (u32)k)], 1u);
+                if (!span_len) continue;
+                const u64 rlen = c_off[ncid + 1] - c_off[ncid];
+                if (rlen > (u64)span_len || rlen < (u64)k) continue;
+                const u32 last = j + 1 + (u32)(rlen - (u64)(k - 1));          // the position of the out-edge behind ncid
+                if (last >= n || !run_in_set(in, j + 1, last, w, m)) continue;
+                atomicAdd(&span_support[16 * (size_t)ncid + 4 * base_at(rs.words, p0 + j) + base_at(rs.words, p0 + last + (u32)k - 1)], 1u);
+            }
+        }
+    }
+    if (lane == 0 && c_skip) atomicAdd(&s_skip, c_skip);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_skip) atomicAdd(&skipped[seg], (unsigned long long)s_skip);
+}
+template __global__ void k_read_thread<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, u32*, u32*, unsigned long long*);
+template __global__ void k_read_thread<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, u32*, u32*, unsigned long long*);

@@ -138,6 +138,11 @@ struct BuildState {
     std::vector<u64> h_ccov_m;
     std::vector<u32> h_ccov_n;
     bool coverage_queued = false;           // k_contig_cov ran on the arrays of this build
+    DBuf d_links;                           // contig links of the last build (pipeline_contig_links): u32 succ[4P], pred[4P], link_support[4P],
+                                            // span_support[16P], then u64 skipped[S]
+    std::vector<u32> h_succ, h_pred, h_link_support, h_span_support;
+    std::vector<u64> h_links_skipped;
+    bool links_queued = false;              // k_contig_links and k_read_thread ran on the arrays of this build
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -235,6 +240,13 @@ int pipeline_fetch_lowcov_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // fetch h_ccov_m / h_ccov_n, one entry per contig in the order of the contig list
 int pipeline_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// Contig links (kernels_links.hip; the rule: include/gasm.h "Contig links") of the finished build: queue k_contig_links and k_read_thread on the
+// build's stream behind it (they read the build's arrays, the contig text and the reads `rd` the build was made from — the both-strand stream
+// of a strands = 2 build, so every read and its reverse complement are threaded), then fetch h_succ / h_pred / h_link_support (4 per contig),
+// h_span_support (16 per contig) and h_links_skipped (per segment; reads, each once whatever the strands).  Positioned reads (pooled
+// builds): GASM_ERR_STATE
+int pipeline_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 span_len);
+int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

@@ -468,7 +468,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_bubble_stats, &d_cov_stats, &d_ccov, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_bubble_stats, &d_cov_stats, &d_ccov, &d_links, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -952,6 +952,7 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs,
     bs.fetched_twins = false;
     bs.spectrum_queued = false;
     bs.coverage_queued = false;
+    bs.links_queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -1177,6 +1178,62 @@ int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs) 
         HIPCHK(hipMemcpyAsync(bs.h_ccov_n.data(), bs.d_ccov.as<u64>() + P, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GASM_OK;
+}
+
+static_assert(GASM_THREAD_KMER_CAP == GASM_THREAD_MAX_KMERS, "kernels.h and gasm.h disagree on read threading");
+
+// contig links: on the stream of the build, behind it; reads the directory, the dense keys, the ranking's links, the contig ids, offsets and
+// text and the packed reads, writes an array of its own (succ, pred, link support, span support, skipped reads)
+int pipeline_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 span_len) {
+    if (rd.positioned) { gasm_set_error("contig links need the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
+    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 S = rd.n_segments, P = bs.n_contigs;
+    const size_t tables = (size_t)P * 28 * 4, bytes = tables + (size_t)S * 8;
+    GCHK(bs.d_links.ensure(bytes));
+    u32* const d_succ = bs.d_links.as<u32>();
+    u32 *const d_pred = d_succ + (size_t)P * 4, *const d_lsup = d_succ + (size_t)P * 8, *const d_ssup = d_succ + (size_t)P * 12;
+    unsigned long long* const d_skip = reinterpret_cast<unsigned long long*>(d_succ + (size_t)P * 28);
+    if (P) HIPCHK(hipMemsetAsync(d_succ, 0xFF, (size_t)P * 8 * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(d_lsup, 0, bytes - (size_t)P * 8 * 4, ctx->stream));
+    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
+    const GraphView gv = graph_view(bs);
+    if (have_graph) {
+        const u32 grid = (u32)std::min<u64>(ceil_div_u64(P, GASM_WG), (u64)ctx->n_cu * 8);
+        GLAUNCH_K(ctx, bs.words, "k_contig_links", k_contig_links<K>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
+                  bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), S, d_succ, d_pred);
+    }
+    if (rd.n_reads && S) {
+        u64 most = 1;
+        for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
+        // 64 reads per workgroup and round, 16 per wave, as the correction kernel: the kernel loops where a segment holds more reads than
+        // the grid covers at once
+        const u32 reads_per_wg = 64;
+        const u32 groups = (S + 7u) / 8u;
+        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
+        GLAUNCH_K(ctx, bs.words, "k_read_thread", k_read_thread<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(),
+                  bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), have_graph, span_len, reads_per_wg, chunks, d_lsup, d_ssup, d_skip);
+    }
+    bs.links_queued = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    if (!bs.links_queued) { gasm_set_error("gasm_batch_fetch_contig_links before gasm_batch_contig_links (of the last build)"); return GASM_ERR_STATE; }
+    const u32 S = rd.n_segments, P = bs.n_contigs;
+    bs.h_succ.assign((size_t)P * 4 + 1, 0); bs.h_pred.assign((size_t)P * 4 + 1, 0); bs.h_link_support.assign((size_t)P * 4 + 1, 0);     // (one entry
+    bs.h_span_support.assign((size_t)P * 16 + 1, 0); bs.h_links_skipped.assign((size_t)S + 1, 0);           // more: a pointer to hand out for no contig at all)
+    const u32* const d = bs.d_links.as<u32>();
+    if (P) {
+        HIPCHK(hipMemcpyAsync(bs.h_succ.data(), d, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_pred.data(), d + (size_t)P * 4, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_link_support.data(), d + (size_t)P * 8, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_span_support.data(), d + (size_t)P * 12, (size_t)P * 64, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (S) HIPCHK(hipMemcpyAsync(bs.h_links_skipped.data(), d + (size_t)P * 28, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (bs.strands == 2) for (u32 s = 0; s < S; ++s) bs.h_links_skipped[s] /= 2;      // (a read and its reverse complement are equally long)
     return GASM_OK;
 }
 

@@ -27,6 +27,18 @@ def make_segment(seed, length=50000, n_short=20, short_len=300, n_long=5, long_l
     return g
 
 
+def plant_repeat(genome, rep_len, seed, min_gap=200):
+    """a copy of `genome` in which one rep_len-base stretch occurs twice, more than min_gap bases apart (the second copy overwrites
+    what was there); returns (genome, position of the first copy, position of the second) — the README's repeat-resolution example"""
+    rng = np.random.Generator(np.random.MT19937(seed))
+    g = genome.copy()
+    L = g.size
+    p1 = int(rng.integers(min_gap, L // 2 - rep_len))
+    p2 = int(rng.integers(p1 + rep_len + min_gap + 1, L - rep_len - min_gap))
+    g[p2:p2 + rep_len] = g[p1:p1 + rep_len]
+    return g, p1, p2
+
+
 def simulate_reads(genome, read_len, coverage, seed, weights=None):
     """(n_reads, read_len) uint8 array of reads; starts uniform, or drawn with `weights` (one per start position)."""
     L = genome.size

@@ -581,6 +581,50 @@ int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, c
 int gasm_batch_correct_reads(gasm_batch* b, gasm_batch** out);
 int gasm_batch_fetch_correct_stats(gasm_batch* b, const uint32_t** stats);
 int gasm_batch_fetch_reads(gasm_batch* b, const char** ascii, const uint64_t** read_off);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Contig links: the graph between the contigs of a build, and what the reads say about it.  (The reference forgets which contig
+ * continues into which and tries 10 000 random orders instead, lib/DeNovoAssembler.cpp:195-203; Velvet writes LastGraph, SPAdes a GFA.)
+ * A build cuts contigs at branching nodes.  A repeat of k-1 < L < read length bases cuts the true sequence into flanks plus one shared
+ * contig, and the reads that run from one flank through the repeat into the next say how to put them back together.
+ * The rule.  The graph is the one of the batch's LAST FINISHED BUILD, whatever its options: edges = the distinct k-mers that build left,
+ * nodes = (k-1)-mers, contigs = what gasm_batch_fetch_contigs returns.  Contig indices are the ones INSIDE THE SEGMENT, as in
+ * gasm_batch_fetch_contig_twins.  For a contig c let u(c) / v(c) = its first / last k-1 bases, e_first(c) / e_last(c) = its first / last
+ * k-mer, n(c) = its edges, len(c) = n(c) + k - 1.
+ *   LINKS.  (a, b) is a LINK if v(a) == u(b).  b == a is allowed — a loop, or an unbranched cycle whose cut point is both its ends —
+ *   and gets no special case.  A node has at most four out-edges and four in-edges, so the links need no lists:
+ *     succ[4 a + x] = the contig whose first k-mer is v(a) followed by base x (A, C, G, T = 0..3), or 0xFFFFFFFF;
+ *     pred[4 b + x] = the contig whose last k-mer is base x followed by u(b), or 0xFFFFFFFF.
+ *   The two tables state the same set of links.
+ *   LINK SUPPORT.  A read of n = len - k + 1 > 0 k-mers is THREADED as given.  Position i is a CROSSING of link (a, b) if k-mer i is
+ *   e_last(a) and k-mer i + 1 is e_first(b), both in the build's set.  link_support[4 a + x] counts crossings (x as in succ): occurrences,
+ *   not reads — a read that goes round a loop twice counts twice.  Two consecutive k-mers of a read that are both in the set either follow
+ *   each other inside one contig or are a crossing.
+ *   SPAN SUPPORT.  For a contig r with len(r) <= span_len, a SPAN (x, r, y) at position i is: k-mer i is the in-edge x u(r), k-mers
+ *   i + 1 .. i + n(r) are the edges of r, and k-mer i + n(r) + 1 is the out-edge v(r) y, all of them in the set.
+ *   span_support[16 r + 4 x + y] counts them.  (r is unbranched inside: after a crossing into r, a run of n(r) + 1 further k-mers in
+ *   the set must be r followed by an out-edge.)  For len(r) > span_len the sixteen entries are 0; span_len = 0 leaves the whole table 0
+ *   and no span work is done.
+ *   STRANDS.  After a strands = 2 build every read AND its reverse complement are threaded, as the build saw them: then
+ *   link_support(a, b) == link_support(twin(b), twin(a)), and likewise for spans.  After a strands = 1 build only the reads as given.
+ *   LIMITS.  A read of more than GASM_THREAD_MAX_KMERS k-mers is not threaded: it is counted in skipped[s] (reads, each once whatever
+ *   the strands).  span_len <= GASM_MAX_SPAN_LEN.  A k-mer of an isolated cycle lies in no contig (gasm_batch_fetch_contigs has none for
+ *   it): for this rule it is not in the set.  Pooled builds (gasm_pool_*) get none of this.
+ * All counts are integers accumulated with atomic adds: exact and independent of the order the reads are taken in.
+ * gasm_batch_contig_links         queues both kernels (k_contig_links, k_read_thread) on the step slot of the last build, behind it;
+ *                                 GASM_ERR_STATE before a build, GASM_ERR_INVALID for span_len > GASM_MAX_SPAN_LEN.  It reads the
+ *                                 build's arrays and the reads only: build, contig, score, coverage and twin results fetched before and
+ *                                 after it are identical, and a batch that never calls it launches exactly what it launched without.
+ * gasm_batch_fetch_contig_links   succ, pred, link_support: 4 entries per contig, span_support: 16 per contig, in the order of
+ *                                 gasm_batch_fetch_contigs (contig c of the batch at 4 c resp. 16 c; the VALUES of succ / pred are
+ *                                 indices inside the contig's segment); skipped: n_segments entries.  Host copies, valid until the
+ *                                 next call or build.  GASM_ERR_STATE before a build or without a links pass over the last build.
+ * What to do with them (GFA output, resolving repeats shorter than a read) is host code: genomeassembler_dev_amd/links.py.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_THREAD_MAX_KMERS 4096
+#define GASM_MAX_SPAN_LEN 65535
+int gasm_batch_contig_links(gasm_batch* b, uint32_t span_len);
+int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const uint32_t** pred, const uint32_t** link_support,
+                                  const uint32_t** span_support, const uint64_t** skipped /* n_segments */);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 

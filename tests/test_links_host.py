@@ -1,0 +1,263 @@
+"""Contig links without a GPU: include/gasm.h declares the entries and states the rule, libgasm.so exports them, the ctypes mirror and
+the Python surface know them; the CPU restatement of the rule (tests/links_ref.py) gives on hand-built cases the tables written out here
+by hand; and resolve_repeats — links.py and its independent restatement in links_ref.py — gives on them what the rule says.
+All cases use k = 5: nodes are 4-mers.  The pieces: X = GCAATAGGG, R = TAATTCGC, Y = CGACGAGTA, Z = AGCGTAGAT."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import links_ref as lr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "genomeassembler_dev_amd", "libgasm.so")
+HEADER = os.path.join(ROOT, "include", "gasm.h")
+K = 5
+N = lr.NONE
+X, R, Y, Z, W = "GCAATAGGG", "TAATTCGC", "CGACGAGTA", "AGCGTAGAT", "GGCTTACAC"
+
+SIGNATURES = {
+    "gasm_batch_contig_links": "int gasm_batch_contig_links(gasm_batch* b, uint32_t span_len);",
+    "gasm_batch_fetch_contig_links": "int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const uint32_t** pred, "
+                                     "const uint32_t** link_support, const uint32_t** span_support, const uint64_t** skipped);",
+}
+
+
+def _flat(text):
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"\s+", " ", text).replace("( ", "(").replace(" )", ")")
+
+
+def test_header_declares_the_entries_and_the_rule():
+    with open(HEADER) as f:
+        raw = f.read()
+    flat = _flat(raw)
+    for name, sig in SIGNATURES.items():
+        assert _flat(sig) in flat, name
+    assert "#define GASM_THREAD_MAX_KMERS 4096" in raw and "#define GASM_MAX_SPAN_LEN 65535" in raw
+    words = " ".join(re.sub(r"(?m)^ \* ?", " ", raw).split())
+    for phrase in ("Contig links", "LAST FINISHED BUILD", "(a, b) is a LINK if v(a) == u(b)", "is a CROSSING of link (a, b)", "occurrences, not reads",
+                   "a SPAN (x, r, y) at position i", "span_support[16 r + 4 x + y]", "span_len = 0 leaves the whole table 0",
+                   "link_support(a, b) == link_support(twin(b), twin(a))", "is not threaded: it is counted in skipped[s]",
+                   "Pooled builds (gasm_pool_*) get none of this", "GASM_ERR_STATE before a build or without a links pass over the last build"):
+        assert phrase in words, phrase
+
+
+def test_library_exports_the_entries():
+    lib = C.CDLL(LIB)                                                # (symbol table only: nothing here calls into the library)
+    for name in SIGNATURES:
+        assert hasattr(lib, name), name
+
+
+def test_ctypes_mirror_and_python_surface():
+    from genomeassembler_dev_amd import _lib, api, batch, links
+    import genomeassembler_dev_amd as ga
+    i, vp, pp, u32 = C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32
+    want = {"gasm_batch_contig_links": (i, [vp, u32]), "gasm_batch_fetch_contig_links": (i, [vp, pp, pp, pp, pp, pp])}
+    for name, (res, args) in want.items():
+        assert _lib.SYMBOLS[name][0] is res and list(_lib.SYMBOLS[name][1]) == args, name
+    assert _lib.THREAD_MAX_KMERS == lr.MAX_KMERS == 4096 and _lib.MAX_SPAN_LEN == 65535
+    assert callable(batch.SegmentBatch.contig_links) and inspect.signature(batch.SegmentBatch.contig_links).parameters["span_len"].default is None
+    for name in ("links", "to_gfa", "resolve_repeats", "succ", "pred", "link_support", "span_support"):
+        assert callable(getattr(links.ContigLinks, name)), name
+    assert inspect.signature(links.ContigLinks.resolve_repeats).parameters["min_support"].default == 2
+    assert ga.contig_graph is api.contig_graph and ga.resolve_repeats is api.resolve_repeats and ga.ContigLinks is links.ContigLinks
+    q = inspect.signature(api.resolve_repeats).parameters
+    assert list(q)[:3] == ["reads", "k", "min_support"] and q["min_support"].default == 2
+    assert list(inspect.signature(api.contig_graph).parameters)[:3] == ["reads", "k", "span_len"]
+
+
+def test_argument_errors_of_the_python_surface():
+    from genomeassembler_dev_amd import batch, links
+    b = batch.SegmentBatch.__new__(batch.SegmentBatch)               # (no library call is reached: the checks come first)
+    b.h = None
+    for bad in (-1, 65536):
+        with pytest.raises(ValueError):
+            b.contig_links(span_len=bad)
+    cl = _contig_links(XRYRZ, [G], 8)
+    with pytest.raises(ValueError):
+        cl.resolve_repeats(0, min_support=0)
+    for bad in (-1, 1):
+        with pytest.raises(IndexError):
+            cl.links(bad)
+
+
+# ---- the hand-built cases: contigs in index order, and the non-empty entries of the tables
+def _tab(n, succ=(), pred=(), link=(), span=()):
+    """tables of n contigs from their non-empty entries: succ {(a, 'x'): b}, pred {(b, 'x'): a}, link {(a, 'x'): count}, span {(r, 'xy'): count}"""
+    t = dict(succ=[[N] * 4 for _ in range(n)], pred=[[N] * 4 for _ in range(n)], link_support=[[0] * 4 for _ in range(n)],
+             span_support=[[[0] * 4 for _ in range(4)] for _ in range(n)], skipped=0)
+    for (a, x), b in dict(succ).items():
+        t["succ"][a]["ACGT".index(x)] = b
+    for (b, x), a in dict(pred).items():
+        t["pred"][b]["ACGT".index(x)] = a
+    for (a, x), c in dict(link).items():
+        t["link_support"][a]["ACGT".index(x)] = c
+    for (r, xy), c in dict(span).items():
+        t["span_support"][r]["ACGT".index(xy[0])]["ACGT".index(xy[1])] = c
+    return t
+
+
+# X R Y R Z: X + TAAT, R, TCGC + Z, TCGC + Y + TAAT (sorted).  X ends with G and Y with A (the in-edges GTAAT, ATAAT); Y starts with C
+# and Z with A (the out-edges TCGCC, TCGCA).  Z's contig is a dead end, X's has nothing in front.
+G = X + R + Y + R + Z
+XRYRZ = [X + "TAAT", R, "TCGC" + Z, "TCGC" + Y + "TAAT"]
+XRYRZ_SUCC = {(0, "T"): 1, (1, "A"): 2, (1, "C"): 3, (3, "T"): 1}
+XRYRZ_PRED = {(1, "G"): 0, (1, "A"): 3, (2, "T"): 1, (3, "T"): 1}
+# three copies: X R Y R Z R W (W starts with G; Z ends with T)
+G3 = X + R + Y + R + Z + R + W
+THREE = [X + "TAAT", R, "TCGC" + Z + "TAAT", "TCGC" + Y + "TAAT", "TCGC" + W]
+# n(r) == 1: the repeat is one k-mer, TAATC (nodes TAAT and AATC)
+G1 = X + "TAATC" + Y + "TAATC" + Z
+ONE = ["AATC" + Z, "AATC" + Y + "TAAT", X + "TAAT", "TAATC"]
+# a loop: node TAAT, once round is TAAT CC TAAT; X comes in over GTAAT, GTCGTAGAC leaves over TAATG
+LOOP = [X + "TAAT", "TAATCCTAAT", "TAATGTCGTAGAC"]
+LOOP_ONCE = X + "TAATCCTAAT" + "GTCGTAGAC"
+LOOP_THRICE = X + "TAATCC" * 3 + "TAAT" + "GTCGTAGAC"
+# an unbranched cycle of five k-mers cut at node ACGT (no build makes this contig: an isolated cycle has no branching node to cut it at)
+CYCLE = ["ACGTTACGT"]
+# chained repeats: A R B R2 C, D R E, F R2 H
+R2, D, E, F, H, CC = "CTGATCTT", "ATATCCCGC", "GGTCGGGCT", "GAACTCACC", "CCGTGCGCA", "TATGTCTGG"
+CHAIN_READS = [X + R + Y + R2 + CC, D + R + E, F + R2 + H]
+# a closing chain: the circle A R B R, read twice round
+CIRCLE = [R, "TCGC" + Z + "TAAT", "TCGC" + Y + "TAAT"]
+CIRCLE_READ = R + Z + R + Y + R + Z + R + Y + R
+
+CASES = {
+    "XRYRZ": (XRYRZ, [G], 8, _tab(4, XRYRZ_SUCC, XRYRZ_PRED, {(0, "T"): 1, (1, "A"): 1, (1, "C"): 1, (3, "T"): 1}, {(1, "GC"): 1, (1, "AA"): 1})),
+    # len(R) == span_len above, span_len + 1 here: no span is counted
+    "XRYRZ, span_len 7": (XRYRZ, [G], 7, _tab(4, XRYRZ_SUCC, XRYRZ_PRED, {(0, "T"): 1, (1, "A"): 1, (1, "C"): 1, (3, "T"): 1})),
+    "XRYRZ, span_len 0": (XRYRZ, [G, G], 0, _tab(4, XRYRZ_SUCC, XRYRZ_PRED, {(0, "T"): 2, (1, "A"): 2, (1, "C"): 2, (3, "T"): 2})),
+    # a chimeric read GGG R AGC beside the genome twice: X -> R -> Z, the mixed matrix
+    "mixed": (XRYRZ, [G, G, "GGG" + R + "AGC", "GGG" + R + "AGC"], 8,
+              _tab(4, XRYRZ_SUCC, XRYRZ_PRED, {(0, "T"): 4, (1, "A"): 4, (1, "C"): 2, (3, "T"): 2}, {(1, "GC"): 2, (1, "AA"): 2, (1, "GA"): 2})),
+    "three copies": (THREE, [G3, G3], 8,
+                     _tab(5, {(0, "T"): 1, (1, "A"): 2, (1, "C"): 3, (1, "G"): 4, (2, "T"): 1, (3, "T"): 1},
+                          {(1, "G"): 0, (1, "T"): 2, (1, "A"): 3, (2, "T"): 1, (3, "T"): 1, (4, "T"): 1},
+                          {(0, "T"): 2, (1, "A"): 2, (1, "C"): 2, (1, "G"): 2, (2, "T"): 2, (3, "T"): 2}, {(1, "GC"): 2, (1, "AA"): 2, (1, "TG"): 2})),
+    "n(r) == 1": (ONE, [G1, G1], 5,
+                  _tab(4, {(1, "C"): 3, (2, "C"): 3, (3, "A"): 0, (3, "C"): 1}, {(0, "T"): 3, (1, "T"): 3, (3, "A"): 1, (3, "G"): 2},
+                       {(1, "C"): 2, (2, "C"): 2, (3, "A"): 2, (3, "C"): 2}, {(3, "GC"): 2, (3, "AA"): 2})),
+    # the read that goes round three times crosses the link (loop, loop) twice; every entry into the loop followed by a whole round is a span
+    "loop": (LOOP, [LOOP_ONCE, LOOP_THRICE], 10,
+             _tab(3, {(0, "C"): 1, (0, "G"): 2, (1, "C"): 1, (1, "G"): 2}, {(1, "G"): 0, (1, "C"): 1, (2, "G"): 0, (2, "C"): 1},
+                  {(0, "C"): 2, (1, "C"): 2, (1, "G"): 2}, {(1, "GG"): 1, (1, "GC"): 1, (1, "CC"): 1, (1, "CG"): 1})),
+    # 15 k-mers, offsets 0 1 2 3 4 three times: crossings behind positions 4 and 9; only the first is followed by a whole round and one more k-mer
+    "unbranched cycle": (CYCLE, ["ACGTT" * 3 + "ACGT"], 9, _tab(1, {(0, "T"): 0}, {(0, "T"): 0}, {(0, "T"): 2}, {(0, "TT"): 1})),
+    # nothing attached, and a read that runs off the contig: its last two k-mers are not in the set
+    "dead end": ([X], [X + "TT", "GCAA"], 9, _tab(1)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_the_restatement_on_hand_built_cases(name):
+    contigs, reads, span_len, want = CASES[name]
+    got = lr.tables(contigs, reads, K, 1, span_len)
+    for key in ("succ", "pred", "link_support", "span_support", "skipped"):
+        assert got[key] == want[key], (name, key)
+    assert lr.consistent(got, contigs, K)
+
+
+def test_the_hand_built_contigs_are_what_a_build_cuts():
+    """(the cases above state their contigs; the plain cutter of links_ref makes the same from the reads, the cycle excepted)"""
+    for name, (contigs, reads, _, _) in CASES.items():
+        if name not in ("unbranched cycle", "dead end"):
+            assert lr.contigs_of_reads(reads, K) == contigs == sorted(contigs), name
+    assert lr.contigs_of_reads(["ACGTT" * 3 + "ACGT"], K) == []
+
+
+def test_long_reads_are_skipped_not_threaded():
+    long_read = "ACGTT" * 820                                        # 4100 bases: 4096 k-mers at k = 5, 4097 at k = 4
+    assert lr.tables(CYCLE, [long_read], 5, 1, 9)["skipped"] == 0 and lr.tables(CYCLE, [long_read], 5, 1, 9)["link_support"] == [[0, 0, 0, 819]]
+    t = lr.tables(["ACGTTACG"], [long_read, "ACGTTACG"], 4, 1, 0)
+    assert t["skipped"] == 1 and t["link_support"] == [[0, 0, 0, 0]]
+
+
+def test_both_strands_thread_the_reverse_complements():
+    contigs = sorted(XRYRZ + [lr.rc(c) for c in XRYRZ])
+    t = lr.tables(contigs, [G], K, 2, 8)
+    twin = [contigs.index(lr.rc(c)) for c in contigs]
+    for a, b in lr.links_of(t["succ"]):
+        x, xt = "ACGT".index(contigs[b][K - 1]), "ACGT".index(contigs[twin[a]][K - 1])
+        assert t["link_support"][a][x] == t["link_support"][twin[b]][xt] == 1
+    r = contigs.index(R)
+    assert t["span_support"][r] == _tab(1, span={(0, "GC"): 1, (0, "AA"): 1})["span_support"][0]
+    assert t["span_support"][twin[r]] == _tab(1, span={(0, "GC"): 1, (0, "TT"): 1})["span_support"][0]      # rc: (x, y) -> (3 - y, 3 - x)
+    res = lr.resolve(contigs, K, 8, t, 1)
+    assert res == sorted([G, lr.rc(G)])
+
+
+# ---- resolve_repeats: links.py against the rule, and against its restatement
+def _contig_links(contigs, reads, span_len, strands=1):
+    from genomeassembler_dev_amd import links
+    t = lr.tables(contigs, reads, K, strands, span_len)
+    a = lambda key: np.array(t[key], dtype=np.uint32).reshape(-1)
+    return links.ContigLinks(K, span_len, strands, [0, len(contigs)], [list(contigs)], a("succ"), a("pred"), a("link_support"), a("span_support"),
+                             [t["skipped"]], [len(c) - K + 1 for c in contigs])
+
+
+RESOLVED = [
+    ("XRYRZ", XRYRZ, [G, G], 8, 2, [G]),
+    ("support below min_support", XRYRZ, [G], 8, 2, sorted(XRYRZ)),
+    ("min_support 1", XRYRZ, [G], 8, 1, [G]),
+    ("repeat longer than span_len", XRYRZ, [G, G], 7, 2, sorted(XRYRZ)),
+    ("mixed matrix", XRYRZ, CASES["mixed"][1], 8, 2, sorted(XRYRZ)),
+    ("three copies", THREE, [G3, G3], 8, 2, [G3]),
+    ("n(r) == 1", ONE, [G1, G1], 5, 2, [G1]),
+    ("a tandem repeat entered from itself", LOOP, [LOOP_ONCE, LOOP_THRICE] * 2, 10, 1, sorted(LOOP)),
+    ("unbranched cycle", CYCLE, ["ACGTT" * 3 + "ACGT"] * 2, 9, 1, CYCLE),
+    ("dead end", [X], [X + "TT"], 9, 1, [X]),
+    ("chained repeats", None, CHAIN_READS * 2, 8, 2, sorted(CHAIN_READS)),
+    ("closing chain", CIRCLE, [CIRCLE_READ] * 2, 8, 2, ["TCGC" + Z + R + Y + R]),
+]
+
+
+@pytest.mark.parametrize("name,contigs,reads,span_len,min_support,want", RESOLVED, ids=[r[0] for r in RESOLVED])
+def test_resolve_repeats(name, contigs, reads, span_len, min_support, want):
+    if contigs is None:
+        contigs = lr.contigs_of_reads(reads, K)
+        assert len(contigs) == 9 and R in contigs and R2 in contigs
+    t = lr.tables(contigs, reads, K, 1, span_len)
+    assert lr.resolve(contigs, K, span_len, t, min_support) == want
+    assert _contig_links(contigs, reads, span_len).resolve_repeats(0, min_support) == want
+
+
+def test_links_and_gfa():
+    cl = _contig_links(XRYRZ, [G, G], 8)
+    assert cl.links(0) == [(0, 1, 2), (1, 2, 2), (1, 3, 2), (3, 1, 2)]
+    gfa = cl.to_gfa(0).splitlines()
+    assert gfa[0] == "H\tVN:Z:1.0"
+    assert gfa[1:5] == [f"S\t{c}\t{s}\tKC:i:{len(s) - K + 1}" for c, s in enumerate(XRYRZ)]
+    assert gfa[5:] == ["L\t0\t+\t1\t+\t4M\tRC:i:2", "L\t1\t+\t2\t+\t4M\tRC:i:2", "L\t1\t+\t3\t+\t4M\tRC:i:2", "L\t3\t+\t1\t+\t4M\tRC:i:2"]
+    assert "SEPARATE S records" in type(cl).to_gfa.__doc__
+    assert cl.span_support(0)[1, 2, 1] == 2 and cl.skipped.tolist() == [0]
+
+
+def test_worked_example_on_the_cpu():
+    """the README's example, by the restatement alone: a 4 kb genome with one 40-base stretch planted twice, error-free 80-base reads at
+    30x, k = 21, forward strand: four contigs X, R, Y, Z; R's span matrix has two non-zero entries; the resolution is the genome"""
+    from genomeassembler_dev_amd import synth
+    seed, k = 28, 21
+    g, p1, p2 = synth.plant_repeat(synth.make_segment(seed, 4000, planted=False), 40, seed)
+    genome = g.tobytes().decode()
+    assert (p1, p2) == (1079, 1777) and genome[p1:p1 + 40] == genome[p2:p2 + 40]
+    reads = [r.tobytes().decode() for r in synth.simulate_reads(g, 80, 30, seed)]
+    contigs = lr.contigs_of_reads(reads, k)
+    assert [len(c) for c in contigs] == [698, 2203, 1099, 40] and contigs[3] == genome[p1:p1 + 40]
+    t = lr.tables(contigs, reads, k, 1, 80)
+    assert lr.consistent(t, contigs, k)
+    assert t["span_support"][3] == [[0, 0, 0, 0], [0, 0, 0, 15], [0, 0, 0, 0], [14, 0, 0, 0]]
+    assert t["link_support"] == [[23, 0, 0, 0], [0, 0, 0, 0], [26, 0, 0, 0], [20, 0, 0, 23]]
+    assert _wl(contigs, t, k).links(0) == [(0, 3, 23), (2, 3, 26), (3, 0, 20), (3, 1, 23)]        # Y -> R, X -> R, R -> Y, R -> Z
+    assert lr.resolve(contigs, k, 80, t, 2) == [genome]
+    assert _wl(contigs, t, k).resolve_repeats(0) == [genome]
+
+
+def _wl(contigs, t, k):
+    from genomeassembler_dev_amd import links
+    a = lambda key: np.array(t[key], dtype=np.uint32).reshape(-1)
+    return links.ContigLinks(k, 80, 1, [0, len(contigs)], [list(contigs)], a("succ"), a("pred"), a("link_support"), a("span_support"), [0],
+                             [0] * len(contigs))
