@@ -134,86 +134,63 @@ def _check_lowcov(cov_cutoff, cov_len, cov_rounds):
         raise ValueError(f"cov_rounds must be 1..{_lib.MAX_COV_ROUNDS} when cov_cutoff > 0 and cov_len > 0")
 
 
-def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
-                           tip_rounds=1):
-    """get_kmers_from_reads + get_contigs in one call (gasm_get_contigs_from_reads): the k-mers are taken on the GPU from the
-    packed reads instead of being exploded into len(reads) * (read_len - k + 1) strings first (lib/DeNovoAssembler.R:109-130).
-    reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed).
-    min_count > 1 (gasm_get_contigs_from_reads_solid): only k-mers seen at least min_count times become edges.
-    strands = 2 (gasm_get_contigs_from_reads_strands): the k-mers of every read and of its reverse complement.
-    tip_len > 0 (gasm_get_contigs_from_reads_tips): tip_rounds rounds of tip clipping before the contigs are cut (include/gasm.h).
-    Bubble popping behind the tips: get_contigs_from_reads_bubbles()."""
+def _check_build_opts(min_count=1, strands=1, tip_len=0, tip_rounds=1, bubble_len=0, bubble_rounds=1, cov_cutoff=0, cov_len=0, cov_rounds=1):
+    """the argument rules of every build entry, of SegmentBatch and of this module: ValueError before anything reaches the library"""
     if int(min_count) < 1:
         raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
     if int(strands) not in (1, 2):
         raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
     _check_tips(tip_len, tip_rounds)
+    _check_bubbles(bubble_len, bubble_rounds)
+    _check_lowcov(cov_cutoff, cov_len, cov_rounds)
+
+
+def _contigs_from_reads(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, **opts):
+    """every get_contigs_from_reads*() below: check the options, hand them to the library as one gasm_build_params
+    (gasm_get_contigs_from_reads_params)"""
+    _check_build_opts(**opts)
     ctx = ctx or default_context()
     buf, off = _pack(reads)
     h = C.c_void_p()
-    if int(tip_len) > 0:
-        check(lib().gasm_get_contigs_from_reads_tips(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
-                                                     int(min_count), int(strands), int(tip_len), int(tip_rounds), C.byref(h)))
-    elif int(strands) == 2:
-        check(lib().gasm_get_contigs_from_reads_strands(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
-                                                        int(min_count), 2, C.byref(h)))
-    elif int(min_count) == 1:
-        check(lib().gasm_get_contigs_from_reads(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows), C.byref(h)))
-    else:
-        check(lib().gasm_get_contigs_from_reads_solid(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
-                                                      int(min_count), C.byref(h)))
+    p = _lib.BuildParams.make(dbg_kmer, **opts)
+    check(lib().gasm_get_contigs_from_reads_params(ctx.h, buf, _ptr(off), len(reads), int(seed), int(matrix_rows), C.byref(p), C.byref(h)))
     return _contig_matrix(h, dbg_kmer, as_lists)
+
+
+def get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
+                           tip_rounds=1):
+    """get_kmers_from_reads + get_contigs in one call: the k-mers are taken on the GPU from the packed reads instead of being
+    exploded into len(reads) * (read_len - k + 1) strings first (lib/DeNovoAssembler.R:109-130).
+    reads: list of str / bytes.  Same ContigMatrix as get_contigs(get_kmers_from_reads(reads, k), k, seed).
+    min_count > 1: only k-mers seen at least min_count times become edges.
+    strands = 2: the k-mers of every read and of its reverse complement.
+    tip_len > 0: tip_rounds rounds of tip clipping before the contigs are cut (include/gasm.h).
+    Bubble popping behind the tips: get_contigs_from_reads_bubbles()."""
+    return _contigs_from_reads(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count=min_count, strands=strands, tip_len=tip_len,
+                               tip_rounds=tip_rounds)
 
 
 def get_contigs_from_reads_bubbles(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, min_count=1, strands=1, tip_len=0,
                                    tip_rounds=1, bubble_len=0, bubble_rounds=1):
-    """get_contigs_from_reads with bubble popping (gasm_get_contigs_from_reads_bubbles): after the tip rounds, bubble_rounds rounds
-    (1.._lib.MAX_BUBBLE_ROUNDS) in which every contig of at most bubble_len bases (<= _lib.MAX_BUBBLE_LEN) beside which a parallel
-    one of strictly higher mean multiplicity runs leaves the k-mer set (the rule: include/gasm.h).  bubble_len = 0 is
-    get_contigs_from_reads(..., tip_len, tip_rounds), and bubble_rounds is not read.  (An entry of its own, as build_bubbles() is
-    beside build_tips(): get_contigs_from_reads keeps its parameter list.)"""
-    _check_bubbles(bubble_len, bubble_rounds)
-    if int(bubble_len) == 0:
-        return get_contigs_from_reads(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count, strands, tip_len, tip_rounds)
-    if int(min_count) < 1:
-        raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-    if int(strands) not in (1, 2):
-        raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
-    _check_tips(tip_len, tip_rounds)
-    ctx = ctx or default_context()
-    buf, off = _pack(reads)
-    h = C.c_void_p()
-    check(lib().gasm_get_contigs_from_reads_bubbles(ctx.h, buf, _ptr(off), len(reads), int(dbg_kmer), int(seed), int(matrix_rows),
-                                                    int(min_count), int(strands), int(tip_len), int(tip_rounds) if int(tip_len) else 0,
-                                                    int(bubble_len), int(bubble_rounds), C.byref(h)))
-    return _contig_matrix(h, dbg_kmer, as_lists)
+    """get_contigs_from_reads with bubble popping: after the tip rounds, bubble_rounds rounds (1.._lib.MAX_BUBBLE_ROUNDS) in which
+    every contig of at most bubble_len bases (<= _lib.MAX_BUBBLE_LEN) beside which a parallel one of strictly higher mean
+    multiplicity runs leaves the k-mer set (the rule: include/gasm.h).  bubble_len = 0 is get_contigs_from_reads(..., tip_len,
+    tip_rounds), and bubble_rounds is not read.  (An entry of its own, as build_bubbles() is beside build_tips():
+    get_contigs_from_reads keeps its parameter list.)"""
+    return _contigs_from_reads(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count=min_count, strands=strands, tip_len=tip_len,
+                               tip_rounds=tip_rounds, bubble_len=bubble_len, bubble_rounds=bubble_rounds)
 
 
 def get_contigs_from_reads_simplified(reads, dbg_kmer, seed, matrix_rows=10000, ctx=None, as_lists=False, *, min_count=1, strands=1, tip_len=0,
                                       tip_rounds=1, bubble_len=0, bubble_rounds=1, cov_cutoff=0, cov_len=0, cov_rounds=1):
-    """get_contigs_from_reads_bubbles with low-coverage removal (gasm_get_contigs_from_reads_params): after the tip and the bubble
-    rounds, cov_rounds rounds (1.._lib.MAX_COV_ROUNDS) in which every contig of at most cov_len bases (<= _lib.MAX_BUBBLE_LEN) whose mean
-    multiplicity is strictly below cov_cutoff leaves the k-mer set, attached or not (the rule: include/gasm.h).  cov_cutoff = 0 or
-    cov_len = 0 is get_contigs_from_reads_bubbles with the other arguments, and cov_rounds is not read.  The knobs are keyword-only:
-    the positional chain ends with get_contigs_from_reads_bubbles."""
-    _check_lowcov(cov_cutoff, cov_len, cov_rounds)
-    if int(cov_cutoff) == 0 or int(cov_len) == 0:
-        return get_contigs_from_reads_bubbles(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count, strands, tip_len, tip_rounds, bubble_len,
-                                              bubble_rounds)
-    if int(min_count) < 1:
-        raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-    if int(strands) not in (1, 2):
-        raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
-    _check_tips(tip_len, tip_rounds)
-    _check_bubbles(bubble_len, bubble_rounds)
-    ctx = ctx or default_context()
-    buf, off = _pack(reads)
-    h = C.c_void_p()
-    p = _lib.BuildParams.make(dbg_kmer, min_count=min_count, strands=strands, tip_len=tip_len, tip_rounds=tip_rounds if int(tip_len) else 0,
-                              bubble_len=bubble_len, bubble_rounds=bubble_rounds if int(bubble_len) else 0, cov_cutoff=cov_cutoff, cov_len=cov_len,
-                              cov_rounds=cov_rounds)
-    check(lib().gasm_get_contigs_from_reads_params(ctx.h, buf, _ptr(off), len(reads), int(seed), int(matrix_rows), C.byref(p), C.byref(h)))
-    return _contig_matrix(h, dbg_kmer, as_lists)
+    """get_contigs_from_reads_bubbles with low-coverage removal: after the tip and the bubble rounds, cov_rounds rounds
+    (1.._lib.MAX_COV_ROUNDS) in which every contig of at most cov_len bases (<= _lib.MAX_BUBBLE_LEN) whose mean multiplicity is
+    strictly below cov_cutoff leaves the k-mer set, attached or not (the rule: include/gasm.h).  cov_cutoff = 0 or cov_len = 0 is
+    get_contigs_from_reads_bubbles with the other arguments, and cov_rounds is not read.  The knobs are keyword-only: the
+    positional chain ends with get_contigs_from_reads_bubbles."""
+    return _contigs_from_reads(reads, dbg_kmer, seed, matrix_rows, ctx, as_lists, min_count=min_count, strands=strands, tip_len=tip_len,
+                               tip_rounds=tip_rounds, bubble_len=bubble_len, bubble_rounds=bubble_rounds, cov_cutoff=cov_cutoff, cov_len=cov_len,
+                               cov_rounds=cov_rounds)
 
 
 def _contig_matrix(h, dbg_kmer, as_lists):

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import qtable, readkmers
 from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
-from .api import _check_bubbles, _check_lowcov, _check_tips, unpack_kmers
+from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 
 
@@ -119,86 +119,50 @@ class SegmentBatch:
         self.dropped_reads = int(dropped.value)
         return self
 
-    def build(self, k, genome_len_hint=0, min_count=1, strands=1):
-        """queue a build.  min_count > 1 (gasm_batch_build_solid): only the k-mers seen at least min_count times in their segment
-        become edges — the cutoff for reads with sequencing errors; everything after the build sees the survivors only.
-        genome_len_hint then counts the distinct k-mers before the cutoff (include/gasm.h).
-        strands = 2 (gasm_batch_build_strands): the k-mers of every read and of its reverse complement — reads of both strands
-        then meet in one graph, multiplicities (and min_count) are sums over both strands, and the contigs come in
-        reverse-complement pairs (contig_twins).  Scores are over the reads as they were given, each once.
-        Tip clipping: build_tips().  Bubble popping: build_bubbles().  Low-coverage removal: build_simplified()."""
-        if int(min_count) < 1:
-            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-        if int(strands) not in (1, 2):
-            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
-        if int(strands) == 2:
-            check(lib().gasm_batch_build_strands(self.h, int(k), int(genome_len_hint), int(min_count), 2))
-        elif int(min_count) == 1:
-            check(lib().gasm_batch_build(self.h, int(k), int(genome_len_hint)))
-        else:
-            check(lib().gasm_batch_build_solid(self.h, int(k), int(genome_len_hint), int(min_count)))
-        self.k, self._min_count = int(k), int(min_count)
+    def _build(self, k, genome_len_hint, **opts):
+        """every build*() below: check the options, hand them to the library as one gasm_build_params (gasm_batch_build_params).  The
+        rounds of a feature that is off are not read, here or there."""
+        _check_build_opts(**opts)
+        check(lib().gasm_batch_build_params(self.h, C.byref(BuildParams.make(k, genome_len_hint=genome_len_hint, **opts))))
+        self.k, self._min_count = int(k), int(opts.get("min_count", 1))
         return self
+
+    def build(self, k, genome_len_hint=0, min_count=1, strands=1):
+        """queue a build.  min_count > 1: only the k-mers seen at least min_count times in their segment become edges — the cutoff
+        for reads with sequencing errors; everything after the build sees the survivors only.  genome_len_hint then counts the
+        distinct k-mers before the cutoff (include/gasm.h).
+        strands = 2: the k-mers of every read and of its reverse complement — reads of both strands then meet in one graph,
+        multiplicities (and min_count) are sums over both strands, and the contigs come in reverse-complement pairs
+        (contig_twins).  Scores are over the reads as they were given, each once.
+        Tip clipping: build_tips().  Bubble popping: build_bubbles().  Low-coverage removal: build_simplified()."""
+        return self._build(k, genome_len_hint, min_count=min_count, strands=strands)
 
     def build_tips(self, k, genome_len_hint=0, min_count=1, strands=1, tip_len=0, tip_rounds=1):
-        """build() with tip clipping (gasm_batch_build_tips): exactly tip_rounds rounds (1.._lib.MAX_TIP_ROUNDS) behind the cutoff
-        — a contig of at most tip_len bases that dead-ends on one side and hangs, on the other, on a node with a strictly
-        stronger sibling edge leaves the k-mer set with all its k-mers (the rule: include/gasm.h); 2k - 1 is the intended
-        length.  tip_stats() tells what each round removed.  tip_len = 0 is build(k, genome_len_hint, min_count, strands):
-        the same call into the library, and tip_rounds is not read."""
-        if int(tip_len) == 0:
-            return self.build(k, genome_len_hint, min_count, strands)
-        if int(min_count) < 1:
-            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-        if int(strands) not in (1, 2):
-            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
-        _check_tips(tip_len, tip_rounds)
-        check(lib().gasm_batch_build_tips(self.h, int(k), int(genome_len_hint), int(min_count), int(strands), int(tip_len), int(tip_rounds)))
-        self.k, self._min_count = int(k), int(min_count)
-        return self
+        """build() with tip clipping: exactly tip_rounds rounds (1.._lib.MAX_TIP_ROUNDS) behind the cutoff — a contig of at most
+        tip_len bases that dead-ends on one side and hangs, on the other, on a node with a strictly stronger sibling edge leaves
+        the k-mer set with all its k-mers (the rule: include/gasm.h); 2k - 1 is the intended length.  tip_stats() tells what each
+        round removed.  tip_len = 0 is build(k, genome_len_hint, min_count, strands): the same build, and tip_rounds is not read."""
+        return self._build(k, genome_len_hint, min_count=min_count, strands=strands, tip_len=tip_len, tip_rounds=tip_rounds)
 
     def build_bubbles(self, k, genome_len_hint=0, min_count=1, strands=1, tip_len=0, tip_rounds=1, bubble_len=0, bubble_rounds=1):
-        """build_tips() with bubble popping (gasm_batch_build_bubbles): exactly bubble_rounds rounds (1.._lib.MAX_BUBBLE_ROUNDS)
-        behind the tip rounds — a contig of at most bubble_len bases (<= _lib.MAX_BUBBLE_LEN) beside which a parallel one (same
-        first and last node, at most bubble_len bases too) of strictly higher mean multiplicity runs leaves the k-mer set with
-        all its k-mers (the rule: include/gasm.h); 2k - 1 is the intended length.  bubble_stats() tells what each round removed.
-        bubble_len = 0 is build_tips(k, genome_len_hint, min_count, strands, tip_len, tip_rounds), and bubble_rounds is not read."""
-        if int(bubble_len) == 0:
-            return self.build_tips(k, genome_len_hint, min_count, strands, tip_len, tip_rounds)
-        if int(min_count) < 1:
-            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-        if int(strands) not in (1, 2):
-            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
-        _check_tips(tip_len, tip_rounds)
-        _check_bubbles(bubble_len, bubble_rounds)
-        check(lib().gasm_batch_build_bubbles(self.h, int(k), int(genome_len_hint), int(min_count), int(strands), int(tip_len),
-                                             int(tip_rounds) if int(tip_len) else 0, int(bubble_len), int(bubble_rounds)))
-        self.k, self._min_count = int(k), int(min_count)
-        return self
+        """build_tips() with bubble popping: exactly bubble_rounds rounds (1.._lib.MAX_BUBBLE_ROUNDS) behind the tip rounds — a contig
+        of at most bubble_len bases (<= _lib.MAX_BUBBLE_LEN) beside which a parallel one (same first and last node, at most
+        bubble_len bases too) of strictly higher mean multiplicity runs leaves the k-mer set with all its k-mers (the rule:
+        include/gasm.h); 2k - 1 is the intended length.  bubble_stats() tells what each round removed.  bubble_len = 0 is
+        build_tips(k, genome_len_hint, min_count, strands, tip_len, tip_rounds), and bubble_rounds is not read."""
+        return self._build(k, genome_len_hint, min_count=min_count, strands=strands, tip_len=tip_len, tip_rounds=tip_rounds, bubble_len=bubble_len,
+                           bubble_rounds=bubble_rounds)
 
     def build_simplified(self, k, genome_len_hint=0, *, min_count=1, strands=1, tip_len=0, tip_rounds=1, bubble_len=0, bubble_rounds=1, cov_cutoff=0,
                          cov_len=0, cov_rounds=1):
-        """build_bubbles() with low-coverage removal (gasm_batch_build_params): exactly cov_rounds rounds (1.._lib.MAX_COV_ROUNDS) behind
-        the tip and the bubble rounds — a contig of at most cov_len bases (<= _lib.MAX_BUBBLE_LEN) whose mean multiplicity is strictly
-        below cov_cutoff leaves the k-mer set with all its k-mers, whatever is attached to it (the rule: include/gasm.h).  The intended
-        setting is cov_len = 2k - 1, cov_cutoff = min_count + 1, one round; suggest_cov_cutoff() derives a cutoff from a build's own
-        contigs.  lowcov_stats() tells what each round removed.  cov_cutoff = 0 or cov_len = 0 is build_bubbles() with the other
-        arguments, and cov_rounds is not read.  The knobs are keyword-only: the positional chain ends with build_bubbles()."""
-        _check_lowcov(cov_cutoff, cov_len, cov_rounds)
-        if int(cov_cutoff) == 0 or int(cov_len) == 0:
-            return self.build_bubbles(k, genome_len_hint, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds)
-        if int(min_count) < 1:
-            raise ValueError("min_count must be >= 1 (1 keeps every k-mer)")
-        if int(strands) not in (1, 2):
-            raise ValueError("strands must be 1 (forward k-mers only) or 2 (both strands)")
-        _check_tips(tip_len, tip_rounds)
-        _check_bubbles(bubble_len, bubble_rounds)
-        p = BuildParams.make(k, genome_len_hint=genome_len_hint, min_count=min_count, strands=strands, tip_len=tip_len,
-                             tip_rounds=tip_rounds if int(tip_len) else 0, bubble_len=bubble_len, bubble_rounds=bubble_rounds if int(bubble_len) else 0,
-                             cov_cutoff=cov_cutoff, cov_len=cov_len, cov_rounds=cov_rounds)
-        check(lib().gasm_batch_build_params(self.h, C.byref(p)))
-        self.k, self._min_count = int(k), int(min_count)
-        return self
+        """build_bubbles() with low-coverage removal: exactly cov_rounds rounds (1.._lib.MAX_COV_ROUNDS) behind the tip and the bubble
+        rounds — a contig of at most cov_len bases (<= _lib.MAX_BUBBLE_LEN) whose mean multiplicity is strictly below cov_cutoff leaves
+        the k-mer set with all its k-mers, whatever is attached to it (the rule: include/gasm.h).  The intended setting is
+        cov_len = 2k - 1, cov_cutoff = min_count + 1, one round; suggest_cov_cutoff() derives a cutoff from a build's own contigs.
+        lowcov_stats() tells what each round removed.  cov_cutoff = 0 or cov_len = 0 is build_bubbles() with the other arguments, and
+        cov_rounds is not read.  The knobs are keyword-only: the positional chain ends with build_bubbles()."""
+        return self._build(k, genome_len_hint, min_count=min_count, strands=strands, tip_len=tip_len, tip_rounds=tip_rounds, bubble_len=bubble_len,
+                           bubble_rounds=bubble_rounds, cov_cutoff=cov_cutoff, cov_len=cov_len, cov_rounds=cov_rounds)
 
     def solid_stats(self):
         """(distinct k-mers per segment before the last build's cutoff, after it): two uint64 arrays, equal at min_count = 1"""
@@ -208,41 +172,31 @@ class SegmentBatch:
         return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint64)), shape=(n,)).copy(),
                 np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint64)), shape=(n,)).copy())
 
-    def tip_stats(self):
-        """(contigs clipped, k-mers clipped) by the last build's tip clipping: two (n_segments, MAX_TIP_ROUNDS) uint32 arrays,
-        column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would clip more."""
+    def _round_stats(self, fetch, max_rounds):
+        """the two (n_segments, max_rounds) uint32 arrays of one gasm_batch_fetch_*_stats entry"""
         a, b = C.c_void_p(), C.c_void_p()
-        check(lib().gasm_batch_fetch_tip_stats(self.h, C.byref(a), C.byref(b)))
-        n = self.n_segments * MAX_TIP_ROUNDS
-        shape = (self.n_segments, MAX_TIP_ROUNDS)
+        check(fetch(self.h, C.byref(a), C.byref(b)))
+        n = self.n_segments * max_rounds
+        shape = (self.n_segments, max_rounds)
         if not n:
             return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
         return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
                 np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
+
+    def tip_stats(self):
+        """(contigs clipped, k-mers clipped) by the last build's tip clipping: two (n_segments, MAX_TIP_ROUNDS) uint32 arrays,
+        column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would clip more."""
+        return self._round_stats(lib().gasm_batch_fetch_tip_stats, MAX_TIP_ROUNDS)
 
     def bubble_stats(self):
         """(contigs popped, k-mers popped) by the last build's bubble popping: two (n_segments, MAX_BUBBLE_ROUNDS) uint32 arrays,
         column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would pop more."""
-        a, b = C.c_void_p(), C.c_void_p()
-        check(lib().gasm_batch_fetch_bubble_stats(self.h, C.byref(a), C.byref(b)))
-        n = self.n_segments * MAX_BUBBLE_ROUNDS
-        shape = (self.n_segments, MAX_BUBBLE_ROUNDS)
-        if not n:
-            return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
-        return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
-                np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
+        return self._round_stats(lib().gasm_batch_fetch_bubble_stats, MAX_BUBBLE_ROUNDS)
 
     def lowcov_stats(self):
         """(contigs removed, k-mers removed) by the last build's low-coverage removal: two (n_segments, MAX_COV_ROUNDS) uint32 arrays,
         column r = round r, zero for rounds not run.  A non-zero last round run: more rounds would remove more."""
-        a, b = C.c_void_p(), C.c_void_p()
-        check(lib().gasm_batch_fetch_lowcov_stats(self.h, C.byref(a), C.byref(b)))
-        n = self.n_segments * MAX_COV_ROUNDS
-        shape = (self.n_segments, MAX_COV_ROUNDS)
-        if not n:
-            return np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
-        return (np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape),
-                np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_uint32)), shape=(n,)).copy().reshape(shape))
+        return self._round_stats(lib().gasm_batch_fetch_lowcov_stats, MAX_COV_ROUNDS)
 
     def contig_coverage(self, segment=None):
         """(mult_sum uint64, n_edges uint32) of the last build's contigs (gasm_batch_contig_coverage), one entry per contig in the

@@ -62,7 +62,7 @@ struct gasm_batch {
     // such build and shared read-only by every step slot; scoring, read k-mer counts and the guided traversal keep `rd`
     DevReads rd2;
     // the reads the build a slot holds was made from (whoever finishes, repeats or fetches that build hands them on)
-    DevReads& build_reads(const StepSlot& x) { return x.bs.strands == 2 ? rd2 : rd; }
+    DevReads& build_reads(const StepSlot& x) { return x.bs.opts.strands == 2 ? rd2 : rd; }
     // the breakage tables of gasm_batch_score(_tables) (table 0: what gasm_batch_score, gasm_batch_guided and the plain
     // fetches use) and what each was set from (empty: never); a table stays resident until another takes its place
     ScoreTable tb[GASM_MAX_TABLES];
@@ -161,18 +161,17 @@ static int breakscore_impl(gasm_ctx* ctx, DevPaths& dp, const std::function<std:
                            int variant, int flags, gasm_scores** out);
 
 // ------------------------------------------------------------------------------------------------- get_contigs
-// reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix
-static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_off, u64 n_reads, u32 fixed_len, int dbg_kmer, int seed, int matrix_rows,
-                            gasm_contigs** out, u32 min_count = 1, u32 strands = 1, u32 tip_len = 0, u32 tip_rounds = 0, u32 bubble_len = 0,
-                            u32 bubble_rounds = 0, u32 cov_cutoff = 0, u32 cov_len = 0, u32 cov_rounds = 0) {
+// reads (ragged when read_off != nullptr, else n_reads reads of fixed_len) of ONE segment -> contigs + shuffle matrix; `o` has passed
+// build_opts_check
+static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_off, u64 n_reads, u32 fixed_len, int seed, int matrix_rows, gasm_contigs** out,
+                            const BuildOpts& o) {
     DevReads rd, rd2;
     BuildState bs;
     const u64 seg_off[2] = {0, n_reads};
     int st = rd.upload(ctx, bases, read_off, n_reads, fixed_len, seg_off, 1);
-    if (st == GASM_OK && strands == 2) st = rd2.make_both_strands(ctx, rd);
-    DevReads& br = strands == 2 ? rd2 : rd;
-    if (st == GASM_OK) st = pipeline_build(ctx, br, dbg_kmer, 0, bs, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds, cov_cutoff, cov_len,
-                                            cov_rounds);
+    if (st == GASM_OK && o.strands == 2) st = rd2.make_both_strands(ctx, rd);
+    DevReads& br = o.strands == 2 ? rd2 : rd;
+    if (st == GASM_OK) st = pipeline_build(ctx, br, bs, o);
     if (st == GASM_OK) st = pipeline_fetch_distinct(ctx, br, bs);
     if (st == GASM_OK) st = pipeline_fetch_contigs(ctx, br, bs);
     gasm_contigs* c = nullptr;
@@ -194,60 +193,32 @@ static int contigs_of_reads(gasm_ctx* ctx, const char* bases, const u64* read_of
     return GASM_OK;
 }
 
-// the argument checks the gasm_get_contigs_from_reads* entries share; `entry`: the one that was called
-static int check_from_reads_args(const char* entry, const gasm_ctx* ctx, const char* reads, const u64* read_off, u64 n_reads, int matrix_rows, u32 min_count,
-                                 u32 strands, gasm_contigs** out) {
+// what every gasm_get_contigs_from_reads* entry does with the options it filled `o` from; `entry`: the one that was called
+static int contigs_from_reads(const char* entry, gasm_ctx* ctx, const char* reads, const u64* read_off, u64 n_reads, int seed, int matrix_rows, const BuildOpts& o,
+                              gasm_contigs** out) {
     if (!ctx || !out || (n_reads && (!reads || !read_off))) { gasm_set_error("%s: null argument", entry); return GASM_ERR_INVALID; }
     if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
-    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
-    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
+    // (min_count and strands in front of *out = nullptr, the other options behind it: the order the entries have always had)
+    BuildOpts first;
+    first.min_count = o.min_count; first.strands = o.strands;
+    GCHK(build_opts_check(first));
     *out = nullptr;
-    return GASM_OK;
+    GCHK(build_opts_check(o));
+    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, seed, matrix_rows, out, o);
 }
 
-// tip_len == 0: no clipping, tip_rounds is not read
-static int check_tip_args(u32 tip_len, u32 tip_rounds) {
-    if (tip_len && (tip_rounds < 1 || tip_rounds > GASM_MAX_TIP_ROUNDS)) {
-        gasm_set_error("tip_rounds must be 1..%d when tip_len > 0 (got %u)", GASM_MAX_TIP_ROUNDS, tip_rounds);
-        return GASM_ERR_INVALID;
-    }
-    return GASM_OK;
-}
-
-// bubble_len == 0: no popping, bubble_rounds is not read
-static int check_bubble_args(u32 bubble_len, u32 bubble_rounds) {
-    if (bubble_len > GASM_MAX_BUBBLE_LEN) {
-        gasm_set_error("bubble_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, bubble_len);
-        return GASM_ERR_INVALID;
-    }
-    if (bubble_len && (bubble_rounds < 1 || bubble_rounds > GASM_MAX_BUBBLE_ROUNDS)) {
-        gasm_set_error("bubble_rounds must be 1..%d when bubble_len > 0 (got %u)", GASM_MAX_BUBBLE_ROUNDS, bubble_rounds);
-        return GASM_ERR_INVALID;
-    }
-    return GASM_OK;
-}
-
-// cov_cutoff == 0 or cov_len == 0: no low-coverage removal, cov_rounds is not read
-static int check_cov_args(u32 cov_cutoff, u32 cov_len, u32 cov_rounds) {
-    if (!cov_cutoff || !cov_len) return GASM_OK;
-    if (cov_len > GASM_MAX_BUBBLE_LEN) {
-        gasm_set_error("cov_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, cov_len);
-        return GASM_ERR_INVALID;
-    }
-    if (cov_rounds < 1 || cov_rounds > GASM_MAX_COV_ROUNDS) {
-        gasm_set_error("cov_rounds must be 1..%d when cov_cutoff > 0 and cov_len > 0 (got %u)", GASM_MAX_COV_ROUNDS, cov_rounds);
-        return GASM_ERR_INVALID;
-    }
-    return GASM_OK;
-}
-
-// the struct form's own checks; the fields' are those of the positional entries
-static int check_build_params(const char* entry, const gasm_build_params* p) {
+// the struct form: its own checks (null, size) and its "0 means default" mapping; the fields' rules are build_opts_check's
+static int opts_from_params(const char* entry, const gasm_build_params* p, BuildOpts& o) {
     if (!p) { gasm_set_error("%s: params is null", entry); return GASM_ERR_INVALID; }
     if (p->size != sizeof(gasm_build_params)) {
         gasm_set_error("%s: params->size is %u, this library's gasm_build_params has %zu bytes", entry, p->size, sizeof(gasm_build_params));
         return GASM_ERR_INVALID;
     }
+    o.k = p->k; o.genome_len_hint = p->genome_len_hint;
+    o.min_count = p->min_count ? p->min_count : 1; o.strands = p->strands ? p->strands : 1;
+    o.tip_len = p->tip_len; o.tip_rounds = p->tip_rounds;
+    o.bubble_len = p->bubble_len; o.bubble_rounds = p->bubble_rounds;
+    o.cov_cutoff = p->cov_cutoff; o.cov_len = p->cov_len; o.cov_rounds = p->cov_rounds;
     return GASM_OK;
 }
 
@@ -258,31 +229,36 @@ int gasm_get_contigs(gasm_ctx* ctx, const char* kmers, uint64_t n_kmers, int dbg
     if (matrix_rows < 0) { gasm_set_error("matrix_rows must be >= 0"); return GASM_ERR_INVALID; }
     *out = nullptr;
     // the exploded k-mers are reads of length k with one k-mer each
-    return contigs_of_reads(ctx, kmers, nullptr, n_kmers, (u32)dbg_kmer, dbg_kmer, seed, matrix_rows, out);
+    BuildOpts o;
+    o.k = dbg_kmer;
+    return contigs_of_reads(ctx, kmers, nullptr, n_kmers, (u32)dbg_kmer, seed, matrix_rows, out, o);
     API_GUARD_END
 }
 
 int gasm_get_contigs_from_reads(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                 int matrix_rows, gasm_contigs** out) {
     API_GUARD_BEGIN
-    GCHK(check_from_reads_args("gasm_get_contigs_from_reads", ctx, reads, read_off, n_reads, matrix_rows, 1, 1, out));
-    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out);
+    BuildOpts o;
+    o.k = dbg_kmer;
+    return contigs_from_reads("gasm_get_contigs_from_reads", ctx, reads, read_off, n_reads, seed, matrix_rows, o, out);
     API_GUARD_END
 }
 
 int gasm_get_contigs_from_reads_solid(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                       int matrix_rows, uint32_t min_count, gasm_contigs** out) {
     API_GUARD_BEGIN
-    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_solid", ctx, reads, read_off, n_reads, matrix_rows, min_count, 1, out));
-    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count);
+    BuildOpts o;
+    o.k = dbg_kmer; o.min_count = min_count;
+    return contigs_from_reads("gasm_get_contigs_from_reads_solid", ctx, reads, read_off, n_reads, seed, matrix_rows, o, out);
     API_GUARD_END
 }
 
 int gasm_get_contigs_from_reads_strands(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int dbg_kmer, int seed,
                                         int matrix_rows, uint32_t min_count, uint32_t strands, gasm_contigs** out) {
     API_GUARD_BEGIN
-    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_strands", ctx, reads, read_off, n_reads, matrix_rows, min_count, strands, out));
-    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count, strands);
+    BuildOpts o;
+    o.k = dbg_kmer; o.min_count = min_count; o.strands = strands;
+    return contigs_from_reads("gasm_get_contigs_from_reads_strands", ctx, reads, read_off, n_reads, seed, matrix_rows, o, out);
     API_GUARD_END
 }
 
@@ -290,9 +266,9 @@ int gasm_get_contigs_from_reads_tips(gasm_ctx* ctx, const char* reads, const uin
                                      int matrix_rows, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
                                      gasm_contigs** out) {
     API_GUARD_BEGIN
-    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_tips", ctx, reads, read_off, n_reads, matrix_rows, min_count, strands, out));
-    GCHK(check_tip_args(tip_len, tip_rounds));
-    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count, strands, tip_len, tip_rounds);
+    BuildOpts o;
+    o.k = dbg_kmer; o.min_count = min_count; o.strands = strands; o.tip_len = tip_len; o.tip_rounds = tip_rounds;
+    return contigs_from_reads("gasm_get_contigs_from_reads_tips", ctx, reads, read_off, n_reads, seed, matrix_rows, o, out);
     API_GUARD_END
 }
 
@@ -300,26 +276,19 @@ int gasm_get_contigs_from_reads_bubbles(gasm_ctx* ctx, const char* reads, const 
                                         int matrix_rows, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
                                         uint32_t bubble_len, uint32_t bubble_rounds, gasm_contigs** out) {
     API_GUARD_BEGIN
-    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_bubbles", ctx, reads, read_off, n_reads, matrix_rows, min_count, strands, out));
-    GCHK(check_tip_args(tip_len, tip_rounds));
-    GCHK(check_bubble_args(bubble_len, bubble_rounds));
-    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, dbg_kmer, seed, matrix_rows, out, min_count, strands, tip_len, tip_len ? tip_rounds : 0,
-                            bubble_len, bubble_len ? bubble_rounds : 0);
+    BuildOpts o;
+    o.k = dbg_kmer; o.min_count = min_count; o.strands = strands; o.tip_len = tip_len; o.tip_rounds = tip_rounds;
+    o.bubble_len = bubble_len; o.bubble_rounds = bubble_rounds;
+    return contigs_from_reads("gasm_get_contigs_from_reads_bubbles", ctx, reads, read_off, n_reads, seed, matrix_rows, o, out);
     API_GUARD_END
 }
 
 int gasm_get_contigs_from_reads_params(gasm_ctx* ctx, const char* reads, const uint64_t* read_off, uint64_t n_reads, int seed, int matrix_rows,
                                        const gasm_build_params* params, gasm_contigs** out) {
     API_GUARD_BEGIN
-    GCHK(check_build_params("gasm_get_contigs_from_reads_params", params));
-    const gasm_build_params& p = *params;
-    const u32 min_count = p.min_count ? p.min_count : 1, strands = p.strands ? p.strands : 1;
-    GCHK(check_from_reads_args("gasm_get_contigs_from_reads_params", ctx, reads, read_off, n_reads, matrix_rows, min_count, strands, out));
-    GCHK(check_tip_args(p.tip_len, p.tip_rounds));
-    GCHK(check_bubble_args(p.bubble_len, p.bubble_rounds));
-    GCHK(check_cov_args(p.cov_cutoff, p.cov_len, p.cov_rounds));
-    return contigs_of_reads(ctx, reads, read_off, n_reads, 0, p.k, seed, matrix_rows, out, min_count, strands, p.tip_len, p.tip_len ? p.tip_rounds : 0,
-                            p.bubble_len, p.bubble_len ? p.bubble_rounds : 0, p.cov_cutoff, p.cov_len, p.cov_cutoff && p.cov_len ? p.cov_rounds : 0);
+    BuildOpts o;
+    GCHK(opts_from_params("gasm_get_contigs_from_reads_params", params, o));
+    return contigs_from_reads("gasm_get_contigs_from_reads_params", ctx, reads, read_off, n_reads, seed, matrix_rows, o, out);
     API_GUARD_END
 }
 
@@ -867,17 +836,10 @@ void gasm_batch_free(gasm_batch* b) {
     delete b;
 }
 
-// gasm_batch_build (min_count = 1), gasm_batch_build_solid (strands = 1), gasm_batch_build_strands (tip_len = 0), gasm_batch_build_tips
-// (bubble_len = 0), gasm_batch_build_bubbles (cov_cutoff = 0) and gasm_batch_build_params
-static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands = 1, uint32_t tip_len = 0,
-                       uint32_t tip_rounds = 0, uint32_t bubble_len = 0, uint32_t bubble_rounds = 0, uint32_t cov_cutoff = 0, uint32_t cov_len = 0,
-                       uint32_t cov_rounds = 0) {
+// every gasm_batch_build* entry, with the options it filled `o` from
+static int batch_build(gasm_batch* b, const BuildOpts& o) {
     if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
-    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
-    GCHK(check_tip_args(tip_len, tip_rounds));
-    GCHK(check_bubble_args(bubble_len, bubble_rounds));
-    GCHK(check_cov_args(cov_cutoff, cov_len, cov_rounds));
+    GCHK(build_opts_check(o));                // (everything is refused here: nothing below is undone, and the build before stays fetchable)
     b->built = false; b->scored = false;
     // consecutive steps take the slots in turn: this build does not wait for the last steps' graph and scoring, it runs
     // beside them.  A change of k rewrites the tile tables every slot reads: everything drains first.  GASM_PINGPONG=0: the
@@ -886,111 +848,111 @@ static int batch_build(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t 
     if (pingpong && b->slot[0].cx == nullptr && b->slot[1].cx == nullptr)       // (fixed with the first build)
         b->n_slots = std::max(2, std::min(4, env_int("GASM_STEP_SLOTS", 3)));
     if (pingpong) {
-        if (b->last_k && b->last_k != k) for (StepSlot& x : b->slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));
+        if (b->last_k && b->last_k != o.k) for (StepSlot& x : b->slot) if (x.cx) HIPCHK(hipStreamSynchronize(x.cx->stream));
         b->cur = (b->cur + 1) % b->n_slots;
     }
     StepSlot& st = b->S();
     st.paths_ready = false; st.ss.valid = false; st.ss.launched = false;
     // both strands: the reverse-complemented stream is made once per upload (on this slot's stream, complete before the call
     // returns: the other slots read it without waiting for this one)
-    if (strands == 2 && b->rd2.strands_of != b->rd.upload_id) GCHK(b->rd2.make_both_strands(st.cx, b->rd));
-    // (the slot's BuildState keeps the cutoff, the strands, the tip clipping, the bubble popping and the low-coverage removal of the
-    // build it holds)
-    GCHK(pipeline_build(st.cx, strands == 2 ? b->rd2 : b->rd, k, genome_len_hint, st.bs, min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds,
-                        cov_cutoff, cov_len, cov_rounds));
-    b->last_k = k;
+    if (o.strands == 2 && b->rd2.strands_of != b->rd.upload_id) GCHK(b->rd2.make_both_strands(st.cx, b->rd));
+    // (the slot's BuildState keeps the options of the build it holds)
+    GCHK(pipeline_build(st.cx, o.strands == 2 ? b->rd2 : b->rd, st.bs, o));
+    b->last_k = o.k;
     b->built = true;
     return GASM_OK;
 }
 
 int gasm_batch_build(gasm_batch* b, int k, uint64_t genome_len_hint) {
     API_GUARD_BEGIN
-    return batch_build(b, k, genome_len_hint, 1);
+    BuildOpts o;
+    o.k = k; o.genome_len_hint = genome_len_hint;
+    return batch_build(b, o);
     API_GUARD_END
 }
 
 int gasm_batch_build_solid(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count) {
     API_GUARD_BEGIN
-    return batch_build(b, k, genome_len_hint, min_count);
+    BuildOpts o;
+    o.k = k; o.genome_len_hint = genome_len_hint; o.min_count = min_count;
+    return batch_build(b, o);
     API_GUARD_END
 }
 
 int gasm_batch_build_strands(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands) {
     API_GUARD_BEGIN
-    return batch_build(b, k, genome_len_hint, min_count, strands);
+    BuildOpts o;
+    o.k = k; o.genome_len_hint = genome_len_hint; o.min_count = min_count; o.strands = strands;
+    return batch_build(b, o);
     API_GUARD_END
 }
-
-uint32_t gasm_batch_strands(const gasm_batch* b) { return b && b->built ? b->S().bs.strands : 0; }
 
 int gasm_batch_build_tips(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds) {
     API_GUARD_BEGIN
-    return batch_build(b, k, genome_len_hint, min_count, strands, tip_len, tip_len ? tip_rounds : 0);
-    API_GUARD_END
-}
-
-uint32_t gasm_batch_tip_len(const gasm_batch* b) { return b && b->built ? b->S().bs.tip_len : 0; }
-uint32_t gasm_batch_tip_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.tip_rounds : 0; }
-
-int gasm_batch_fetch_tip_stats(gasm_batch* b, const uint32_t** tips, const uint32_t** kmers) {
-    API_GUARD_BEGIN
-    if (!b || !tips || !kmers) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_tip_stats before a build"); return GASM_ERR_STATE; }
-    if (!b->S().bs.tip_len) { gasm_set_error("the last build clipped no tips (tip_len = 0)"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
-    BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_tip_stats(b->S().cx, b->build_reads(b->S()), bs));
-    *tips = bs.h_tip_tips.data(); *kmers = bs.h_tip_kmers.data();
-    return GASM_OK;
+    BuildOpts o;
+    o.k = k; o.genome_len_hint = genome_len_hint; o.min_count = min_count; o.strands = strands; o.tip_len = tip_len; o.tip_rounds = tip_rounds;
+    return batch_build(b, o);
     API_GUARD_END
 }
 
 int gasm_batch_build_bubbles(gasm_batch* b, int k, uint64_t genome_len_hint, uint32_t min_count, uint32_t strands, uint32_t tip_len, uint32_t tip_rounds,
                              uint32_t bubble_len, uint32_t bubble_rounds) {
     API_GUARD_BEGIN
-    return batch_build(b, k, genome_len_hint, min_count, strands, tip_len, tip_len ? tip_rounds : 0, bubble_len, bubble_len ? bubble_rounds : 0);
-    API_GUARD_END
-}
-
-uint32_t gasm_batch_bubble_len(const gasm_batch* b) { return b && b->built ? b->S().bs.bubble_len : 0; }
-uint32_t gasm_batch_bubble_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.bubble_rounds : 0; }
-
-int gasm_batch_fetch_bubble_stats(gasm_batch* b, const uint32_t** bubbles, const uint32_t** kmers) {
-    API_GUARD_BEGIN
-    if (!b || !bubbles || !kmers) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_bubble_stats before a build"); return GASM_ERR_STATE; }
-    if (!b->S().bs.bubble_len) { gasm_set_error("the last build popped no bubbles (bubble_len = 0)"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
-    BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_bubble_stats(b->S().cx, b->build_reads(b->S()), bs));
-    *bubbles = bs.h_bubble_bubbles.data(); *kmers = bs.h_bubble_kmers.data();
-    return GASM_OK;
+    BuildOpts o;
+    o.k = k; o.genome_len_hint = genome_len_hint; o.min_count = min_count; o.strands = strands; o.tip_len = tip_len; o.tip_rounds = tip_rounds;
+    o.bubble_len = bubble_len; o.bubble_rounds = bubble_rounds;
+    return batch_build(b, o);
     API_GUARD_END
 }
 
 int gasm_batch_build_params(gasm_batch* b, const gasm_build_params* params) {
     API_GUARD_BEGIN
-    GCHK(check_build_params("gasm_batch_build_params", params));
-    const gasm_build_params& p = *params;
-    return batch_build(b, p.k, p.genome_len_hint, p.min_count ? p.min_count : 1, p.strands ? p.strands : 1, p.tip_len, p.tip_len ? p.tip_rounds : 0,
-                       p.bubble_len, p.bubble_len ? p.bubble_rounds : 0, p.cov_cutoff, p.cov_len, p.cov_cutoff && p.cov_len ? p.cov_rounds : 0);
+    BuildOpts o;
+    GCHK(opts_from_params("gasm_batch_build_params", params, o));
+    return batch_build(b, o);
     API_GUARD_END
 }
 
-uint32_t gasm_batch_cov_cutoff(const gasm_batch* b) { return b && b->built ? b->S().bs.cov_cutoff : 0; }
-uint32_t gasm_batch_cov_len(const gasm_batch* b) { return b && b->built ? b->S().bs.cov_len : 0; }
-uint32_t gasm_batch_cov_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.cov_rounds : 0; }
+// the options of the last build as its slot keeps them (normalised); 0 before the first
+uint32_t gasm_batch_strands(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.strands : 0; }
+uint32_t gasm_batch_tip_len(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.tip_len : 0; }
+uint32_t gasm_batch_tip_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.tip_rounds : 0; }
+uint32_t gasm_batch_bubble_len(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.bubble_len : 0; }
+uint32_t gasm_batch_bubble_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.bubble_rounds : 0; }
+uint32_t gasm_batch_cov_cutoff(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.cov_cutoff : 0; }
+uint32_t gasm_batch_cov_len(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.cov_len : 0; }
+uint32_t gasm_batch_cov_rounds(const gasm_batch* b) { return b && b->built ? b->S().bs.opts.cov_rounds : 0; }
+
+// gasm_batch_fetch_tip_stats, _bubble_stats and _lowcov_stats: what the last build's rounds of `kind` removed
+static int batch_fetch_round_stats(gasm_batch* b, u32 kind, const uint32_t** contigs, const uint32_t** kmers) {
+    static const char* const entry[ROUND_KINDS] = {"gasm_batch_fetch_tip_stats", "gasm_batch_fetch_bubble_stats", "gasm_batch_fetch_lowcov_stats"};
+    static const char* const off[ROUND_KINDS] = {"the last build clipped no tips (tip_len = 0)", "the last build popped no bubbles (bubble_len = 0)",
+                                                 "the last build removed no low-coverage contigs (cov_cutoff = 0 or cov_len = 0)"};
+    if (!b || !contigs || !kmers) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("%s before a build", entry[kind]); return GASM_ERR_STATE; }
+    if (!b->S().bs.opts.rounds(kind)) { gasm_set_error("%s", off[kind]); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_round_stats(b->S().cx, b->build_reads(b->S()), bs, kind));
+    *contigs = bs.round_stats[kind].h_contigs.data(); *kmers = bs.round_stats[kind].h_kmers.data();
+    return GASM_OK;
+}
+
+int gasm_batch_fetch_tip_stats(gasm_batch* b, const uint32_t** tips, const uint32_t** kmers) {
+    API_GUARD_BEGIN
+    return batch_fetch_round_stats(b, ROUNDS_TIP, tips, kmers);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_bubble_stats(gasm_batch* b, const uint32_t** bubbles, const uint32_t** kmers) {
+    API_GUARD_BEGIN
+    return batch_fetch_round_stats(b, ROUNDS_BUBBLE, bubbles, kmers);
+    API_GUARD_END
+}
 
 int gasm_batch_fetch_lowcov_stats(gasm_batch* b, const uint32_t** contigs, const uint32_t** kmers) {
     API_GUARD_BEGIN
-    if (!b || !contigs || !kmers) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_lowcov_stats before a build"); return GASM_ERR_STATE; }
-    if (!b->S().bs.lowcov()) { gasm_set_error("the last build removed no low-coverage contigs (cov_cutoff = 0 or cov_len = 0)"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
-    BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_lowcov_stats(b->S().cx, b->build_reads(b->S()), bs));
-    *contigs = bs.h_cov_contigs.data(); *kmers = bs.h_cov_kmers.data();
-    return GASM_OK;
+    return batch_fetch_round_stats(b, ROUNDS_LOWCOV, contigs, kmers);
     API_GUARD_END
 }
 

@@ -73,6 +73,39 @@ struct DevPaths {
     void release();
 };
 
+// Every option of a build, the one form in which they travel from the public entries (capi.hip) to the launches; the defaults are
+// gasm_batch_build's.
+// min_count > 1: only the distinct k-mers seen at least min_count times in their segment enter the graph (k_bucket_solid behind the
+// de-duplication; 1: all of them, and not a launch more)
+// strands = 2: built from the reads and their reverse complements (the caller hands pipeline_build the both-strand DevReads); the twin
+// map exists for such a build only
+// tip_len > 0: tip_rounds (1 .. GASM_MAX_TIP_ROUNDS) rounds of tip clipping behind the cutoff, contigs of at most tip_len bases
+// bubble_len > 0 (<= GASM_MAX_BUBBLE_LEN): bubble_rounds (1 .. GASM_MAX_BUBBLE_ROUNDS) rounds of bubble popping behind the tip rounds
+// cov_cutoff > 0 and cov_len > 0 (<= GASM_MAX_BUBBLE_LEN): cov_rounds (1 .. GASM_MAX_COV_ROUNDS) rounds of low-coverage removal behind the
+// bubble rounds, contigs of at most cov_len bases whose mean multiplicity is below cov_cutoff
+// A feature that is off costs not a launch.  Normalised (build_opts_normalised): the rounds of a feature that is off are 0
+enum RoundKind : u32 { ROUNDS_TIP = 0, ROUNDS_BUBBLE, ROUNDS_LOWCOV, ROUND_KINDS };     // in the order the rounds run
+struct BuildOpts {
+    int k = 0;
+    u64 genome_len_hint = 0;
+    u32 min_count = 1, strands = 1, tip_len = 0, tip_rounds = 0, bubble_len = 0, bubble_rounds = 0, cov_cutoff = 0, cov_len = 0, cov_rounds = 0;
+    bool lowcov() const { return cov_cutoff != 0 && cov_len != 0; }
+    // rounds of one kind; normalised, 0 exactly when the kind is off
+    u32 rounds(u32 kind) const { return kind == ROUNDS_TIP ? tip_rounds : kind == ROUNDS_BUBBLE ? bubble_rounds : cov_rounds; }
+    u32 total_rounds() const { return tip_rounds + bubble_rounds + cov_rounds; }
+};
+// the argument rules of every build entry (GASM_ERR_INVALID and the error text), and the rounds of the features that are off set to 0
+int build_opts_check(const BuildOpts& o);
+BuildOpts build_opts_normalised(BuildOpts o);
+
+// What the rounds of one kind removed in the last build.  The three kinds run the same mechanism (mark, k_bucket_solid compaction) and
+// count the same way
+struct RoundStats {
+    u32 max_rounds;                         // GASM_MAX_TIP_ROUNDS / GASM_MAX_BUBBLE_ROUNDS / GASM_MAX_COV_ROUNDS
+    DBuf d_stats;                           // the kind is on: u32[2][max_rounds][S], contigs then k-mers removed per round and segment
+    std::vector<u32> h_contigs, h_kmers;    // pipeline_fetch_round_stats: [s * max_rounds + r]
+};
+
 struct BuildState {
     // ---- plan (host-side, from the reads): key width, tile shape, partition
     int k = 0, bbits = 0, fbits = 9, words = 1, bb_cap = 0;
@@ -88,20 +121,10 @@ struct BuildState {
     bool ranked_in_lds = false;
     u32 tile_g = 1;                         // threads per read of the tile kernels
     u64 n_kmers = 0, hint = 0, reads_id = 0;
-    u32 min_count = 1;                      // multiplicity cutoff of this build (gasm_batch_build_solid): every attempt of the retry ladder
-                                            // filters with it (k_bucket_solid behind the de-duplication), and scores of its graph compare bases
-    u32 strands = 1;                        // 2: built from the reads and their reverse complements (the caller handed pipeline_build the
-                                            // both-strand DevReads); the twin map exists for such a build only
-    u32 tip_len = 0, tip_rounds = 0;        // tip clipping of this build (gasm_batch_build_tips): contigs of at most tip_len bases, for
-                                            // exactly tip_rounds rounds behind the cutoff; 0: none.  Every attempt of the retry ladder
-                                            // clips again, and scores of its graph compare bases
-    u32 bubble_len = 0, bubble_rounds = 0;  // bubble popping of this build (gasm_batch_build_bubbles): contigs of at most bubble_len bases,
-                                            // for exactly bubble_rounds rounds behind the tip rounds; 0: none.  Kept and repeated like tip_len
-    u32 cov_cutoff = 0, cov_len = 0, cov_rounds = 0;   // low-coverage removal of this build (gasm_batch_build_params): contigs of at most
-                                            // cov_len bases whose mean multiplicity is below cov_cutoff, for exactly cov_rounds rounds behind
-                                            // the bubble rounds; cov_cutoff = 0 or cov_len = 0: none (cov_rounds is 0 then).  Kept and
-                                            // repeated like tip_len
-    bool lowcov() const { return cov_cutoff != 0 && cov_len != 0; }
+    BuildOpts opts;                         // what this build was asked for, normalised (pipeline_build).  Every attempt of the retry ladder filters,
+                                            // clips, pops and removes with it again, each step slot keeps its own, and scores of a graph that any of
+                                            // them changed compare bases.  (k and hint above are what plan_build planned with: the hint doubled for
+                                            // strands = 2.)  Pooled builds never set it: every feature off
     std::vector<u64> h_seg_nk;              // k-mers per segment
     // upper bounds the arrays are allocated at, and estimates the grids are sized from (the kernels loop beyond them)
     u64 D_cap = 0, maxD_cap = 0, bases_cap = 0;
@@ -128,12 +151,7 @@ struct BuildState {
     DBuf d_keys2;                           // output of the multi-pass de-duplication (its passes re-read d_keys)
     DBuf d_keys, d_mult, d_hist, d_toff, d_tcnt, d_fdir, d_bstart, d_bucket_d, d_dstart, d_flags, d_rtab;
     DBuf d_solid_removed;                   // min_count > 1: distinct k-mers the cutoff removed, per segment (u32, zeroed with every attempt)
-    DBuf d_tip_stats;                       // tip_len > 0: u32[2][GASM_MAX_TIP_ROUNDS][S], contigs then k-mers clipped per round and segment
-    std::vector<u32> h_tip_tips, h_tip_kmers;      // pipeline_fetch_tip_stats: [s * GASM_MAX_TIP_ROUNDS + r]
-    DBuf d_bubble_stats;                    // bubble_len > 0: u32[2][GASM_MAX_BUBBLE_ROUNDS][S], contigs then k-mers popped per round and segment
-    std::vector<u32> h_bubble_bubbles, h_bubble_kmers;   // pipeline_fetch_bubble_stats: [s * GASM_MAX_BUBBLE_ROUNDS + r]
-    DBuf d_cov_stats;                       // lowcov(): u32[2][GASM_MAX_COV_ROUNDS][S], contigs then k-mers removed per round and segment
-    std::vector<u32> h_cov_contigs, h_cov_kmers;         // pipeline_fetch_lowcov_stats: [s * GASM_MAX_COV_ROUNDS + r]
+    RoundStats round_stats[ROUND_KINDS] = {{GASM_MAX_TIP_ROUNDS}, {GASM_MAX_BUBBLE_ROUNDS}, {GASM_MAX_COV_ROUNDS}};
     DBuf d_ccov;                            // per-contig coverage of the last build (u64 sums[P], then u32 edges[P]: pipeline_contig_coverage)
     std::vector<u64> h_ccov_m;
     std::vector<u32> h_ccov_n;
@@ -199,19 +217,12 @@ struct ScoreState {
 // queues a whole build on the ctx stream and returns; pipeline_build_finish (called by every fetch) waits for its report
 // and repeats it with a larger configuration if it failed.  *rebuilt: the device arrays were produced anew (a score
 // queued behind the first attempt must be queued again).
-// min_count > 1: only the distinct k-mers seen at least min_count times in their segment enter the graph (1: all of them, and not
-// a launch more than without the argument)
-// strands = 2: `rd` is the both-strand form of the batch's reads (DevReads::make_both_strands) and must be handed to every later
-// call that takes this build's reads (finish, fetches); genome_len_hint still means the genome: the estimate of the distinct
-// k-mers is doubled here
-// tip_len > 0: tip_rounds (1 .. GASM_MAX_TIP_ROUNDS) rounds of tip clipping behind the cutoff, each a graph pass up to the chain
-// lengths, k_tip_mark and a compaction of the buckets' runs; the last graph pass alone writes the report.  0: not a launch more
-// bubble_len > 0 (<= GASM_MAX_BUBBLE_LEN): bubble_rounds (1 .. GASM_MAX_BUBBLE_ROUNDS) rounds of bubble popping behind the tip rounds,
-// the same passes with k_bubble_mark as the marking kernel.  0: not a launch more
-// cov_cutoff > 0 and cov_len > 0 (<= GASM_MAX_BUBBLE_LEN): cov_rounds (1 .. GASM_MAX_COV_ROUNDS) rounds of low-coverage removal behind the
-// bubble rounds, the same passes with k_lowcov_mark as the marking kernel.  Either 0: not a launch more
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 genome_len_hint, BuildState& bs, u32 min_count = 1, u32 strands = 1, u32 tip_len = 0,
-                   u32 tip_rounds = 0, u32 bubble_len = 0, u32 bubble_rounds = 0, u32 cov_cutoff = 0, u32 cov_len = 0, u32 cov_rounds = 0);
+// `o` has passed build_opts_check and is stored normalised in bs.opts.  strands = 2: `rd` is the both-strand form of the batch's reads
+// (DevReads::make_both_strands, else GASM_ERR_STATE) and must be handed to every later call that takes this build's reads (finish,
+// fetches); genome_len_hint still means the genome: the estimate of the distinct k-mers is doubled here.  Every round of tip clipping,
+// bubble popping and low-coverage removal is a graph pass up to the chain lengths, the kind's marking kernel and a compaction of the
+// buckets' runs; the last graph pass alone writes the report
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, const BuildOpts& o);
 int pipeline_build_finish(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool* rebuilt);
 int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 n_segments, BuildState& bs, bool* rebuilt);
 // The overflow retry ladder of every build path: after an attempt raised the GASM_OVF_* bits `ovf`, advance the configuration by
@@ -230,12 +241,9 @@ int pipeline_fetch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_contigs(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // distinct k-mers per segment before and after the cutoff of the finished build (equal at min_count = 1)
 int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
-// contigs and k-mers clipped per segment and round of the finished build (zero for rounds not run and for tip_len = 0)
-int pipeline_fetch_tip_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
-// contigs and k-mers popped per segment and round of the finished build (zero for rounds not run and for bubble_len = 0)
-int pipeline_fetch_bubble_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
-// contigs and k-mers removed for low coverage per segment and round of the finished build (zero for rounds not run and with the feature off)
-int pipeline_fetch_lowcov_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// contigs and k-mers removed per segment and round by the finished build's rounds of `kind`, into bs.round_stats[kind] (zero for rounds
+// not run and with the kind off)
+int pipeline_fetch_round_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 kind);
 // per-contig sum of multiplicities and number of edges of the finished build: queue (k_contig_cov, reads the build's arrays only), then
 // fetch h_ccov_m / h_ccov_n, one entry per contig in the order of the contig list
 int pipeline_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

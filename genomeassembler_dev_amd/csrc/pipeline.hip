@@ -468,10 +468,11 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_tip_stats, &d_bubble_stats, &d_cov_stats, &d_ccov, &d_links, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_ccov, &d_links, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
+    for (RoundStats& rs : round_stats) rs.d_stats.release();
     part_valid = false;         // (d_bstart no longer holds the partition's region layout)
     if (h_report) { (void)hipHostFree(h_report); h_report = nullptr; h_report_words = 0; }
 }
@@ -666,14 +667,14 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         fprintf(stderr, "[dedup stamps, 100 MHz ticks per workgroup] init %.1f  first-iter %.1f  stream %.1f  barrier %.1f  order %.1f  writeback %.1f\n",
                 (double)h[0] / nbt, (double)h[1] / nbt, (double)h[2] / nbt, (double)h[3] / nbt, (double)h[4] / nbt, (double)h[5] / nbt);
     }
-    if (bs.min_count > 1) {
+    if (bs.opts.min_count > 1) {
         // the multiplicity cutoff, behind whichever de-duplication ran (every rung of pipeline_build_finish's ladder comes through
         // here): weak keys leave the buckets' runs before anything reads them.  Its last workgroup redoes the offsets, counting on
         // a flag word of its own
         GCHK(bs.d_solid_removed.ensure((size_t)S * 4));
         HIPCHK(hipMemsetAsync(bs.d_solid_removed.p, 0, (size_t)S * 4, ctx->stream));
         GLAUNCH_K(ctx, W, "k_bucket_solid", k_bucket_solid<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(),
-                  bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.min_count, bs.d_solid_removed.as<u32>(),
+                  bs.d_bucket_d.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits, bs.fbits, bbits, bs.opts.min_count, bs.d_solid_removed.as<u32>(),
                   bs.d_flags.as<u32>() + GASM_FLAG_SOLID_DONE, d_scan_out);
     }
     if (!scan_in_dedup) GLAUNCH(ctx, "k_scan_excl", k_scan_excl<u32>, dim3(1), dim3(1024), 0, bs.d_bucket_d.as<u32>(), bs.d_dstart.as<u32>(), nbt);
@@ -707,64 +708,54 @@ static int alloc_graph(BuildState& bs, u32 S) {
 
 // ---- dense arrays -> (k-1)-mer graph -> chains -> contigs + the report.  Inputs: d_keys/d_mult/d_bstart (the buckets'
 // distinct runs) and d_dstart/d_fdir.
-// With tip clipping (bs.tip_len > 0) the graph is made tip_rounds + 1 times.  A round = a graph pass up to the chains' lengths
+// With tip clipping (bs.opts.tip_len > 0) the graph is made tip_rounds + 1 times.  A round = a graph pass up to the chains' lengths
 // (no contigs, no report), k_tip_mark, which zeroes the multiplicities of the tips' edges in the buckets' runs, and
 // k_bucket_solid with a cutoff of 1, which compacts the runs in place, rewrites the directory rows and redoes the offsets as it
 // does behind the de-duplication; then the next pass gathers what is left.  All of it is queued: the host waits for nothing
 // between rounds, and only the last pass's k_contig_scan publishes the report.
-// Bubble popping (bs.bubble_len > 0) adds bubble_rounds such rounds behind the tip rounds, with k_bubble_mark as the marking
-// kernel: tip_rounds + bubble_rounds + 1 passes in all.  (Tips first: a tip that hangs on a bubble's branch splits it.)
-// Low-coverage removal (bs.lowcov()) adds cov_rounds such rounds behind all of those, with k_lowcov_mark as the marking kernel:
-// tip_rounds + bubble_rounds + cov_rounds + 1 passes in all.
+// Bubble popping (bubble_len > 0) adds bubble_rounds such rounds behind the tip rounds, with k_bubble_mark as the marking
+// kernel.  (Tips first: a tip that hangs on a bubble's branch splits it.)  Low-coverage removal (lowcov()) adds cov_rounds such rounds
+// behind all of those, with k_lowcov_mark as the marking kernel: tip_rounds + bubble_rounds + cov_rounds + 1 passes in all.  The rounds
+// of a kind that is off are 0 in bs.opts (normalised), and a round's statistics go to its kind's row of bs.round_stats.
 int launch_graph(gasm_ctx* ctx, u32 S, BuildState& bs) {
     const int W = bs.words, bbits = bs.bbits;
     const u32 nb = 1u << bbits, nbt = S * nb;
     GCHK(alloc_graph(bs, S));
     u32* const d_claim = bs.d_nxt.as<u32>();      // claim words of the degree kernels live in nxt until k_edge_next overwrites them
-    const u32 tip_rounds = bs.tip_len ? bs.tip_rounds : 0;
-    const u32 pop_rounds = tip_rounds + (bs.bubble_len ? bs.bubble_rounds : 0);
-    const u32 rounds = pop_rounds + (bs.lowcov() ? bs.cov_rounds : 0);
-    if (tip_rounds) {
-        GCHK(bs.d_tip_stats.ensure((size_t)2 * GASM_MAX_TIP_ROUNDS * S * 4));
-        HIPCHK(hipMemsetAsync(bs.d_tip_stats.p, 0, (size_t)2 * GASM_MAX_TIP_ROUNDS * S * 4, ctx->stream));
-    }
-    if (pop_rounds > tip_rounds) {
-        GCHK(bs.d_bubble_stats.ensure((size_t)2 * GASM_MAX_BUBBLE_ROUNDS * S * 4));
-        HIPCHK(hipMemsetAsync(bs.d_bubble_stats.p, 0, (size_t)2 * GASM_MAX_BUBBLE_ROUNDS * S * 4, ctx->stream));
-    }
-    if (rounds > pop_rounds) {
-        GCHK(bs.d_cov_stats.ensure((size_t)2 * GASM_MAX_COV_ROUNDS * S * 4));
-        HIPCHK(hipMemsetAsync(bs.d_cov_stats.p, 0, (size_t)2 * GASM_MAX_COV_ROUNDS * S * 4, ctx->stream));
+    const BuildOpts& o = bs.opts;
+    const u32 rounds = o.total_rounds();
+    for (u32 kind = 0; kind < ROUND_KINDS; ++kind) {
+        RoundStats& rs = bs.round_stats[kind];
+        if (!o.rounds(kind)) continue;
+        GCHK(rs.d_stats.ensure((size_t)2 * rs.max_rounds * S * 4));
+        HIPCHK(hipMemsetAsync(rs.d_stats.p, 0, (size_t)2 * rs.max_rounds * S * 4, ctx->stream));
     }
     for (u32 r = 0; r <= rounds; ++r) {
         GLAUNCH_K(ctx, W, "k_bucket_gather", k_bucket_gather<K>, dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(),
                   bs.d_bstart.as<u64>(), bs.d_dstart.as<u32>(), bs.d_dk_key.as<K>(), bs.d_dk_cnt.as<u32>(), d_claim, bs.d_eflag.as<u8>(), bs.d_flags.as<u32>());
         GCHK(launch_graph_dense(ctx, S, bs, r == rounds));
         if (r == rounds) break;
-        const bool tips = r < tip_rounds;
-        GasmRange range(tips ? "gasm:tips (mark, compact)" : r < pop_rounds ? "gasm:bubbles (mark, compact)" : "gasm:lowcov (mark, compact)");
+        // round r of the build = round kr of its kind
+        u32 kind = ROUNDS_TIP, kr = r;
+        while (kr >= o.rounds(kind)) kr -= o.rounds(kind++);
+        static const char* const range_name[ROUND_KINDS] = {"gasm:tips (mark, compact)", "gasm:bubbles (mark, compact)", "gasm:lowcov (mark, compact)"};
+        GasmRange range(range_name[kind]);
+        const RoundStats& rs = bs.round_stats[kind];
+        u32* const d_contigs = rs.d_stats.as<u32>() + (size_t)kr * S;
+        u32* const d_kmers = rs.d_stats.as<u32>() + ((size_t)rs.max_rounds + kr) * S;
         const u32 est = std::max<u32>(1, (u32)std::min<u64>(bs.maxD_est, bs.maxD_cap));
         const u32 dchunks = (u32)ceil_div_u64(est, GASM_WG);
-        u32* d_kmers;
-        if (tips) {
-            u32* const d_tips = bs.d_tip_stats.as<u32>() + (size_t)r * S;
-            d_kmers = bs.d_tip_stats.as<u32>() + ((size_t)GASM_MAX_TIP_ROUNDS + r) * S;
+        if (kind == ROUNDS_TIP) {
             GLAUNCH_K(ctx, W, "k_tip_mark", k_tip_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(), bs.d_clen.as<u32>(),
-                      bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.tip_len, bs.d_flags.as<u32>(), d_tips);
-        } else if (r < pop_rounds) {
-            const u32 br = r - tip_rounds;
-            u32* const d_bubbles = bs.d_bubble_stats.as<u32>() + (size_t)br * S;
-            d_kmers = bs.d_bubble_stats.as<u32>() + ((size_t)GASM_MAX_BUBBLE_ROUNDS + br) * S;
+                      bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), o.tip_len, bs.d_flags.as<u32>(), d_contigs);
+        } else if (kind == ROUNDS_BUBBLE) {
             GLAUNCH_K(ctx, W, "k_bubble_mark", k_bubble_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(),
-                      bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.bubble_len,
-                      bs.d_flags.as<u32>(), d_bubbles);
+                      bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), o.bubble_len,
+                      bs.d_flags.as<u32>(), d_contigs);
         } else {
-            const u32 cr = r - pop_rounds;
-            u32* const d_removed = bs.d_cov_stats.as<u32>() + (size_t)cr * S;
-            d_kmers = bs.d_cov_stats.as<u32>() + ((size_t)GASM_MAX_COV_ROUNDS + cr) * S;
             GLAUNCH_K(ctx, W, "k_lowcov_mark", k_lowcov_mark<K>, seg_grid(dchunks, S), dim3(GASM_WG), 0, graph_view(bs), S, dchunks, bs.d_eflag.as<u8>(),
-                      bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), bs.cov_len, bs.cov_cutoff,
-                      bs.d_flags.as<u32>(), d_removed);
+                      bs.d_clen.as<u32>(), bs.d_nxt.as<u32>(), bs.d_dk_cnt.as<u32>(), bs.d_bstart.as<u64>(), bs.d_mult.as<u32>(), o.cov_len, o.cov_cutoff,
+                      bs.d_flags.as<u32>(), d_contigs);
         }
         // (the done word is zero: the gather of this pass cleared it behind the cutoff's or the last round's compaction)
         u32* const d_scan_out = bs.scan_in_dedup ? bs.d_dstart.as<u32>() : nullptr;
@@ -929,26 +920,40 @@ static void zero_results(BuildState& bs, u32 S) {
     bs.d_total = 0; bs.n_contigs = 0; bs.contig_bases = 0;
 }
 
-int pipeline_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs, u32 min_count, u32 strands, u32 tip_len, u32 tip_rounds, u32 bubble_len,
-                   u32 bubble_rounds, u32 cov_cutoff, u32 cov_len, u32 cov_rounds) {
-    if (min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
-    if (strands != 1 && strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", strands); return GASM_ERR_INVALID; }
-    if (strands == 2 && !rd.strands_of) { gasm_set_error("a both-strand build needs the both-strand reads"); return GASM_ERR_STATE; }
+int build_opts_check(const BuildOpts& o) {
+    if (o.min_count < 1) { gasm_set_error("min_count must be >= 1 (1 keeps every k-mer)"); return GASM_ERR_INVALID; }
+    if (o.strands != 1 && o.strands != 2) { gasm_set_error("strands must be 1 or 2 (got %u)", o.strands); return GASM_ERR_INVALID; }
+    if (o.tip_len && (o.tip_rounds < 1 || o.tip_rounds > GASM_MAX_TIP_ROUNDS)) {
+        gasm_set_error("tip_rounds must be 1..%d when tip_len > 0 (got %u)", GASM_MAX_TIP_ROUNDS, o.tip_rounds);
+        return GASM_ERR_INVALID;
+    }
     // (the bound of every walk of k_bubble_mark, and what keeps its products inside 64 bits)
-    if (bubble_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("bubble_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, bubble_len); return GASM_ERR_INVALID; }
-    // (the same bound and the same two reasons for k_lowcov_mark)
-    if (cov_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("cov_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, cov_len); return GASM_ERR_INVALID; }
+    if (o.bubble_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("bubble_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, o.bubble_len); return GASM_ERR_INVALID; }
+    if (o.bubble_len && (o.bubble_rounds < 1 || o.bubble_rounds > GASM_MAX_BUBBLE_ROUNDS)) {
+        gasm_set_error("bubble_rounds must be 1..%d when bubble_len > 0 (got %u)", GASM_MAX_BUBBLE_ROUNDS, o.bubble_rounds);
+        return GASM_ERR_INVALID;
+    }
+    // (the same bound and the same two reasons for k_lowcov_mark; refused whatever cov_cutoff is, as it always was)
+    if (o.cov_len > GASM_MAX_BUBBLE_LEN) { gasm_set_error("cov_len must be <= %d (got %u)", GASM_MAX_BUBBLE_LEN, o.cov_len); return GASM_ERR_INVALID; }
+    if (o.lowcov() && (o.cov_rounds < 1 || o.cov_rounds > GASM_MAX_COV_ROUNDS)) {
+        gasm_set_error("cov_rounds must be 1..%d when cov_cutoff > 0 and cov_len > 0 (got %u)", GASM_MAX_COV_ROUNDS, o.cov_rounds);
+        return GASM_ERR_INVALID;
+    }
+    return GASM_OK;
+}
+
+BuildOpts build_opts_normalised(BuildOpts o) {
+    if (!o.tip_len) o.tip_rounds = 0;
+    if (!o.bubble_len) o.bubble_rounds = 0;
+    if (!o.lowcov()) o.cov_rounds = 0;
+    return o;
+}
+
+int pipeline_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, const BuildOpts& o) {
+    if (o.strands == 2 && !rd.strands_of) { gasm_set_error("a both-strand build needs the both-strand reads"); return GASM_ERR_STATE; }
     // (both strands: up to twice the distinct k-mers of the genome; without a hint the estimate follows the doubled k-mer count)
-    GCHK(plan_build(ctx, rd, k, strands == 2 ? 2 * hint : hint, bs));
-    bs.min_count = min_count;
-    bs.strands = strands;
-    bs.tip_len = tip_len;
-    bs.tip_rounds = tip_len ? tip_rounds : 0;
-    bs.bubble_len = bubble_len;
-    bs.bubble_rounds = bubble_len ? bubble_rounds : 0;
-    bs.cov_cutoff = cov_cutoff;
-    bs.cov_len = cov_len;
-    bs.cov_rounds = cov_cutoff && cov_len ? cov_rounds : 0;
+    GCHK(plan_build(ctx, rd, o.k, o.strands == 2 ? 2 * o.genome_len_hint : o.genome_len_hint, bs));
+    bs.opts = build_opts_normalised(o);
     bs.fetched_twins = false;
     bs.spectrum_queued = false;
     bs.coverage_queued = false;
@@ -1018,7 +1023,7 @@ int pipeline_build_finish_n(gasm_ctx* ctx, DevReads* rd, u32 S, BuildState& bs, 
             ++bs.attempts_graph;
             // a clipped, popped or low-coverage-filtered build has compacted its runs round by round: a repeat of the graph alone would start from what the rounds
             // so far left and count them twice.  It starts over from the reads (same configuration, so the same k-mer set)
-            if ((bs.tip_len || bs.bubble_len || bs.lowcov()) && rd) { ++bs.attempts_distinct; GCHK(launch_distinct(ctx, *rd, bs)); }
+            if (bs.opts.total_rounds() && rd) { ++bs.attempts_distinct; GCHK(launch_distinct(ctx, *rd, bs)); }
         }
         GCHK(launch_graph(ctx, S, bs));
     }
@@ -1077,39 +1082,16 @@ int pipeline_fetch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     return GASM_OK;
 }
 
-int pipeline_fetch_tip_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+int pipeline_fetch_round_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 kind) {
     GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
-    const u32 S = rd.n_segments, R = GASM_MAX_TIP_ROUNDS;
-    bs.h_tip_tips.assign((size_t)S * R, 0); bs.h_tip_kmers.assign((size_t)S * R, 0);
-    if (!bs.tip_len || !bs.n_kmers) return GASM_OK;          // (a build without k-mers launched nothing)
+    RoundStats& rs = bs.round_stats[kind];
+    const u32 S = rd.n_segments, R = rs.max_rounds;
+    rs.h_contigs.assign((size_t)S * R, 0); rs.h_kmers.assign((size_t)S * R, 0);
+    if (!bs.opts.rounds(kind) || !bs.n_kmers) return GASM_OK;          // (a build without k-mers launched nothing)
     std::vector<u32> h((size_t)2 * R * S);
-    GCHK(d2h_sync(ctx, h.data(), bs.d_tip_stats.p, h.size() * 4));
+    GCHK(d2h_sync(ctx, h.data(), rs.d_stats.p, h.size() * 4));
     for (u32 s = 0; s < S; ++s)
-        for (u32 r = 0; r < R; ++r) { bs.h_tip_tips[(size_t)s * R + r] = h[(size_t)r * S + s]; bs.h_tip_kmers[(size_t)s * R + r] = h[((size_t)R + r) * S + s]; }
-    return GASM_OK;
-}
-
-int pipeline_fetch_bubble_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
-    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
-    const u32 S = rd.n_segments, R = GASM_MAX_BUBBLE_ROUNDS;
-    bs.h_bubble_bubbles.assign((size_t)S * R, 0); bs.h_bubble_kmers.assign((size_t)S * R, 0);
-    if (!bs.bubble_len || !bs.n_kmers) return GASM_OK;       // (a build without k-mers launched nothing)
-    std::vector<u32> h((size_t)2 * R * S);
-    GCHK(d2h_sync(ctx, h.data(), bs.d_bubble_stats.p, h.size() * 4));
-    for (u32 s = 0; s < S; ++s)
-        for (u32 r = 0; r < R; ++r) { bs.h_bubble_bubbles[(size_t)s * R + r] = h[(size_t)r * S + s]; bs.h_bubble_kmers[(size_t)s * R + r] = h[((size_t)R + r) * S + s]; }
-    return GASM_OK;
-}
-
-int pipeline_fetch_lowcov_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
-    GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
-    const u32 S = rd.n_segments, R = GASM_MAX_COV_ROUNDS;
-    bs.h_cov_contigs.assign((size_t)S * R, 0); bs.h_cov_kmers.assign((size_t)S * R, 0);
-    if (!bs.lowcov() || !bs.n_kmers) return GASM_OK;         // (a build without k-mers launched nothing)
-    std::vector<u32> h((size_t)2 * R * S);
-    GCHK(d2h_sync(ctx, h.data(), bs.d_cov_stats.p, h.size() * 4));
-    for (u32 s = 0; s < S; ++s)
-        for (u32 r = 0; r < R; ++r) { bs.h_cov_contigs[(size_t)s * R + r] = h[(size_t)r * S + s]; bs.h_cov_kmers[(size_t)s * R + r] = h[((size_t)R + r) * S + s]; }
+        for (u32 r = 0; r < R; ++r) { rs.h_contigs[(size_t)s * R + r] = h[(size_t)r * S + s]; rs.h_kmers[(size_t)s * R + r] = h[((size_t)R + r) * S + s]; }
     return GASM_OK;
 }
 
@@ -1118,18 +1100,17 @@ int pipeline_fetch_solid_stats(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     const u32 S = rd.n_segments;
     std::vector<u32> removed(S, 0);
     // (a build without k-mers launched nothing, and min_count = 1 removed nothing)
-    if (bs.min_count > 1 && bs.n_kmers) GCHK(d2h_sync(ctx, removed.data(), bs.d_solid_removed.p, (size_t)S * 4));
+    if (bs.opts.min_count > 1 && bs.n_kmers) GCHK(d2h_sync(ctx, removed.data(), bs.d_solid_removed.p, (size_t)S * 4));
     bs.h_solid_before.resize(S); bs.h_solid_after.resize(S);
     // (the tips clipped, the bubbles popped and the low-coverage contigs removed behind the cutoff are not the cutoff's: they count as
     // survivors here)
-    if (bs.tip_len) GCHK(pipeline_fetch_tip_stats(ctx, rd, bs));
-    if (bs.bubble_len) GCHK(pipeline_fetch_bubble_stats(ctx, rd, bs));
-    if (bs.lowcov()) GCHK(pipeline_fetch_lowcov_stats(ctx, rd, bs));
+    for (u32 kind = 0; kind < ROUND_KINDS; ++kind) if (bs.opts.rounds(kind)) GCHK(pipeline_fetch_round_stats(ctx, rd, bs, kind));
     for (u32 s = 0; s < S; ++s) {
         bs.h_solid_after[s] = bs.h_dstart.empty() ? 0 : bs.h_dstart[s + 1] - bs.h_dstart[s];
-        if (bs.tip_len) for (u32 r = 0; r < GASM_MAX_TIP_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_tip_kmers[(size_t)s * GASM_MAX_TIP_ROUNDS + r];
-        if (bs.bubble_len) for (u32 r = 0; r < GASM_MAX_BUBBLE_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_bubble_kmers[(size_t)s * GASM_MAX_BUBBLE_ROUNDS + r];
-        if (bs.lowcov()) for (u32 r = 0; r < GASM_MAX_COV_ROUNDS; ++r) bs.h_solid_after[s] += bs.h_cov_kmers[(size_t)s * GASM_MAX_COV_ROUNDS + r];
+        for (u32 kind = 0; kind < ROUND_KINDS; ++kind) {
+            const RoundStats& rs = bs.round_stats[kind];
+            if (bs.opts.rounds(kind)) for (u32 r = 0; r < rs.max_rounds; ++r) bs.h_solid_after[s] += rs.h_kmers[(size_t)s * rs.max_rounds + r];
+        }
         bs.h_solid_before[s] = bs.h_solid_after[s] + removed[s];
     }
     return GASM_OK;
@@ -1233,7 +1214,7 @@ int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     }
     if (S) HIPCHK(hipMemcpyAsync(bs.h_links_skipped.data(), d + (size_t)P * 28, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (bs.strands == 2) for (u32 s = 0; s < S; ++s) bs.h_links_skipped[s] /= 2;      // (a read and its reverse complement are equally long)
+    if (bs.opts.strands == 2) for (u32 s = 0; s < S; ++s) bs.h_links_skipped[s] /= 2;      // (a read and its reverse complement are equally long)
     return GASM_OK;
 }
 
@@ -1300,7 +1281,7 @@ int pipeline_fetch_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
 // ranking's links, the contig ids and the contig text, writes an array of its own
 int pipeline_fetch_contig_twins(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
-    if (bs.strands != 2) { gasm_set_error("the twin map exists after a strands = 2 build only"); return GASM_ERR_STATE; }
+    if (bs.opts.strands != 2) { gasm_set_error("the twin map exists after a strands = 2 build only"); return GASM_ERR_STATE; }
     if (bs.fetched_twins) return GASM_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const u32 P = bs.n_contigs;
@@ -1664,7 +1645,7 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     // a mismatch raises GASM_FLAG_SCORE_MISMATCH of the build and pipeline_score_fetch refuses the scores
     // A graph built with a multiplicity cutoff does not hold every k-mer of every read: the comparison is then part of the match
     // (verify = 2: a mismatch is "no match" and raises nothing)
-    const int verify = (graph.min_count > 1 || graph.tip_len || graph.bubble_len || graph.lowcov()) ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
+    const int verify = (graph.opts.min_count > 1 || graph.opts.total_rounds()) ? 2 : env_int("GASM_SCORE_VERIFY", 0) != 0 ? 1 : 0;
     ss.verify = verify == 1;
     const u32 reads_per_wg = 256;     // one read per thread: the match is a chain of dependent loads
     const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import bubbles_ref as br
+import build_entries as be
 import genomeassembler_dev_amd as ga
 import tips_ref as tr
 from genomeassembler_dev_amd._lib import check, lib
@@ -342,6 +343,7 @@ def test_bad_arguments_at_the_c_abi():
     assert lib().gasm_batch_build_bubbles(b.h, 5, 0, 1, 1, 0, 0, 65535, 8) == 0
     assert b.bubble_stats()[0].sum() == 0 and b.contigs() == [br.expected(rs, 5, 1, 1, 0, 0, 65535, 8)["ref"]["contigs"]] == [rs]
     b.close()
+    be.refused_builds_change_nothing(("_bubbles",))                          # a refused build leaves the build before it as it was
 
 
 @pytest.mark.parametrize("slots", [2, 3])

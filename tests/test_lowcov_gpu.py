@@ -10,10 +10,11 @@ import numpy as np
 import pytest
 
 import bubbles_ref as br
+import build_entries as be
 import genomeassembler_dev_amd as ga
 import lowcov_ref as lr
 import tips_ref as tr
-from genomeassembler_dev_amd._lib import BuildParams, check, lib
+from genomeassembler_dev_amd._lib import BuildParams, check, default_context, lib
 from oracle import exact_scores as xs
 from oracle import orc
 
@@ -262,6 +263,61 @@ def test_struct_form_at_the_c_abi(qtable):
     b.score(8, prob)
     assert _all_fetches(b) == snap and b.strands() == 1
     b.close()
+    # a refused build leaves the build before it as it was, through every entry; the one-shot entries refuse the same values with the
+    # same words
+    texts = be.refused_builds_change_nothing()
+    assert set(texts) == {what for what, *_ in be.REFUSED}
+    ctx = default_context()
+    assert be.refused_calls(lambda sfx, opts, size_off: be.contigs_from_reads(ctx, rs, sfx, 5, 1, 3, opts, size_off)[0], tuple(be.TAKES)) == texts
+
+
+# the settings of test_every_entry_*: everything off; cutoff, both strands and tips; the same plus bubbles
+SETTINGS = [dict(), dict(min_count=2, strands=2, tip_len=21, tip_rounds=2),
+            dict(min_count=2, strands=2, tip_len=21, tip_rounds=2, bubble_len=21, bubble_rounds=2)]
+
+
+@pytest.mark.parametrize("opts", SETTINGS, ids=["off", "tips", "tips+bubbles"])
+def test_every_entry_builds_what_the_struct_entry_builds(qtable, monkeypatch, opts):
+    """each positional gasm_batch_build* entry that can express the setting against gasm_batch_build_params: every fetch, the plan and
+    the getters.  (The Python wrappers call the struct entry only: these raw calls are what covers the positional ones.)  Two segments
+    of the smallest row of tests/test_lowcov_host.py's table, where tips, bubbles and low-coverage contigs all occur"""
+    keys, prob = qtable
+    monkeypatch.setenv("GASM_PINGPONG", "0")        # one slot: every build starts from the same BuildState, so the plans compare
+    reads, seg_off, segs = br.noisy_segments(400, 40, 15, 9, 1, n_seg=2)
+    b = ga.SegmentBatch(reads.reshape(-1), seg_off, fixed_len=40)
+    b.k = 11
+
+    def built(sfx):
+        assert be.batch_build(b, sfx, 11, opts) == 0, sfx
+        b.score(8, prob)
+        return _all_fetches(b), b.build_plan(), be.getters(b)
+    built("_params")                                 # (the batch's shape is known from here on: every build below plans alike)
+    want = built("_params")
+    assert want[2] == tuple(opts.get(name, 0 if name != "strands" else 1) for name in be.GETTERS)
+    took = be.entries_for(opts)
+    assert took[-1] == "_params" and len(took) == {0: 6, 4: 3, 6: 2}[len(opts)]
+    for sfx in took[:-1]:
+        assert built(sfx) == want, sfx
+    if opts:                                         # the setting does something: what is compared is not trivially equal
+        assert sum(int(t.sum()) for t in b.tip_stats()) > 0
+    b.close()
+
+
+@pytest.mark.parametrize("opts", SETTINGS, ids=["off", "tips", "tips+bubbles"])
+def test_every_one_shot_entry_gives_what_the_struct_entry_gives(opts):
+    """the same for gasm_get_contigs_from_reads* on one segment with matrix_rows = 3: contigs (and with them their offsets), perm, the
+    distinct keys and their multiplicities"""
+    rs = br.noisy_segments(400, 40, 15, 9, 1)[2][0]
+    ctx = default_context()
+
+    def got(sfx):
+        st, m = be.contigs_from_reads(ctx, rs, sfx, 11, 7, 3, opts)
+        assert st == 0, sfx
+        return m.contigs, m.perm.shape, m.perm.tobytes(), m.words, m.distinct_keys.tobytes(), m.distinct_mult.tobytes()
+    want = got("_params")
+    assert want[1] == (3, len(want[0])) and len(want[0]) > 1
+    for sfx in be.entries_for(opts)[:-1]:
+        assert got(sfx) == want, sfx
 
 
 @pytest.mark.parametrize("slots", [2, 3])

@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import build_entries as be
 import genomeassembler_dev_amd as ga
 import tips_ref as tr
 from genomeassembler_dev_amd import synth
@@ -306,6 +307,7 @@ def test_bad_arguments_at_the_c_abi():
     assert lib().gasm_batch_build_tips(b.h, 5, 0, 1, 1, 3, 8) == 0                            # tip_len < k: allowed, matches no contig
     assert b.tip_stats()[0].sum() == 0
     b.close()
+    be.refused_builds_change_nothing(("_solid", "_strands", "_tips"))        # a refused build leaves the build before it as it was
 
 
 @pytest.mark.parametrize("slots", [2, 3])
