@@ -18,6 +18,8 @@ CORRECT_FIELDS = ("no_kmer", "clean", "corrected", "partial", "left", "bases_cha
 CORRECT_MAX_KMERS = 4096   # GASM_CORRECT_MAX_KMERS: k-mers of the longest read that read correction looks at
 THREAD_MAX_KMERS = 4096    # GASM_THREAD_MAX_KMERS: k-mers of the longest read that contig_links() threads
 MAX_SPAN_LEN = 65535       # GASM_MAX_SPAN_LEN: longest contig (bases) that span support looks at
+MAX_INSERT = 65535         # GASM_MAX_INSERT: the last (overflow) bin of place_pairs()' insert histogram
+PAIR_FIELDS = ("skipped", "none_placed", "one_placed", "same_contig", "reversed", "diff_contig")   # GASM_PAIR_FIELDS counters, in the header's order
 MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
@@ -154,6 +156,8 @@ SYMBOLS = {
     "gasm_batch_fetch_contig_twins": (_int, [_vp, _PP]),
     "gasm_batch_contig_links": (_int, [_vp, _u32]),
     "gasm_batch_fetch_contig_links": (_int, [_vp, _PP, _PP, _PP, _PP, _PP]),
+    "gasm_batch_place_pairs": (_int, [_vp, _u32]),
+    "gasm_batch_fetch_pair_places": (_int, [_vp, _PP, _PP, _PP, C.POINTER(_u32)]),
     "gasm_batch_fetch_solid_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_kmer_spectrum": (_int, [_vp]),
     "gasm_batch_fetch_kmer_spectrum": (_int, [_vp, _PP]),

@@ -465,3 +465,17 @@ def resolve_repeats(reads, k, min_support=2, ctx=None, **build):
     through a repeat say so unambiguously (links.ContigLinks.resolve_repeats: the rule and its limits); a sorted list of str.
     build: as for contig_graph."""
     return contig_graph(reads, k, None, ctx, **build)[1].resolve_repeats(0, min_support)
+
+
+def resolve_repeats_paired(reads, k, min_support=2, max_insert=None, ctx=None, **build):
+    """the contigs of one segment's PAIRED reads (a list of str: reads 2p and 2p + 1 are the mates of pair p, forward-reverse) with the
+    repeats put back into their flanks where the read pairs say so unambiguously — repeats longer than a read among them
+    (pairs.PairPlaces.resolve_repeats: the rule and its limits); a sorted list of str.  max_insert: as SegmentBatch.place_pairs;
+    build: as for contig_graph."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        cl = b.build_simplified(int(k), **build).contig_links()
+        return b.place_pairs(max_insert).resolve_repeats(0, cl, min_support)
+    finally:
+        b.close()

@@ -7,9 +7,10 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
+from .pairs import PairPlaces
 
 
 def weighted_median_half(mult_sum, n_edges):
@@ -224,10 +225,7 @@ class SegmentBatch:
         be spanned), at most _lib.MAX_SPAN_LEN; 0: no span work.  After a strands = 2 build every read and its reverse complement are
         threaded.  Reads the build only: contigs, scores, coverage and twins are what they were."""
         if span_len is None:
-            if getattr(self, "_max_read_len", None) is None:
-                off = self.reads()[1]
-                self._max_read_len = int(np.diff(off).max()) if len(off) > 1 else 0
-            span_len = min(self._max_read_len, MAX_SPAN_LEN)
+            span_len = min(self._longest_read(), MAX_SPAN_LEN)
         if not 0 <= int(span_len) <= MAX_SPAN_LEN:
             raise ValueError(f"span_len must be 0..{MAX_SPAN_LEN} (0: no span support)")
         seg, o, raw = self.contigs_raw()
@@ -243,6 +241,34 @@ class SegmentBatch:
         contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
         ms, _ = self.contig_coverage()
         return ContigLinks(self.k, int(span_len), self.strands(), seg, contigs, succ, pred, lsup, ssup, skipped, ms)
+
+    def _longest_read(self):
+        if getattr(self, "_max_read_len", None) is None:
+            off = self.reads()[1]
+            self._max_read_len = int(np.diff(off).max()) if len(off) > 1 else 0
+        return self._max_read_len
+
+    def place_pairs(self, max_insert=None):
+        """where the batch's read pairs lie on the last build's contigs (gasm_batch_place_pairs; the rule: include/gasm.h "Read pairs") as
+        a pairs.PairPlaces: per segment the records (c1, S, c2, E) of every oriented pair, the insert histogram and the six counters.
+        Reads 2p and 2p + 1 of a segment are the mates of pair p, forward-reverse.  max_insert: the histogram's overflow bin, 1 ..
+        _lib.MAX_INSERT; None: max(1024, 4 x the longest read), at most _lib.MAX_INSERT.  After a strands = 2 build both orientations of
+        every pair are placed.  Reads the build only: contigs, scores, coverage, twins and links are what they were."""
+        if max_insert is None:
+            max_insert = min(max(1024, 4 * self._longest_read()), MAX_INSERT)
+        if not 1 <= int(max_insert) <= MAX_INSERT:
+            raise ValueError(f"max_insert must be 1..{MAX_INSERT}")
+        max_insert = int(max_insert)
+        check(lib().gasm_batch_place_pairs(self.h, max_insert))
+        ps, orient = [C.c_void_p() for _ in range(3)], C.c_uint32()
+        check(lib().gasm_batch_fetch_pair_places(self.h, *[C.byref(p) for p in ps], C.byref(orient)))
+
+        def arr(p, ct, n):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
+        o, n_pairs = int(orient.value), self.n_reads // 2
+        rec = arr(ps[0], C.c_int32, 4 * o * n_pairs)
+        hist, cnt = arr(ps[1], C.c_uint32, self.n_segments * (max_insert + 1)), arr(ps[2], C.c_uint64, self.n_segments * len(PAIR_FIELDS))
+        return PairPlaces(self.k, self.strands(), max_insert, o, self.contigs(), rec, hist, cnt)
 
     def suggest_cov_cutoff(self, segment):
         """a cov_cutoff for build_simplified() from the last build's own contigs of `segment`: half the length-weighted median of the

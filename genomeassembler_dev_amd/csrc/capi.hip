@@ -999,6 +999,27 @@ int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const ui
     API_GUARD_END
 }
 
+int gasm_batch_place_pairs(gasm_batch* b, uint32_t max_insert) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (max_insert < 1 || max_insert > GASM_MAX_INSERT) { gasm_set_error("max_insert must be 1..%d (got %u)", GASM_MAX_INSERT, max_insert); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_place_pairs before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    return pipeline_place_pairs(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, max_insert);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint32_t** insert_hist, const uint64_t** counters, uint32_t* orientations) {
+    API_GUARD_BEGIN
+    if (!b || !rec || !insert_hist || !counters || !orientations) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_pair_places before a build"); return GASM_ERR_STATE; }
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_pair_places(b->S().cx, b->rd, bs));
+    *rec = bs.h_pair_rec.data(); *insert_hist = bs.h_pair_hist.data(); *counters = bs.h_pair_counters.data(); *orientations = bs.pairs_orient;
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin) {
     API_GUARD_BEGIN
     if (!b || !twin) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }

@@ -257,6 +257,12 @@ __global__ void k_contig_links(GraphView gv, const u64* link, const u32* e_cid, 
 template <class K>
 __global__ void k_read_thread(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph, u32 span_len,
                               u32 reads_per_wg, u32 chunks, u32* link_support, u32* span_support, unsigned long long* skipped);
+// read pairs (include/gasm.h, "Read pairs"): orient = 1 or 2 orientations per pair; rec: 4 int32 per oriented pair (16-byte aligned), n_pairs
+// pairs per orientation; hist: max_insert + 1 bins per segment, counters: GASM_PAIR_COUNTERS per segment, both zeroed by the caller
+#define GASM_PAIR_COUNTERS 6          // = GASM_PAIR_FIELDS of include/gasm.h (checked in pipeline.hip)
+template <class K>
+__global__ void k_pair_place(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, int have_graph, u32 orient, u32 max_insert,
+                             u64 n_pairs, u32 chunks, int32_t* rec, u32* hist, unsigned long long* counters);
 
 // ---- kernels_score.hip
 struct SeedTable {

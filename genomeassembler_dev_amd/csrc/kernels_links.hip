@@ -2,9 +2,10 @@
 //   k_contig_links    one thread per contig: the contigs its last node leads to (succ) and the ones that lead to its first node (pred)
 //   k_read_thread     one wave per read: every k-mer's contig and offset, the crossings from contig to contig (link support) and the
 //                     short contigs a read passes through from an in-edge to an out-edge (span support)
-// Both read the build's arrays only.  Where an edge lies: list ranking left (head, distance) on every edge (link), the head carries the
+//   k_pair_place      one lane per mate: where the two mates of a read pair lie on the contigs (include/gasm.h, "Read pairs")
+// All read the build's arrays only.  Where an edge lies: list ranking left (head, distance) on every edge (link), the head carries the
 // contig's id (e_cid), the contig's bases start at c_off[id] — what k_score_reads_graph and k_contig_cov go by.  An edge of an isolated
-// cycle has no head and lies in no contig: for both kernels it is not there.
+// cycle has no head and lies in no contig: for these kernels it is not there.
 #include "kernels.h"
 
 #define GASM_THREAD_WAVES (GASM_WG / 64)
@@ -200,3 +201,134 @@ __global__ void __launch_bounds__(GASM_WG) k_read_thread(ReadSet rs, GraphView g
 }
 template __global__ void k_read_thread<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, u32*, u32*, unsigned long long*);
 template __global__ void k_read_thread<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, u32*, u32*, unsigned long long*);
+
+// ================================================================================================================
+// Read pairs (include/gasm.h, "Read pairs").  Reads 2p and 2p + 1 of a segment are the mates of pair p; an ORIENTED pair (first, second)
+// is placed by two SCANS: the first in-set k-mer of `first` as given, and the first k-mer of `second` whose reverse complement is in the
+// set (key_revcomp: the reads are taken as the batch holds them, whatever the build's strands — the both-strand stream has another read
+// numbering and would save one ALU op per look-up of a kernel that waits on L2).  orient = 2 (after a strands = 2 build) adds
+// (mate 2, mate 1): four scans per pair, two otherwise.
+// Layout: ONE LANE PER SCAN, lane = (pair in the wave) * 2 orient + orientation * 2 + role, role 0 = `first`, role 1 = `second`: 32 or 16
+// pairs per wave, 4 waves of pairs per workgroup and round, the workgroups of a segment on one XCD (seg_chunk), as k_read_thread.
+//   1. every lane looks up position 0 of its mate: after a good build nearly every mate hits there, so one round of dependent requests
+//      (graph_lower_bound's three + the key, the edge's link, the head's contig id) places 64 scans at once;
+//   2. the lanes that missed are taken one after the other by the whole wave: 64 positions per chunk from position 1 on, one look-up per
+//      lane, ballot, first set bit, next chunk — a mate without any k-mer in the set costs one look-up per k-mer, as in k_read_correct;
+//   3. the two roles of an oriented pair sit in neighbouring lanes: the even lane takes (c2, E) from the odd one, writes the record as
+//      one 16-byte store, classifies, and adds to its histogram bin (a no-return atomic; the bins of a segment are few and hot, which
+//      the memory side serialises — measured in profiles/pairs/README.md).  The six counters are ballots summed per wave in
+//      scalars, then through LDS per workgroup, then six atomics per workgroup, as s_skip of k_read_thread.
+// A pair with a mate of more than GASM_THREAD_KMER_CAP k-mers is skipped before any look-up.  rec: 4 int32 per oriented pair at
+// (o * n_pairs + p) * 4 (16-byte aligned), every pair of every segment written; hist: max_insert + 1 bins per segment, counters:
+// GASM_PAIR_COUNTERS per segment, both zeroed by the caller.  Every segment holds an even number of reads (the host checked).
+// have_graph = 0: the build holds no contig at all (its arrays may not exist): no mate is placed.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
+                                                        const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, int have_graph, u32 orient,
+                                                        u32 max_insert, u64 n_pairs, u32 chunks, int32_t* __restrict__ rec, u32* __restrict__ hist,
+                                                        unsigned long long* __restrict__ counters) {
+    __shared__ u32 s_cnt[GASM_PAIR_COUNTERS];
+    u32 seg, chunk;
+    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
+    if (threadIdx.x < GASM_PAIR_COUNTERS) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int k = gv.k;
+    u32 elo = 0, ehi = 0, c_lo = 0, c_hi = 0;
+    if (have_graph) {
+        const u32 nb = 1u << gv.bbits;
+        elo = gv.dstart[seg * nb]; ehi = gv.dstart[(seg + 1) * nb];
+        c_lo = seg_cstart[seg]; c_hi = seg_cstart[seg + 1];
+    }
+    const bool graph = elo < ehi && c_lo < c_hi;
+    const u64 pbeg = rs.seg_read_off[seg] >> 1, pend = rs.seg_read_off[seg + 1] >> 1;
+    const u32 two = orient == 2 ? 1u : 0u;
+    const u32 role = lane & 1u, o = two ? (lane >> 1) & 1u : 0u, lp = lane >> (1 + two);
+    const u32 pairs_per_wave = 32u >> two, pairs_per_wg = GASM_THREAD_WAVES * pairs_per_wave;
+    u32 c_cnt[GASM_PAIR_COUNTERS] = {0, 0, 0, 0, 0, 0};                       // of this wave's oriented pairs (wave-uniform)
+    for (u64 base = pbeg + (u64)chunk * pairs_per_wg; base < pend; base += (u64)chunks * pairs_per_wg) {
+        const u64 p = base + (u64)wv * pairs_per_wave + lp;
+        const bool valid = p < pend;
+        u64 p0 = 0;
+        u32 n = 0;                                                            // k-mers of this lane's mate
+        bool skip = false;
+        if (valid) {
+            const u32 mate = role ^ o;                                        // `first` is mate 1 in orientation 0, mate 2 in orientation 1
+            u64 q0;
+            u32 len, olen;
+            read_span(rs, 2 * p + mate, &p0, &len);
+            read_span(rs, 2 * p + (mate ^ 1u), &q0, &olen);
+            n = len >= (u32)k ? len - (u32)k + 1 : 0;
+            const u32 on = olen >= (u32)k ? olen - (u32)k + 1 : 0;
+            skip = n > GASM_THREAD_KMER_CAP || on > GASM_THREAD_KMER_CAP;
+        }
+        const bool active = valid && !skip && graph && n > 0;
+        // ---- 1. position 0 of every mate
+        bool found = false;
+        u32 r_cid = GASM_NONE32;
+        int r_pos = 0;                                                        // S of a `first`, E of a `second`
+        if (active) {
+            K key = kmer_key_at<K>(rs.words, p0, k);
+            if (role) key = key_revcomp<K>(key, k);
+            u32 cid, off;
+            if (kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, key, &cid, &off)) {
+                found = true; r_cid = cid; r_pos = role ? (int)off + k : (int)off;
+            }
+        }
+        // ---- 2. the mates that missed, one after the other, 64 positions at a time
+        u64 need = __ballot(active && !found && n > 1);
+        while (need) {
+            const int L = __builtin_ctzll(need);
+            need &= need - 1;
+            const u64 b_p0 = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(p0 >> 32), L) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)p0, L);
+            const u32 b_n = (u32)__builtin_amdgcn_readlane((int)n, L);
+            const bool b_rc = (L & 1) != 0;
+            for (u32 j0 = 1; j0 < b_n; j0 += 64) {
+                const u32 j = j0 + lane;
+                u32 cid = GASM_NONE32, off = 0;
+                bool hit = false;
+                if (j < b_n) {
+                    K key = kmer_key_at<K>(rs.words, b_p0 + j, k);
+                    if (b_rc) key = key_revcomp<K>(key, k);
+                    hit = kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, key, &cid, &off);
+                }
+                const u64 m = __ballot(hit);
+                if (!m) continue;
+                const int f = __builtin_ctzll(m);
+                const u32 h_cid = (u32)__builtin_amdgcn_readlane((int)cid, f), h_off = (u32)__builtin_amdgcn_readlane((int)off, f);
+                const int i = (int)j0 + f;
+                if ((int)lane == L) { found = true; r_cid = h_cid; r_pos = b_rc ? (int)h_off + k + i : (int)h_off - i; }
+                break;
+            }
+        }
+        // ---- 3. the record of every oriented pair, from its even lane
+        const u32 n_cid = (u32)__shfl_down((int)r_cid, 1, 64);
+        const int n_pos = __shfl_down(r_pos, 1, 64);
+        const bool mine = valid && role == 0;
+        u32 cls = GASM_PAIR_COUNTERS;
+        if (mine) {
+            const bool a = r_cid != GASM_NONE32, b = n_cid != GASM_NONE32;
+            const int d = n_pos - r_pos;
+            cls = skip ? 0u : !a && !b ? 1u : a != b ? 2u : r_cid != n_cid ? 5u : d > 0 ? 3u : 4u;
+            int4 v;
+            v.x = a ? (int)(r_cid - c_lo) : -1; v.y = a ? r_pos : 0;
+            v.z = b ? (int)(n_cid - c_lo) : -1; v.w = b ? n_pos : 0;
+            *reinterpret_cast<int4*>(rec + ((u64)o * n_pairs + p) * 4) = v;
+            if (cls == 3u) atomicAdd(&hist[(size_t)seg * (max_insert + 1) + ((u32)d < max_insert ? (u32)d : max_insert)], 1u);
+        }
+#pragma unroll
+        for (u32 f = 0; f < GASM_PAIR_COUNTERS; ++f) c_cnt[f] += (u32)__popcll(__ballot(cls == f));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (u32 f = 0; f < GASM_PAIR_COUNTERS; ++f)
+            if (c_cnt[f]) atomicAdd(&s_cnt[f], c_cnt[f]);
+    }
+    __syncthreads();
+    if (threadIdx.x < GASM_PAIR_COUNTERS && s_cnt[threadIdx.x]) atomicAdd(&counters[(size_t)seg * GASM_PAIR_COUNTERS + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+template __global__ void k_pair_place<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, int, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);
+template __global__ void k_pair_place<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, int, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);

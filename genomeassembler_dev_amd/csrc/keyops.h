@@ -63,6 +63,17 @@ __device__ __forceinline__ u32 kfield(const K128& a, int s) { return (u32)kshr(a
 __device__ __forceinline__ u32 klow2(u64 a) { return (u32)a & 3u; }
 __device__ __forceinline__ u32 klow2(const K128& a) { return (u32)a.lo & 3u; }
 
+// the reverse complement of a k-mer key: complement every base (A0 C1 G2 T3: 3 - x = ~x), reverse the order of the 2-bit groups
+// (reverse all bits, then swap the two bits of every group back) and move the 2k bits, now at the top, down again.  k <= 31 resp.
+// 32 <= k <= 63, as the keys themselves
+__device__ __forceinline__ u64 rev_groups2(u64 x) {
+    x = __brevll(x);
+    return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+}
+template <class K> __device__ __forceinline__ K key_revcomp(const K& a, int k);
+template <> __device__ __forceinline__ u64 key_revcomp<u64>(const u64& a, int k) { return rev_groups2(~a) >> (64 - 2 * k); }
+template <> __device__ __forceinline__ K128 key_revcomp<K128>(const K128& a, int k) { return kshr(K128{rev_groups2(~a.lo), rev_groups2(~a.hi)}, 128 - 2 * k); }
+
 // Home-set hash of the de-duplication tables.  A 64-bit multiply is a handful of quarter-rate 32-bit multiplies on CDNA —
 // a third of the vector time of k_bucket_dedup; two 24-bit multiplies (full rate) over a folded key spread real k-mer
 // sets just as evenly (same overflow fraction on random keys, genome buckets and two-letter sequences).

@@ -161,6 +161,13 @@ struct BuildState {
     std::vector<u32> h_succ, h_pred, h_link_support, h_span_support;
     std::vector<u64> h_links_skipped;
     bool links_queued = false;              // k_contig_links and k_read_thread ran on the arrays of this build
+    DBuf d_pairs;                           // read-pair places of the last build (pipeline_place_pairs): int32 rec[4 * orientations * pairs], then
+                                            // u32 insert_hist[S * (max_insert + 1)] (padded to 8 bytes), then u64 counters[S * GASM_PAIR_FIELDS]
+    std::vector<int32_t> h_pair_rec;
+    std::vector<u32> h_pair_hist;
+    std::vector<u64> h_pair_counters;
+    u32 pairs_orient = 0, pairs_max_insert = 0;     // of the last placement
+    bool pairs_queued = false;              // k_pair_place ran on the arrays of this build
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -255,6 +262,13 @@ int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // builds): GASM_ERR_STATE
 int pipeline_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 span_len);
 int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// Read pairs (k_pair_place in kernels_links.hip; the rule: include/gasm.h "Read pairs") of the finished build: queue the kernel on the build's
+// stream behind it (it reads the build's arrays and the batch's OWN reads `rd`, in which reads 2p and 2p + 1 are pair p — `rd_build` is what
+// the build was made from: the both-strand stream of a strands = 2 build, which then makes two orientations per pair), then fetch h_pair_rec
+// (4 per oriented pair), h_pair_hist (max_insert + 1 per segment) and h_pair_counters (GASM_PAIR_FIELDS per segment).  A segment with an odd
+// number of reads: GASM_ERR_INVALID.  Positioned reads (pooled builds): GASM_ERR_STATE
+int pipeline_place_pairs(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_insert);
+int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

@@ -468,7 +468,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_ccov, &d_links, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_ccov, &d_links, &d_pairs, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -958,6 +958,7 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, const BuildOpts&
     bs.spectrum_queued = false;
     bs.coverage_queued = false;
     bs.links_queued = false;
+    bs.pairs_queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -1215,6 +1216,74 @@ int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     if (S) HIPCHK(hipMemcpyAsync(bs.h_links_skipped.data(), d + (size_t)P * 28, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (bs.opts.strands == 2) for (u32 s = 0; s < S; ++s) bs.h_links_skipped[s] /= 2;      // (a read and its reverse complement are equally long)
+    return GASM_OK;
+}
+
+static_assert(GASM_PAIR_COUNTERS == GASM_PAIR_FIELDS, "kernels.h and gasm.h disagree on read pairs");
+
+// where the three tables of a placement lie in d_pairs
+struct PairTables {
+    size_t rec_words, hist_words, hist_off, cnt_off, bytes;
+    PairTables(u64 n_pairs, u32 orient, u32 S, u32 max_insert) {
+        rec_words = (size_t)n_pairs * orient * 4;
+        hist_words = (size_t)S * ((size_t)max_insert + 1);
+        hist_off = rec_words * 4;                                           // (a multiple of 16: the records are stored 16 bytes at a time)
+        cnt_off = (hist_off + hist_words * 4 + 7) & ~(size_t)7;
+        bytes = cnt_off + (size_t)S * GASM_PAIR_FIELDS * 8;
+    }
+};
+
+// read pairs: on the stream of the build, behind it; reads the directory, the dense keys, the ranking's links, the contig ids and offsets and
+// the packed reads, writes an array of its own (records, insert histogram, counters)
+int pipeline_place_pairs(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_insert) {
+    if (rd.positioned) { gasm_set_error("read pairs need the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
+    const u32 S = rd.n_segments;
+    for (u32 s = 0; s < S; ++s)
+        if ((rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]) & 1) {
+            gasm_set_error("segment %u holds an odd number of reads (%llu): reads 2p and 2p + 1 are the mates of pair p", s,
+                           (unsigned long long)(rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]));
+            return GASM_ERR_INVALID;
+        }
+    GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 P = bs.n_contigs, orient = bs.opts.strands == 2 ? 2u : 1u;
+    const u64 n_pairs = rd.n_reads / 2;
+    const PairTables t(n_pairs, orient, S, max_insert);
+    GCHK(bs.d_pairs.ensure(t.bytes));
+    u8* const d = bs.d_pairs.as<u8>();
+    HIPCHK(hipMemsetAsync(d + t.hist_off, 0, t.bytes - t.hist_off, ctx->stream));
+    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
+    if (n_pairs && S) {
+        u64 most = 1;
+        for (u32 s = 0; s < S; ++s) most = std::max(most, (rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]) / 2);
+        // a wave holds 64 scans (a mate of an oriented pair each), a workgroup four waves of them: the kernel loops where a segment holds
+        // more pairs than the grid covers at once
+        const u32 pairs_per_wg = (GASM_WG / 64) * (32u / orient);
+        const u32 groups = (S + 7u) / 8u;
+        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, pairs_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
+        GLAUNCH_K(ctx, bs.words, "k_pair_place", k_pair_place<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), bs.d_link.as<u64>(),
+                  bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), have_graph, orient, max_insert, n_pairs, chunks,
+                  reinterpret_cast<int32_t*>(d), reinterpret_cast<u32*>(d + t.hist_off), reinterpret_cast<unsigned long long*>(d + t.cnt_off));
+    }
+    bs.pairs_orient = orient;
+    bs.pairs_max_insert = max_insert;
+    bs.pairs_queued = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    if (!bs.pairs_queued) { gasm_set_error("gasm_batch_fetch_pair_places before gasm_batch_place_pairs (of the last build)"); return GASM_ERR_STATE; }
+    const u32 S = rd.n_segments;
+    const PairTables t(rd.n_reads / 2, bs.pairs_orient, S, bs.pairs_max_insert);
+    bs.h_pair_rec.assign(t.rec_words + 1, 0); bs.h_pair_hist.assign(t.hist_words + 1, 0);       // (one entry more: a pointer to hand out for
+    bs.h_pair_counters.assign((size_t)S * GASM_PAIR_FIELDS + 1, 0);                             // no pair and no segment at all)
+    const u8* const d = bs.d_pairs.as<u8>();
+    if (t.rec_words) HIPCHK(hipMemcpyAsync(bs.h_pair_rec.data(), d, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (S) {
+        HIPCHK(hipMemcpyAsync(bs.h_pair_hist.data(), d + t.hist_off, t.hist_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_pair_counters.data(), d + t.cnt_off, (size_t)S * GASM_PAIR_FIELDS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return GASM_OK;
 }
 

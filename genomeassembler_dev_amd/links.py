@@ -46,6 +46,15 @@ def resolve_segment(contigs, k, span_len, succ, pred, span_support, min_support=
             assert a not in right and b not in left, "a flank has at most one join on each side"
             right[a] = (r, b)
             left[b] = (a, r)
+    return chain_joins(contigs, k, right, left, resolved)
+
+
+def chain_joins(contigs, k, right, left, resolved):
+    """the output of a repeat resolution from its joins a . r . b: right[a] = (r, b), left[b] = (a, r), resolved = the repeats r.  The joins
+    form simple chains of flanks with copies of repeats in between, overlapping by k-1 bases: each chain is one contig, a chain that closes
+    on itself is cut in front of its smallest flank, contigs in no join come out unchanged, resolved repeats do not come out on their
+    own.  Returns the sorted unique list of str (shared by ContigLinks.resolve_repeats and pairs.PairPlaces.resolve_repeats)."""
+    n = len(contigs)
     assert not (resolved & (set(right) | set(left))), "a resolved repeat is never the flank of another one"
 
     def text(chain):

@@ -39,6 +39,30 @@ def plant_repeat(genome, rep_len, seed, min_gap=200):
     return g, p1, p2
 
 
+def simulate_pairs(genome, read_len, coverage, insert_mean, insert_sd, seed, both_strands=False):
+    """(2 * pairs, read_len) uint8 array of forward-reverse read pairs, interleaved (rows 2p and 2p + 1 are the mates of pair p): fragments
+    with uniform starts and normal lengths (rounded, at least read_len; a fragment that runs past the genome's end is dropped), with
+    both_strands each from either strand; mate 1 = the fragment's first read_len bases, mate 2 = the reverse complement of its last —
+    the README's paired example"""
+    rng = np.random.Generator(np.random.MT19937(seed))
+    L = genome.size
+    n = int(np.ceil(coverage * L / (2 * read_len)))
+    starts = rng.integers(0, L, size=n)
+    ins = np.maximum(read_len, np.rint(rng.normal(insert_mean, insert_sd, size=n))).astype(np.int64)
+    flip = rng.integers(0, 2, size=n) if both_strands else np.zeros(n, dtype=np.int64)
+    comp = np.zeros(256, dtype=np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    keep = starts + ins <= L
+    s, d, f = starts[keep], ins[keep], flip[keep].astype(bool)
+    j = np.arange(read_len)
+    head = genome[s[:, None] + j]                                   # the fragment's first bases on the genome's strand ...
+    tail = comp[genome[(s + d - 1)[:, None] - j]]                   # ... and the reverse complement of its last
+    out = np.empty((2 * s.size, read_len), dtype=np.uint8)
+    out[0::2] = np.where(f[:, None], tail, head)                    # (a flipped fragment starts where the other ends)
+    out[1::2] = np.where(f[:, None], head, tail)
+    return out
+
+
 def simulate_reads(genome, read_len, coverage, seed, weights=None):
     """(n_reads, read_len) uint8 array of reads; starts uniform, or drawn with `weights` (one per start position)."""
     L = genome.size

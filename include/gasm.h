@@ -625,6 +625,48 @@ int gasm_batch_fetch_reads(gasm_batch* b, const char** ascii, const uint64_t** r
 int gasm_batch_contig_links(gasm_batch* b, uint32_t span_len);
 int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const uint32_t** pred, const uint32_t** link_support,
                                   const uint32_t** span_support, const uint64_t** skipped /* n_segments */);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Read pairs: where the two reads of a sequenced fragment lie on the contigs.  (The reference writes read_2 as reverse complements,
+ * lib/GenerateReads.R:437-458, and hands both files to Velvet as -shortPaired, lib/DeNovoAssembler.R:182-203.)  A repeat longer than the
+ * reads stays cut whatever the reads that run through it say (Contig links, above); a fragment whose mates lie in the two flanks still
+ * says which flank continues into which.
+ * The rule.  PAIRS.  Inside every segment reads 2p and 2p + 1 are the two MATES of pair p: an interleaved layout, which
+ * gasm_batch_from_files yields for an interleaved FASTQ.  The pairs are forward-reverse: mate 1 is the fragment's first bases, mate 2
+ * the reverse complement of its last bases.  A segment with an odd number of reads makes the call fail with GASM_ERR_INVALID.  Dropping
+ * non-ACGT reads at ingest breaks the pairing: that is the caller's business.
+ *   THE SET.  The graph is the one of the batch's LAST FINISHED BUILD, whatever its options, exactly as for contig links.  A k-mer is IN
+ *   THE SET if the build holds it and it lies in a contig; a k-mer of an isolated cycle is not in the set.  Contig indices are the ones
+ *   INSIDE THE SEGMENT; len(c) is counted in bases.
+ *   PLACEMENT of an oriented pair (first, second).  i1 = the smallest k-mer start of `first` whose k-mer is in the set, at contig c1,
+ *   offset o1: S = o1 - i1 is where the fragment starts on c1 (it may be negative).  i2 = the smallest k-mer start of `second` whose
+ *   REVERSE-COMPLEMENTED k-mer is in the set, at contig c2, offset o2: E = o2 + k + i2 is one past where the fragment ends on c2 (it may
+ *   exceed len(c2)).  A mate shorter than k, or with no such position, is UNPLACED.  A pair with a mate of more than
+ *   GASM_THREAD_MAX_KMERS k-mers is SKIPPED: neither mate is looked at.
+ *   ORIENTATIONS.  Orientation 0 is (mate 1, mate 2).  After a strands = 2 build orientation 1 = (mate 2, mate 1) is placed as well, as
+ *   the build saw the reads; after a strands = 1 build only orientation 0.  After a both-strand build, orientation 1 of a pair is
+ *   (twin(c2), len(c2) - E, twin(c1), len(c1) - S) of its orientation 0.
+ *   OUTPUTS, all exact integers, accumulated with integer atomics: independent of the order the pairs are taken in.
+ *     rec[(o * n_pairs + p) * 4 + 0..3] = c1, S, c2, E as int32; p = the pair's index in the batch (read index / 2), n_pairs = reads of
+ *       the batch / 2, o = the orientation.  A contig of -1 with position 0: the mate is unplaced.  Both contigs -1: skipped (or neither
+ *       placed: the counters tell).
+ *     insert_hist[s * (max_insert + 1) + d] counts the oriented pairs of segment s with both mates placed on the SAME contig and
+ *       d = E - S > 0; bin max_insert collects every d >= max_insert.  max_insert is in 1..GASM_MAX_INSERT, else GASM_ERR_INVALID.
+ *     counters[s * GASM_PAIR_FIELDS + f] counts oriented pairs, f in this order: skipped, none_placed, one_placed, same_contig (d > 0),
+ *       reversed (same contig, d <= 0), diff_contig.  The six sum to the segment's pairs x orientations.
+ * gasm_batch_place_pairs          finishes the pending build and queues k_pair_place on the step slot of the last build, behind it;
+ *                                 GASM_ERR_STATE before a build and for the positioned reads of pooled builds, GASM_ERR_INVALID for a
+ *                                 null batch, a bad max_insert or an odd segment.  It reads the build's arrays and the reads only:
+ *                                 build, contig, score, coverage, twin and link results fetched before and after it are identical,
+ *                                 and a batch that never calls it launches exactly what it launched without.
+ * gasm_batch_fetch_pair_places    host copies, valid until the next call or build; *orientations = 1 or 2.  GASM_ERR_STATE before a
+ *                                 build or without a placement over the last build.
+ * What to do with them (insert size, mate links, resolving repeats longer than a read) is host code: genomeassembler_dev_amd/pairs.py.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAX_INSERT 65535
+#define GASM_PAIR_FIELDS 6
+int gasm_batch_place_pairs(gasm_batch* b, uint32_t max_insert);
+int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint32_t** insert_hist, const uint64_t** counters,
+                                 uint32_t* orientations);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 

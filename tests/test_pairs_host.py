@@ -1,0 +1,302 @@
+"""Read pairs without a GPU: include/gasm.h declares the entries and states the rule, libgasm.so exports them, the ctypes mirror and the
+Python surface know them; the CPU restatement of the rule (tests/pairs_ref.py) gives on hand-built contigs and pairs the records,
+histogram and counters written out here by hand; pairs.PairPlaces — quantiles, mate links, repeat resolution — and its independent
+restatement give on them what the rule says; and the README's worked example holds through the restatement.
+The hand-built cases use k = 5 and the pieces of tests/test_links_host.py: X = GCAATAGGG, R = TAATTCGC, Y = CGACGAGTA, Z = AGCGTAGAT; the
+genome X R Y R Z is cut into Xc = g[0:13], R = g[9:17] = g[26:34], Zc = g[30:43], Yc = g[13:30] (contigs 0, 1, 2, 3)."""
+import ctypes as C
+import inspect
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import links_ref as lr
+import pairs_ref as pr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "genomeassembler_dev_amd", "libgasm.so")
+HEADER = os.path.join(ROOT, "include", "gasm.h")
+K = 5
+X, R, Y, Z = "GCAATAGGG", "TAATTCGC", "CGACGAGTA", "AGCGTAGAT"
+G = X + R + Y + R + Z
+CONTIGS = [X + "TAAT", R, "TCGC" + Z, "TCGC" + Y + "TAAT"]
+
+SIGNATURES = {
+    "gasm_batch_place_pairs": "int gasm_batch_place_pairs(gasm_batch* b, uint32_t max_insert);",
+    "gasm_batch_fetch_pair_places": "int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint32_t** insert_hist, "
+                                    "const uint64_t** counters, uint32_t* orientations);",
+}
+
+
+def _flat(text):
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"\s+", " ", text).replace("( ", "(").replace(" )", ")")
+
+
+def test_header_declares_the_entries_and_the_rule():
+    with open(HEADER) as f:
+        raw = f.read()
+    flat = _flat(raw)
+    for name, sig in SIGNATURES.items():
+        assert _flat(sig) in flat, name
+    assert "#define GASM_MAX_INSERT 65535" in raw and "#define GASM_PAIR_FIELDS 6" in raw
+    words = " ".join(re.sub(r"(?m)^ \* ?", " ", raw).split())
+    for phrase in ("Read pairs", "reads 2p and 2p + 1 are the two MATES of pair p", "an odd number of reads makes the call fail with GASM_ERR_INVALID",
+                   "breaks the pairing: that is the caller's business", "a k-mer of an isolated cycle is not in the set",
+                   "S = o1 - i1 is where the fragment starts on c1 (it may be negative)", "REVERSE-COMPLEMENTED k-mer is in the set",
+                   "E = o2 + k + i2 is one past where the fragment ends on c2", "is SKIPPED: neither mate is looked at",
+                   "orientation 1 = (mate 2, mate 1) is placed as well", "(twin(c2), len(c2) - E, twin(c1), len(c1) - S) of its orientation 0",
+                   "rec[(o * n_pairs + p) * 4 + 0..3] = c1, S, c2, E as int32", "bin max_insert collects every d >= max_insert",
+                   "skipped, none_placed, one_placed, same_contig (d > 0), reversed (same contig, d <= 0), diff_contig",
+                   "The six sum to the segment's pairs x orientations", "GASM_ERR_STATE before a build or without a placement over the last build"):
+        assert phrase in words, phrase
+    assert "A repeat longer than the reads stays cut" in words
+
+
+def test_library_exports_the_entries():
+    lib = C.CDLL(LIB)                                                # (symbol table only: nothing here calls into the library)
+    for name in SIGNATURES:
+        assert hasattr(lib, name), name
+
+
+def test_ctypes_mirror_and_python_surface():
+    from genomeassembler_dev_amd import _lib, api, batch, links, pairs, synth
+    import genomeassembler_dev_amd as ga
+    i, vp, pp, u32 = C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32
+    want = {"gasm_batch_place_pairs": (i, [vp, u32]), "gasm_batch_fetch_pair_places": (i, [vp, pp, pp, pp, C.POINTER(u32)])}
+    for name, (res, args) in want.items():
+        assert _lib.SYMBOLS[name][0] is res and list(_lib.SYMBOLS[name][1]) == args, name
+    assert _lib.MAX_INSERT == pr.MAX_INSERT == 65535 and tuple(_lib.PAIR_FIELDS) == pr.FIELDS and len(_lib.PAIR_FIELDS) == 6
+    assert inspect.signature(batch.SegmentBatch.place_pairs).parameters["max_insert"].default is None
+    for name in ("records", "insert_hist", "counters", "insert_size", "mate_links", "resolve_repeats"):
+        assert callable(getattr(pairs.PairPlaces, name)), name
+    q = inspect.signature(pairs.PairPlaces.resolve_repeats).parameters
+    assert list(q)[1:] == ["segment", "links", "min_support", "insert_range"] and q["min_support"].default == 2 and q["insert_range"].default is None
+    assert inspect.signature(pairs.PairPlaces.counters).parameters["as_dict"].default is False
+    assert ga.resolve_repeats_paired is api.resolve_repeats_paired and ga.PairPlaces is pairs.PairPlaces
+    q = inspect.signature(api.resolve_repeats_paired).parameters
+    assert list(q)[:4] == ["reads", "k", "min_support", "max_insert"] and q["min_support"].default == 2 and q["max_insert"].default is None
+    assert list(inspect.signature(synth.simulate_pairs).parameters) == ["genome", "read_len", "coverage", "insert_mean", "insert_sd", "seed", "both_strands"]
+    # one chaining for both resolutions
+    assert pairs.chain_joins is links.chain_joins and "chain_joins(" in inspect.getsource(links.resolve_segment)
+
+
+def _places(contigs, t, k=K, strands=1, max_insert=64):
+    from genomeassembler_dev_amd import pairs
+    rec = np.array(t["records"], dtype=np.int32)
+    return pairs.PairPlaces(k, strands, max_insert, rec.shape[0], [contigs], rec.reshape(-1), np.array(t["insert_hist"], dtype=np.uint32),
+                            np.array(t["counters"], dtype=np.uint64))
+
+
+def _links(contigs, k=K, strands=1):
+    from genomeassembler_dev_amd import links
+    t = lr.tables(contigs, [], k, strands, 0)
+    n = len(contigs)
+    return links.ContigLinks(k, 0, strands, [0, n], [contigs], np.array(t["succ"], dtype=np.uint32), np.array(t["pred"], dtype=np.uint32),
+                             np.zeros((n, 4), np.uint32), np.zeros((n, 4, 4), np.uint32), [0], np.zeros(n, np.uint64))
+
+
+def test_argument_errors_of_the_python_surface():
+    from genomeassembler_dev_amd import batch
+    b = batch.SegmentBatch.__new__(batch.SegmentBatch)               # (no library call is reached: the checks come first)
+    b.h = None
+    for bad in (0, -1, 65536):
+        with pytest.raises(ValueError):
+            b.place_pairs(max_insert=bad)
+    pp = _places(CONTIGS, pr.place(CONTIGS, [], K, 1, 64))
+    cl = _links(CONTIGS)
+    with pytest.raises(ValueError):
+        pp.resolve_repeats(0, cl, min_support=0)
+    with pytest.raises(ValueError):
+        pp.resolve_repeats(0, cl, insert_range=(30, 20))
+    with pytest.raises(ValueError):
+        pp.resolve_repeats(0, _links(CONTIGS[:1]))                   # the links of another build
+    with pytest.raises(ValueError):
+        pp.insert_size(0)                                            # an empty histogram
+    for bad in (-1, 1):
+        with pytest.raises(IndexError):
+            pp.records(bad)
+    assert pp.records(0).shape == (1, 0, 4) and pp.mate_links(0) == [] and pp.resolve_repeats(0, cl) == sorted(CONTIGS)
+
+
+# ---- the hand-built pairs: (mate 1, mate 2, the record of orientation 0, its counter field)
+HAND = [
+    (G[0:7], pr.rc(G[23:30]), [0, 0, 3, 17], "diff_contig"),                 # the fragment g[0:30): starts Xc, ends with Yc's last base
+    (G[14:21], pr.rc(G[22:29]), [3, 1, 3, 16], "same_contig"),               # g[14:29) inside Yc = g[13:30): d = 15
+    (G[22:29], pr.rc(G[14:21]), [3, 9, 3, 8], "reversed"),                   # the same two reads as an outie: d = -1
+    ("GCA", pr.rc(G[22:29]), [-1, 0, 3, 16], "one_placed"),                  # mate 1 shorter than k
+    ("ACACACA", "CCCCCCC", [-1, 0, -1, 0], "none_placed"),
+    (G[0:15], pr.rc(G[23:30]), [-1, 0, -1, 0], "skipped"),                   # 11 k-mers against max_kmers = 10
+    ("TT" + G[0:7], "GG" + pr.rc(G[38:43]), [0, -2, 2, 15], "diff_contig"),  # first hits at i1 = 2 and i2 = 2: S < 0, E > len(Zc) = 13
+    (G[9:16], pr.rc(G[27:34]), [1, 0, 1, 8], "same_contig"),                 # both inside the repeat's contig R: d = 8 = len(R)
+]
+
+
+def test_restatement_on_hand_built_pairs_every_counter_field():
+    reads = [m for m1, m2, _, _ in HAND for m in (m1, m2)]
+    t = pr.place(CONTIGS, reads, K, 1, 12, max_kmers=10)
+    assert t["records"] == [[rec for _, _, rec, _ in HAND]]
+    want = [sum(1 for h in HAND if h[3] == f) for f in pr.FIELDS]
+    assert t["counters"] == want == [1, 1, 1, 2, 1, 2]
+    hist = [0] * 13
+    hist[8], hist[12] = 1, 1                                          # d = 8, and d = 15 in the overflow bin of max_insert = 12
+    assert t["insert_hist"] == hist
+    pp = _places(CONTIGS, t, max_insert=12)
+    assert pp.records(0).tolist() == t["records"] and pp.insert_hist(0).tolist() == hist
+    assert pp.counters(0).tolist() == want and pp.counters(0, as_dict=True) == dict(zip(pr.FIELDS, want))
+    assert pp.n_pairs == len(HAND) and pp.orientations == 1
+    assert pp.insert_size(0) == pr.quantiles(hist, 12) == (8, 8, 8)   # (the overflow bin is left out)
+
+
+def test_twin_identity_of_orientation_one():
+    both = sorted(CONTIGS + [pr.rc(c) for c in CONTIGS])
+    reads = [m for m1, m2, _, _ in HAND for m in (m1, m2)]
+    t = pr.place(both, reads, K, 2, 64, max_kmers=10)
+    assert len(t["records"]) == 2 and pr.twin_identity(both, t["records"])
+    assert sum(t["counters"]) == 2 * len(HAND) and t["counters"][0] == 2
+    # by hand, for the first pair: orientation 0 = (Xc, 0, Yc, 17), so orientation 1 = (rc(Yc), 17 - 17, rc(Xc), 13 - 0)
+    xc, yc, xr, yr = (both.index(s) for s in (CONTIGS[0], CONTIGS[3], pr.rc(CONTIGS[0]), pr.rc(CONTIGS[3])))
+    assert t["records"][0][0] == [xc, 0, yc, 17] and t["records"][1][0] == [yr, 0, xr, 13]
+
+
+def test_quantile_rule_on_a_hand_made_histogram():
+    from genomeassembler_dev_amd import pairs
+    hist = [7] + [0] * 20                                            # bin 0 and the overflow bin (20) are not looked at
+    hist[3], hist[5], hist[9], hist[20] = 1, 197, 2, 1000            # total 200: ceil(2) = 2, ceil(100) = 100, ceil(198) = 198
+    assert pairs.quantiles(hist, 20) == pr.quantiles(hist, 20) == (5, 5, 5)
+    hist[3], hist[5] = 2, 196                                        # now the 2nd value is still 3, the 198th is 5, the 199th is 9
+    assert pairs.quantiles(hist, 20) == pr.quantiles(hist, 20) == (3, 5, 5)
+    hist[5], hist[9] = 195, 3
+    assert pairs.quantiles(hist, 20) == pr.quantiles(hist, 20) == (3, 5, 9)
+    one = [0] * 21
+    one[19] = 1                                                      # a single value is all three quantiles; 101 values: ceil(1.01) = 2
+    assert pairs.quantiles(one, 20) == pr.quantiles(one, 20) == (19, 19, 19)
+    many = [0] * 21
+    many[1], many[2] = 1, 100
+    assert pairs.quantiles(many, 20) == pr.quantiles(many, 20) == (2, 2, 2)
+    for f in (pairs.quantiles, pr.quantiles):
+        with pytest.raises(ValueError):
+            f([5] + [0] * 19 + [5], 20)
+
+
+def _records(rows):
+    return dict(records=[[list(r) for r in rows]], insert_hist=[0] * 65, counters=[0, 0, 0, 0, 0, len(rows)])
+
+
+def test_mate_links_and_the_gap_of_adjacent_contigs():
+    # Xc = g[0:13] and R = g[9:17] overlap by k - 1 = 4.  A fragment g[2:17) of 15 bases: S = 2 on Xc, E = 8 on R; with the median at
+    # 15 its gap is 15 - (13 - 2) - 8 = -4 = -(k - 1).  A second one, g[0:15): S = 0, E = 6: gap 15 - 13 - 6 = -4 again
+    rows = [(0, 2, 1, 8), (0, 0, 1, 6), (3, 1, 3, 16), (1, 0, 2, 7), (-1, 0, 2, 7)]
+    t = _records(rows)
+    t["insert_hist"][15] = 1
+    pp = _places(CONTIGS, t)
+    assert pp.insert_size(0) == (15, 15, 15)
+    want = [(0, 1, 2, -4.0), (1, 2, 1, 15.0 - 8 - 7)]
+    assert pp.mate_links(0) == want == pr.mate_links(CONTIGS, t["records"], 15)
+    # for real, through the restatement: the reads of those two fragments
+    reads = [G[2:9], pr.rc(G[10:17]), G[0:7], pr.rc(G[8:15])]
+    got = pr.place(CONTIGS, reads, K, 1, 64)
+    assert got["records"] == [[[0, 2, 1, 8], [0, 0, 1, 6]]] and pr.mate_links(CONTIGS, got["records"], 15) == [(0, 1, 2, -(K - 1.0))]
+
+
+# through R (8 bases) from Xc into Yc: (13 - S) + 8 - 8 + E; the true fragment g[0:30) has 30 bases, g[17:39) from Yc into Zc 22
+XY, YZ, XZ, XZ_SHORT, YY, YY_LONG = (0, 0, 3, 17), (3, 4, 2, 9), (0, 0, 2, 9), (0, 5, 2, 9), (3, 4, 3, 10), (3, 0, 3, 17)
+
+
+@pytest.mark.parametrize("name, rows, min_support, insert_range, resolved", [
+    ("permutation", [XY, XY, YZ, YZ], 2, (20, 30), True),
+    ("mixed matrix: X -> Z as well", [XY, XY, YZ, YZ, XZ, XZ], 2, (20, 30), False),
+    ("one stray pair is enough to mix", [XY, XY, YZ, YZ, XZ], 2, (20, 30), False),
+    ("min_support", [XY, YZ, YZ], 2, (20, 30), False),
+    ("min_support = 1", [XY, YZ, YZ], 1, (20, 30), True),
+    ("wrong pairing outside the range (17 bases)", [XY, XY, YZ, YZ, XZ_SHORT, XZ_SHORT], 2, (20, 30), True),
+    ("the same, a wider range lets it in", [XY, XY, YZ, YZ, XZ_SHORT, XZ_SHORT], 2, (17, 30), False),
+    ("a same-contig pair that would fit through R counts (23 bases)", [XY, XY, YZ, YZ, YY], 2, (20, 30), False),
+    ("... and does not when it would not (34 bases)", [XY, XY, YZ, YZ, YY_LONG], 2, (20, 30), True),
+    ("a row without pairs", [XY, XY], 2, (20, 30), False),
+])
+def test_resolve_repeats_cases(name, rows, min_support, insert_range, resolved):
+    t = _records(rows)
+    pp, cl = _places(CONTIGS, t), _links(CONTIGS)
+    want = [G] if resolved else sorted(CONTIGS)
+    assert pp.resolve_repeats(0, cl, min_support, insert_range) == want, name
+    assert pr.resolve(CONTIGS, K, t["records"], min_support, insert_range) == want, name
+    ins, outs, M = pr.matrix(CONTIGS, K, t["records"], 1, insert_range)
+    assert (ins, outs) == ([0, 3], [2, 3]) and sum(M.values()) <= len(rows)
+    assert all(pr.matrix(CONTIGS, K, t["records"], r) is None for r in (0, 2, 3))
+
+
+def test_resolve_repeats_default_range_is_q01_q99():
+    rows = [XY, XY, YZ, YZ, XZ_SHORT, XZ_SHORT]
+    t = _records(rows)
+    t["insert_hist"][20], t["insert_hist"][30] = 5, 5
+    pp, cl = _places(CONTIGS, t), _links(CONTIGS)
+    assert pp.insert_size(0) == (20, 20, 30) and pp.resolve_repeats(0, cl) == [G]
+    t["insert_hist"][17] = 5
+    assert _places(CONTIGS, t).insert_size(0)[0] == 17 and _places(CONTIGS, t).resolve_repeats(0, cl) == sorted(CONTIGS)
+    t["insert_hist"] = [0] * 65                                      # no insert size: nothing is resolved
+    assert _places(CONTIGS, t).resolve_repeats(0, cl) == sorted(CONTIGS)
+
+
+def test_simulate_pairs_follows_its_recipe():
+    from genomeassembler_dev_amd import synth
+    g = synth.make_segment(3, 900, planted=False)
+    text = g.tobytes().decode()
+    for both in (False, True):
+        got = synth.simulate_pairs(g, 50, 12, 200, 25, 7, both_strands=both)
+        rng = np.random.Generator(np.random.MT19937(7))
+        n = math.ceil(12 * 900 / 100)
+        starts = rng.integers(0, 900, size=n)
+        ins = np.maximum(50, np.rint(rng.normal(200, 25, size=n)))
+        flip = rng.integers(0, 2, size=n) if both else np.zeros(n)
+        want = []
+        for s, d, f in zip(starts.tolist(), ins.tolist(), flip.tolist()):
+            s, d = int(s), int(d)
+            if s + d > 900:
+                continue
+            frag = pr.rc(text[s:s + d]) if f else text[s:s + d]
+            want += [frag[:50], pr.rc(frag[-50:])]
+        assert got.dtype == np.uint8 and got.shape == (len(want), 50) and 0 < len(want) < 2 * n
+        assert [r.tobytes().decode() for r in got] == want
+        if both:
+            assert 0 < flip.sum() < n
+
+
+# ---- the README's worked example, through the restatement
+def worked_example():
+    from genomeassembler_dev_amd import synth
+    g, p1, p2 = synth.plant_repeat(synth.make_segment(28, 4000, planted=False), 200, 28)
+    reads = [r.tobytes().decode() for r in synth.simulate_pairs(g, 80, 30, 400, 30, 28, both_strands=True)]
+    return g.tobytes().decode(), (p1, p2), reads
+
+
+def test_worked_example_through_the_restatement():
+    k = 21
+    genome, (p1, p2), reads = worked_example()
+    assert (p1, p2) == (999, 1812) and genome[p1:p1 + 200] == genome[p2:p2 + 200] and len(reads) == 2 * 668
+    contigs = pr.contigs_of_reads(reads, k, 2)
+    assert sorted(map(len, contigs)) == [200, 200, 653, 653, 1019, 1019, 2008, 2008]
+    t = pr.place(contigs, reads, k, 2, 1024)
+    assert dict(zip(pr.FIELDS, t["counters"])) == dict(skipped=0, none_placed=0, one_placed=0, same_contig=936, reversed=0, diff_contig=400)
+    assert pr.twin_identity(contigs, t["records"])
+    q = pr.quantiles(t["insert_hist"], 1024)
+    assert q == (324, 397, 475)
+    xc, rr, yc, zc = (contigs.index(s) for s in (genome[:p1 + k - 1], genome[p1:p1 + 200], genome[p1 + 200 - (k - 1):p2 + k - 1], genome[p2 + 200 - (k - 1):]))
+    ins, outs, M = pr.matrix(contigs, k, t["records"], rr)
+    assert (ins, outs) == (sorted([xc, yc]), sorted([yc, zc]))
+    assert (M[(xc, yc)], M[(yc, zc)], M[(yc, yc)], M[(xc, zc)]) == (38, 25, 52, 0)                  # unfiltered: Y -> Y blocks
+    _, _, M = pr.matrix(contigs, k, t["records"], rr, (q[0], q[2]))
+    assert (M[(xc, yc)], M[(yc, zc)], M[(yc, yc)], M[(xc, zc)]) == (37, 24, 0, 0)
+    want = sorted([genome, pr.rc(genome)])
+    assert pr.resolve(contigs, k, t["records"], 2, (q[0], q[2])) == want
+    assert pr.resolve(contigs, k, t["records"], 2, (1, 4000)) == sorted(contigs)
+    # pairs.py on the same tables, with the links of the same contigs
+    pp, cl = _places(contigs, t, k, 2, 1024), _links(contigs, k, 2)
+    assert pp.insert_size(0) == q and pp.resolve_repeats(0, cl) == want and pp.resolve_repeats(0, cl, insert_range=(1, 4000)) == sorted(contigs)
+    assert pp.mate_links(0) == pr.mate_links(contigs, t["records"], q[1]) and len(pp.mate_links(0)) == 12
+    # reads alone do not get through a 200-base repeat: spans of up to the read length leave all eight contigs
+    tl = lr.tables(contigs, reads, k, 2, 80)
+    assert lr.resolve(contigs, k, 80, tl, 2) == sorted(contigs)
