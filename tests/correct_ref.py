@@ -33,6 +33,18 @@ def weak_runs(read, trusted, k):
     return runs
 
 
+def fitting(read, trusted, k, a, b, p):
+    """the bases other than read[p] with which every k-mer a .. b of the read is trusted"""
+    fits = []
+    for x in "ACGT":
+        if x == read[p]:
+            continue
+        cand = read[:p] + x + read[p + 1:]                      # (the read as given: other runs' fixes are not in it)
+        if all(cand[j:j + k] in trusted for j in range(a, b + 1)):
+            fits.append(x)
+    return fits
+
+
 def correct(read, trusted, k):
     """the rule on one read: (the read afterwards, bases changed, category)"""
     n = len(read) - k + 1
@@ -55,13 +67,7 @@ def correct(read, trusted, k):
             if b - a + 1 > k:
                 continue
             p = a + k - 1
-        fits = []
-        for x in "ACGT":
-            if x == read[p]:
-                continue
-            cand = read[:p] + x + read[p + 1:]                  # (the read as given: other runs' fixes are not in it)
-            if all(cand[j:j + k] in trusted for j in range(a, b + 1)):
-                fits.append(x)
+        fits = fitting(read, trusted, k, a, b, p)
         if len(fits) == 1:
             out[p] = fits[0]
             fixed += 1
@@ -130,12 +136,14 @@ def _sub(read, *positions):
 
 
 def backbone(rng, k):
-    """k = 21: lowcov_ref._backbone (300 random bases, their 60-base windows, each four times); larger k: the same with 100-base windows"""
+    """k = 21: lowcov_ref._backbone (300 random bases, their 60-base windows, each four times); larger k: the same with 100-base windows;
+    k > 41: windows of 2k + 24 bases, so that an error k + 1 behind position 10 still leaves an interior run and one trusted k-mer follows"""
     if k <= 21:
         G, reads = lr._backbone(rng)
         return G, reads, 60
     G = br._rnd(rng, 300)
-    return G, [G[i:i + 100] for i in range(300 - 100 + 1)] * 4, 100
+    W = 100 if k <= 41 else 2 * k + 24
+    return G, [G[i:i + W] for i in range(300 - W + 1)] * 4, W
 
 
 def hand_cases(k, seed=7):
@@ -201,3 +209,68 @@ def long_read_cases(seed=8):
         cases.append((name, 0, len(seg), src, len(subs), cat))
         seg.append(_sub(src, *subs))
     return seg, cases
+
+
+def candidate_round_cases(seed=9):
+    """k = 63, min_count = 2: a run of 63 k-mers has 189 candidates, three rounds of 64 look-ups, and the candidates' boundaries (63, 126)
+    fall inside rounds.  A backbone G (400 random bases, its 241 windows of 160 bases, each four times; 98 k-mers per read) plus one read
+    per case, each a window of G starting at `start`:
+        fixed_x1 .. x3  the base at 80 with its 2-bit code XOR-ed with 1, 2, 3: an interior run [18, 80] of exactly 63; the candidate
+                        that fits is the first, second, third of the three: all three rounds are needed                 -> corrected
+        inserted        a base that differs from both neighbours inserted at 78 (the window's last base drops out): an interior run [16, 78] of exactly 63 that no
+                        substitution repairs; every candidate fails at its first or second k-mer (look-ups 0 1, 63 64, 126 127), so
+                        none is left after the second round                                                                     -> left
+        ambiguous       H = G with base 330 cycled once, its 70 windows of 160 bases that hold base 330 given twice; the read has base 330
+                        cycled twice: G's base and H's both fit over the run [18, 80]                                    -> left
+        end_run         the base at 139: an end-touching run [77, 97] of 21                                              -> corrected
+        start_run       the base at 30: a start-touching run [0, 30] of 31                                               -> corrected
+    Returns (the segment, cases, runs): cases as hand_cases gives them, runs = {name: (a, b, p, the number of fitting candidates)}"""
+    k, W = 63, 160
+    rng = np.random.default_rng(seed)
+    G = br._rnd(rng, 400)
+    seg = [G[i:i + W] for i in range(len(G) - W + 1)] * 4
+    H = _sub(G, 330)
+    seg += [H[i:i + W] for i in range(330 - W + 1, len(H) - W + 1)] * 2         # starts 171 .. 240
+    xor = lambda r, p, x: r[:p] + "ACGT"["ACGT".index(r[p]) ^ x] + r[p + 1:]
+    win = lambda s: G[s:s + W]
+    assert G[138] != G[139]                                           # (so G's own base at 78 fits the run's first k-mer only)
+    ins = win(60)[:78] + next(x for x in "ACGT" if x not in G[137:139]) + win(60)[78:W - 1]
+    spec = [("fixed_x1", win(0), xor(win(0), 80, 1), "corrected", (18, 80, 80, 1)), ("fixed_x2", win(20), xor(win(20), 80, 2), "corrected", (18, 80, 80, 1)),
+            ("fixed_x3", win(40), xor(win(40), 80, 3), "corrected", (18, 80, 80, 1)), ("inserted", ins, ins, "left", (16, 78, 78, 0)),
+            ("ambiguous", _sub(win(250), 80, 80), _sub(win(250), 80, 80), "left", (18, 80, 80, 2)),
+            ("end_run", win(100), _sub(win(100), 139), "corrected", (77, 97, 139, 1)), ("start_run", win(130), _sub(win(130), 30), "corrected", (0, 30, 30, 1))]
+    cases, runs = [], {}
+    for name, want, given, cat, run in spec:
+        cases.append((name, 0, len(seg), want, 1 if cat == "corrected" else 0, cat))
+        runs[name] = run
+        seg.append(given)
+    return seg, cases, runs
+
+
+def check_candidate_round_cases(seg, cases, runs):
+    """what candidate_round_cases' docstring says, by the restatement: every case has the one weak run named, with that many fitting
+    candidates; `inserted` loses every candidate at the run's first two k-mers; the rule makes of every read what the case says"""
+    k = 63
+    e = expected(seg, k, min_count=2)
+    t = e["trusted"]
+    for name, _, i, want, changed, cat in cases:
+        a, b, p, n_fit = runs[name]
+        assert weak_runs(seg[i], t, k) == [(a, b)], name
+        assert len(fitting(seg[i], t, k, a, b, p)) == n_fit, name
+        assert correct(seg[i], t, k) == (want, changed, cat) and e["reads"][i] == want, name
+    n = len(seg[0]) - k + 1
+    for name in ("fixed_x1", "fixed_x2", "fixed_x3", "inserted", "ambiguous"):
+        a, b, p, _ = runs[name]
+        assert 0 < a and b < n - 1 and b - a + 1 == k and p == b, name                    # interior, exactly k: 3k = 189 candidates
+    i = next(c[2] for c in cases if c[0] == "inserted")
+    a, b, p, _ = runs["inserted"]
+    cand = lambda x, j: (seg[i][:p] + x + seg[i][p + 1:])[j:j + k]
+    assert all(cand(x, a) not in t or cand(x, a + 1) not in t for x in "ACGT")             # look-ups 0 1, 63 64 and 126 127 of 189
+    fixes = ["ACGT".index(seg[c[2]][80]) ^ "ACGT".index(c[3][80]) for c in cases if c[0].startswith("fixed_x")]
+    assert fixes == [1, 2, 3]
+    a, b, p, _ = runs["end_run"]
+    assert b == n - 1 and a > 0 and b - a + 1 < k and p == a + k - 1
+    a, b, p, _ = runs["start_run"]
+    assert a == 0 and b < n - 1 and b - a + 1 < k and p == b
+    assert e["stats"] == [0, len(seg) - len(cases), 5, 0, 2, 5]
+    return e

@@ -26,17 +26,17 @@ def by_segment(flat, segs):
     return out
 
 
-def check_correction(b, segs, k, **build):
-    """correct_reads() of the built batch `b` against the restatement under the same build options; returns (the corrected batch, the
-    restatement's result per segment)"""
+def check_correction(b, segs, k, sample=None, **build):
+    """correct_reads() of the built batch `b` against the restatement under the same build options, in every (sampled) segment; returns
+    (the corrected batch, {segment: the restatement's result})"""
     c = b.correct_reads()
     assert (c.n_segments, c.n_reads) == (len(segs), sum(len(rs) for rs in segs))
     got, stats = by_segment(c.read_strings(), segs), c.correction_stats()
     assert stats.shape == (len(segs), 6) and stats.dtype == np.uint32
-    refs = []
-    for s, rs in enumerate(segs):
-        e = cr.expected(rs, k, **build)
-        refs.append(e)
+    refs = {}
+    for s in (range(len(segs)) if sample is None else sample):
+        rs = segs[s]
+        e = refs[s] = cr.expected(rs, k, **build)
         print(f"segment {s}: k {k} {build}: restatement {e['stats']}, device {stats[s].tolist()}")
         bad = [i for i, (x, y) in enumerate(zip(got[s], e["reads"])) if x != y]
         assert not bad, (s, bad[:5], [(rs[i], got[s][i], e["reads"][i]) for i in bad[:2]])
@@ -46,9 +46,10 @@ def check_correction(b, segs, k, **build):
     return c, refs
 
 
-@pytest.mark.parametrize("k", [21, 41])
+@pytest.mark.parametrize("k", [21, 31, 32, 41, 63])
 def test_hand_built_cases(k):
-    """64-bit and 128-bit keys: a substitution in the middle, at 0, k - 2, k - 1, at the last base and k - 1 bases from the end, two
+    """64-bit and 128-bit keys and the seams between them (31: all 62 bits, 32: the first 128-bit key, the candidates' XOR shifts pass 62
+    and 64; 63: 126 bits): a substitution in the middle, at 0, k - 2, k - 1, at the last base and k - 1 bases from the end, two
     k + 1 apart (both fixed), two k - 1 apart (left), reads without a k-mer, a random read, a read of one k-mer, an ambiguous one"""
     segs, cases = cr.hand_cases(k)
     b = ga.SegmentBatch.from_strings(segs)
@@ -58,6 +59,23 @@ def test_hand_built_cases(k):
     for name, s, i, want, changed, cat in cases:
         assert got[s][i] == want, name
     assert c.correction_stats().tolist() == [[2, len(segs[0]) - 12, 7, 0, 3, 8], [0, len(segs[1]) - 1, 0, 0, 1, 0]]
+    c.close()
+    b.close()
+
+
+def test_candidate_rounds_at_k63():
+    """runs of 63 k-mers: 189 candidates in three rounds of 64, the candidates' boundaries inside rounds.  Fixed by the first, second and
+    third candidate (all three rounds), no candidate left after the second round (the early exit), two candidates fit (left), and
+    shorter runs at both ends.  The restatement says so of every case before the device is asked"""
+    seg, cases, runs = cr.candidate_round_cases()
+    cr.check_candidate_round_cases(seg, cases, runs)
+    b = ga.SegmentBatch.from_strings([seg])
+    b.build(63, min_count=2)
+    c, _ = check_correction(b, [seg], 63, min_count=2)
+    got = c.read_strings()
+    for name, _, i, want, changed, cat in cases:
+        assert got[i] == want, name
+    assert c.correction_stats().tolist() == [[0, len(seg) - len(cases), 5, 0, 2, 5]]
     c.close()
     b.close()
 
@@ -151,8 +169,9 @@ def test_several_segments():
 
 
 # the issue's table rows 1, 2 and 4: L, read length, coverage, k, seed, strands; clean, corrected, partial, left, bases changed under
-# build(k, min_count = 2) (None: not compared, the row is the 128-bit-key case under the simplified build only)
-ROWS = [((4000, 80, 20, 21, 5, 1), (433, 419, 25, 103, 518)), ((4000, 80, 20, 21, 5, 2), (433, 419, 25, 103, 518)), ((8000, 100, 40, 41, 11, 2), None)]
+# build(k, min_count = 2) (None: not compared, the rows are the 128-bit-key cases, k = 41 and k = 63, under the simplified build only)
+ROWS = [((4000, 80, 20, 21, 5, 1), (433, 419, 25, 103, 518)), ((4000, 80, 20, 21, 5, 2), (433, 419, 25, 103, 518)), ((8000, 100, 40, 41, 11, 2), None),
+        ((3000, 150, 24, 63, 5, 2), None)]
 
 
 @pytest.mark.parametrize("row,table", ROWS)

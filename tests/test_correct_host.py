@@ -104,16 +104,20 @@ def test_idempotent(row):
     assert stats[1] == e["stats"][1] + e["stats"][2] and stats[4] == e["stats"][3] + e["stats"][4]
 
 
-@pytest.mark.parametrize("k", [21, 41])
+@pytest.mark.parametrize("k", [21, 31, 32, 41, 63])
 def test_hand_built_cases(k):
+    """the key-width seams as well: 31 (all 62 bits of a 64-bit key), 32 (the first 128-bit key) and 63 (126 bits, 150-base windows)"""
     segs, cases = cr.hand_cases(k)
-    assert {len(r) for r in segs[0][:4]} == {60 if k == 21 else 100}
+    assert {len(r) for r in segs[0][:4]} == {60 if k == 21 else 100 if k <= 41 else 2 * k + 24}
     for name, s, i, want, changed, cat in cases:
         e = cr.expected(segs[s], k, min_count=2)
         assert cr.correct(segs[s][i], e["trusted"], k) == (want, changed, cat), name
         assert e["reads"][i] == want, name
     assert cr.expected(segs[0], k, min_count=2)["stats"][0::2] == [2, 7, 3] and cr.expected(segs[0], k, min_count=2)["stats"][5] == 8
     assert cr.expected(segs[1], k, min_count=2)["stats"][2:] == [0, 0, 1, 0]
+    if k == 63:                                                       # the named cases behave as at k = 41
+        segs41, _ = cr.hand_cases(41)
+        assert [cr.expected(segs[s], k, min_count=2)["stats"][2:] for s in range(2)] == [cr.expected(segs41[s], 41, min_count=2)["stats"][2:] for s in range(2)]
     # what the docstring says about the runs
     t = cr.expected(segs[0], k, min_count=2)["trusted"]
     runs = {name: cr.weak_runs(segs[s][i], t, k) for name, s, i, _, _, _ in cases if s == 0}
@@ -123,6 +127,13 @@ def test_hand_built_cases(k):
     assert runs["last"] == [(n - 1, n - 1)] and runs["k-1_from_end"] == [(n - k, n - 1)]
     assert runs["two_apart_k+1"] == [(0, 10), (12, 10 + k + 1)] and runs["two_apart_k-1"] == [(0, 5 + k - 1)]
     assert runs["random"] == [(0, n - 1)] and runs["one_kmer"] == [(0, 0)] and runs["clean"] == runs["short"] == runs["empty"] == []
+
+
+def test_candidate_round_cases():
+    """k = 63: runs of 63 k-mers (three rounds of candidates on the device) that are fixed, that no candidate fits, that two fit, and
+    shorter runs at the ends"""
+    e = cr.check_candidate_round_cases(*cr.candidate_round_cases())
+    print(e["stats"])
 
 
 def test_long_read_cases():

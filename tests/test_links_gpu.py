@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import genomeassembler_dev_amd as ga
+import links_cases as lc
 import links_ref as lr
 from genomeassembler_dev_amd import synth
 from genomeassembler_dev_amd._lib import lib
@@ -25,13 +26,14 @@ def ref_tables(contigs, reads, k, strands, span_len):
     return _REF[key]
 
 
-def check_links(b, segs, k, strands, span_len):
-    """every segment's five tables against the restatement; returns (ContigLinks, the restatement's tables per segment)"""
+def check_links(b, segs, k, strands, span_len, sample=None):
+    """every (sampled) segment's five tables against the restatement; returns (ContigLinks, {segment: the restatement's tables})"""
     cl = b.contig_links(span_len)
     assert (cl.k, cl.span_len, cl.strands, cl.n_segments) == (k, span_len, strands, len(segs))
     contigs = b.contigs()
-    out = []
-    for s, rs in enumerate(segs):
+    out = {}
+    for s in (range(len(segs)) if sample is None else sample):
+        rs = segs[s]
         assert cl.contigs(s) == contigs[s]
         t = ref_tables(contigs[s], rs, k, strands, span_len)
         n = len(contigs[s])
@@ -47,7 +49,7 @@ def check_links(b, segs, k, strands, span_len):
         assert lr.consistent(got, contigs[s], k), (s, "succ and pred state different links")
         assert cl.links(s) == sorted((a, row[x], t["link_support"][a][x]) for a, row in enumerate(t["succ"]) for x in range(4) if row[x] != lr.NONE)
         assert cl.resolve_repeats(s) == lr.resolve(contigs[s], k, span_len, t, 2), (s, "resolve_repeats")
-        out.append(t)
+        out[s] = t
     return cl, out
 
 
@@ -88,13 +90,14 @@ def long_segment(k):
     return [g[:4096 + k - 1], g, g[3900:4090], g[50:300]]
 
 
-@pytest.mark.parametrize("k", [11, 21, 33])
+@pytest.mark.parametrize("k", [11, 21, 31, 32, 33, 63])
 def test_three_segments_and_the_chunk_seams(k):
+    """also at the key-width seams: the in-edge of a contig's first node is built with a shift of 2 (k - 1) = 60, 62 and 124 bits"""
     g, reads, special, (p1, Lr, n_r) = seamed_segment(k, 5 + k)
     segs = [reads, [], [g[100:100 + 4 * k]]]
     b = ga.SegmentBatch.from_strings(segs)
     b.build(k)
-    span_len = max(map(len, reads))
+    span_len = max(len(r) for rs in segs for r in rs)                # (segment 2's read of 4k bases is the batch's longest from k = 49 on)
     cl, ts = check_links(b, segs, k, 1, span_len)
     contigs = b.contigs(0)
     r = contigs.index(g[p1:p1 + Lr])                                 # the repeat is a contig of its own
@@ -103,11 +106,44 @@ def test_three_segments_and_the_chunk_seams(k):
     assert len(special[0][0]) - k + 1 == 64 and len(special[1][0]) - k + 1 == 65 and len(special[2][0]) - k + 1 == 130
     at = special[3][1]
     assert at < 63 < at + 1 + n_r and lr.tables(contigs, [special[3][0]], k, 1, span_len)["span_support"][r] != [[0] * 4] * 4
-    assert sum(map(sum, ts[0]["span_support"][r])) >= 4 and ts[0]["skipped"] == 0
-    assert len(contigs) == 4 and cl.resolve_repeats(0) == [g]
+    # two spans on either path through the repeat resolve it; at k = 63 the 126-base repeat leaves too few reads that span it
+    resolved = lr.resolve(contigs, k, span_len, ts[0], 2) == [g]
+    assert resolved or k == 63
+    assert sum(map(sum, ts[0]["span_support"][r])) >= (4 if resolved else 1) and ts[0]["skipped"] == 0
+    assert len(contigs) == 4 and cl.resolve_repeats(0) == ([g] if resolved else lr.resolve(contigs, k, span_len, ts[0], 2))
     assert b.contigs(1) == [] and len(b.contigs(2)) == 1 and cl.links(2) == [] and cl.resolve_repeats(1) == []
     # default span_len: the longest read of the batch
     assert b.contig_links().span_len == span_len
+    b.close()
+
+
+def test_hand_built_tables_on_the_device():
+    """the k = 5 cases of tests/links_cases.py, one segment each and an empty one, against the tables written out by hand: no restatement
+    is asked.  (The unbranched cycle and the dead end stay on the host: a build does not cut those contigs.)  One links pass per span_len"""
+    names = [n for n in sorted(lc.CASES) if n not in ("unbranched cycle", "dead end")]
+    assert len(names) == 7
+    segs = [lc.CASES[n][1] for n in names] + [[]]
+    b = ga.SegmentBatch.from_strings(segs)
+    b.build(lc.K)
+    for s, n in enumerate(names):
+        assert b.contigs(s) == lc.CASES[n][0], n
+    assert b.contigs(len(names)) == []
+    seen = []
+    for span_len in sorted({lc.CASES[n][2] for n in names}):
+        cl = b.contig_links(span_len)
+        for s, n in enumerate(names):
+            contigs, _, sl, want = lc.CASES[n]
+            if sl != span_len:
+                continue
+            seen.append(n)
+            assert cl.contigs(s) == contigs, n
+            assert cl.succ(s).tolist() == want["succ"], (n, "succ")
+            assert cl.pred(s).tolist() == want["pred"], (n, "pred")
+            assert cl.link_support(s).tolist() == want["link_support"], (n, "link_support")
+            assert cl.span_support(s).tolist() == want["span_support"], (n, "span_support")
+            assert int(cl.skipped[s]) == want["skipped"] == 0, (n, "skipped")
+        assert cl.links(len(names)) == [] and int(cl.skipped[len(names)]) == 0
+    assert sorted(seen) == names
     b.close()
 
 
@@ -123,8 +159,8 @@ def test_a_read_of_4096_kmers_is_threaded_and_one_of_4097_is_skipped():
     b.close()
 
 
-def test_both_strands_twin_symmetry():
-    k = 21
+@pytest.mark.parametrize("k", [21, 32, 63])
+def test_both_strands_twin_symmetry(k):
     g, reads, _, _ = seamed_segment(k, 8)
     reads = [r if i % 2 else lr.rc(r) for i, r in enumerate(reads)]
     segs = [reads, [g[:90]]]
@@ -143,7 +179,9 @@ def test_both_strands_twin_symmetry():
             assert sp[r].tolist() == [[int(sp[tw[r], 3 - y, 3 - x]) for y in range(4)] for x in range(4)], (s, r)
         res = cl.resolve_repeats(s)
         assert sorted(lr.rc(x) for x in res) == res
-    assert sorted(cl.resolve_repeats(0)) == sorted([g, lr.rc(g)])
+    want = lr.resolve(b.contigs(0), k, span_len, ts[0], 2)
+    assert sorted(want) == sorted([g, lr.rc(g)]) or k == 63          # (at k = 63 too few reads span the 126-base repeat)
+    assert cl.resolve_repeats(0) == want
     b.close()
 
 

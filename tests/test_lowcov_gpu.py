@@ -84,10 +84,14 @@ def check_segments(b, segs, k, c, strands, tip, bub, cov, keys, prob, scored=Tru
 
 
 # L, read length, coverage, k, seed, min_count, strands, cov_len, cov_cutoff: contigs and k-mers removed in round 0 of segment 0,
-# contigs before -> after (the small rows of tests/test_lowcov_host.py's table; the last row is the 128-bit-key case)
+# contigs before -> after (the small rows of tests/test_lowcov_host.py's table; the k = 41 row is the 128-bit-key case)
 ROWS = [(4000, 80, 20, 21, 5, 2, 1, 41, 3, 3, 21, 4, 1), (4000, 80, 20, 21, 5, 2, 2, 41, 3, 6, 42, 8, 2), (4000, 80, 40, 21, 5, 2, 1, 41, 3, 14, 147, 23, 1),
         (600, 50, 12, 15, 3, 1, 1, 29, 2, 16, 230, 55, 11), (400, 40, 15, 11, 9, 1, 1, 21, 2, 21, 228, 63, 5),
-        (2000, 100, 30, 41, 5, 2, 2, 81, 3, 6, 60, 8, 2)]
+        (2000, 100, 30, 41, 5, 2, 2, 81, 3, 6, 60, 8, 2),
+        # the key-width seams: all 62 bits of a 64-bit key, the first 128-bit key (its high word is 0) and 126 bits (both-strand rows on
+        # half the genome: three segments of 3 kb took 15 s of the oracle's scoring)
+        (3000, 100, 20, 31, 5, 1, 1, 61, 2, 142, 4245, 547, 160), (1500, 100, 20, 32, 5, 1, 2, 63, 2, 142, 4350, 546, 146),
+        (3000, 150, 24, 63, 5, 1, 1, 125, 2, 49, 2567, 250, 128), (1500, 150, 24, 63, 5, 1, 2, 125, 2, 54, 2484, 256, 144)]
 
 
 @pytest.mark.parametrize("L,rl,cov,k,seed,c,strands,cl,cc,n_rm,n_kmers,n_before,n_after", ROWS)

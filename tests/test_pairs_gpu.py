@@ -2,6 +2,7 @@
 tests/pairs_ref.py: per segment the records of every oriented pair, the insert histogram and the six counters, all with ==.  The contigs
 the restatement starts from are the build's own (other tests hold them against the oracle).  Shapes: segments of at most 4 kb; mates
 built so that the first k-mer in the set lies at position 0, inside the first 64-position chunk, behind it, or nowhere."""
+import collections
 import ctypes as C
 import random
 
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 import genomeassembler_dev_amd as ga
+import links_cases as lc
 import links_ref as lr
 import pairs_ref as pr
 from genomeassembler_dev_amd import synth
@@ -26,14 +28,15 @@ def ref_place(contigs, reads, k, strands, max_insert):
     return _REF[key]
 
 
-def check_places(b, segs, k, strands, max_insert):
-    """every segment's three tables against the restatement; returns (PairPlaces, the restatement's tables per segment)"""
+def check_places(b, segs, k, strands, max_insert, sample=None):
+    """every (sampled) segment's three tables against the restatement; returns (PairPlaces, {segment: the restatement's tables})"""
     pp = b.place_pairs(max_insert)
     assert (pp.k, pp.strands, pp.max_insert, pp.n_segments, pp.orientations) == (k, strands, max_insert, len(segs), strands)
     assert pp.n_pairs == sum(len(rs) for rs in segs) // 2
     contigs = b.contigs()
-    out = []
-    for s, rs in enumerate(segs):
+    out = {}
+    for s in (range(len(segs)) if sample is None else sample):
+        rs = segs[s]
         assert pp.contigs(s) == contigs[s]
         t = ref_place(contigs[s], rs, k, strands, max_insert)
         print(f"segment {s}: k {k} strands {strands} max_insert {max_insert}: {len(contigs[s])} contigs, {len(rs) // 2} pairs, "
@@ -43,7 +46,7 @@ def check_places(b, segs, k, strands, max_insert):
         assert pp.counters(s).tolist() == t["counters"], (s, "counters")
         assert int(pp.counters(s).sum()) == len(rs) // 2 * strands
         assert int(pp.insert_hist(s).sum()) == t["counters"][3], (s, "the histogram holds the same_contig pairs")
-        out.append(t)
+        out[s] = t
     return pp, out
 
 
@@ -120,22 +123,34 @@ def noisy_pairs(genome, read_len, k, seed):
             r[p] = "ACGT"[("ACGT".index(r[p]) + 1 + rnd.randrange(3)) % 4]
         return "".join(r)
     n = read_len - k + 1
-    firsts = [1, k, 63, 64, 65, n - 1, n]                           # n: no k-mer is left
+    firsts = []                                                     # n: no k-mer is left
+    for first in (1, k, 63, 64, 65, n - 1, n):
+        if first not in firsts and first <= n:
+            firsts.append(first)
+    seen = collections.Counter(r[i:i + k] for r in reads for i in range(n))
+    covered = lambda read: all(seen[read[i:i + k]] >= 2 for i in range(n))
     for first in firsts:
-        s = rnd.randrange(len(genome) - 4 * read_len)
-        frag = genome[s:s + 3 * read_len]
+        while True:                                                  # (a fragment whose ends the error-free pairs cover twice: its clean k-mers are in the set)
+            s = rnd.randrange(len(genome) - 4 * read_len)
+            frag = genome[s:s + 3 * read_len]
+            if covered(frag[:read_len]) and covered(frag[-read_len:]):
+                break
         reads += [spoil(frag[:read_len], first), pr.rc(frag[-read_len:]), frag[:read_len], spoil(pr.rc(frag[-read_len:]), first)]
     reads += [junk(rnd, read_len), junk(rnd, read_len)]
     return reads, firsts
 
 
-def test_128_bit_keys_and_two_chunks():
+@pytest.mark.parametrize("k,read_len,genome_len", [(31, 100, 2500), (32, 100, 2500), (33, 100, 2500), (63, 150, 3000)])
+def test_128_bit_keys_and_two_chunks(k, read_len, genome_len):
     """k = 33, 100-base reads: 68 k-mers, two 64-position chunks.  Mates with substitutions hit first inside the first chunk, at its last
-    position, in the second chunk, or nowhere"""
-    k = 33
-    genome = synth.make_segment(41, 2500, planted=False).tobytes().decode()
-    reads, firsts = noisy_pairs(genome, 100, k, 41)
-    assert firsts == [1, 33, 63, 64, 65, 67, 68]
+    position, in the second chunk, or nowhere.  The same at the key-width seams: k = 31 (the reverse complement moves down by 2 bits),
+    32 (by exactly 64) and 63 (by 2 bits of a 128-bit key; 150-base reads, 88 k-mers)"""
+    n = read_len - k + 1
+    genome = synth.make_segment(41, genome_len, planted=False).tobytes().decode()
+    reads, firsts = noisy_pairs(genome, read_len, k, 41)
+    assert firsts == list(dict.fromkeys([1, k, 63, 64, 65, n - 1, n])) and n > 65 and len(firsts) >= 6
+    if k == 33:
+        assert firsts == [1, 33, 63, 64, 65, 67, 68]
     segs = [reads, reads[:40]]
     b = ga.SegmentBatch.from_strings(segs)
     b.build(k, min_count=2)
@@ -148,11 +163,37 @@ def test_128_bit_keys_and_two_chunks():
     for i, first in enumerate(firsts):
         a, bb = rec[base + 2 * i], rec[base + 2 * i + 1]               # (mate 1 spoiled, mate 2 clean), (clean, spoiled)
         m1, m2 = reads[2 * (base + 2 * i)], reads[2 * (base + 2 * i + 1) + 1]
-        assert [j for j in range(68) if m1[j:j + k] in where][:1] == [j for j in range(68) if pr.rc(m2[j:j + k]) in where][:1] == [first][:68 - first]
-        assert (a[2:] == bb[2:] and bb[:2] == a[:2]) if first < 68 else (a[:2] == [-1, 0] and bb[2:] == [-1, 0]), (first, a, bb)
+        assert [j for j in range(n) if m1[j:j + k] in where][:1] == [j for j in range(n) if pr.rc(m2[j:j + k]) in where][:1] == [first][:n - first]
+        assert (a[2:] == bb[2:] and bb[:2] == a[:2]) if first < n else (a[:2] == [-1, 0] and bb[2:] == [-1, 0]), (first, a, bb)
         assert bb[0] >= 0 and a[2] >= 0
     b.build(k, min_count=2, strands=2)
     check_places(b, segs, k, 2, 600)
+    b.close()
+
+
+def test_hand_built_pairs_on_the_device():
+    """the k = 5 pairs of tests/links_cases.py against the records, counters and histogram written out by hand: the pairs of HAND, then
+    three pairs (G, G), built with min_count = 5 — every k-mer of G is then seen 6 times or more, no other k-mer (the junk, the
+    reverse-complemented mates) more than 4 times, so the contigs are the hand-built four.  One row differs from the host test's: the
+    "skipped" pair has 11 k-mers, far below the device's cap of 4096 (the host test sets max_kmers = 10), so it is placed as its first
+    row is — [0, 0, 3, 17], diff_contig.  The added pairs' records come from the restatement"""
+    copies, min_count, max_insert = 3, 5, 12
+    hand = [(m1, m2, [0, 0, 3, 17] if f == "skipped" else rec, "diff_contig" if f == "skipped" else f) for m1, m2, rec, f in lc.HAND]
+    assert sum(1 for h in lc.HAND if h[3] == "skipped") == 1
+    added = [lc.G, lc.G] * copies
+    reads = [m for m1, m2, _, _ in hand for m in (m1, m2)] + added
+    b = ga.SegmentBatch.from_strings([reads])
+    b.build(lc.K, min_count=min_count)
+    assert b.contigs(0) == lc.CONTIGS
+    pp = b.place_pairs(max_insert)
+    extra = pr.place(lc.CONTIGS, added, lc.K, 1, max_insert)
+    assert pp.records(0).tolist() == [[rec for _, _, rec, _ in hand] + extra["records"][0]]
+    by_hand = [sum(1 for h in hand if h[3] == f) for f in pr.FIELDS]
+    assert by_hand == [0, 1, 1, 2, 1, 3]
+    assert pp.counters(0).tolist() == [x + y for x, y in zip(by_hand, extra["counters"])]
+    hist = [0] * (max_insert + 1)
+    hist[8], hist[12] = 1, 1                                          # d = 8, and d = 15 in the overflow bin of max_insert = 12
+    assert pp.insert_hist(0).tolist() == [x + y for x, y in zip(hist, extra["insert_hist"])]
     b.close()
 
 

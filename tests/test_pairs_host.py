@@ -15,14 +15,11 @@ import pytest
 
 import links_ref as lr
 import pairs_ref as pr
+from links_cases import CONTIGS, G, HAND, K, R, X, Y, Z
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "genomeassembler_dev_amd", "libgasm.so")
 HEADER = os.path.join(ROOT, "include", "gasm.h")
-K = 5
-X, R, Y, Z = "GCAATAGGG", "TAATTCGC", "CGACGAGTA", "AGCGTAGAT"
-G = X + R + Y + R + Z
-CONTIGS = [X + "TAAT", R, "TCGC" + Z, "TCGC" + Y + "TAAT"]
 
 SIGNATURES = {
     "gasm_batch_place_pairs": "int gasm_batch_place_pairs(gasm_batch* b, uint32_t max_insert);",
@@ -122,19 +119,7 @@ def test_argument_errors_of_the_python_surface():
     assert pp.records(0).shape == (1, 0, 4) and pp.mate_links(0) == [] and pp.resolve_repeats(0, cl) == sorted(CONTIGS)
 
 
-# ---- the hand-built pairs: (mate 1, mate 2, the record of orientation 0, its counter field)
-HAND = [
-    (G[0:7], pr.rc(G[23:30]), [0, 0, 3, 17], "diff_contig"),                 # the fragment g[0:30): starts Xc, ends with Yc's last base
-    (G[14:21], pr.rc(G[22:29]), [3, 1, 3, 16], "same_contig"),               # g[14:29) inside Yc = g[13:30): d = 15
-    (G[22:29], pr.rc(G[14:21]), [3, 9, 3, 8], "reversed"),                   # the same two reads as an outie: d = -1
-    ("GCA", pr.rc(G[22:29]), [-1, 0, 3, 16], "one_placed"),                  # mate 1 shorter than k
-    ("ACACACA", "CCCCCCC", [-1, 0, -1, 0], "none_placed"),
-    (G[0:15], pr.rc(G[23:30]), [-1, 0, -1, 0], "skipped"),                   # 11 k-mers against max_kmers = 10
-    ("TT" + G[0:7], "GG" + pr.rc(G[38:43]), [0, -2, 2, 15], "diff_contig"),  # first hits at i1 = 2 and i2 = 2: S < 0, E > len(Zc) = 13
-    (G[9:16], pr.rc(G[27:34]), [1, 0, 1, 8], "same_contig"),                 # both inside the repeat's contig R: d = 8 = len(R)
-]
-
-
+# ---- the hand-built pairs (mate 1, mate 2, the record of orientation 0, its counter field) are HAND of tests/links_cases.py
 def test_restatement_on_hand_built_pairs_every_counter_field():
     reads = [m for m1, m2, _, _ in HAND for m in (m1, m2)]
     t = pr.place(CONTIGS, reads, K, 1, 12, max_kmers=10)

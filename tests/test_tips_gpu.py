@@ -97,7 +97,11 @@ def _uniform(prob):
 TABLE = [(4000, 80, 20, 21, 5, 1, 1, 1548, 1031, 286, 2945), (4000, 80, 20, 21, 5, 2, 1, 34, 16, 9, 78),
          (4000, 80, 20, 21, 5, 1, 2, 3096, 2062, 572, 5890), (4000, 80, 20, 21, 5, 2, 2, 68, 32, 18, 156),
          (6000, 100, 20, 41, 9, 2, 1, 45, 9, 18, 269), (6000, 100, 20, 41, 9, 2, 2, 90, 18, 36, 538),
-         (3000, 60, 30, 8, 7, 2, 1, 822, 662, 91, 141), (4000, 80, 20, 20, 5, 2, 2, 72, 44, 14, 76)]
+         (3000, 60, 30, 8, 7, 2, 1, 822, 662, 91, 141), (4000, 80, 20, 20, 5, 2, 2, 72, 44, 14, 76),
+         # the key-width seams: all 62 bits of a 64-bit key, the first 128-bit key (its high word is 0) and 126 bits (both-strand rows on
+         # half the genome: the oracle's scoring of twice as many contigs took 15 s)
+         (3000, 100, 20, 31, 5, 1, 1, 1022, 559, 246, 3570), (1500, 100, 20, 32, 5, 1, 2, 1022, 546, 260, 3942),
+         (3000, 150, 24, 63, 5, 1, 1, 858, 253, 318, 10160), (1500, 150, 24, 63, 5, 1, 2, 878, 260, 324, 10032)]
 
 
 @pytest.mark.parametrize("L,rl,cov,k,seed,c,strands,n_before,n_after,n_tips,n_kmers", TABLE)
