@@ -606,6 +606,14 @@ template __global__ void k_bucket_partition<K128>(ReadSet, const uint4*, int, in
 //   128-bit keys: no 128-bit CAS in LDS — the slot's count word is the lock: CAS 0 -> LOCKED, write the key, then
 //                 count = 1.  Readers compare keys only in slots whose count says "ready"; a LOCKED slot means "try
 //                 again" (never a spin inside a divergent branch: the caller's round loop simply comes back).
+// What every path of the 64-bit table keeps (and what the miss loop's shortcut rests on):
+//   * a key occupies exactly one slot; the probe sequence (home set, then the next sets) is a pure function of the key;
+//   * slots never change once written, and a set fills left to right — a set seen full of other keys stays so;
+//   * a lane's snapshot of a set is ONE 16-byte LDS read (lds_load128: ds_read_b128 on an aligned pair of slots), so both
+//     slots are seen at the same moment: "second slot taken" implies "first slot taken", in the snapshot as in the table;
+//   * a lane claims only the first empty slot of its latest read of a set, and reads the set again after a lost CAS;
+//   * nothing spins inside a divergent branch: every probe loop is bounded by 8 * NSETS;
+//   * a table that cannot take its bucket raises GASM_OVF_TABLE and leaves the bucket empty and searchable.
 // Ordering: a counting sort on the key bits below the bucket prefix (TBL/4 bins; close to uniform there) puts every key
 // into its bin's range, bins of more than one key are finished by a per-bin insertion sort; if any bin is long (skewed
 // keys) the workgroup falls back to a bitonic sort.  The bin offsets are kept as the fine directory of the graph
@@ -613,12 +621,14 @@ template __global__ void k_bucket_partition<K128>(ReadSet, const uint4*, int, in
 // LDS and launch bounds: the workgroup's LDS is the table and nothing else (the ordering phase's bins live in the table's
 // tail, and with 128-bit keys the workgroup's counters live in the table's last set), so 2048 slots of 128-bit keys are
 // exactly a quarter of the CU's 160 KB: four workgroups per CU instead of three took the kernel from 2.46 to 2.04 ms on
-// cfg4 — it lives on LDS round trips in flight, i.e. on waves.  64-bit keys: 24 KB, six workgroups would fit, but 80
-// registers per lane spill in the streaming loop (0.61 ms against 0.45): five.  4096 slots: three.
+// cfg4 — it lives on LDS round trips in flight, i.e. on waves.  64-bit keys: 24 KB, six workgroups per CU (GASM_DEDUP_WGS):
+// the streaming loop has to stay within 80 registers per lane for that (70 today, no scratch; a form that spilled ran at
+// 0.61 ms against 0.45).  4096 slots: three.
 // ================================================================================================================
 #define GASM_SLOT_LOCKED 0xFFFFFFFFu
 
-// 16-byte LDS read that the compiler may not reuse from an earlier read (other lanes change the table meanwhile)
+// 16-byte LDS read that the compiler may not reuse from an earlier read (other lanes change the table meanwhile).  One
+// ds_read_b128 per lane (the sets are 16-byte aligned): the two slots of a set are never seen at different times
 __device__ __forceinline__ u64x2 lds_load128(const void* p) {
     __asm__ volatile("" ::: "memory");
     return *reinterpret_cast<const u64x2*>(p);
@@ -751,7 +761,7 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
     }
     // the bins of the ordering phase live in the table's tail, behind the LIMIT entries a sorted bucket can have (dedup_order):
     // the workgroup's LDS is the table (+ 32 bytes for 64-bit keys) — 24 / 40 / 48 KB: four workgroups per CU with 128-bit
-    // keys, three with 4096 slots; with 64-bit keys and 2048 slots registers, not LDS, keep it at five
+    // keys, three with 4096 slots, six with 64-bit keys and 2048 slots (where 80 registers per lane are the other limit)
     static_assert((TBL - LIMIT) * sizeof(K) >= 2 * BINS * sizeof(u32), "the bins must fit behind the sorted entries");
     u32* const s_start = reinterpret_cast<u32*>(t_key + LIMIT);
     u32* const s_cur = s_start + BINS;
@@ -825,12 +835,13 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
                 }
                 continue;
             }
-            // two batches of four keys: the four home sets are read together (8 x ds_read_b128 in flight) and hits are
-            // counted.  Keys that miss their home set (new keys, and the ~1.5 % whose home set has overflowed) are only
-            // noted: with 64 lanes some lane misses for almost every key index, and handling misses in place ran the
-            // slow probe loop — a few dependent LDS round trips — eight times per iteration for the whole wave.  They
-            // are worked off afterwards in one loop in which every lane takes its own next missed key.
-            u32 missed = 0;
+            // One batch of KPL keys (six with 2048 slots, eight with 4096): their home sets are read together (KPL x
+            // ds_read_b128 in flight) and hits are counted.  Keys that miss their home set (new keys, and the ~4.5 % that live
+            // away from home because it had filled up) are only noted: with 64 lanes some lane misses for almost every key
+            // index, and handling misses in place ran the slow probe loop — a few dependent LDS round trips — KPL times per
+            // iteration for the whole wave.  They are worked off afterwards in one loop in which every lane takes its own
+            // next missed key.
+            u32 missed = 0, mfull = 0;              // mfull: the home set of the missed key was full of other keys
             {
                 u32 set[KPL];
                 u64x2 c[KPL];
@@ -845,7 +856,10 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
                     if (kis_filler(key)) continue;            // (before the slot test: the all-ones filler equals a free slot)
                     const int slot = c[q].x == key ? 0 : c[q].y == key ? 1 : -1;
                     if (slot >= 0) atomicAdd(&t_cnt[2 * set[q] + slot], 1u);
-                    else missed |= 1u << q;
+                    else {
+                        missed |= 1u << q;
+                        if (c[q].y != GASM_EMPTY64) mfull |= 1u << q;      // (sets fill left to right: no room in this one)
+                    }
                 }
             }
             while (missed) {
@@ -854,7 +868,11 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
                 u64 key = kx[0];
 #pragma unroll
                 for (u32 e = 1; e < (u32)KPL; ++e) if (e == q) key = kx[e];
-                u32 st = khash(key) >> (32 - LOG_SETS);
+                // A home set that was full of other keys in the snapshot stays so (slots never change once written), and the
+                // key cannot be in it: such a key — the ~4.5 % that live away from home — starts at the next set and saves the
+                // dependent re-read of its home set (0.923 -> 0.905 ms/step, the kernel alone 0.393 -> 0.368 ms:
+                // profiles/dedup_batch/README.md).  A set with room is read again: the slot may be gone by now.
+                u32 st = ((khash(key) >> (32 - LOG_SETS)) + (mfull >> q & 1u)) & (NSETS - 1);
                 bool ok = false;
                 for (u32 probe = 0; probe < 8 * NSETS && !ok; ++probe) ok = dedup_step<TBL>(t_key, t_cnt, w_distinct, key, st);
                 if (!ok) *w_overflow = 1;
