@@ -445,14 +445,31 @@ template __global__ void k_bucket_scatter<K128>(ReadSet, const uint4*, int, int,
 // does nothing but count (2·10^8 LDS atomics for cfg2: 0.07 ms, plus two scans).  Here every (segment, bucket) owns a
 // region of fixed capacity (bstart[gb] .. bstart[gb + 1], sized by the host from the segment's k-mer count with some room
 // to spare) and a cursor; a tile counts its k-mers per bucket in LDS — the ds_add_rtn that counts IS the rank of the k-mer
-// in its (bucket, sub-counter) — then reserves its line-padded runs with one global atomic per bucket and flushes whole
-// lines as before.  Runs of a bucket therefore lie in the order the tiles got there, which the de-duplication does not
-// care about (its result is ordered and counted).  cursor[gb] ends up as the bucket's padded length (what `hist` is in the
-// two-pass form).  A run that does not fit its region goes to the scratch line, GASM_OVF_REGION is raised, the
-// de-duplication leaves such a bucket empty, and pipeline_build_finish repeats the build with the two-pass kernels.
+// in its (bucket, sub-counter) — then reserves whole lines (padm + 1 keys) with one global atomic per bucket and flushes
+// them.  Runs of a bucket therefore lie in the order the tiles got there, which the de-duplication does not care about (its
+// result is ordered and counted).
+//
+// Carry.  A workgroup's tiles are consecutive, so the next tile almost always fills the same buckets of the same segment.
+// The keys of a bucket beyond its last whole line — at most padm — are not padded with fillers: they wait for the next
+// tile.  After the third barrier (padm + 1) / KPU threads per bucket read one 16-byte unit each of the bucket's remainder
+// from the staging area into registers; after the next tile's second barrier they put it at the head of the bucket's new
+// staging range, and it leaves with that tile's first line; the same threads fill the gap behind the bucket's new remainder
+// with keys of that bucket (the flush takes a unit's bucket from its key: the gap must not look like another bucket's).  Only the last tile a
+// workgroup spends on a segment (the next tile is another segment's, or there is none) completes the remainder with
+// fillers: the same threads store that one line straight to the region, ahead of the flush.  So a region holds at most
+// padm fillers per (workgroup, segment) visit instead of per tile.  cursor[gb] still ends up as the bucket's padded length
+// (what `hist` is in the two-pass form).  With padm == 0 nothing is carried: every tile is a last one.
+// Staging ranges start on whole lines as long as the tile's and the carried keys leave room for that (a line of the region
+// is then written by one aligned group of lanes of one store: unaligned, the kernel alone takes 0.40 instead of 0.34 ms on
+// cfg2); else on 16-byte units, and a tile stages at most its own keys + nb * (padm + 1) <= CAP.
+//
+// A reservation that does not fit its region is not flushed (its units go to the scratch line, the bucket's carry is lost
+// with it), GASM_OVF_REGION is raised, the de-duplication leaves such a bucket empty, and pipeline_build_finish repeats the
+// build with the two-pass kernels.
 // Memory operations of a wave: [next tile's words, region bounds] [cursor atomic: wave(s) of the bucket threads]
-// [NFL stores]; the atomic's value is used before the flush, so the wait at the top stays "all but the NFL stores".
-// LDS: staging as above + nb * 44 + 80 bytes: two workgroups per CU up to 128 buckets.
+// [last tile of a visit: the remainder's line] [NFL stores]; the atomic's value is used before the flush, so the wait at the
+// top stays "all but the NFL stores".  Three barriers per tile, as before the carry.
+// LDS: staging as above + nb * 52 + 80 bytes: two workgroups per CU up to 128 buckets.
 // ================================================================================================================
 template <class K>
 __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs, const uint4* __restrict__ tinfo, int k, int bbits, u32 g, u32 padm,
@@ -466,12 +483,19 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
     const u32 nb = 1u << bbits;                                               // <= GASM_TILE_WG: one bucket per thread
     const u32 tid = threadIdx.x, wv = tid >> 6, ln = tid & 63, sub = tid & 3u;
     K* s_key = reinterpret_cast<K*>(s_raw);                                  // CAP + eight trash slots per wave
-    u64* s_comb = reinterpret_cast<u64*>(s_key + CAP + GASM_TILE_WG / 8);    // nb
-    u32* s_base = reinterpret_cast<u32*>(s_comb + ((nb + 1) & ~1u));         // 4 per bucket: staging index of rank 0 of every sub-counter
+    uint4* s_comb = reinterpret_cast<uint4*>(s_key + CAP + GASM_TILE_WG / 8); // nb: {where staging index 0 would go in `keys` (64 bits), end of the
+                                                                             // flushed part of the staging range (negative: no room), ranges on whole lines << 31 | that end << 5 | keys that stay behind}
+    u32* s_base = reinterpret_cast<u32*>(s_comb + nb);                       // 4 per bucket: staging index of rank 0 of every sub-counter
     u32* s_cnt = s_base + 4 * nb + 4;                                        // 4 per bucket (sub-counters) + dummy bin; 16-byte aligned
     u32* s_tmp = s_cnt + 4 * nb + 4;                                         // 12
-    u32* s_fill = s_tmp + 12;                                                // nb: where a bucket's fillers start << 4 | how many
+    u32* s_cin = s_tmp + 12;                                                 // nb: start of a bucket's staging range << 5 | keys carried into it
     const int bshift = 2 * k - bbits;
+    // the threads that carry: (padm + 1) / KPU per bucket, one 16-byte unit each (nb * (padm + 1) <= 2 * GASM_TILE_WG resp.
+    // GASM_TILE_WG keys: the host's bound on padm)
+    const bool carry = padm != 0;
+    const u32 ush = carry ? (u32)__builtin_ctz(padm + 1) - (KPU == 2 ? 1u : 0u) : 0u;
+    const u32 n_carry = carry ? nb << ush : 0u;
+    const u32 unit_m = carry ? KPU - 1 : 0u;
 
     const u32 per_wg = (n_tiles + gridDim.x - 1) / gridDim.x;
     const u32 tile_end = min(n_tiles, (blockIdx.x + 1) * per_wg);
@@ -486,6 +510,8 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
     fetch(ti);
     rl.template wait_all_but<0>();
     __syncthreads();
+    bool fresh = true;                             // no remainder is pending: the first tile, or the one after a visit's last
+    u64x2 cu = {0, 0};                             // the pending remainder's unit this thread carries
     for (;;) {
         // ---- count = rank
         const auto w = rl.prep();
@@ -503,6 +529,7 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
         const u32 tnext = tile + 1 < tile_end ? tile + 1 : tile;
         const TileInfo tin = tile_decode(tinfo, tnext);
         fetch(tin);
+        const bool last = !carry || tile + 1 >= tile_end || tin.seg != seg;      // the workgroup's last tile of this segment: nothing stays behind
         __syncthreads();
         // ---- staging ranges of the buckets, and the reservation of their runs.  `t` is the thread index again, opaque to
         // the compiler: everything a bucket thread addresses through it (counters, bases, cursor, region, scratch line) is then
@@ -510,30 +537,53 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
         // spilled, and a spill reload is a vector-memory load: its wait also waits for the next tile's words and the stores
         u32 t = tid, zero = 0;
         __asm__ volatile("" : "+v"(t), "+v"(zero));
-        u32 c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        u32 c0 = 0, c1 = 0, c2 = 0, c3 = 0, cin = 0;
         if (t < nb) {
             const uint4 c = *reinterpret_cast<const uint4*>(&s_cnt[4 * t]);
             c0 = c.x; c1 = c.y; c2 = c.z; c3 = c.w;
+            if (!fresh) cin = s_comb[t].w & 31u;       // what the previous tile left behind (this thread wrote it)
         }
-        const u32 cnt = c0 + c1 + c2 + c3, padc = (cnt + padm) & ~padm;
+        const u32 cnt = cin + c0 + c1 + c2 + c3, flush = cnt & ~padm;
+        const u32 res = last ? (cnt + padm) & ~padm : flush;                           // whole lines; the last tile's include the fillers
+        // staging ranges start on whole lines, so that a line of the region is one aligned group of lanes of one store; where
+        // the carried keys leave no room for that (a full tile with long remainders) on 16-byte units.  One scan for both.
         u32 total;
-        const u32 soff = block_excl_scan_open<GASM_TILE_WG>(padc, s_tmp, &total);      // (s_tmp is next written two barriers on)
+        const u32 both = block_excl_scan_open<GASM_TILE_WG>((((cnt + padm) & ~padm) << 16) | ((cnt + unit_m) & ~unit_m), s_tmp, &total);      // (s_tmp is next written two barriers on)
+        const bool lines = (total >> 16) <= CAP;
+        const u32 soff = lines ? both >> 16 : both & 0xFFFFu;
         u32 run = 0;
         u64 beg = 0, end = 0;                      // the region of bucket `tid` (a few KB of directory per segment: L2 hits, used after the staging)
         if (t < nb) {
             const u32 gb = seg * nb + t;
-            if (padc) run = atomicAdd(&cursor[gb], padc);
+            if (res) run = atomicAdd(&cursor[gb], res);
             beg = bstart[gb]; end = bstart[gb + 1];
-            *reinterpret_cast<uint4*>(&s_base[4 * t]) = make_uint4(soff, soff + c0, soff + c0 + c1, soff + c0 + c1 + c2);
+            const u32 s0 = soff + cin;             // the carried keys come first
+            *reinterpret_cast<uint4*>(&s_base[4 * t]) = make_uint4(s0, s0 + c0, s0 + c0 + c1, s0 + c0 + c1 + c2);
             *reinterpret_cast<uint4*>(&s_cnt[4 * t]) = make_uint4(zero, zero, zero, zero);
-            s_fill[t] = ((soff + cnt) << 4) | (padc - cnt);
+            s_cin[t] = (soff << 5) | cin;
+            s_comb[t].w = (lines ? 1u << 31 : 0u) | ((soff + flush) << 5) | (cnt - flush);      // (the other three words: after the staging)
         }
         __syncthreads();
-        // ---- fillers of the padded runs: eight threads per bucket (one wave writing up to 15 fillers for each of its buckets
-        // one after the other kept the other seven waiting at the barrier above)
-        for (u32 x = t; x < 8 * nb; x += GASM_TILE_WG) {
-            const u32 b = x >> 3, v = s_fill[b];
-            for (u32 f = x & 7u; f < (v & 15u); f += 8) s_key[(v >> 4) + f] = key_filler<K>(b, bshift);
+        // ---- the carried keys, at the head of their bucket's range; and the rest of the bucket's unfinished line, which is
+        // staged but not flushed: the flush takes a unit's bucket from its key, so what lies there must be of this bucket
+        if (t < n_carry) {
+            const u32 b = t >> ush, f = (t & ((1u << ush) - 1u)) * KPU;
+            if (!fresh) {
+                const u32 v = s_cin[b], n = v & 31u;
+                K* const dst = s_key + (v >> 5) + f;
+                if constexpr (KPU == 2) {
+                    if (f < n) dst[0] = cu.x;
+                    if (f + 1 < n) dst[1] = cu.y;
+                } else {
+                    if (f < n) *reinterpret_cast<u64x2*>(dst) = cu;
+                }
+            }
+            const u32 v = s_comb[b].w, n = v & 31u;
+            if ((v >> 31) && n) {                  // (ranges on 16-byte units leave no gap to fill)
+                K* const dst = s_key + ((v << 1) >> 6) + f;
+                if (f >= n) dst[0] = key_filler<K>(b, bshift);
+                if constexpr (KPU == 2) if (f + 1 >= n) dst[1] = key_filler<K>(b, bshift);
+            }
         }
         // ---- stage
         {
@@ -551,20 +601,40 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
             });
         }
         if (t < nb) {
-            const bool fits = (u64)run + padc <= end - beg;
-            s_comb[t] = fits ? beg + run - soff : ~0ull;        // staging index i goes to keys[s_comb[bucket] + i]
+            const bool fits = (u64)run + res <= end - beg;
+            const u64 cb = beg + run - soff;                      // staging index i < soff + flush goes to keys[cb + i]
+            s_comb[t] = make_uint4((u32)cb, (u32)(cb >> 32), fits ? soff + flush : 1u << 31, (lines ? 1u << 31 : 0u) | ((soff + flush) << 5) | (cnt - flush));
             if (!fits) atomicOr(flags + GASM_FLAG_OVERFLOW, GASM_OVF_REGION);
         }
         __syncthreads();
+        // ---- what stays behind: into registers for the next tile, or (last tile of the visit) with fillers to the region
+        if (t < n_carry) {
+            const u32 b = t >> ush, f = (t & ((1u << ush) - 1u)) * KPU;
+            const uint4 c = s_comb[b];
+            const u32 rbeg = (c.w << 1) >> 6, n = c.w & 31u;
+            cu = *reinterpret_cast<const u64x2*>(s_key + rbeg + f);       // (past the remainder: whatever the staging area holds, never used)
+            if (last && n && !(c.z >> 31)) {
+                u64x2 o = cu;
+                if constexpr (KPU == 2) {
+                    const u64 fl = key_filler<u64>(b, bshift);
+                    if (f >= n) o.x = fl;
+                    if (f + 1 >= n) o.y = fl;
+                } else if (f >= n) {
+                    const K128 fl = key_filler<K128>(b, bshift);
+                    o.x = fl.hi; o.y = fl.lo;
+                }
+                GASM_STREAM_STORE(o, reinterpret_cast<u64x2*>(keys + ((((u64)c.y << 32) | c.x) + rbeg + f)));
+            }
+        }
         // (one 16-byte slot per wave, shared by its lanes past the end: 128 KB in all, resident in L2 — a slot per lane was an
         // 8 MB region that kept being written back: 0.2 GB of the kernel's 1.9 GB of HBM writes)
         const u64 my_scratch = scratch + (u64)((blockIdx.x & 1023u) * (GASM_TILE_WG / 64) + (t >> 6)) * KPU;
-        // ---- stream out (as k_bucket_scatter; a run without room goes to the scratch line)
+        // ---- stream out (as k_bucket_scatter; what stays behind and a run without room go to the scratch line)
         static_assert(NFL % 3 == 0, "flush passes come in threes");
 #pragma unroll
         for (u32 u0 = 0; u0 < NFL; u0 += 3) {
             u64x2 wd[3];
-            u64 cb[3];
+            uint4 cb[3];
 #pragma unroll
             for (u32 u = 0; u < 3; ++u) wd[u] = *reinterpret_cast<const u64x2*>(s_key + (t + GASM_TILE_WG * (u0 + u)) * KPU);
 #pragma unroll
@@ -579,13 +649,14 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
 #pragma unroll
             for (u32 u = 0; u < 3; ++u) {
                 const u32 i = (t + GASM_TILE_WG * (u0 + u)) * KPU;
-                GASM_STREAM_STORE(wd[u], reinterpret_cast<u64x2*>(keys + ((i < total && cb[u] != ~0ull) ? cb[u] + i : my_scratch)));
+                GASM_STREAM_STORE(wd[u], reinterpret_cast<u64x2*>(keys + ((int)i < (int)cb[u].z ? (((u64)cb[u].y << 32) | cb[u].x) + i : my_scratch)));
             }
         }
         if (++tile >= tile_end) break;
         // (no barrier here: the next tile's first writes to the staging area, the bases and the run offsets all lie behind its
         // first barrier, which a thread reaches only after its own reads of this flush; its counting touches the counters only)
         ti = tin;
+        fresh = last;
         rl.template wait_all_but<NFL>();
     }
 }

@@ -56,6 +56,7 @@ static const Knobs& knobs() { static const Knobs k; return k; }
 // knobs read at every build (tests switch them inside one process):
 //   GASM_SINGLE_PASS=0     two-pass partition (count, scan, scatter) from the start       GASM_PART_SLACK=percent   room per bucket region (100)
 //   GASM_DBG_PART_CAP=n    force the capacity of every bucket region to n keys (exercises the overflow path)
+//   GASM_DBG_PART_GRID=n   at most n workgroups for k_bucket_partition (small batches: several tiles, and segments, per workgroup — the carry)
 // and at every batch score through the graph (one table or several):
 //   GASM_DBG_SCORE_LDS_PATHS=n   cap the paths per segment whose accumulators k_score_reads_graph keeps in LDS (segments
 //                                with more go to global atomics: same numbers; exercises that branch)
@@ -559,7 +560,10 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     const u32 line_keys = 128 / KB, pad_room = W == 1 ? 2 * GASM_TILE_WG : GASM_TILE_WG;
     u32 padm = line_keys - 1;
     if (knobs().padm >= 0) padm = std::min<u32>(padm, (u32)knobs().padm);
-    while (padm && (u64)nb * padm > pad_room) padm >>= 1;
+    while (padm & (padm + 1)) padm >>= 1;     // a mask: 2^n - 1
+    // (128-bit keys: + 1, so that k_bucket_partition has a thread for every key of a bucket's unfinished line — nb * (padm + 1)
+    // <= GASM_TILE_WG; with 64-bit keys a thread takes two, and nb <= GASM_TILE_WG buckets keep that within the workgroup)
+    while (padm && (u64)nb * (padm + (W == 2 ? 1u : 0u)) > pad_room) padm >>= 1;
     const ReadSet rs = rd.view();
     const u32 g = bs.tile_g;
     const u32 grid_tiles = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().hist_wgs);
@@ -602,8 +606,9 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, GASM_FLAG_BYTES + (size_t)nbt * 4, ctx->stream));
         u32* const d_cursor = bs.d_flags.as<u32>() + GASM_FLAG_CURSORS;
         d_blen = d_cursor;
-        const size_t lds = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB + (size_t)((nb + 1) & ~1u) * 8 + (size_t)(4 * nb + 4) * 8 + 48 + (size_t)nb * 4;
-        const u32 grid_part = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().scatter_wgs);
+        const size_t lds = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB + (size_t)nb * 16 + (size_t)(4 * nb + 4) * 8 + 48 + (size_t)nb * 4;
+        u32 grid_part = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().scatter_wgs);
+        if (const int cap = env_int("GASM_DBG_PART_GRID", 0)) grid_part = std::min<u32>(grid_part, (u32)std::max(1, cap));
         GLAUNCH_K(ctx, W, "k_bucket_partition", k_bucket_partition<K>, dim3(grid_part), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
                   bs.d_bstart.as<u64>(), d_cursor, bs.d_keys.as<K>(), n_alloc, bs.d_flags.as<u32>());
     } else {
@@ -634,7 +639,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o1, k_bucket_dedup<u64, 2048>, GASM_WG, 0);
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, k_bucket_dedup<u64, 4096>, GASM_WG, 0);
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o3, k_bucket_scatter<u64>, GASM_TILE_WG, lds_stage + (size_t)nb * 24 + 96);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o4, k_bucket_partition<u64>, GASM_TILE_WG, lds_stage + (size_t)nb * 40 + 96);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o4, k_bucket_partition<u64>, GASM_TILE_WG, lds_stage + (size_t)nb * 52 + 80);
         fprintf(stderr, "[occupancy API] dedup<2048> %d  dedup<4096> %d  scatter %d  partition %d blocks/CU\n", o1, o2, o3, o4);
         GCHK(stamp_buf.ensure(64 + (size_t)nbt * 24));
         HIPCHK(hipMemsetAsync(stamp_buf.p, 0, 64 + (size_t)nbt * 24, ctx->stream));
