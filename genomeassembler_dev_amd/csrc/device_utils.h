@@ -128,6 +128,7 @@ __device__ __forceinline__ void for_seg_edges(const u32* __restrict__ dstart, u3
 // per edge and live on loads in flight — with one edge per thread the 2048 threads of a CU are all the parallelism there is.
 // f(seg, lo, hi, i[ILP], ok[ILP]); launch with chunks = ceil(edges / (GASM_WG * GASM_EDGE_ILP)).
 #define GASM_EDGE_ILP 4
+#define GASM_JUMP_ILP 4      // the same for k_link_jump: links per thread, advanced together — the steps are dependent gathers, so the kernel lives on loads in flight
 template <class F>
 __device__ __forceinline__ void for_seg_edge_groups(const u32* __restrict__ dstart, u32 nb, u32 n_segments, u32 chunks, F&& f) {
     u32 seg, chunk;

@@ -84,6 +84,11 @@ struct PathSet {
 #define GASM_SCORE_PATH_CAP 6144   // paths of one segment whose score accumulators k_score_reads_graph keeps in LDS
 #define GASM_TBL 4096       // slots of the large LDS de-duplication table (the small one has 2048)
 #define GASM_TBL_LIMIT 2816 // distinct keys one bucket may hold (11/16 of the table) before the host re-partitions
+// Bins of the counting sort that orders a table of `tbl` slots (k_bucket_dedup, k_bucket_dedup_multi, k_bucket_merge) = entries
+// of a bucket's row of the fine directory, and their logarithm: GraphView::fbits of what such a kernel wrote
+constexpr int dedup_bins(int tbl) { return tbl / 4; }
+constexpr int dedup_fbits(int tbl) { return tbl <= 4 ? 0 : 1 + dedup_fbits(tbl / 2); }
+static_assert(1 << dedup_fbits(2048) == dedup_bins(2048) && 1 << dedup_fbits(GASM_TBL) == dedup_bins(GASM_TBL), "the bins are a power of two");
 
 // ---- the flag area of a build (BuildState::d_flags): GASM_FLAG_WORDS u32 words, behind them the one-pass partition's cursors.
 // The one definition of who writes which word, shared by the kernels and the host.
@@ -136,6 +141,44 @@ struct BuildReport {
 // ---- kernels_build.hip
 __global__ void k_pack_ascii(const u8* ascii, u64 nbases_host, const u64* nbases_dev, u64* words, u32* err);
 #define GASM_TILE_WG 512     // threads of a tile workgroup (k_tile_hist, k_bucket_scatter)
+// ---- what k_bucket_scatter / k_bucket_partition and their launches (pipeline.hip) share: the one definition of each
+// The staging area of a tile: NFL flush passes of 16 bytes per thread (the tile's keys + room for the padding of the staged
+// runs), then eight trash slots per wave for the starts past a read's end.
+template <class K> struct TileStage {
+    static constexpr u32 KPU = 16 / sizeof(K);                                                 // keys per 16-byte unit
+    static constexpr u32 CAP = KeyTraits<K>::NFL * GASM_TILE_WG * KPU;                         // keys staged at most
+    static constexpr u32 TRASH = GASM_TILE_WG / 8;                                             // trash slots
+    static constexpr u32 BYTES = (CAP + TRASH) * (u32)sizeof(K);
+    static constexpr u32 PAD_ROOM = (KeyTraits<K>::NFL * KPU - KeyTraits<K>::KT) * GASM_TILE_WG; // keys of padding one tile may stage beyond its own
+};
+// Dynamic LDS of the two kernels for nb buckets: the arrays behind the staging area in the order the kernel carves them from
+// one block (element counts; each array starts where the one before it ends), and the launch's total in bytes.  The
+// per-bucket words and the dummy bin behind them are two counts, added to the pointer one after the other as the kernels
+// always did: the sum formed first, in 32 bits, costs the compiler what it knows about the alignment of what follows.
+template <class K> struct ScatterLds {
+    u32 nb;
+    static constexpr u32 n_key = TileStage<K>::CAP + TileStage<K>::TRASH;    // K
+    constexpr u32 n_comb() const { return (nb + 1) & ~1u; }                   // u64: nb, rounded so that the cursors are 16-byte aligned
+    constexpr u32 n_sub() const { return 4 * nb; }                            // u32: 4 per bucket (sub-cursors) ...
+    static constexpr u32 n_dummy = 4;                                         // ... + the dummy bin
+    static constexpr u32 n_tmp = 12;                                          // u32
+    constexpr size_t total() const { return TileStage<K>::BYTES + (size_t)nb * 8 + ((size_t)n_sub() + n_dummy + n_tmp) * 4 + 32; }   // + 32 bytes: the rounding above, the rest spare
+};
+template <class K> struct PartitionLds {
+    u32 nb;
+    static constexpr u32 n_key = TileStage<K>::CAP + TileStage<K>::TRASH;    // K
+    constexpr u32 n_comb() const { return nb; }                               // uint4
+    constexpr u32 n_sub() const { return 4 * nb; }                            // u32, twice (bases, then sub-counters): 4 per bucket ...
+    static constexpr u32 n_dummy = 4;                                         // ... + the dummy bin
+    static constexpr u32 n_tmp = 12;                                          // u32
+    constexpr u32 n_cin() const { return nb; }                                // u32
+    constexpr size_t total() const { return TileStage<K>::BYTES + (size_t)n_comb() * 16 + (2 * ((size_t)n_sub() + n_dummy) + n_tmp + n_cin()) * 4; }
+};
+// The scratch line of the flush: one 16-byte slot per wave of GASM_FLUSH_WGS workgroup slots, behind the key array; the lanes
+// of a store that have nothing to flush write there, so that the number of stores per thread does not vary
+#define GASM_FLUSH_WGS 1024
+#define GASM_FLUSH_SLOTS (GASM_FLUSH_WGS * (GASM_TILE_WG / 64))
+__device__ __forceinline__ u32 flush_slot(u32 wave) { return (blockIdx.x % GASM_FLUSH_WGS) * (GASM_TILE_WG / 64) + wave; }      // < GASM_FLUSH_SLOTS
 template <class K> __global__ void k_tile_hist(ReadSet rs, const uint4* tinfo, int k, int bbits, u32 g, u32 n_tiles, ushort4* tcnt);
 __global__ void k_tile_scan(ReadSet rs, int bbits, u32 padm, const ushort4* tcnt, u32* toff, u32* hist, u32* flags);
 template <class TO> __global__ void k_scan_excl(const u32* in, TO* out, u32 n);
@@ -148,8 +191,7 @@ template <class K>
 __global__ void k_bucket_partition(ReadSet rs, const uint4* tinfo, int k, int bbits, u32 g, u32 padm, u32 n_tiles, const u64* bstart, u32* cursor,
                                    K* keys, u64 scratch, u32* flags);
 template <class K, int TBL>
-__global__ void k_bucket_dedup(K* keys, u32* mult, const u64* bstart, const u32* blen, u32* bucket_d, u32* overflow, u16* fdir, int low_bits, int dbg,
-                               unsigned long long* stamps, u32* dstart);
+__global__ void k_bucket_dedup(K* keys, u32* mult, const u64* bstart, const u32* blen, u32* bucket_d, u32* overflow, u16* fdir, int low_bits, u32* dstart);
 #define GASM_BUCKET_MAX 65535   // distinct keys of one bucket (16-bit fine directory)
 template <class K>
 __global__ void k_bucket_dedup_multi(const K* keys, K* keys_out, u32* mult, const u64* bstart, u32* bucket_d, u32* overflow, u16* fdir, int low_bits);

@@ -33,19 +33,12 @@ typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 // (de-duplication 0.455 ms); nt loads 1.103 (0.393); nt stores 1.113 (0.401 — the stores are the partition's, the gain is the
 // de-duplication's: it no longer reads through dirty lines the previous kernel left in L2 / Infinity Cache); both 1.081 (0.378).
 // Other policies on the stores (sc1, sc0 sc1, sc1 nt, sc0 sc1 nt, sc0 nt, inline asm) were all slower than plain nt.
-// GASM_NO_NT (compile time) restores plain accesses.
 typedef unsigned int u32x4nt __attribute__((ext_vector_type(4)));
-#ifndef GASM_NO_NT
 __device__ __forceinline__ uint4 stream_load16(const uint4* p) {
     const u32x4nt v = __builtin_nontemporal_load(reinterpret_cast<const u32x4nt*>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
 }
-#define GASM_STREAM_LOAD(p) stream_load16(p)
-#define GASM_STREAM_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define GASM_STREAM_LOAD(p) (*(p))
-#define GASM_STREAM_STORE(v, p) (*(p) = (v))
-#endif
+__device__ __forceinline__ void stream_store16(u64x2 v, u64x2* p) { __builtin_nontemporal_store(v, p); }
 
 // ================================================================================================================
 // ASCII -> 2-bit.  One thread per output word (32 bases) and grid-stride round; 2 x 16-byte loads where the word is fully
@@ -303,7 +296,7 @@ __device__ __forceinline__ void seg_offsets_wave(const u32* __restrict__ seg_nco
 // words) are requested BEFORE the flush, and the flush issues exactly NFL stores per thread whatever the tile holds
 // (lanes past the end write to a per-wave scratch slot): the wait at the top of the next tile is then "all but the
 // last NFL operations", written out explicitly.
-// LDS: NFL * 512 x 16 bytes (72 KB) + 64 trash slots + nb * 24 + 96 -> two workgroups per CU, for both key widths.
+// LDS (ScatterLds, kernels.h): NFL * 512 x 16 bytes (72 KB) + 64 trash slots + nb * 24 + 96 -> two workgroups per CU, for both key widths.
 // ================================================================================================================
 template <class K> struct TilePrefetch {
     Roll<K> rl;
@@ -322,14 +315,15 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 1024 / GASM_TILE_WG) k_bucket_sc
     extern __shared__ __align__(16) unsigned char s_raw[];
     constexpr u32 KT = KeyTraits<K>::KT;
     constexpr u32 NFL = KeyTraits<K>::NFL;               // flush passes of 16 bytes per thread: the tile + room for the padding
-    constexpr u32 KPU = 16 / sizeof(K);                  // keys per 16-byte unit
-    constexpr u32 CAP = NFL * GASM_TILE_WG * KPU;
+    constexpr u32 KPU = TileStage<K>::KPU;               // keys per 16-byte unit
+    constexpr u32 CAP = TileStage<K>::CAP;
     const u32 nb = 1u << bbits;
     const u32 tid = threadIdx.x, wv = tid >> 6, ln = tid & 63, sub = tid & 3u;
+    const ScatterLds<K> lds{nb};                                             // (kernels.h: the launch takes its size from the same place)
     K* s_key = reinterpret_cast<K*>(s_raw);                                  // CAP + eight trash slots per wave
-    u64* s_comb = reinterpret_cast<u64*>(s_key + CAP + GASM_TILE_WG / 8);    // nb
-    u32* s_cur = reinterpret_cast<u32*>(s_comb + ((nb + 1) & ~1u));          // 4 per bucket (sub-cursors) + dummy bin; 16-byte aligned
-    u32* s_tmp = s_cur + 4 * nb + 4;                                         // 12
+    u64* s_comb = reinterpret_cast<u64*>(s_key + lds.n_key);                 // nb
+    u32* s_cur = reinterpret_cast<u32*>(s_comb + lds.n_comb());              // 4 per bucket (sub-cursors) + dummy bin; 16-byte aligned
+    u32* s_tmp = s_cur + lds.n_sub() + lds.n_dummy;                          // 12
     const int bshift = 2 * k - bbits;
     const bool one = nb <= GASM_TILE_WG;                                     // one bucket per thread, prefetched
 
@@ -338,7 +332,7 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 1024 / GASM_TILE_WG) k_bucket_sc
     const u32 tile_end = min(n_tiles, (blockIdx.x + 1) * per_wg);
     u32 tile = blockIdx.x * per_wg;
     if (tile >= tile_end) return;
-    const u64 my_scratch = scratch + (u64)((blockIdx.x & 1023u) * (GASM_TILE_WG / 64) + wv) * KPU;     // one 16-byte slot per wave (see k_bucket_partition)
+    const u64 my_scratch = scratch + (u64)flush_slot(wv) * KPU;     // one 16-byte slot per wave (see k_bucket_partition)
 
     auto fetch = [&](u32 t, const TileInfo& ti, TilePrefetch<K>& pf) {
         pf.c01 = 0; pf.c23 = 0; pf.toff = 0; pf.bs_lo = 0; pf.bs_hi = 0;
@@ -426,7 +420,7 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 1024 / GASM_TILE_WG) k_bucket_sc
 #pragma unroll
             for (u32 u = 0; u < 3; ++u) {
                 const u32 i = (tid + GASM_TILE_WG * (u0 + u)) * KPU;
-                GASM_STREAM_STORE(w[u], reinterpret_cast<u64x2*>(keys + (i < total ? cb[u] + i : my_scratch)));   // (no branch: the number of stores must not vary)
+                stream_store16(w[u], reinterpret_cast<u64x2*>(keys + (i < total ? cb[u] + i : my_scratch)));   // (no branch: the number of stores must not vary)
             }
         }
         if (++tile >= tile_end) break;
@@ -469,7 +463,7 @@ template __global__ void k_bucket_scatter<K128>(ReadSet, const uint4*, int, int,
 // Memory operations of a wave: [next tile's words, region bounds] [cursor atomic: wave(s) of the bucket threads]
 // [last tile of a visit: the remainder's line] [NFL stores]; the atomic's value is used before the flush, so the wait at the
 // top stays "all but the NFL stores".  Three barriers per tile, as before the carry.
-// LDS: staging as above + nb * 52 + 80 bytes: two workgroups per CU up to 128 buckets.
+// LDS (PartitionLds, kernels.h): staging as above + nb * 52 + 80 bytes: two workgroups per CU up to 128 buckets.
 // ================================================================================================================
 template <class K>
 __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs, const uint4* __restrict__ tinfo, int k, int bbits, u32 g, u32 padm,
@@ -478,17 +472,18 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
     extern __shared__ __align__(16) unsigned char s_raw[];
     constexpr u32 KT = KeyTraits<K>::KT;
     constexpr u32 NFL = KeyTraits<K>::NFL;
-    constexpr u32 KPU = 16 / sizeof(K);
-    constexpr u32 CAP = NFL * GASM_TILE_WG * KPU;
+    constexpr u32 KPU = TileStage<K>::KPU;
+    constexpr u32 CAP = TileStage<K>::CAP;
     const u32 nb = 1u << bbits;                                               // <= GASM_TILE_WG: one bucket per thread
     const u32 tid = threadIdx.x, wv = tid >> 6, ln = tid & 63, sub = tid & 3u;
+    const PartitionLds<K> lds{nb};                                           // (kernels.h: the launch takes its size from the same place)
     K* s_key = reinterpret_cast<K*>(s_raw);                                  // CAP + eight trash slots per wave
-    uint4* s_comb = reinterpret_cast<uint4*>(s_key + CAP + GASM_TILE_WG / 8); // nb: {where staging index 0 would go in `keys` (64 bits), end of the
+    uint4* s_comb = reinterpret_cast<uint4*>(s_key + lds.n_key);             // nb: {where staging index 0 would go in `keys` (64 bits), end of the
                                                                              // flushed part of the staging range (negative: no room), ranges on whole lines << 31 | that end << 5 | keys that stay behind}
-    u32* s_base = reinterpret_cast<u32*>(s_comb + nb);                       // 4 per bucket: staging index of rank 0 of every sub-counter
-    u32* s_cnt = s_base + 4 * nb + 4;                                        // 4 per bucket (sub-counters) + dummy bin; 16-byte aligned
-    u32* s_tmp = s_cnt + 4 * nb + 4;                                         // 12
-    u32* s_cin = s_tmp + 12;                                                 // nb: start of a bucket's staging range << 5 | keys carried into it
+    u32* s_base = reinterpret_cast<u32*>(s_comb + lds.n_comb());             // 4 per bucket: staging index of rank 0 of every sub-counter
+    u32* s_cnt = s_base + lds.n_sub() + lds.n_dummy;                         // 4 per bucket (sub-counters) + dummy bin; 16-byte aligned
+    u32* s_tmp = s_cnt + lds.n_sub() + lds.n_dummy;                          // 12
+    u32* s_cin = s_tmp + lds.n_tmp;                                          // nb: start of a bucket's staging range << 5 | keys carried into it
     const int bshift = 2 * k - bbits;
     // the threads that carry: (padm + 1) / KPU per bucket, one 16-byte unit each (nb * (padm + 1) <= 2 * GASM_TILE_WG resp.
     // GASM_TILE_WG keys: the host's bound on padm)
@@ -623,12 +618,12 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
                     const K128 fl = key_filler<K128>(b, bshift);
                     o.x = fl.hi; o.y = fl.lo;
                 }
-                GASM_STREAM_STORE(o, reinterpret_cast<u64x2*>(keys + ((((u64)c.y << 32) | c.x) + rbeg + f)));
+                stream_store16(o, reinterpret_cast<u64x2*>(keys + ((((u64)c.y << 32) | c.x) + rbeg + f)));
             }
         }
         // (one 16-byte slot per wave, shared by its lanes past the end: 128 KB in all, resident in L2 — a slot per lane was an
         // 8 MB region that kept being written back: 0.2 GB of the kernel's 1.9 GB of HBM writes)
-        const u64 my_scratch = scratch + (u64)((blockIdx.x & 1023u) * (GASM_TILE_WG / 64) + (t >> 6)) * KPU;
+        const u64 my_scratch = scratch + (u64)flush_slot(t >> 6) * KPU;
         // ---- stream out (as k_bucket_scatter; what stays behind and a run without room go to the scratch line)
         static_assert(NFL % 3 == 0, "flush passes come in threes");
 #pragma unroll
@@ -649,7 +644,7 @@ __global__ void __launch_bounds__(GASM_TILE_WG, 4) k_bucket_partition(ReadSet rs
 #pragma unroll
             for (u32 u = 0; u < 3; ++u) {
                 const u32 i = (t + GASM_TILE_WG * (u0 + u)) * KPU;
-                GASM_STREAM_STORE(wd[u], reinterpret_cast<u64x2*>(keys + ((int)i < (int)cb[u].z ? (((u64)cb[u].y << 32) | cb[u].x) + i : my_scratch)));
+                stream_store16(wd[u], reinterpret_cast<u64x2*>(keys + ((int)i < (int)cb[u].z ? (((u64)cb[u].y << 32) | cb[u].x) + i : my_scratch)));
             }
         }
         if (++tile >= tile_end) break;
@@ -693,7 +688,7 @@ template __global__ void k_bucket_partition<K128>(ReadSet, const uint4*, int, in
 // tail, and with 128-bit keys the workgroup's counters live in the table's last set), so 2048 slots of 128-bit keys are
 // exactly a quarter of the CU's 160 KB: four workgroups per CU instead of three took the kernel from 2.46 to 2.04 ms on
 // cfg4 — it lives on LDS round trips in flight, i.e. on waves.  64-bit keys: 24 KB, six workgroups per CU (GASM_DEDUP_WGS):
-// the streaming loop has to stay within 80 registers per lane for that (70 today, no scratch; a form that spilled ran at
+// the streaming loop has to stay within 80 registers per lane for that (68 today, no scratch; a form that spilled ran at
 // 0.61 ms against 0.45).  4096 slots: three.
 // ================================================================================================================
 #define GASM_SLOT_LOCKED 0xFFFFFFFFu
@@ -756,15 +751,7 @@ __device__ __forceinline__ bool dedup_step(K128* t_key, u32* t_cnt, u32* n_disti
 // per CU, measured on MI355X: 64-bit keys 3 loads 0.463 ms (4: 0.475, 2: 0.489; five or six workgroups per CU: the same),
 // 128-bit keys (cfg4) 6 loads 1.94 ms (5: 2.01, 4: 2.04, 3: 2.26) — the wide table costs three LDS reads per key, and more
 // keys per wave in flight is what hides them.
-#ifndef GASM_DEDUP_NLD
-#define GASM_DEDUP_NLD 3
-#endif
-#ifndef GASM_DEDUP_NLDW
-#define GASM_DEDUP_NLDW 6
-#endif
-#ifndef GASM_DEDUP_WGS
-#define GASM_DEDUP_WGS 6
-#endif
+constexpr int GASM_DEDUP_NLD = 3, GASM_DEDUP_NLDW = 6, GASM_DEDUP_WGS = 6;
 // "Last workgroup done" without a release fence.  An agent-scope release (__threadfence) on this part writes back EVERY dirty
 // line of the XCD's L2 (buffer_wbl2) — with the de-duplication's 6 400 workgroups and an L2 full of freshly written keys that
 // took the kernel from 0.38 to 0.63 ms (measured; round 3).  What the last workgroup needs from the others is one word each,
@@ -805,10 +792,9 @@ __device__ __forceinline__ void dedup_last_scan(const u32* __restrict__ bucket_d
 template <class K, int TBL>
 __global__ void __launch_bounds__(GASM_WG, TBL == 4096 ? 3 : sizeof(K) == 8 ? GASM_DEDUP_WGS : 4)
 k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restrict__ bstart, const u32* __restrict__ blen, u32* __restrict__ bucket_d,
-               u32* __restrict__ overflow, u16* __restrict__ fdir, int low_bits, int dbg, unsigned long long* __restrict__ stamps,
-               u32* __restrict__ dstart) {
+               u32* __restrict__ overflow, u16* __restrict__ fdir, int low_bits, u32* __restrict__ dstart) {
     constexpr int LIMIT = TBL / 16 * 11;
-    constexpr int BINS = TBL / 4;
+    constexpr int BINS = dedup_bins(TBL);
     constexpr int LOG_TBL = TBL == 4096 ? 12 : 11;
     constexpr bool WIDE = sizeof(K) == 16;
     constexpr int LOG_SETS = LOG_TBL - 1;                     // sets of two slots
@@ -836,11 +822,6 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
     static_assert((TBL - LIMIT) * sizeof(K) >= 2 * BINS * sizeof(u32), "the bins must fit behind the sorted entries");
     u32* const s_start = reinterpret_cast<u32*>(t_key + LIMIT);
     u32* const s_cur = s_start + BINS;
-    // diagnostic only (stamps == nullptr in production): per-phase wave-0 tick totals, summed over workgroups
-    unsigned long long tph = stamps ? wall_clock64() : 0ull;
-    auto phase = [&](int i) {
-        if (stamps && threadIdx.x == 0) { const unsigned long long t = wall_clock64(); atomicAdd(&stamps[i], t - tph); tph = t; }
-    };
     const u32 bucket = blockIdx.x;
     const u64 beg = bstart[bucket], end = bstart[bucket + 1];
     u64 n = end - beg;
@@ -856,28 +837,24 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
         }
         n = len;
     }
-    const u32 warm = (u32)(dbg >> 2) & 3u;        // iterations taken key by key (64-bit keys)
     for (u32 i = threadIdx.x; i < TBL; i += GASM_WG) { t_key[i] = key_empty<K>(); t_cnt[i] = 0; }
     if (!WIDE && threadIdx.x == 0) { *w_distinct = 0; *w_overflow = 0; s_tmp[6] = 0; }   // ([6] longest bin: dedup_order zeroes it when the bins live in the table)
     __syncthreads();
-    phase(0);
     // stream: NLD 16-byte loads per thread in flight (the loop is latency-bound otherwise), each fully coalesced across
     // the wave.  Bucket ranges start and end on 128-byte lines (filler keys = EMPTY are skipped).
     constexpr int NLD = WIDE ? GASM_DEDUP_NLDW : TBL == 2048 ? GASM_DEDUP_NLD : 4;   // 16-byte loads per thread and iteration
     constexpr int KPL = NLD * 16 / sizeof(K);    // keys per thread and iteration
     const u64 nch = n * sizeof(K) / 16;          // 16-byte chunks in the bucket
     const uint4* src = reinterpret_cast<const uint4*>(keys + beg);
-    if (dbg & 16) src = reinterpret_cast<const uint4*>(keys + bstart[bucket & 7u]);      // ablation: every workgroup streams one of eight buckets (L2-resident): the table work without HBM
     // the loads of the next iteration are issued before this iteration's keys go into the table, so the table work
     // (LDS latency) and the HBM latency overlap inside every wave
     uint4 v[NLD];
     auto fetch = [&](u64 c) {
 #pragma unroll
-        for (int q = 0; q < NLD; ++q) v[q] = c + (u64)q * GASM_WG < nch ? GASM_STREAM_LOAD(&src[c + (u64)q * GASM_WG]) : make_uint4(~0u, ~0u, ~0u, ~0u);
+        for (int q = 0; q < NLD; ++q) v[q] = c + (u64)q * GASM_WG < nch ? stream_load16(&src[c + (u64)q * GASM_WG]) : make_uint4(~0u, ~0u, ~0u, ~0u);
     };
     if (threadIdx.x < nch) fetch(threadIdx.x);
     for (u64 c = threadIdx.x; c < nch; c += NLD * GASM_WG) {
-        if (c == (u64)threadIdx.x + NLD * GASM_WG) phase(1);   // first iteration (table fill) done
         K kx[KPL];
         if constexpr (WIDE) {
 #pragma unroll
@@ -887,31 +864,16 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
             for (int q = 0; q < NLD; ++q) { kx[2 * q] = (u64)v[q].x | ((u64)v[q].y << 32); kx[2 * q + 1] = (u64)v[q].z | ((u64)v[q].w << 32); }
         }
         if (c + NLD * GASM_WG < nch) fetch(c + NLD * GASM_WG);
-        if ((dbg & 3) == 1) { u64 x = 0; for (int q = 0; q < KPL; ++q) x ^= khash(kx[q]); if (x == 0x1234567) *w_overflow = 1; continue; }
         if (__hip_atomic_load(w_distinct, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > (u32)LIMIT) { *w_overflow = 1; break; }
         if constexpr (!WIDE) {
-            // While the table fills (the first `warm` iterations: 2048 keys each, ~600 distinct per bucket) nearly every
-            // key misses its home set, and the batched form below would send all eight keys of every lane through the slow
-            // loop — 17 of a workgroup's 95 us (GASM_DBG_STAMPS).  There the keys are taken one after the other instead:
-            // a key inserted by any lane at step q is a plain hit for everybody from step q + 1 on.
-            if (c < (u64)warm * NLD * GASM_WG) {
-#pragma unroll
-                for (int q = 0; q < KPL; ++q) {
-                    const u64 key = kx[q];
-                    if (kis_filler(key)) continue;
-                    u32 st = khash(key) >> (32 - LOG_SETS);
-                    bool ok = false;
-                    for (u32 probe = 0; probe < 8 * NSETS && !ok; ++probe) ok = dedup_step<TBL>(t_key, t_cnt, w_distinct, key, st);
-                    if (!ok) *w_overflow = 1;
-                }
-                continue;
-            }
             // One batch of KPL keys (six with 2048 slots, eight with 4096): their home sets are read together (KPL x
             // ds_read_b128 in flight) and hits are counted.  Keys that miss their home set (new keys, and the ~4.5 % that live
             // away from home because it had filled up) are only noted: with 64 lanes some lane misses for almost every key
             // index, and handling misses in place ran the slow probe loop — a few dependent LDS round trips — KPL times per
             // iteration for the whole wave.  They are worked off afterwards in one loop in which every lane takes its own
-            // next missed key.
+            // next missed key.  This holds from the first iteration on: while the table fills (2048 keys per iteration, ~600
+            // distinct per bucket) nearly every key goes through that loop — 17 of a workgroup's 95 us by the kernel's clock —
+            // and taking those iterations key by key instead did not pay.
             u32 missed = 0, mfull = 0;              // mfull: the home set of the missed key was full of other keys
             {
                 u32 set[KPL];
@@ -985,9 +947,7 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
             }
         }
     }
-    phase(2);
     __syncthreads();
-    phase(3);
     if (*w_overflow || *w_distinct > (u32)LIMIT) {
         // The host repeats the build with a larger configuration — but it does not wait for this report before the graph
         // kernels of THIS attempt run (pipeline_build_finish), so the bucket must be left empty AND searchable: an all-zero
@@ -998,18 +958,14 @@ k_bucket_dedup(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restri
         return;
     }
     const u32 d = *w_distinct;
-    if ((dbg & 3) == 1 || (dbg & 3) == 2) { if (threadIdx.x == 0) publish_u32(&bucket_d[bucket], d); dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + GASM_FLAG_DEDUP_DONE, s_tmp + 7, s_tmp); return; }
     dedup_order<K, TBL, true>(t_key, t_cnt, s_start, s_cur, s_tmp, fdir, bucket, low_bits, d);
-    phase(4);
     for (u32 i = threadIdx.x; i < d; i += GASM_WG) { keys[beg + i] = t_key[i]; mult[beg + i] = t_cnt[i]; }
     if (threadIdx.x == 0) publish_u32(&bucket_d[bucket], d);
-    phase(5);
-    if (stamps && threadIdx.x == 0) stamps[8 + 3 * (u64)blockIdx.x + 1] = wall_clock64();
     dedup_last_scan(bucket_d, dstart, gridDim.x, overflow + GASM_FLAG_DEDUP_DONE, s_tmp + 7, s_tmp);
 }
-template __global__ void k_bucket_dedup<u64, 4096>(u64*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, int, unsigned long long*, u32*);
-template __global__ void k_bucket_dedup<u64, 2048>(u64*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, int, unsigned long long*, u32*);
-template __global__ void k_bucket_dedup<K128, 2048>(K128*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, int, unsigned long long*, u32*);
+template __global__ void k_bucket_dedup<u64, 4096>(u64*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, u32*);
+template __global__ void k_bucket_dedup<u64, 2048>(u64*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, u32*);
+template __global__ void k_bucket_dedup<K128, 2048>(K128*, u32*, const u64*, const u32*, u32*, u32*, u16*, int, u32*);
 
 // ================================================================================================================
 // De-duplication of buckets that no table can hold (the last rung of pipeline_build_finish's ladder: ten bucket bits and
@@ -1025,7 +981,7 @@ template <class K>
 __global__ void __launch_bounds__(GASM_WG) k_bucket_dedup_multi(const K* __restrict__ keys, K* __restrict__ keys_out, u32* __restrict__ mult,
                                                                 const u64* __restrict__ bstart, u32* __restrict__ bucket_d,
                                                                 u32* __restrict__ overflow, u16* __restrict__ fdir, int low_bits) {
-    constexpr int TBL = 4096, LIMIT = TBL / 16 * 11, BINS = TBL / 4, LOG_SETS = 11, LOG_BINS = 10;
+    constexpr int TBL = 4096, LIMIT = TBL / 16 * 11, BINS = dedup_bins(TBL), LOG_SETS = 11, LOG_BINS = dedup_fbits(TBL);
     constexpr u32 NSETS = 1u << LOG_SETS;
     __shared__ __align__(32) K t_key[TBL];
     __shared__ __align__(16) u32 t_cnt[TBL];
@@ -1105,7 +1061,7 @@ template <class K>
 __global__ void __launch_bounds__(GASM_WG) k_bucket_solid(K* __restrict__ keys, u32* __restrict__ mult, const u64* __restrict__ bstart,
                                                           u32* __restrict__ bucket_d, u16* __restrict__ fdir, int low_bits, int fbits, int bbits,
                                                           u32 min_count, u32* __restrict__ removed, u32* __restrict__ done, u32* __restrict__ dstart) {
-    constexpr u32 MAX_BINS = GASM_TBL / 4;
+    constexpr u32 MAX_BINS = dedup_bins(GASM_TBL);
     constexpr u32 CHUNK = GASM_WG * GASM_SOLID_ITEMS;
     __shared__ u32 s_bin[MAX_BINS];
     __shared__ u32 s_tmp[8];
@@ -1316,7 +1272,7 @@ __global__ void __launch_bounds__(GASM_WG) k_edge_next(GraphView gv, u32 n_segme
 // and a segment's ~15 rounds of gathers through a single CU took 0.28 ms against 5 launches of ~10 us here.
 // `active` (one of the GASM_FLAG_ACTIVE words per launch, kernels.h): set when some link is still short of its head; a launch returns
 // at once when the previous one left it clear.  Members of isolated cycles never finish: the number of launches bounds them.
-#define GASM_JUMP_ILP 4      // links per thread, advanced together: the steps are dependent gathers, so the kernel lives on loads in flight
+// GASM_JUMP_ILP links per thread (device_utils.h); launch with chunks = ceil(edges / (GASM_WG * GASM_JUMP_ILP)).
 // nxt / clen (optional): the launch also does k_chain_len's work for the links it sees final — a chain's last edge publishes
 // the chain's length at its head; the first launch for every edge, later ones for the edges they finish.
 __global__ void __launch_bounds__(GASM_WG) k_link_jump(GraphView gv, u32 n_segments, u32 chunks, u64* __restrict__ link,

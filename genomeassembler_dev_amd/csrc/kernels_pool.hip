@@ -89,7 +89,7 @@ k_bucket_merge(const K* __restrict__ in_keys, const u32* __restrict__ in_cnt, co
                u32 n_src, K* __restrict__ out_keys, u32* __restrict__ out_cnt, const u64* __restrict__ bstart, u32* __restrict__ bucket_d,
                u32* __restrict__ overflow, u16* __restrict__ fdir, int low_bits, const u64* __restrict__ src_base) {
     constexpr int LIMIT = TBL / 16 * 11;
-    constexpr int BINS = TBL / 4;
+    constexpr int BINS = dedup_bins(TBL);
     constexpr int LOG_SETS = (TBL == 4096 ? 12 : 11) - 1;
     constexpr u32 NSETS = 1u << LOG_SETS;
     __shared__ __align__(32) K t_key[TBL];

@@ -113,10 +113,16 @@ struct BuildState {
     bool rank_global = false;               // list ranking by whole-GPU pointer doubling only (set after the LDS ranking gave up)
     bool single_pass = true;                // partition in one pass into regions of fixed capacity (k_bucket_partition); cleared when a region overflowed
     // the region layout in d_bstart belongs to ... (uploaded once per batch shape)
+    struct PartLayout {
+        u64 reads_id = 0;
+        int k = 0, bbits = 0, slack = 0, forced = 0;
+        u32 padm = 0, g = 0;
+        bool operator==(const PartLayout& o) const {
+            return reads_id == o.reads_id && k == o.k && bbits == o.bbits && slack == o.slack && forced == o.forced && padm == o.padm && g == o.g;
+        }
+    } part;
     bool part_valid = false;
-    u64 part_reads_id = 0, part_alloc = 0;
-    int part_k = 0, part_bbits = 0, part_slack = 0, part_forced = 0;
-    u32 part_padm = 0, part_g = 0;
+    u64 part_alloc = 0;                     // keys of all regions of that layout
     bool multi_pass = false;                // de-duplication in passes over key sub-ranges (set after the bucket bits ran out: k_bucket_dedup_multi)
     bool ranked_in_lds = false;
     u32 tile_g = 1;                         // threads per read of the tile kernels

@@ -24,23 +24,17 @@ __global__ void k_add_empty_reads(PathSet ps, const u64* __restrict__ seg_empty,
     else total[p] += e;   // an empty path has no position counter: carried as an extra addend
 }
 
-// Tuning / diagnostic knobs, read from the environment once (none changes results except GASM_DBG_DEDUP, an ablation):
+// Tuning / diagnostic knobs, read from the environment once (none changes results):
 //   GASM_DEDUP_TBL=2048|4096   force the de-duplication table size        GASM_SCATTER_WGS=n   scatter workgroups per CU (8)
 //   GASM_HIST_WGS=n            histogram workgroups per CU (64)           GASM_DBG_BBITS_ADD=n extra bucket bits (tuning)
-//   GASM_DBG_PADM=m            cap the run padding at m + 1 keys          GASM_RANK_GLOBAL=1   whole-GPU list ranking only
-//   GASM_RULER_SHIFT=1..4      rulers of the LDS list ranking = every 2^n-th edge
-//   GASM_DBG_RANK_ROUNDS=n     cap the LDS ranking rounds (ablation)      GASM_DBG_DEDUP=1|2   loads only / no ordering (ablation)
-//   GASM_DBG_STAMPS=file       per-phase clock stamps of k_bucket_dedup to stderr and `file`
+//   GASM_RULER_SHIFT=1..4      rulers of the LDS list ranking = every 2^n-th edge     GASM_RANK_GLOBAL=1   whole-GPU list ranking only
+//   GASM_DBG_RANK_ROUNDS=n     cap the LDS ranking rounds (ablation)
 //   GASM_SYNC_BUILD=1          every build waits for its own report (no queued-ahead builds)
 struct Knobs {
-    int dedup_tbl = 0, dbg_dedup = 0, padm = -1, scatter_wgs = 8, hist_wgs = 64, rank_rounds = 18, bbits_add = 0, ruler_shift = 0;
+    int dedup_tbl = 0, scatter_wgs = 8, hist_wgs = 64, rank_rounds = 18, bbits_add = 0, ruler_shift = 0;
     bool rank_global = false, sync_build = false;
-    int dedup_warm = 0;
-    const char* stamps = nullptr;
     Knobs() {
         if (const char* v = getenv("GASM_DEDUP_TBL")) dedup_tbl = atoi(v);
-        if (const char* v = getenv("GASM_DBG_DEDUP")) dbg_dedup = atoi(v);
-        if (const char* v = getenv("GASM_DBG_PADM")) padm = atoi(v);
         if (const char* v = getenv("GASM_SCATTER_WGS")) scatter_wgs = std::max(1, atoi(v));
         if (const char* v = getenv("GASM_HIST_WGS")) hist_wgs = std::max(1, atoi(v));
         if (const char* v = getenv("GASM_DBG_BBITS_ADD")) bbits_add = std::max(0, atoi(v));
@@ -48,8 +42,6 @@ struct Knobs {
         if (const char* v = getenv("GASM_DBG_RANK_ROUNDS")) rank_rounds = atoi(v);
         rank_global = getenv("GASM_RANK_GLOBAL") != nullptr;
         sync_build = getenv("GASM_SYNC_BUILD") != nullptr;       // wait for every build's report at once (diagnostic)
-        if (const char* v = getenv("GASM_DEDUP_WARM")) dedup_warm = std::max(0, std::min(3, atoi(v)));     // first iterations of the 64-bit de-duplication taken key by key
-        stamps = getenv("GASM_DBG_STAMPS");
     }
 };
 static const Knobs& knobs() { static const Knobs k; return k; }
@@ -537,15 +529,15 @@ static GraphView graph_view(const BuildState& bs) {
 
 // k_bucket_dedup over the key width and the table size of `bs`: 64-bit keys have both tables, 128-bit keys the small one
 template <class K, int TBL>
-static int launch_bucket_dedup_as(gasm_ctx* ctx, BuildState& bs, u32 nbt, const u32* d_blen, int dbg_d, unsigned long long* d_stamps, u32* d_scan_out) {
+static int launch_bucket_dedup_as(gasm_ctx* ctx, BuildState& bs, u32 nbt, const u32* d_blen, u32* d_scan_out) {
     GLAUNCH(ctx, "k_bucket_dedup", (k_bucket_dedup<K, TBL>), dim3(nbt), dim3(GASM_WG), 0, bs.d_keys.as<K>(), bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), d_blen,
-            bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * bs.k - bs.bbits, dbg_d, d_stamps, d_scan_out);
+            bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * bs.k - bs.bbits, d_scan_out);
     return GASM_OK;
 }
-static int launch_bucket_dedup(gasm_ctx* ctx, BuildState& bs, u32 nbt, const u32* d_blen, int dbg_d, unsigned long long* d_stamps, u32* d_scan_out) {
-    if (bs.words == 2) return launch_bucket_dedup_as<K128, 2048>(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out);
-    if (bs.small_tbl) return launch_bucket_dedup_as<u64, 2048>(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out);
-    return launch_bucket_dedup_as<u64, 4096>(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out);
+static int launch_bucket_dedup(gasm_ctx* ctx, BuildState& bs, u32 nbt, const u32* d_blen, u32* d_scan_out) {
+    if (bs.words == 2) return launch_bucket_dedup_as<K128, 2048>(ctx, bs, nbt, d_blen, d_scan_out);
+    if (bs.small_tbl) return launch_bucket_dedup_as<u64, 2048>(ctx, bs, nbt, d_blen, d_scan_out);
+    return launch_bucket_dedup_as<u64, 4096>(ctx, bs, nbt, d_blen, d_scan_out);
 }
 
 // ---- reads -> per-(segment, bucket) distinct k-mers with multiplicities (in place in d_keys / d_mult) + dstart
@@ -557,17 +549,16 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     const u64 N = bs.n_kmers;
     // every (tile, bucket) run is padded to a multiple of padm + 1 keys (a 128-byte line when the bucket count allows;
     // the padding of one tile must fit the flush passes k_bucket_scatter has beyond KT)
-    const u32 line_keys = 128 / KB, pad_room = W == 1 ? 2 * GASM_TILE_WG : GASM_TILE_WG;
-    u32 padm = line_keys - 1;
-    if (knobs().padm >= 0) padm = std::min<u32>(padm, (u32)knobs().padm);
-    while (padm & (padm + 1)) padm >>= 1;     // a mask: 2^n - 1
+    const u32 line_keys = 128 / KB;
+    const u32 pad_room = (u32)with_key(W, [](auto tag) -> int { return TileStage<typename decltype(tag)::type>::PAD_ROOM; });
+    u32 padm = line_keys - 1;                 // a mask: 2^n - 1
     // (128-bit keys: + 1, so that k_bucket_partition has a thread for every key of a bucket's unfinished line — nb * (padm + 1)
     // <= GASM_TILE_WG; with 64-bit keys a thread takes two, and nb <= GASM_TILE_WG buckets keep that within the workgroup)
     while (padm && (u64)nb * (padm + (W == 2 ? 1u : 0u)) > pad_room) padm >>= 1;
     const ReadSet rs = rd.view();
     const u32 g = bs.tile_g;
     const u32 grid_tiles = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().hist_wgs);
-    constexpr u32 SCRATCH_KEYS = 1024 * (GASM_TILE_WG / 64) * 64 * 2;   // 16 bytes per lane and wave of 1024 workgroup slots (k_bucket_scatter)
+    const u32 scratch_keys = GASM_FLUSH_SLOTS * (16 / KB);      // the flush's scratch line behind the keys: 16 bytes per slot (kernels.h)
     GCHK(bs.d_bstart.ensure(((size_t)nbt + 1) * 8));
     GCHK(bs.d_bucket_d.ensure((size_t)nbt * 4));
     GCHK(bs.d_dstart.ensure(((size_t)nbt + 2) * 4));
@@ -580,9 +571,9 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         // bucket with `part_slack` percent to spare, room for Poisson noise and for the padding of its tiles' runs, in whole
         // lines — and a cursor per region behind the build's flag words
         const int slack = env_int("GASM_PART_SLACK", 100), forced = env_int("GASM_DBG_PART_CAP", 0);
-        const bool same_layout = bs.part_valid && bs.part_reads_id == rd.upload_id && bs.part_k == k && bs.part_bbits == bbits && bs.part_padm == padm &&
-                                 bs.part_g == g && bs.part_slack == slack && bs.part_forced == forced;
-        if (!same_layout) {
+        BuildState::PartLayout layout;
+        layout.reads_id = rd.upload_id; layout.k = k; layout.bbits = bbits; layout.slack = slack; layout.forced = forced; layout.padm = padm; layout.g = g;
+        if (!(bs.part_valid && bs.part == layout)) {
             std::vector<u64> h((size_t)nbt + 1);
             u64 at = 0;
             for (u32 s = 0; s < S; ++s) {
@@ -596,20 +587,19 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
             bs.part_alloc = at;
             GCHK(h2d(ctx, bs.d_bstart, h.data(), h.size() * 8));
             HIPCHK(hipStreamSynchronize(ctx->stream));          // (`h` goes out of scope; only when the batch shape changes)
-            bs.part_valid = true; bs.part_reads_id = rd.upload_id; bs.part_k = k; bs.part_bbits = bbits; bs.part_padm = padm; bs.part_g = g;
-            bs.part_slack = slack; bs.part_forced = forced;
+            bs.part_valid = true;
+            bs.part = layout;
         }
         n_alloc = bs.part_alloc;
-        GCHK(bs.d_keys.ensure((n_alloc + SCRATCH_KEYS) * KB));
+        GCHK(bs.d_keys.ensure((n_alloc + scratch_keys) * KB));
         GCHK(bs.d_mult.ensure(n_alloc * 4));
         GCHK(bs.d_flags.ensure(GASM_FLAG_BYTES + (size_t)nbt * 4));
         HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, GASM_FLAG_BYTES + (size_t)nbt * 4, ctx->stream));
         u32* const d_cursor = bs.d_flags.as<u32>() + GASM_FLAG_CURSORS;
         d_blen = d_cursor;
-        const size_t lds = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB + (size_t)nb * 16 + (size_t)(4 * nb + 4) * 8 + 48 + (size_t)nb * 4;
         u32 grid_part = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().scatter_wgs);
         if (const int cap = env_int("GASM_DBG_PART_GRID", 0)) grid_part = std::min<u32>(grid_part, (u32)std::max(1, cap));
-        GLAUNCH_K(ctx, W, "k_bucket_partition", k_bucket_partition<K>, dim3(grid_part), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
+        GLAUNCH_K(ctx, W, "k_bucket_partition", k_bucket_partition<K>, dim3(grid_part), dim3(GASM_TILE_WG), PartitionLds<K>{nb}.total(), rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
                   bs.d_bstart.as<u64>(), d_cursor, bs.d_keys.as<K>(), n_alloc, bs.d_flags.as<u32>());
     } else {
         // ---- two passes: count, scan, scatter (exact layout; the retry path of the single pass, > 512 buckets, multi-pass builds)
@@ -617,7 +607,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         GCHK(bs.d_hist.ensure((size_t)nbt * 4));
         GCHK(bs.d_toff.ensure((size_t)rd.n_tiles * nb * 4));
         n_alloc = N + (u64)padm * rd.n_tiles * nb;
-        GCHK(bs.d_keys.ensure((n_alloc + SCRATCH_KEYS) * KB));
+        GCHK(bs.d_keys.ensure((n_alloc + scratch_keys) * KB));
         GCHK(bs.d_mult.ensure(n_alloc * 4));
         GCHK(bs.d_tcnt.ensure((size_t)rd.n_tiles * nb * 8 + 64));      // four 16-bit sub-counts per (tile, bucket)
         GLAUNCH_K(ctx, W, "k_tile_hist", k_tile_hist<K>, dim3(grid_tiles), dim3(GASM_TILE_WG), (size_t)nb * 16, rs, rs.tile_info, k, bbits, g, rd.n_tiles,
@@ -625,32 +615,16 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
         GLAUNCH(ctx, "k_tile_scan", k_tile_scan, dim3(S, std::max(1u, nb / 32u)), dim3(1024), 0, rs, bbits, padm, bs.d_tcnt.as<ushort4>(),
                 bs.d_toff.as<u32>(), bs.d_hist.as<u32>(), bs.d_flags.as<u32>());
         GLAUNCH(ctx, "k_scan_excl", k_scan_excl<u64>, dim3(1), dim3(1024), 0, bs.d_hist.as<u32>(), bs.d_bstart.as<u64>(), nbt);
-        const size_t lds = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB + (size_t)nb * 24 + 96;   // KeyTraits<K>::NFL passes + trash slots + cursors
         // two workgroups per CU fit (LDS); a few tiles per workgroup so that the prefetch of the next tile pays
         const u32 grid_scatter = std::min<u32>(rd.n_tiles, (u32)ctx->n_cu * (u32)knobs().scatter_wgs);
-        GLAUNCH_K(ctx, W, "k_bucket_scatter", k_bucket_scatter<K>, dim3(grid_scatter), dim3(GASM_TILE_WG), lds, rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
+        GLAUNCH_K(ctx, W, "k_bucket_scatter", k_bucket_scatter<K>, dim3(grid_scatter), dim3(GASM_TILE_WG), ScatterLds<K>{nb}.total(), rs, rs.tile_info, k, bbits, g, padm, rd.n_tiles,
                   bs.d_bstart.as<u64>(), bs.d_toff.as<u32>(), bs.d_tcnt.as<ushort4>(), bs.d_keys.as<K>(), n_alloc);
     }
-    unsigned long long* d_stamps = nullptr;
-    static DBuf stamp_buf;
-    if (knobs().stamps) {   // diagnostic: per-phase cycle totals of k_bucket_dedup to stderr
-        int o1 = 0, o2 = 0, o3 = 0, o4 = 0;
-        const size_t lds_stage = (size_t)(W == 1 ? 18 : 9) * GASM_TILE_WG * KB + (GASM_TILE_WG / 8) * KB;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o1, k_bucket_dedup<u64, 2048>, GASM_WG, 0);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, k_bucket_dedup<u64, 4096>, GASM_WG, 0);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o3, k_bucket_scatter<u64>, GASM_TILE_WG, lds_stage + (size_t)nb * 24 + 96);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o4, k_bucket_partition<u64>, GASM_TILE_WG, lds_stage + (size_t)nb * 52 + 80);
-        fprintf(stderr, "[occupancy API] dedup<2048> %d  dedup<4096> %d  scatter %d  partition %d blocks/CU\n", o1, o2, o3, o4);
-        GCHK(stamp_buf.ensure(64 + (size_t)nbt * 24));
-        HIPCHK(hipMemsetAsync(stamp_buf.p, 0, 64 + (size_t)nbt * 24, ctx->stream));
-        d_stamps = stamp_buf.as<unsigned long long>();
-    }
-    const int dbg_d = knobs().dbg_dedup | (knobs().dedup_warm << 2);
     // the buckets' distinct counts -> dstart by the de-duplication's last workgroup; beyond 16 384 buckets one workgroup of 256 is too slow a scanner: k_scan_excl in a launch of its own
     const bool scan_in_dedup = !bs.multi_pass && nbt <= 16384 && env_int("GASM_SCAN_IN_DEDUP", 1) != 0;
     bs.scan_in_dedup = scan_in_dedup;
     u32* const d_scan_out = scan_in_dedup ? bs.d_dstart.as<u32>() : nullptr;
-    bs.fbits = (bs.small_tbl && !bs.multi_pass) ? 9 : 10;   // bins of the de-duplication kernel's counting sort = TBL / 4 (the multi-pass kernel: 4096 slots)
+    bs.fbits = dedup_fbits(bs.small_tbl && !bs.multi_pass ? 2048 : GASM_TBL);   // bins of the de-duplication kernel's counting sort (the multi-pass kernel: 4096 slots)
     GCHK(bs.d_fdir.ensure((size_t)nbt * ((1u << bs.fbits) + 1) * 2));
     // (k_bucket_dedup writes every entry of its bucket's fine directory)
     if (bs.multi_pass) {
@@ -661,16 +635,7 @@ int launch_distinct(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
                   bs.d_mult.as<u32>(), bs.d_bstart.as<u64>(), bs.d_bucket_d.as<u32>(), bs.d_flags.as<u32>(), bs.d_fdir.as<u16>(), 2 * k - bbits);
         HIPCHK(hipMemcpyAsync(bs.d_keys.p, bs.d_keys2.p, n_alloc * KB, hipMemcpyDeviceToDevice, ctx->stream));
     } else {
-        GCHK(launch_bucket_dedup(ctx, bs, nbt, d_blen, dbg_d, d_stamps, d_scan_out));
-    }
-    if (d_stamps) {
-        std::vector<unsigned long long> hv(8 + (size_t)nbt * 3);
-        HIPCHK(hipMemcpyAsync(hv.data(), d_stamps, hv.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        const unsigned long long* h = hv.data();
-        if (FILE* f = fopen(knobs().stamps, "wb")) { fwrite(hv.data(), 8, hv.size(), f); fclose(f); }
-        fprintf(stderr, "[dedup stamps, 100 MHz ticks per workgroup] init %.1f  first-iter %.1f  stream %.1f  barrier %.1f  order %.1f  writeback %.1f\n",
-                (double)h[0] / nbt, (double)h[1] / nbt, (double)h[2] / nbt, (double)h[3] / nbt, (double)h[4] / nbt, (double)h[5] / nbt);
+        GCHK(launch_bucket_dedup(ctx, bs, nbt, d_blen, d_scan_out));
     }
     if (bs.opts.min_count > 1) {
         // the multiplicity cutoff, behind whichever de-duplication ran (every rung of pipeline_build_finish's ladder comes through
@@ -793,7 +758,7 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs, bool last_pa
     GLAUNCH_K(ctx, W, "k_node_flags", k_node_flags<K>, grid_seg, dim3(GASM_WG), 0, gv, S, dchunks, d_claim, bs.d_eflag.as<u8>(), bs.d_link.as<u64>(), bs.d_clen.as<u32>());
     GLAUNCH(ctx, "k_edge_next", k_edge_next, grid_grp, dim3(GASM_WG), 0, gv, S, gchunks, d_tgt, bs.d_eflag.as<u8>(), bs.d_nxt.as<u32>(), bs.d_link.as<u64>());
     u32* const act = d_fl + GASM_FLAG_ACTIVE;     // "still active" words of the k_link_jump launches
-    const u32 jchunks = (u32)ceil_div_u64(est, GASM_WG * 4);      // GASM_JUMP_ILP links per thread
+    const u32 jchunks = (u32)ceil_div_u64(est, GASM_WG * GASM_JUMP_ILP);
     bs.ranked_in_lds = est <= 65534 && !bs.rank_global && !knobs().rank_global;
     bs.ruler_shift = 0;
     if (bs.ranked_in_lds) {
@@ -859,7 +824,7 @@ static int launch_graph_dense(gasm_ctx* ctx, u32 S, BuildState& bs, bool last_pa
 int plan_build(gasm_ctx* ctx, DevReads& rd, int k, u64 hint, BuildState& bs) {
     if (k < 2 || k > GASM_MAX_K) { gasm_set_error("k = %d not supported (2..%d)", k, GASM_MAX_K); return GASM_ERR_INVALID; }
     const int W = k <= 31 ? 1 : 2;            // 64-bit keys up to k = 31, 128-bit keys (K128) up to k = 63
-    const u32 KT = W == 1 ? 16u : 8u;         // k-mers per thread and round of the tile kernels (KeyTraits<K>::KT)
+    const u32 KT = (u32)with_key(W, [](auto tag) -> int { return KeyTraits<typename decltype(tag)::type>::KT; });   // k-mers per thread and round of the tile kernels
     HIPCHK(hipSetDevice(ctx->device));
     GCHK(ensure_lds_attrs(ctx));
     const u32 S = rd.n_segments;

@@ -62,7 +62,7 @@ int launch_bucket_merge(gasm_pool* p, u32 n_out, u32 n_src, const void* keys_in,
     BuildState& bs = p->bs;
     GCHK(bs.d_bucket_d.ensure(((size_t)n_out + 2) * 4));
     bs.small_tbl = bs.words == 2;
-    bs.fbits = bs.small_tbl ? 9 : 10;
+    bs.fbits = dedup_fbits(bs.small_tbl ? 2048 : GASM_TBL);
     GCHK(bs.d_fdir.ensure(((size_t)n_out + 1) * ((1u << bs.fbits) + 1) * 2));
     HIPCHK(hipMemsetAsync(bs.d_flags.p, 0, GASM_FLAG_BYTES, p->ctx->stream));
     if (!n_out) return GASM_OK;

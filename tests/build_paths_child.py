@@ -1,6 +1,6 @@
 """Child process of tests/test_build_paths_gpu.py::test_process_wide_knobs_in_child_processes (not a test module).
 
-The Knobs of pipeline.hip (GASM_RANK_GLOBAL, GASM_RULER_SHIFT, GASM_DEDUP_TBL, GASM_DEDUP_WARM, GASM_SCATTER_WGS,
+The Knobs of pipeline.hip (GASM_RANK_GLOBAL, GASM_RULER_SHIFT, GASM_DEDUP_TBL, GASM_SCATTER_WGS,
 GASM_HIST_WGS) are read once per process, so each set runs here in a fresh process, from the environment it was started
 with.  A fixed set of small batches — 64- and 128-bit keys, more than 64 segments, ragged reads with an empty segment, a
 4096-slot-table build and a two-pass partition — is built and checked against the oracle (contigs, distinct k-mers and
@@ -21,7 +21,7 @@ import genomeassembler_dev_amd as ga  # noqa: E402
 from genomeassembler_dev_amd import synth  # noqa: E402
 from oracle import orc  # noqa: E402
 
-KNOBS = ("GASM_RANK_GLOBAL", "GASM_RULER_SHIFT", "GASM_DEDUP_TBL", "GASM_DEDUP_WARM", "GASM_SCAN_IN_DEDUP", "GASM_SCATTER_WGS",
+KNOBS = ("GASM_RANK_GLOBAL", "GASM_RULER_SHIFT", "GASM_DEDUP_TBL", "GASM_SCAN_IN_DEDUP", "GASM_SCATTER_WGS",
          "GASM_HIST_WGS")
 
 

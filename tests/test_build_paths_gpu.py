@@ -295,8 +295,8 @@ def test_build_plan_rows_per_block_and_state():
 
 # ------------------------------------------------------------------------------------------------ process-wide knobs
 KNOB_SETS = [{"GASM_RANK_GLOBAL": "1"}, {"GASM_RULER_SHIFT": "1"}, {"GASM_RULER_SHIFT": "2"}, {"GASM_RULER_SHIFT": "3"},
-             {"GASM_RULER_SHIFT": "4"}, {"GASM_DEDUP_TBL": "2048"}, {"GASM_DEDUP_TBL": "4096"}, {"GASM_DEDUP_WARM": "1"},
-             {"GASM_DEDUP_WARM": "3"}, {"GASM_SCAN_IN_DEDUP": "0"}, {"GASM_SCATTER_WGS": "1", "GASM_HIST_WGS": "1"}]
+             {"GASM_RULER_SHIFT": "4"}, {"GASM_DEDUP_TBL": "2048"}, {"GASM_DEDUP_TBL": "4096"},
+             {"GASM_SCAN_IN_DEDUP": "0"}, {"GASM_SCATTER_WGS": "1", "GASM_HIST_WGS": "1"}]
 
 
 @pytest.mark.timeout(1200)

@@ -34,6 +34,21 @@ def test_build_plan_fields_match_the_header():
     assert [_lib.PLAN_FIELDS[i] for i in sorted(idx.values())] == [f for f, _ in sorted(idx.items(), key=lambda t: t[1])]
 
 
+def test_tile_kernel_layouts_match_the_launch_figures():
+    """The LDS layouts, staging area, pad room, scratch slots and directory bits that the tile kernels and their launches take
+    from one definition (csrc/kernels.h) equal the figures the launches used to restate, for every bucket count 1 .. 1024:
+    tests/lds_layout_check.cpp, built for the host only."""
+    import subprocess
+    csrc = os.path.join(ROOT, "genomeassembler_dev_amd", "csrc")
+    exe = os.path.join(ROOT, "oracle", "_build", "lds_layout_check")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-std=c++17", "-O1", "-x", "hip", "--offload-host-only", "-Wall", "-Wno-unused-function", "-I" + csrc,
+                    os.path.join(ROOT, "tests", "lds_layout_check.cpp"), "-o", exe], check=True, cwd=ROOT)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "0 mismatches over nb = 1 .. 1024" in r.stdout, r.stdout + r.stderr
+
+
 def test_no_device_fails_loudly():
     import torch
     if torch.cuda.is_available():

@@ -1,11 +1,10 @@
 """The batch paths of the 64-bit de-duplication (k_bucket_dedup / dedup_step, kernels_build.hip) at the inputs where a change to
 its probe or claim protocol would show first: every lane after one slot, tables filled to their limit and past it, key
-counts around the iteration size, both table sizes with and without the key-by-key first iterations, and the multi-pass
-rung.  Every case builds through SegmentBatch.build and compares distinct k-mers, multiplicities and contigs with the
+counts around the iteration size, both table sizes, and the multi-pass rung.  Every case builds through SegmentBatch.build and compares distinct k-mers, multiplicities and contigs with the
 oracle, as tests/test_gpu_parity.py does.
 
-Run as a script (`--child`) this file is the child process of test_random_batches_tables_and_warm: the table size and
-GASM_DEDUP_WARM are read once per process."""
+Run as a script (`--child`) this file is the child process of test_random_batches_both_tables: the table size
+(GASM_DEDUP_TBL) is read once per process."""
 import json
 import os
 import subprocess
@@ -141,15 +140,11 @@ def _child():
 
 
 @pytest.mark.parametrize("tbl", ["2048", "4096"])
-@pytest.mark.parametrize("warm", [None, "2"])
-def test_random_batches_tables_and_warm(tbl, warm):
-    """Random batches through both table sizes, with GASM_DEDUP_WARM set (the first two iterations of a workgroup taken key
-    by key) and unset (every iteration a batch).  The knobs are read once per process: one child per combination."""
+def test_random_batches_both_tables(tbl):
+    """Random batches through both table sizes.  The knob is read once per process: one child per table size."""
     env = {n: v for n, v in os.environ.items() if not n.startswith("GASM_DEDUP_")}
     env["PYTHONPATH"] = ROOT + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
     env["GASM_DEDUP_TBL"] = tbl
-    if warm is not None:
-        env["GASM_DEDUP_WARM"] = warm
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
     assert r.returncode == 0 and lines, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-3000:]}"
