@@ -460,6 +460,18 @@ def contig_graph(reads, k, span_len=None, ctx=None, **build):
         b.close()
 
 
+def map_reads(reads, k, max_mismatch=4, ctx=None, **build):
+    """one segment's reads (a list of str) mapped onto the contigs of their own build within max_mismatch substitutions: a
+    readmap.ReadMap that speaks of segment 0 (records(0), pileup(0), depth(0), mapped_fraction(0), error_rate(0), consensus(0),
+    variants(0); the rule and its limits: include/gasm.h "Read mapping").  build: as for contig_graph."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        return b.build_simplified(int(k), **build).map_reads(max_mismatch)
+    finally:
+        b.close()
+
+
 def resolve_repeats(reads, k, min_support=2, ctx=None, **build):
     """the contigs of one segment's reads with the repeats shorter than a read put back into their flanks, where the reads that run
     through a repeat say so unambiguously (links.ContigLinks.resolve_repeats: the rule and its limits); a sorted list of str.

@@ -7,10 +7,11 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_MISMATCH, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 from .pairs import PairPlaces
+from .readmap import ReadMap
 
 
 def weighted_median_half(mult_sum, n_edges):
@@ -46,6 +47,7 @@ class SegmentBatch:
         self.h = h
         self.k = None
         self._table = None
+        self._seg_read_off = seg.copy()
 
     @classmethod
     def from_strings(cls, segments, ctx=None):
@@ -75,6 +77,7 @@ class SegmentBatch:
                                              self.n_reads, 0 if ro is not None else int(fixed_len), seg.ctypes.data_as(C.c_void_p),
                                              self.n_segments, C.byref(h)))
         self.h, self.k, self._table = h, None, None
+        self._seg_read_off = seg.copy()
         return self
 
     @classmethod
@@ -269,6 +272,30 @@ class SegmentBatch:
         rec = arr(ps[0], C.c_int32, 4 * o * n_pairs)
         hist, cnt = arr(ps[1], C.c_uint32, self.n_segments * (max_insert + 1)), arr(ps[2], C.c_uint64, self.n_segments * len(PAIR_FIELDS))
         return PairPlaces(self.k, self.strands(), max_insert, o, self.contigs(), rec, hist, cnt)
+
+    def map_reads(self, max_mismatch=4):
+        """where the batch's reads lie on the last build's contigs within max_mismatch substitutions (gasm_batch_map_reads; the rule:
+        include/gasm.h "Read mapping") as a readmap.ReadMap: per read its best place, per contig base the four base counts of the reads
+        laid over it, per segment the mismatch histogram and the seven counters.  max_mismatch: 0 .. _lib.MAP_MAX_MISMATCH.  The reads
+        are mapped as given, whatever the build's strands.  Reads the build only: contigs, scores, coverage, twins, links and pair
+        places are what they were."""
+        if not 0 <= int(max_mismatch) <= MAP_MAX_MISMATCH:
+            raise ValueError(f"max_mismatch must be 0..{MAP_MAX_MISMATCH}")
+        max_mismatch = int(max_mismatch)
+        check(lib().gasm_batch_map_reads(self.h, max_mismatch))
+        ps = [C.c_void_p() for _ in range(4)]
+        check(lib().gasm_batch_fetch_read_map(self.h, *[C.byref(p) for p in ps]))
+
+        def arr(p, ct, n):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
+        seg, o, raw = self.contigs_raw()
+        contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+        total = int(o[-1]) if int(seg[-1]) else 0
+        rec, pile = arr(ps[0], C.c_int32, 4 * self.n_reads), arr(ps[1], C.c_uint32, 4 * total)
+        hist, cnt = arr(ps[2], C.c_uint32, self.n_segments * (max_mismatch + 1)), arr(ps[3], C.c_uint64, self.n_segments * len(MAP_FIELDS))
+        strands = self.strands()
+        return ReadMap(self.k, strands, max_mismatch, contigs, rec, pile, hist, cnt,
+                       [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
 
     def suggest_cov_cutoff(self, segment):
         """a cov_cutoff for build_simplified() from the last build's own contigs of `segment`: half the length-weighted median of the

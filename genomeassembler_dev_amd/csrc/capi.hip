@@ -1020,6 +1020,27 @@ int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint3
     API_GUARD_END
 }
 
+int gasm_batch_map_reads(gasm_batch* b, uint32_t max_mismatch) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (max_mismatch > GASM_MAP_MAX_MISMATCH) { gasm_set_error("max_mismatch must be <= %d (got %u)", GASM_MAP_MAX_MISMATCH, max_mismatch); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_map_reads before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    return pipeline_map_reads(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, max_mismatch);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t** pile, const uint32_t** mismatch_hist, const uint64_t** counters) {
+    API_GUARD_BEGIN
+    if (!b || !rec || !pile || !mismatch_hist || !counters) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_read_map before a build"); return GASM_ERR_STATE; }
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, bs));
+    *rec = bs.h_map_rec.data(); *pile = bs.h_map_pile.data(); *mismatch_hist = bs.h_map_hist.data(); *counters = bs.h_map_counters.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin) {
     API_GUARD_BEGIN
     if (!b || !twin) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }

@@ -305,6 +305,13 @@ __global__ void k_read_thread(ReadSet rs, GraphView gv, const u64* link, const u
 template <class K>
 __global__ void k_pair_place(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, int have_graph, u32 orient, u32 max_insert,
                              u64 n_pairs, u32 chunks, int32_t* rec, u32* hist, unsigned long long* counters);
+// read mapping (include/gasm.h, "Read mapping"): rec: 4 int32 per read (16-byte aligned); text: the contigs' ASCII; pile: 4 u32 per base of it,
+// hist: max_mismatch + 1 bins per segment, counters: GASM_MAP_COUNTERS per segment, the three zeroed by the caller
+#define GASM_MAP_COUNTERS 7           // = GASM_MAP_FIELDS of include/gasm.h (checked in pipeline.hip)
+#define GASM_MAP_BLOCKS 8             // = GASM_MAP_MAX_BLOCKS: distinct heads of a read that are verified (one per lane 0 .. 7 of its wave)
+template <class K>
+__global__ void k_read_map(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph,
+                           u32 max_mismatch, u32 reads_per_wg, u32 chunks, int32_t* rec, u32* pile, u32* hist, unsigned long long* counters);
 
 // ---- kernels_score.hip
 struct SeedTable {

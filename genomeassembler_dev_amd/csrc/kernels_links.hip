@@ -332,3 +332,140 @@ __global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv
 }
 template __global__ void k_pair_place<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, int, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);
 template __global__ void k_pair_place<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, int, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);
+
+// ================================================================================================================
+// Read mapping (include/gasm.h, "Read mapping").  One wave per read, GASM_THREAD_WAVES reads of one segment per workgroup and round, the
+// workgroups of a segment on one XCD (seg_chunk), chunks of 64 k-mer positions taken first to last, as k_read_thread.
+//   SEEDS.  One look-up per lane and chunk (kmer_contig): lane's position j, its contig and its diagonal d = offset - j.
+//   HEADS.  A seeded lane compares its (contig, d) with the PREVIOUS SEEDED lane's: the highest set bit of the seed ballot below the
+//   lane inside the chunk (one cross-lane move), the scalar carry (prev_c, prev_d) across the chunk seam.  One ballot per chunk.
+//   HEAD LOOP, wave-uniform: a head is taken by count-trailing-zeros, its (contig, d) fetched from its lane, compared with the kept
+//   heads — head i of the read sits in lane i's registers (my_c, my_d), so the compare is one ballot and the list takes no LDS —, then
+//   verified with the 64 lanes striding over the overlap: read base from the packed stream, contig base from the build's ASCII text,
+//   ballot and popcount, stopping once m > max_mismatch.  An accepted block walks its overlap once more for the pileup: one no-return
+//   atomic add per lane and base.  The histogram add is per block, the record one 16-byte store by lane 0.
+//   COUNTERS as in k_pair_place: per wave in scalars, one LDS atomic per non-zero counter and wave, one global atomic per non-zero
+//   counter and workgroup.
+// Every index is bounded before use: a head's contig is inside the segment (kmer_contig), the overlap [lo, hi) is clamped to the read and
+// to the contig's bases, so d + i lies in [0, len(c)) and the pileup entry inside the contig's 4 len(c) words.
+// rec: 4 int32 per read (16-byte aligned), every read of every segment written; pile: 4 u32 per base of the contig text, hist:
+// max_mismatch + 1 per segment, counters: GASM_MAP_COUNTERS per segment, all three zeroed by the caller.
+// have_graph = 0: the build holds no contig at all (its arrays may not exist): only short, skipped and unseeded are counted.
+// ================================================================================================================
+template <class K>
+__global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
+                                                      const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, const u8* __restrict__ text,
+                                                      int have_graph, u32 max_mismatch, u32 reads_per_wg, u32 chunks, int32_t* __restrict__ rec,
+                                                      u32* __restrict__ pile, u32* __restrict__ hist, unsigned long long* __restrict__ counters) {
+    __shared__ u32 s_cnt[GASM_MAP_COUNTERS];
+    u32 seg, chunk;
+    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
+    if (threadIdx.x < GASM_MAP_COUNTERS) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int k = gv.k;
+    u32 elo = 0, ehi = 0, c_lo = 0, c_hi = 0;
+    if (have_graph) {
+        const u32 nb = 1u << gv.bbits;
+        elo = gv.dstart[seg * nb]; ehi = gv.dstart[(seg + 1) * nb];
+        c_lo = seg_cstart[seg]; c_hi = seg_cstart[seg + 1];
+    }
+    const bool graph = elo < ehi && c_lo < c_hi;
+    const u64 rbeg = rs.seg_read_off[seg], rend = rs.seg_read_off[seg + 1];
+    u32 c_cnt[GASM_MAP_COUNTERS] = {0, 0, 0, 0, 0, 0, 0};                     // of this wave's reads (wave-uniform)
+    for (u64 base = rbeg + (u64)chunk * reads_per_wg; base < rend; base += (u64)chunks * reads_per_wg) {
+        const u64 end = base + reads_per_wg < rend ? base + reads_per_wg : rend;
+        for (u64 r = base + wv; r < end; r += GASM_THREAD_WAVES) {
+            u64 p0;
+            u32 len;
+            read_span(rs, r, &p0, &len);
+            const u32 n = len >= (u32)k ? len - (u32)k + 1 : 0;
+            u32 cls;                                                          // the read's counter
+            u32 n_heads = 0, n_acc = 0, dropped = 0, b_ov = 0, b_m = 0, b_c = 0;
+            int b_d = 0;
+            bool seeded_any = false;
+            if (n == 0) cls = 0;
+            else if (n > GASM_THREAD_KMER_CAP) cls = 1;
+            else if (!graph) cls = 2;
+            else {
+                u32 my_c = GASM_NONE32, prev_c = GASM_NONE32;                 // lane i: kept head i; the last seeded position before this chunk
+                int my_d = 0, prev_d = 0;
+                const u32 nw = (n + 63u) >> 6;
+                for (u32 w = 0; w < nw; ++w) {
+                    const u32 j = (w << 6) + lane;
+                    u32 cid = GASM_NONE32, off = 0;
+                    if (j < n && !kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kmer_key_at<K>(rs.words, p0 + j, k), &cid, &off)) cid = GASM_NONE32;
+                    const int d = (int)off - (int)j;
+                    const u64 sm = __ballot(cid != GASM_NONE32);
+                    if (!sm) continue;
+                    seeded_any = true;
+                    // ---- heads: compare with the previous seeded lane (inside the chunk), or with the carry
+                    const u64 below = sm & ((1ull << lane) - 1ull);
+                    const int src = below ? 63 - __builtin_clzll(below) : (int)lane;
+                    u32 pc = (u32)__shfl((int)cid, src, 64);
+                    int pd = __shfl(d, src, 64);
+                    if (!below) { pc = prev_c; pd = prev_d; }
+                    u64 hb = __ballot(cid != GASM_NONE32 && (pc != cid || pd != d));
+                    const int last = 63 - __builtin_clzll(sm);
+                    prev_c = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)cid, last, 64));
+                    prev_d = __builtin_amdgcn_readfirstlane(__shfl(d, last, 64));
+                    // ---- the head loop (wave-uniform)
+                    while (hb) {
+                        const int L = __builtin_ctzll(hb);
+                        hb &= hb - 1;
+                        const u32 h_c = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)cid, L, 64));
+                        const int h_d = __builtin_amdgcn_readfirstlane(__shfl(d, L, 64));
+                        if (__ballot(lane < n_heads && my_c == h_c && my_d == h_d)) continue;      // A, B, A
+                        if (n_heads == GASM_MAP_BLOCKS) { ++dropped; continue; }
+                        if (lane == n_heads) { my_c = h_c; my_d = h_d; }
+                        ++n_heads;
+                        // ---- verify: read base i against contig base d + i over [lo, hi)
+                        const u64 cb = c_off[h_c];
+                        const long long clen = (long long)(c_off[h_c + 1] - cb);
+                        const long long lo = h_d < 0 ? -(long long)h_d : 0;
+                        long long hi = clen - (long long)h_d;
+                        if (hi > (long long)len) hi = (long long)len;
+                        if (hi <= lo) continue;                                // (no finished build gives this: a k-mer of c lies inside c)
+                        u32 m = 0;
+                        for (long long i0 = lo; i0 < hi && m <= max_mismatch; i0 += 64) {
+                            const long long i = i0 + lane;
+                            const bool differ = i < hi && base_at(rs.words, p0 + (u64)i) != base_code(text[cb + (u64)((long long)h_d + i)]);
+                            m += (u32)__popcll(__ballot(differ));
+                        }
+                        if (m > max_mismatch) continue;
+                        // ---- accepted: pileup, histogram, best block
+                        for (long long i0 = lo; i0 < hi; i0 += 64) {
+                            const long long i = i0 + lane;
+                            if (i < hi) atomicAdd(&pile[4 * (cb + (u64)((long long)h_d + i)) + base_at(rs.words, p0 + (u64)i)], 1u);
+                        }
+                        if (lane == 0) atomicAdd(&hist[(size_t)seg * (max_mismatch + 1) + m], 1u);
+                        const u32 ov = (u32)(hi - lo);
+                        if (n_acc == 0 || ov > b_ov || (ov == b_ov && m < b_m)) { b_ov = ov; b_m = m; b_c = h_c; b_d = h_d; }
+                        ++n_acc;
+                    }
+                }
+                cls = !seeded_any ? 2u : n_acc == 0 ? 3u : n_acc == 1 ? 4u : 5u;
+            }
+            if (lane == 0) {
+                int4 v;
+                v.x = n_acc ? (int)(b_c - c_lo) : -1; v.y = n_acc ? b_d : 0;
+                v.z = n_acc ? (int)(b_m | (n_acc << 16)) : 0; v.w = (int)b_ov;
+                *reinterpret_cast<int4*>(rec + r * 4) = v;
+            }
+#pragma unroll
+            for (u32 f = 0; f < 6; ++f) c_cnt[f] += cls == f ? 1u : 0u;
+            c_cnt[6] += dropped;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (u32 f = 0; f < GASM_MAP_COUNTERS; ++f)
+            if (c_cnt[f]) atomicAdd(&s_cnt[f], c_cnt[f]);
+    }
+    __syncthreads();
+    if (threadIdx.x < GASM_MAP_COUNTERS && s_cnt[threadIdx.x]) atomicAdd(&counters[(size_t)seg * GASM_MAP_COUNTERS + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+template __global__ void k_read_map<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, int32_t*, u32*, u32*, unsigned long long*);
+template __global__ void k_read_map<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, int32_t*, u32*, u32*, unsigned long long*);

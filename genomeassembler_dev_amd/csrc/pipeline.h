@@ -174,6 +174,13 @@ struct BuildState {
     std::vector<u64> h_pair_counters;
     u32 pairs_orient = 0, pairs_max_insert = 0;     // of the last placement
     bool pairs_queued = false;              // k_pair_place ran on the arrays of this build
+    DBuf d_map;                             // read mapping of the last build (pipeline_map_reads): int32 rec[4 * reads], then u32 pile[4 * contig bases],
+                                            // u32 mismatch_hist[S * (max_mismatch + 1)] (padded to 8 bytes), then u64 counters[S * GASM_MAP_FIELDS]
+    std::vector<int32_t> h_map_rec;
+    std::vector<u32> h_map_pile, h_map_hist;
+    std::vector<u64> h_map_counters;
+    u32 map_max_mismatch = 0;               // of the last mapping
+    bool map_queued = false;                // k_read_map ran on the arrays of this build
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -275,6 +282,11 @@ int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // number of reads: GASM_ERR_INVALID.  Positioned reads (pooled builds): GASM_ERR_STATE
 int pipeline_place_pairs(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_insert);
 int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// Read mapping (k_read_map in kernels_links.hip; the rule: include/gasm.h "Read mapping") of the finished build: queue the kernel on the build's
+// stream behind it (it reads the build's arrays and the batch's OWN reads `rd`, as given, whatever the build's strands), then fetch h_map_rec
+// (4 per read), h_map_pile (4 per contig base), h_map_hist (max_mismatch + 1 per segment) and h_map_counters (GASM_MAP_FIELDS per segment)
+int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_mismatch);
+int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

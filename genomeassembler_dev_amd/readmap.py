@@ -1,0 +1,116 @@
+"""ReadMap: what SegmentBatch.map_reads() returns — per read its best place on the contigs within max_mismatch substitutions, per contig
+base the four base counts of the reads laid over it, per segment a mismatch histogram and seven counters (the rule and its limits:
+include/gasm.h "Read mapping") — and the host arithmetic on top: depth, mapped fraction, error rate, consensus, variants."""
+import numpy as np
+
+from ._lib import MAP_FIELDS
+
+RECORD = np.dtype([("contig", np.int32), ("diagonal", np.int32), ("mismatches", np.int32), ("blocks", np.int32), ("overlap", np.int32)])
+_BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+class ReadMap:
+    def __init__(self, k, strands, max_mismatch, contigs, rec, pile, mismatch_hist, counters, twins=None, seg_read_off=None):
+        """contigs: per segment the list of contig strings; rec: 4 int32 per read of the batch; pile: 4 uint32 per contig base of the
+        batch; mismatch_hist: max_mismatch + 1 per segment; counters: len(MAP_FIELDS) per segment; twins (strands = 2): per segment
+        the twin map; seg_read_off: n_segments + 1 read indices (None, for a batch that does not know them: the segments' read counts
+        are then taken from the sums of their first six counters)."""
+        self.k, self.strands, self.max_mismatch = int(k), int(strands), int(max_mismatch)
+        self._contigs = [list(c) for c in contigs]
+        self.n_segments = len(self._contigs)
+        self._cnt = np.asarray(counters, dtype=np.uint64).reshape(self.n_segments, len(MAP_FIELDS))
+        self._hist = np.asarray(mismatch_hist, dtype=np.uint32).reshape(self.n_segments, self.max_mismatch + 1)
+        if seg_read_off is None:
+            self._read_off = np.concatenate([[0], np.cumsum(self._cnt[:, :6].sum(axis=1).astype(np.int64))])
+        else:
+            self._read_off = np.asarray(seg_read_off, dtype=np.int64)
+        self._rec = np.asarray(rec, dtype=np.int32).reshape(-1, 4)
+        if len(self._read_off) != self.n_segments + 1 or len(self._rec) != int(self._read_off[-1]):
+            raise ValueError("the segments' read offsets do not fit the records")
+        lens = [len(s) for cs in self._contigs for s in cs]
+        self._pile = np.asarray(pile, dtype=np.uint32).reshape(-1, 4)
+        if len(self._pile) != sum(lens):
+            raise ValueError("the pileup does not have four counts per contig base")
+        self._base_off = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+        self._seg_c = np.concatenate([[0], np.cumsum([len(cs) for cs in self._contigs])])
+        self._twins = twins
+
+    def _seg(self, segment):
+        if not 0 <= int(segment) < self.n_segments:
+            raise IndexError(f"segment {segment} of {self.n_segments}")
+        return int(segment)
+
+    def contigs(self, segment):
+        return list(self._contigs[self._seg(segment)])
+
+    def records(self, segment, as_struct=False):
+        """(reads, 5) int32: contig inside the segment, diagonal, mismatches, accepted blocks, overlap of every read's best block;
+        -1, 0, 0, 0, 0 for a read with no place.  as_struct: the same as a structured array of dtype readmap.RECORD"""
+        s = self._seg(segment)
+        r = self._rec[int(self._read_off[s]):int(self._read_off[s + 1])]
+        out = np.stack([r[:, 0], r[:, 1], r[:, 2] & 0xFFFF, r[:, 2] >> 16, r[:, 3]], axis=1).astype(np.int32) if len(r) else np.zeros((0, 5), np.int32)
+        return out.view(RECORD).reshape(-1) if as_struct else out
+
+    def pileup(self, segment, fold_twins=False):
+        """one (len(c), 4) uint32 array per contig: the A, C, G, T counts of the reads laid over every base.  fold_twins (after a
+        strands = 2 build): contig c gets pile[twin(c)][len - 1 - p][3 - x] added — the reads of the other strand"""
+        s = self._seg(segment)
+        c0 = int(self._seg_c[s])
+        own = [self._pile[int(self._base_off[c0 + c]):int(self._base_off[c0 + c + 1])].copy() for c in range(len(self._contigs[s]))]
+        if not fold_twins:
+            return own
+        if self._twins is None:
+            raise ValueError("fold_twins needs a strands = 2 build")
+        return [own[c] + own[int(self._twins[s][c])][::-1, ::-1] for c in range(len(own))]
+
+    def mismatch_hist(self, segment):
+        return self._hist[self._seg(segment)].copy()
+
+    def counters(self, segment, as_dict=False):
+        c = self._cnt[self._seg(segment)].copy()
+        return {name: int(v) for name, v in zip(MAP_FIELDS, c)} if as_dict else c
+
+    def depth(self, segment, fold_twins=False):
+        """one uint32 array per contig: reads laid over every base"""
+        return [p.sum(axis=1, dtype=np.uint32) for p in self.pileup(segment, fold_twins)]
+
+    def mapped_fraction(self, segment):
+        """(mapped_one + mapped_multi) / reads; 0.0 for a segment without reads"""
+        c = self.counters(segment)
+        n = int(c[:6].sum())
+        return (int(c[4]) + int(c[5])) / n if n else 0.0
+
+    def error_rate(self, segment):
+        """mismatches / overlap over the reads' best blocks; 0.0 if nothing is mapped"""
+        r = self.records(segment)
+        r = r[r[:, 0] >= 0]
+        ov = int(r[:, 4].sum())
+        return int(r[:, 2].sum()) / ov if ov else 0.0
+
+    def consensus(self, segment, min_depth=3, fold_twins=False):
+        """the contigs with every base replaced where another base holds a strict majority of a depth of at least min_depth"""
+        out = []
+        for s, p in zip(self._contigs[self._seg(segment)], self.pileup(segment, fold_twins)):
+            t = np.frombuffer(s.encode(), dtype=np.uint8).copy()
+            if len(t):
+                dp, top = p.sum(axis=1, dtype=np.int64), p.argmax(axis=1)
+                win = (dp >= int(min_depth)) & (2 * p.max(axis=1).astype(np.int64) > dp) & (_BASES[top] != t)
+                t[win] = _BASES[top][win]
+            out.append(t.tobytes().decode())
+        return out
+
+    def variants(self, segment, min_depth=8, min_frac=0.2, fold_twins=False):
+        """sorted [(contig, position, contig base, other base, its count, depth)] for every position of a depth of at least min_depth
+        whose strongest other base (the first in ACGT of equals) has a count > 0 that reaches min_frac of the depth"""
+        out = []
+        for c, (s, p) in enumerate(zip(self._contigs[self._seg(segment)], self.pileup(segment, fold_twins))):
+            if not len(s):
+                continue
+            t = np.frombuffer(s.encode(), dtype=np.uint8)
+            other = p.astype(np.int64)
+            other[np.arange(len(t)), np.searchsorted(_BASES, t)] = -1
+            dp, top = p.sum(axis=1, dtype=np.int64), other.argmax(axis=1)
+            n = other[np.arange(len(t)), top]
+            for i in np.nonzero((dp >= int(min_depth)) & (n > 0) & (n >= float(min_frac) * dp))[0]:
+                out.append((c, int(i), s[i], "ACGT"[int(top[i])], int(n[i]), int(dp[i])))
+        return sorted(out)

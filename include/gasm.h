@@ -667,6 +667,54 @@ int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const ui
 int gasm_batch_place_pairs(gasm_batch* b, uint32_t max_insert);
 int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint32_t** insert_hist, const uint64_t** counters,
                                  uint32_t* orientations);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Read mapping: where every read lies on the contigs once it carries substitutions.  (Contig links and read pairs match k-mers exactly:
+ * a read with one wrong base in every k-mer is invisible to them.)  A seed-and-verify pass: exact k-mers seed a place, the whole read is
+ * then compared with the contig's text base by base.
+ * The rule.  INPUTS.  The contigs of the batch's LAST FINISHED BUILD, whatever its options; the batch's reads AS GIVEN (never the
+ * both-strand stream); max_mismatch in 0..GASM_MAP_MAX_MISMATCH.  A k-mer of an isolated cycle lies in no contig: for this rule it is
+ * not in the set.  Contig indices are the ones INSIDE THE SEGMENT.  Pooled builds (gasm_pool_*) get none of this.
+ *   PER READ of len bases and n = len - k + 1 k-mers:
+ *   1. len < k: the read is SHORT.  n > GASM_THREAD_MAX_KMERS: it is SKIPPED.  Neither does anything more.
+ *   2. Position j is a SEED if k-mer j lies in a contig c at offset off.  Its DIAGONAL is d = off - j, signed: read base i lies over
+ *      base d + i of c.  A read with no seed is UNSEEDED.
+ *   3. The seeds are walked in increasing j; positions without a seed are ignored.  A seed whose (c, d) differs from the previous
+ *      seed's is a HEAD.  A head whose (c, d) equals an earlier head's of the same read is ignored (an error can produce A, B, A).  At
+ *      most GASM_MAP_MAX_BLOCKS distinct heads are kept per read; each further distinct head adds 1 to blocks_dropped and is ignored.
+ *      ("Earlier" means KEPT: a dropped head is not remembered, so if it comes again behind another head it adds 1 again.)
+ *   4. Each kept head is VERIFIED.  The overlap is i in [max(0, -d), min(len, len(c) - d)); it always holds at least k bases.  m = the
+ *      number of overlap bases that differ from the contig's text.  The head is ACCEPTED iff m <= max_mismatch.  Bases outside the
+ *      overlap are clipped and never counted.
+ *   5. Every accepted block adds 1 to pile[4 * (c_off[c] + d + i) + base(read[i])] for every i of its overlap, and 1 to
+ *      mismatch_hist[m].  A read that runs from one contig into the next is accepted on both: the k - 1 bases the two contigs share
+ *      are counted on each, which is what depth per contig base should mean.
+ *   6. The read's record is that of its BEST accepted block: largest overlap, then fewest mismatches, then smallest head position.
+ *      With no accepted block the read is REJECTED, with exactly one MAPPED_ONE, with several MAPPED_MULTI.
+ *   OUTPUTS, all exact integers, accumulated with integer atomics where shared: independent of the order the reads are taken in.
+ *     rec[4 r + 0..3] = c, d, m | accepted blocks << 16, overlap as int32, r = the read's index in the batch; -1, 0, 0, 0 for a read
+ *       with no place.
+ *       (readmap.ReadMap.records() splits the packed word: FIVE columns c, d, m, accepted blocks, overlap — the overlap is column 4.)
+ *     pile: 4 uint32 (A, C, G, T) per base of the batch's contig text, in the order of gasm_batch_fetch_contigs.
+ *     mismatch_hist[s * (max_mismatch + 1) + m] counts the accepted blocks of segment s.
+ *     counters[s * GASM_MAP_FIELDS + f], f in this order: short, skipped, unseeded, rejected, mapped_one, mapped_multi, blocks_dropped.
+ *       The first six sum to the segment's reads; mismatch_hist sums to the accepted blocks, pile to their overlaps.
+ *   STRANDS.  After a strands = 2 build the reads are still mapped as given: a read lies on whichever contig of a twin pair has its
+ *   orientation.  Folding the twin's pileup in is host arithmetic.
+ *   LIMITS.  Insertions and deletions are not mapped.  Two placements of one read on the same contig at different diagonals are both
+ *   counted.  The cap of GASM_MAP_MAX_BLOCKS heads.  A read whose every k-mer holds an error is unseeded.
+ * gasm_batch_map_reads            finishes the pending build and queues k_read_map on the step slot of the last build, behind it;
+ *                                 GASM_ERR_STATE before a build and for the positioned reads of pooled builds, GASM_ERR_INVALID for a
+ *                                 null batch or max_mismatch > GASM_MAP_MAX_MISMATCH.  It reads the build's arrays and the reads only.
+ * gasm_batch_fetch_read_map       host copies, valid until the next call or build.  GASM_ERR_STATE before a build or without a mapping
+ *                                 over the last build.
+ * What to do with them (depth, error rate, consensus, variants) is host code: genomeassembler_dev_amd/readmap.py.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAP_MAX_MISMATCH 255
+#define GASM_MAP_MAX_BLOCKS 8
+#define GASM_MAP_FIELDS 7
+int gasm_batch_map_reads(gasm_batch* b, uint32_t max_mismatch);
+int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t** pile, const uint32_t** mismatch_hist,
+                              const uint64_t** counters);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
