@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import genomeassembler_dev_amd as ga
+import handoff_cases as hc
 from genomeassembler_dev_amd import synth
 from oracle import exact_scores as xs
 from oracle import orc
@@ -36,14 +37,7 @@ def _fixed(n_seg, L, rl, cov, seed0, planted=True):
     return dict(reads=reads, seg_off=seg_off, rl=rl)
 
 
-def _fixed_mixed(parts, rl, seed0):
-    """fixed-length reads of segments of different lengths: parts = [(genome length, coverage), ...]"""
-    reads, off = [], [0]
-    for i, (L, cov) in enumerate(parts):
-        r = synth.simulate_reads(synth.make_segment(seed0 + i, L, planted=False), rl, cov, seed0 + 7919 * (i + 1))
-        reads.append(r)
-        off.append(off[-1] + r.shape[0])
-    return dict(reads=np.concatenate(reads, axis=0), seg_off=np.array(off, dtype=np.uint64), rl=rl)
+_fixed_mixed = hc.fixed_mixed          # (fixed-length reads of segments of different lengths: parts = [(genome length, coverage), ...])
 
 
 def _skewed(alphabet, L, rl, cov, seed):
@@ -189,11 +183,8 @@ def _launches_of_one_attempt(p):
 
 
 def _snapshot(b):
-    seg, keys, mult, w = b.distinct()
-    so, off, raw = b.contigs_raw()
-    sc = b.scores()
-    return (seg.tobytes(), keys.tobytes(), mult.tobytes(), w, so.tobytes(), off.tobytes(), raw,
-            *(sc[n].tobytes() for n in ("bp_score", "bp_score_norm_by_break_freqs", "bp_score_norm_by_len", "kmer_breaks", "sequence_len")))
+    """the twelve fields of handoff_cases.FIELDS, arrays as bytes"""
+    return hc.snapshot(b, scores=True)
 
 
 def _check_oracle_and_exact(b, segs, k, sample, keys, prob, tag):
@@ -366,7 +357,7 @@ def test_distinct_batches_interleaved_on_one_context(qtable, monkeypatch):
     and shared by its slots: this exercises that pattern; it cannot force the race the upload once had.)"""
     keys, prob = qtable
     A = _fixed(6, 2000, 50, 15, 200)
-    B = _fixed_mixed([(800, 12)] * 35 + [(12000, 8)] + [(800, 12)] * 34, 60, 210)
+    B = hc.ladder_input()                 # (_fixed_mixed([(800, 12)] * 35 + [(12000, 8)] + [(800, 12)] * 34, 60, 210))
     rng = np.random.default_rng(11)
     g = _strs(synth.make_segment(220, 2500, planted=False)[None, :])[0]
     C = dict(strings=[[g[a:a + int(rng.integers(20, 70))] for a in rng.integers(0, 2430, 300)], [], [g[:40], g[10:35]]])
@@ -399,6 +390,6 @@ def _interleaved_against_alone(prob, keys, A, B, C, ctx, monkeypatch):
             monkeypatch.setenv(n, v)
         mid, end, plans = _interleaved(prob, A, B, C, ctx)
         for name, snap in list(mid.items()) + list(end.items()):
-            assert snap == ref[name], (env, name)
+            hc.assert_same(snap, ref[name], (env, name))            # (equal, or: which of the twelve fields differs first, in which segment)
         assert (plans["A15"]["tile_g"], plans["A21"]["tile_g"]) == (4, 2), env
         assert plans["B10"]["distinct_attempts"] == 2 and plans["B10"]["bucket_bits"] == ref_plan["B10"]["bucket_bits"], env
