@@ -23,6 +23,8 @@ PAIR_FIELDS = ("skipped", "none_placed", "one_placed", "same_contig", "reversed"
 MAP_MAX_MISMATCH = 255     # GASM_MAP_MAX_MISMATCH: the most substitutions map_reads() accepts in a block
 MAP_MAX_BLOCKS = 8         # GASM_MAP_MAX_BLOCKS: distinct heads of a read that map_reads() verifies
 MAP_FIELDS = ("short", "skipped", "unseeded", "rejected", "mapped_one", "mapped_multi", "blocks_dropped")   # GASM_MAP_FIELDS counters, in the header's order
+MAP_MAX_GAP = 16           # GASM_MAP_MAX_GAP: the longest gap map_reads_gapped() joins two heads over
+MAPG_FIELDS = MAP_FIELDS + ("gapped",)   # GASM_MAPG_FIELDS counters, in the header's order
 MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
@@ -163,6 +165,8 @@ SYMBOLS = {
     "gasm_batch_fetch_pair_places": (_int, [_vp, _PP, _PP, _PP, C.POINTER(_u32)]),
     "gasm_batch_map_reads": (_int, [_vp, _u32]),
     "gasm_batch_fetch_read_map": (_int, [_vp, _PP, _PP, _PP, _PP]),
+    "gasm_batch_map_reads_gapped": (_int, [_vp, _u32, _u32]),
+    "gasm_batch_fetch_read_map_gapped": (_int, [_vp, _PP, _PP, _PP, _PP, _PP, _PP]),
     "gasm_batch_fetch_solid_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_kmer_spectrum": (_int, [_vp]),
     "gasm_batch_fetch_kmer_spectrum": (_int, [_vp, _PP]),

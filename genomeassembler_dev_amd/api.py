@@ -472,6 +472,19 @@ def map_reads(reads, k, max_mismatch=4, ctx=None, **build):
         b.close()
 
 
+def map_reads_gapped(reads, k, max_edits=6, max_gap=3, ctx=None, **build):
+    """map_reads for reads with insertions and deletions: heads on neighbouring diagonals, at most max_gap apart, are joined and the
+    read is verified as one alignment of at most max_edits edits: a readmap.GappedReadMap that speaks of segment 0 (ReadMap's methods,
+    and gap_records(0), gap_pileup(0), indels(0); the rule and its limits: include/gasm.h "Gapped read mapping").  build: as for
+    contig_graph."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        return b.build_simplified(int(k), **build).map_reads_gapped(max_edits, max_gap)
+    finally:
+        b.close()
+
+
 def resolve_repeats(reads, k, min_support=2, ctx=None, **build):
     """the contigs of one segment's reads with the repeats shorter than a read put back into their flanks, where the reads that run
     through a repeat say so unambiguously (links.ContigLinks.resolve_repeats: the rule and its limits); a sorted list of str.

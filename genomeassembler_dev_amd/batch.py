@@ -7,11 +7,11 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_MISMATCH, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAPG_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 from .pairs import PairPlaces
-from .readmap import ReadMap
+from .readmap import GappedReadMap, ReadMap
 
 
 def weighted_median_half(mult_sum, n_edges):
@@ -296,6 +296,33 @@ class SegmentBatch:
         strands = self.strands()
         return ReadMap(self.k, strands, max_mismatch, contigs, rec, pile, hist, cnt,
                        [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
+
+    def map_reads_gapped(self, max_edits=6, max_gap=3):
+        """map_reads() for reads that carry insertions and deletions as well (gasm_batch_map_reads_gapped; the rule: include/gasm.h "Gapped
+        read mapping") as a readmap.GappedReadMap: heads of a read on neighbouring diagonals of one contig, at most max_gap apart, are
+        joined into a chain and verified as one alignment of a cost (mismatches + gap lengths) of at most max_edits.  max_edits: 0 ..
+        _lib.MAP_MAX_MISMATCH, max_gap: 0 .. _lib.MAP_MAX_GAP (0: the tables of map_reads(max_edits)).  A pass of its own: what
+        map_reads() returned stays what it was."""
+        if not 0 <= int(max_edits) <= MAP_MAX_MISMATCH:
+            raise ValueError(f"max_edits must be 0..{MAP_MAX_MISMATCH}")
+        if not 0 <= int(max_gap) <= MAP_MAX_GAP:
+            raise ValueError(f"max_gap must be 0..{MAP_MAX_GAP}")
+        max_edits, max_gap = int(max_edits), int(max_gap)
+        check(lib().gasm_batch_map_reads_gapped(self.h, max_edits, max_gap))
+        ps = [C.c_void_p() for _ in range(6)]
+        check(lib().gasm_batch_fetch_read_map_gapped(self.h, *[C.byref(p) for p in ps]))
+
+        def arr(p, ct, n):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
+        seg, o, raw = self.contigs_raw()
+        contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+        total = int(o[-1]) if int(seg[-1]) else 0
+        rec, gap = arr(ps[0], C.c_int32, 4 * self.n_reads), arr(ps[1], C.c_int32, 4 * self.n_reads)
+        pile, gpile = arr(ps[2], C.c_uint32, 4 * total), arr(ps[3], C.c_uint32, 2 * total)
+        hist, cnt = arr(ps[4], C.c_uint32, self.n_segments * (max_edits + 1)), arr(ps[5], C.c_uint64, self.n_segments * len(MAPG_FIELDS))
+        strands = self.strands()
+        return GappedReadMap(self.k, strands, max_edits, max_gap, contigs, rec, gap, pile, gpile, hist, cnt,
+                             [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
 
     def suggest_cov_cutoff(self, segment):
         """a cov_cutoff for build_simplified() from the last build's own contigs of `segment`: half the length-weighted median of the

@@ -1041,6 +1041,30 @@ int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t
     API_GUARD_END
 }
 
+int gasm_batch_map_reads_gapped(gasm_batch* b, uint32_t max_edits, uint32_t max_gap) {
+    API_GUARD_BEGIN
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (max_edits > GASM_MAP_MAX_MISMATCH) { gasm_set_error("max_edits must be <= %d (got %u)", GASM_MAP_MAX_MISMATCH, max_edits); return GASM_ERR_INVALID; }
+    if (max_gap > GASM_MAP_MAX_GAP) { gasm_set_error("max_gap must be <= %d (got %u)", GASM_MAP_MAX_GAP, max_gap); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_map_reads_gapped before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_finish(b));
+    return pipeline_map_reads_gapped(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, max_edits, max_gap);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const int32_t** rec_gap, const uint32_t** pile, const uint32_t** gap_pile,
+                                     const uint32_t** edit_hist, const uint64_t** counters) {
+    API_GUARD_BEGIN
+    if (!b || !rec || !rec_gap || !pile || !gap_pile || !edit_hist || !counters) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("gasm_batch_fetch_read_map_gapped before a build"); return GASM_ERR_STATE; }
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_read_map_gapped(b->S().cx, b->rd, bs));
+    *rec = bs.h_mapg_rec.data(); *rec_gap = bs.h_mapg_gap.data(); *pile = bs.h_mapg_pile.data(); *gap_pile = bs.h_mapg_gpile.data();
+    *edit_hist = bs.h_mapg_hist.data(); *counters = bs.h_mapg_counters.data();
+    return GASM_OK;
+    API_GUARD_END
+}
+
 int gasm_batch_fetch_contig_twins(gasm_batch* b, const uint32_t** twin) {
     API_GUARD_BEGIN
     if (!b || !twin) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }

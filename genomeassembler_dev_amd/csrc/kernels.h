@@ -313,6 +313,16 @@ template <class K>
 __global__ void k_read_map(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph,
                            u32 max_mismatch, u32 reads_per_wg, u32 chunks, int32_t* rec, u32* pile, u32* hist, unsigned long long* counters);
 
+// ---- kernels_mapgap.hip: gapped read mapping (include/gasm.h, "Gapped read mapping"): rec, rec_gap: 4 int32 per read each (16-byte aligned);
+// text: the contigs' ASCII; pile: 4 u32 per base of it, gap_pile: 2 u32 per base of it (deletions, insertions), hist: max_edits + 1 bins per
+// segment, counters: GASM_MAPG_COUNTERS per segment, the four zeroed by the caller
+#define GASM_MAPG_COUNTERS 8          // = GASM_MAPG_FIELDS of include/gasm.h (checked in pipeline.hip)
+#define GASM_MAPG_GAP 16              // = GASM_MAP_MAX_GAP: the longest gap between two heads of a chain (its skipped bases take one lane each)
+template <class K>
+__global__ void k_read_map_gapped(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph,
+                                  u32 max_edits, u32 max_gap, u32 reads_per_wg, u32 chunks, int32_t* rec, int32_t* rec_gap, u32* pile, u32* gap_pile, u32* hist,
+                                  unsigned long long* counters);
+
 // ---- kernels_score.hip
 struct SeedTable {
     u64* seed;            // slot -> seed value

@@ -181,6 +181,14 @@ struct BuildState {
     std::vector<u64> h_map_counters;
     u32 map_max_mismatch = 0;               // of the last mapping
     bool map_queued = false;                // k_read_map ran on the arrays of this build
+    DBuf d_mapg;                            // gapped read mapping of the last build (pipeline_map_reads_gapped): int32 rec[4 * reads], rec_gap[4 * reads],
+                                            // then u32 pile[4 * contig bases], gap_pile[2 * contig bases], edit_hist[S * (max_edits + 1)] (padded to
+                                            // 8 bytes), then u64 counters[S * GASM_MAPG_FIELDS]
+    std::vector<int32_t> h_mapg_rec, h_mapg_gap;
+    std::vector<u32> h_mapg_pile, h_mapg_gpile, h_mapg_hist;
+    std::vector<u64> h_mapg_counters;
+    u32 mapg_max_edits = 0;                 // of the last gapped mapping
+    bool mapg_queued = false;               // k_read_map_gapped ran on the arrays of this build
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -287,6 +295,12 @@ int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // (4 per read), h_map_pile (4 per contig base), h_map_hist (max_mismatch + 1 per segment) and h_map_counters (GASM_MAP_FIELDS per segment)
 int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_mismatch);
 int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// Gapped read mapping (k_read_map_gapped in kernels_mapgap.hip; the rule: include/gasm.h "Gapped read mapping") of the finished build, beside
+// pipeline_map_reads and independent of it (an array, host vectors and a flag of its own): then fetch h_mapg_rec and h_mapg_gap (4 per read
+// each), h_mapg_pile (4 per contig base), h_mapg_gpile (2 per contig base), h_mapg_hist (max_edits + 1 per segment) and h_mapg_counters
+// (GASM_MAPG_FIELDS per segment)
+int pipeline_map_reads_gapped(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_edits, u32 max_gap);
+int pipeline_fetch_read_map_gapped(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

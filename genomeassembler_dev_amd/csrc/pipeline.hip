@@ -461,7 +461,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_ccov, &d_links, &d_pairs, &d_map, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_ccov, &d_links, &d_pairs, &d_map, &d_mapg, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -930,6 +930,7 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, const BuildOpts&
     bs.links_queued = false;
     bs.pairs_queued = false;
     bs.map_queued = false;
+    bs.mapg_queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -1316,6 +1317,78 @@ int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
     if (S) {
         HIPCHK(hipMemcpyAsync(bs.h_map_hist.data(), d + t.hist_off, t.hist_words * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(bs.h_map_counters.data(), d + t.cnt_off, (size_t)S * GASM_MAP_FIELDS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GASM_OK;
+}
+
+static_assert(GASM_MAPG_COUNTERS == GASM_MAPG_FIELDS && GASM_MAPG_GAP == GASM_MAP_MAX_GAP, "kernels.h and gasm.h disagree on gapped read mapping");
+
+// where the six tables of a gapped mapping lie in d_mapg
+struct MapGapTables {
+    size_t rec_words, pile_words, gpile_words, hist_words, gap_off, pile_off, gpile_off, hist_off, cnt_off, bytes;
+    MapGapTables(u64 n_reads, u64 contig_bases, u32 S, u32 max_edits) {
+        rec_words = (size_t)n_reads * 4;
+        pile_words = (size_t)contig_bases * 4;
+        gpile_words = (size_t)contig_bases * 2;
+        hist_words = (size_t)S * ((size_t)max_edits + 1);
+        gap_off = rec_words * 4;                                            // (multiples of 16: both records are stored 16 bytes at a time)
+        pile_off = 2 * gap_off;
+        gpile_off = pile_off + pile_words * 4;
+        hist_off = gpile_off + gpile_words * 4;
+        cnt_off = (hist_off + hist_words * 4 + 7) & ~(size_t)7;
+        bytes = cnt_off + (size_t)S * GASM_MAPG_FIELDS * 8;
+    }
+};
+
+// gapped read mapping: on the stream of the build, behind it; reads what pipeline_map_reads reads, writes an array of its own (records, gap
+// records, pileup, gap pileup, edit histogram, counters)
+int pipeline_map_reads_gapped(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_edits, u32 max_gap) {
+    if (rd.positioned) { gasm_set_error("read mapping needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
+    GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
+    HIPCHK(hipSetDevice(ctx->device));
+    const u32 S = rd.n_segments, P = bs.n_contigs;
+    const MapGapTables t(rd.n_reads, P ? bs.contig_bases : 0, S, max_edits);
+    GCHK(bs.d_mapg.ensure(t.bytes));
+    u8* const d = bs.d_mapg.as<u8>();
+    HIPCHK(hipMemsetAsync(d + t.pile_off, 0, t.bytes - t.pile_off, ctx->stream));
+    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
+    if (rd.n_reads && S) {
+        u64 most = 1;
+        for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
+        // the grid of pipeline_map_reads: a wave per read, GASM_WG / 64 reads per workgroup and round
+        const u32 reads_per_wg = GASM_WG / 64;
+        const u32 groups = (S + 7u) / 8u;
+        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
+        GLAUNCH_K(ctx, bs.words, "k_read_map_gapped", k_read_map_gapped<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), bs.d_link.as<u64>(),
+                  bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), have_graph, max_edits, max_gap, reads_per_wg,
+                  chunks, reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + t.gap_off), reinterpret_cast<u32*>(d + t.pile_off),
+                  reinterpret_cast<u32*>(d + t.gpile_off), reinterpret_cast<u32*>(d + t.hist_off), reinterpret_cast<unsigned long long*>(d + t.cnt_off));
+    }
+    bs.mapg_max_edits = max_edits;
+    bs.mapg_queued = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_read_map_gapped(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    if (!bs.mapg_queued) { gasm_set_error("gasm_batch_fetch_read_map_gapped before gasm_batch_map_reads_gapped (of the last build)"); return GASM_ERR_STATE; }
+    const u32 S = rd.n_segments;
+    const MapGapTables t(rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, S, bs.mapg_max_edits);
+    bs.h_mapg_rec.assign(t.rec_words + 1, 0); bs.h_mapg_gap.assign(t.rec_words + 1, 0);         // (one entry more: a pointer to hand out for
+    bs.h_mapg_pile.assign(t.pile_words + 1, 0); bs.h_mapg_gpile.assign(t.gpile_words + 1, 0);   // no read, contig or segment at all)
+    bs.h_mapg_hist.assign(t.hist_words + 1, 0); bs.h_mapg_counters.assign((size_t)S * GASM_MAPG_FIELDS + 1, 0);
+    const u8* const d = bs.d_mapg.as<u8>();
+    if (t.rec_words) {
+        HIPCHK(hipMemcpyAsync(bs.h_mapg_rec.data(), d, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_mapg_gap.data(), d + t.gap_off, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (t.pile_words) {
+        HIPCHK(hipMemcpyAsync(bs.h_mapg_pile.data(), d + t.pile_off, t.pile_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_mapg_gpile.data(), d + t.gpile_off, t.gpile_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (S) {
+        HIPCHK(hipMemcpyAsync(bs.h_mapg_hist.data(), d + t.hist_off, t.hist_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bs.h_mapg_counters.data(), d + t.cnt_off, (size_t)S * GASM_MAPG_FIELDS * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return GASM_OK;

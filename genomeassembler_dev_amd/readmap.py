@@ -3,7 +3,7 @@ base the four base counts of the reads laid over it, per segment a mismatch hist
 include/gasm.h "Read mapping") — and the host arithmetic on top: depth, mapped fraction, error rate, consensus, variants."""
 import numpy as np
 
-from ._lib import MAP_FIELDS
+from ._lib import MAP_FIELDS, MAPG_FIELDS
 
 RECORD = np.dtype([("contig", np.int32), ("diagonal", np.int32), ("mismatches", np.int32), ("blocks", np.int32), ("overlap", np.int32)])
 _BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -114,3 +114,86 @@ class ReadMap:
             for i in np.nonzero((dp >= int(min_depth)) & (n > 0) & (n >= float(min_frac) * dp))[0]:
                 out.append((c, int(i), s[i], "ACGT"[int(top[i])], int(n[i]), int(dp[i])))
         return sorted(out)
+
+
+class GappedReadMap(ReadMap):
+    """what SegmentBatch.map_reads_gapped() returns (the rule and its limits: include/gasm.h "Gapped read mapping"): ReadMap's tables
+    over chains — the records' third column is the chain's cost (mismatches + gap lengths), the fourth the accepted chains, the
+    histogram is over costs — and beside them per read the gap record of its best chain, per contig base the deletions that skip it and
+    the insertions in front of it, and an eighth counter, gapped."""
+
+    def __init__(self, k, strands, max_edits, max_gap, contigs, rec, rec_gap, pile, gap_pile, edit_hist, counters, twins=None, seg_read_off=None):
+        """as ReadMap, with rec_gap: 4 int32 per read of the batch (pieces, inserted bases, deleted bases, last diagonal); gap_pile: 2
+        uint32 per contig base (deletions, insertions); counters: len(MAPG_FIELDS) per segment"""
+        self._cnt8 = np.asarray(counters, dtype=np.uint64).reshape(len(contigs), len(MAPG_FIELDS))
+        super().__init__(k, strands, max_edits, contigs, rec, pile, edit_hist, self._cnt8[:, :len(MAP_FIELDS)], twins, seg_read_off)
+        self.max_edits, self.max_gap = int(max_edits), int(max_gap)
+        self._gap = np.asarray(rec_gap, dtype=np.int32).reshape(-1, 4)
+        self._gpile = np.asarray(gap_pile, dtype=np.uint32).reshape(-1, 2)
+        if len(self._gap) != len(self._rec) or len(self._gpile) != len(self._pile):
+            raise ValueError("the gap tables do not fit the records and the pileup")
+
+    def counters(self, segment, as_dict=False):
+        c = self._cnt8[self._seg(segment)].copy()
+        return {name: int(v) for name, v in zip(MAPG_FIELDS, c)} if as_dict else c
+
+    def edit_hist(self, segment):
+        return self.mismatch_hist(segment)
+
+    def gap_records(self, segment):
+        """(reads, 4) int32: pieces, inserted bases, deleted bases and last diagonal of every read's best chain; zeros for a read with
+        no place"""
+        s = self._seg(segment)
+        return self._gap[int(self._read_off[s]):int(self._read_off[s + 1])].copy()
+
+    def gap_pileup(self, segment, fold_twins=False):
+        """one (len(c), 2) uint32 array per contig: the accepted chains whose deletion skips the base, and those with an insertion in
+        front of it.  fold_twins (after a strands = 2 build): the twin's deletions of base len - 1 - p and its insertions in front of
+        base len - p (the same place seen from the other strand) are added"""
+        s = self._seg(segment)
+        c0 = int(self._seg_c[s])
+        own = [self._gpile[int(self._base_off[c0 + c]):int(self._base_off[c0 + c + 1])].copy() for c in range(len(self._contigs[s]))]
+        if not fold_twins:
+            return own
+        if self._twins is None:
+            raise ValueError("fold_twins needs a strands = 2 build")
+        out = []
+        for c in range(len(own)):
+            t = own[int(self._twins[s][c])]
+            f = own[c].copy()
+            f[:, 0] += t[::-1, 0]
+            f[1:, 1] += t[:0:-1, 1]
+            out.append(f)
+        return out
+
+    def depth(self, segment, fold_twins=False):
+        """one uint32 array per contig: the reads laid over every base, those whose deletion skips it included"""
+        return [p.sum(axis=1, dtype=np.uint32) + g[:, 0] for p, g in zip(self.pileup(segment, fold_twins), self.gap_pileup(segment, fold_twins))]
+
+    def error_rate(self, segment):
+        """cost / (overlap + inserted bases) over the reads' best chains; 0.0 if nothing is mapped"""
+        r, g = self.records(segment), self.gap_records(segment)
+        keep = r[:, 0] >= 0
+        n = int(r[keep, 4].sum()) + int(g[keep, 1].sum())
+        return int(r[keep, 2].sum()) / n if n else 0.0
+
+    def indels(self, segment, min_depth=8, min_frac=0.2, fold_twins=False):
+        """sorted [(contig, position, 'D' | 'I', count, depth)] for every position of a depth of at least min_depth at which the
+        deletions of the base ('D') or the insertions in front of it ('I') have a count > 0 that reaches min_frac of the depth"""
+        out = []
+        for c, (g, dp) in enumerate(zip(self.gap_pileup(segment, fold_twins), self.depth(segment, fold_twins))):
+            for x, kind in ((0, "D"), (1, "I")):
+                n = g[:, x].astype(np.int64)
+                for i in np.nonzero((dp >= int(min_depth)) & (n > 0) & (n >= float(min_frac) * dp))[0]:
+                    out.append((c, int(i), kind, int(n[i]), int(dp[i])))
+        return sorted(out)
+
+    def consensus(self, segment, min_depth=3, fold_twins=False):
+        """ReadMap.consensus, and in addition every base is dropped where deletions hold a strict majority of a depth of at least
+        min_depth.  Insertions are listed (indels()), not applied: their bases are not recorded"""
+        out = []
+        for s, g, dp in zip(super().consensus(segment, min_depth, fold_twins), self.gap_pileup(segment, fold_twins), self.depth(segment, fold_twins)):
+            t = np.frombuffer(s.encode(), dtype=np.uint8)
+            keep = ~((dp >= int(min_depth)) & (2 * g[:, 0].astype(np.int64) > dp)) if len(t) else np.zeros(0, bool)
+            out.append(t[keep].tobytes().decode())
+        return out

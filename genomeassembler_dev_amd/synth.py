@@ -78,6 +78,33 @@ def simulate_reads(genome, read_len, coverage, seed, weights=None):
     return genome[idx]
 
 
+def simulate_reads_indel(genome, read_len, coverage, seed, sub_rate, indel_rate):
+    """(n_reads, read_len) uint8 array of reads with substitutions, insertions and deletions; starts uniform.  Every read is written
+    by read_len + 32 steps along the genome, each of which is, with probability indel_rate, an insertion (a random base, the genome
+    does not advance) or a deletion (the genome base is skipped) with equal chances, and else copies the genome base, changed with
+    probability sub_rate to one of the three others; the first read_len bases written are the read.  A start too close to the
+    genome's end for all steps, or (next to never) a read with fewer than read_len bases written, is left out."""
+    L, M = genome.size, read_len + 32
+    rng = np.random.Generator(np.random.MT19937(seed))
+    n = int(np.ceil(coverage * L / read_len))
+    starts = rng.integers(0, L, size=n)
+    starts = starts[starts + M <= L]
+    u = rng.random((starts.size, M))
+    ins, dele = u < indel_rate / 2, (u >= indel_rate / 2) & (u < indel_rate)
+    sub = ~ins & ~dele & (rng.random((starts.size, M)) < sub_rate)
+    shift = rng.integers(1, 4, size=(starts.size, M))
+    rand = rng.integers(0, 4, size=(starts.size, M))
+    gpos = starts[:, None] + np.cumsum(~ins, axis=1) - (~ins)                # the genome base of every step
+    code = np.searchsorted(_ACGT, genome[np.minimum(gpos, L - 1)])
+    code = np.where(ins, rand, np.where(sub, (code + shift) % 4, code))
+    opos = np.cumsum(~dele, axis=1) - (~dele)                                # where a step that writes a base writes it
+    keep = (~dele).sum(axis=1) >= read_len
+    out = np.zeros((starts.size, read_len), dtype=np.uint8)
+    rows, cols = np.nonzero(~dele & (opos < read_len))
+    out[rows, opos[rows, cols]] = _ACGT[code[rows, cols]]
+    return out[keep]
+
+
 def make_batch(n_segments, seg_len, read_len, coverage, seed0=1234, planted=True):
     """reads of n_segments segments as one (total_reads, read_len) uint8 array + seg_read_off + the genomes"""
     reads, off, genomes = [], [0], []

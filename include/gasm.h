@@ -700,8 +700,9 @@ int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint3
  *       The first six sum to the segment's reads; mismatch_hist sums to the accepted blocks, pile to their overlaps.
  *   STRANDS.  After a strands = 2 build the reads are still mapped as given: a read lies on whichever contig of a twin pair has its
  *   orientation.  Folding the twin's pileup in is host arithmetic.
- *   LIMITS.  Insertions and deletions are not mapped.  Two placements of one read on the same contig at different diagonals are both
- *   counted.  The cap of GASM_MAP_MAX_BLOCKS heads.  A read whose every k-mer holds an error is unseeded.
+ *   LIMITS.  Insertions and deletions are not mapped (by this pass: see "Gapped read mapping" below).  Two placements of one read on
+ *   the same contig at different diagonals are both counted.  The cap of GASM_MAP_MAX_BLOCKS heads.  A read whose every k-mer holds
+ *   an error is unseeded.
  * gasm_batch_map_reads            finishes the pending build and queues k_read_map on the step slot of the last build, behind it;
  *                                 GASM_ERR_STATE before a build and for the positioned reads of pooled builds, GASM_ERR_INVALID for a
  *                                 null batch or max_mismatch > GASM_MAP_MAX_MISMATCH.  It reads the build's arrays and the reads only.
@@ -715,6 +716,68 @@ int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint3
 int gasm_batch_map_reads(gasm_batch* b, uint32_t max_mismatch);
 int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t** pile, const uint32_t** mismatch_hist,
                               const uint64_t** counters);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Gapped read mapping: read mapping for reads that carry insertions and deletions as well.  (A one-base indel in the middle of a read
+ * moves every later seed to the next diagonal: read mapping sees two heads on one contig, verifies each against the whole read, finds
+ * about three quarters of the far side differing and rejects the read.)  The two heads say where the gap is: this pass joins them.
+ * A second pass beside read mapping, with tables of its own; gasm_batch_map_reads is untouched and with max_gap = 0 this pass gives its
+ * tables.
+ * The rule.  INPUTS.  As for read mapping, plus max_edits in 0..GASM_MAP_MAX_MISMATCH and max_gap in 0..GASM_MAP_MAX_GAP.
+ *   PER READ of len bases:
+ *   1-3. UNCHANGED.  Short, skipped, seeds, diagonals and the kept heads of a read are exactly those of read mapping.  Head i is
+ *      (J_i, c_i, d_i), J_i the seed position at which the head starts; at most GASM_MAP_MAX_BLOCKS heads are kept, in walk order; the
+ *      A, B, A rule and blocks_dropped apply as before.
+ *   4. CHAINS.  The kept heads are walked in order; the first opens a chain.  Head i + 1 JOINS the chain that head i closed when all
+ *      three hold: c_{i+1} = c_i; g = d_{i+1} - d_i satisfies 0 < |g| <= max_gap; and, for g < 0 (an insertion of G = -g read bases),
+ *      J_{i+1} - G >= J_i + 1.  Otherwise head i + 1 opens a new chain.  Only consecutive kept heads join.
+ *   5. BREAKPOINTS.  Between joined heads i and i + 1 there is one breakpoint t_i.  G = -g for an insertion, G = 0 for a deletion.
+ *      The window of t is [J_i + 1, J_{i+1} - G].  t_i is the smallest t in the window that minimises the sum of two counts: the
+ *      positions x in [J_i + 1, t) where read[x] != c[d_i + x], and the positions x in [t + G, J_{i+1}) where read[x] != c[d_{i+1} + x].
+ *      The windows of successive breakpoints are disjoint and increasing, and the bases a piece holds outside them do not depend on any
+ *      t (read bases J_i .. J_i + k - 1 match): each t_i is chosen on its own and together they are the joint optimum.
+ *   6. PIECES.  Piece 1 starts at s_1 = max(0, -d_1).  Piece i is read bases [s_i, t_i) on diagonal d_i; s_{i+1} = t_i + G; the last
+ *      piece ends at min(len, len(c) - d_q), q = the chain's heads.  For an insertion read bases [t_i, t_i + G) lie on nothing; for a
+ *      deletion contig bases [d_i + t_i, d_i + t_i + g) are skipped.  Every piece is non-empty and inside the contig: s_i <= J_i <
+ *      t_i (s_1 <= J_1 because k-mer J_1 lies at d_1 + J_1 >= 0; s_{i+1} = t_i + G <= J_{i+1} by the window), the last piece holds k-mer
+ *      J_q; and a base x of [J_i + 1, J_{i+1}) lies inside c on both diagonals: d_i + x > d_i + J_i >= 0, d_{i+1} + x < d_{i+1} + J_{i+1}
+ *      < len(c), and on the other side d_i + x = d_{i+1} + x - g, where for a deletion (g > 0) the upper bound and for an insertion
+ *      (x < J_{i+1} - G on the left, x >= J_i + 1 + G on the right) both bounds follow from the two just given.
+ *   7. COST AND ACCEPTANCE.  COST = mismatches over all pieces + the sum of |g|; OVERLAP = the sum of the piece lengths.  A chain is
+ *      ACCEPTED iff cost <= max_edits.  A chain of one head is exactly step 4 of read mapping.  A chain of two or more heads is
+ *      verified only as a chain: its heads are not tried alone.
+ *   8. Every accepted chain adds 1 to pile[4 * (c_off[c] + d_i + x) + base(read[x])] for every base x of every piece i, 1 to
+ *      gap_pile[2 p + 0] for every skipped contig base p, 1 to gap_pile[2 p + 1] at p = c_off[c] + d_i + t_i, the contig base that
+ *      the first read base behind an insertion sits on (this counts insertions, not inserted bases), and 1 to edit_hist[cost].
+ *   9. The read's record is that of its BEST accepted chain: largest overlap, then lowest cost, then smallest J_1.  Classes as
+ *      before, over chains: rejected, mapped_one, mapped_multi.
+ *   OUTPUTS, all exact integers, accumulated with integer atomics where shared: independent of the order the reads are taken in.
+ *     rec[4 r + 0..3] = c, d_1, cost | accepted chains << 16, overlap as int32; -1, 0, 0, 0 for a read with no place.
+ *     rec_gap[4 r + 0..3] = pieces q, inserted bases, deleted bases, d_q of the best chain; all zero for a read with no place.
+ *     pile: 4 uint32 per contig base; gap_pile: 2 uint32 (deletions, insertions) per contig base; both in the order of
+ *       gasm_batch_fetch_contigs.
+ *     edit_hist[s * (max_edits + 1) + cost] counts the accepted chains of segment s.
+ *     counters[s * GASM_MAPG_FIELDS + f]: the seven of read mapping in their order, then gapped: the reads whose best chain has
+ *       q >= 2.  The first six sum to the segment's reads.
+ *   STRANDS.  As for read mapping: the reads are mapped as given.
+ *   LIMITS.  An indel closer than k to an end of the read leaves no seed beyond it: that end is compared ungapped, and usually the
+ *   read is rejected (of simulated 80-base reads with an indel about 45 % stay unplaced for this reason at k = 21, of 150-base reads
+ *   about a third).  A spurious head between two heads of a chain cuts the chain.  A read that returns to an earlier diagonal is not
+ *   chained through, because of A, B, A.  The sequence of inserted bases is not recorded.  A gap longer than max_gap is not joined.
+ *   Gaps cost their length: no affine score.  Pooled builds (gasm_pool_*) get none of this.
+ * gasm_batch_map_reads_gapped        finishes the pending build and queues k_read_map_gapped on the step slot of the last build, behind
+ *                                    it; GASM_ERR_STATE before a build and for the positioned reads of pooled builds, GASM_ERR_INVALID
+ *                                    for a null batch, max_edits > GASM_MAP_MAX_MISMATCH or max_gap > GASM_MAP_MAX_GAP.  It reads the
+ *                                    build's arrays and the reads only; a gasm_batch_map_reads over the same build stays fetchable, and
+ *                                    the other way round; a batch that never calls it launches exactly what it launched without.
+ * gasm_batch_fetch_read_map_gapped   host copies, valid until the next call or build.  GASM_ERR_STATE before a build or without a
+ *                                    gapped mapping over the last build.
+ * What to do with them (depth, error rate, consensus, indels) is host code: genomeassembler_dev_amd/readmap.py, GappedReadMap.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAP_MAX_GAP 16
+#define GASM_MAPG_FIELDS 8
+int gasm_batch_map_reads_gapped(gasm_batch* b, uint32_t max_edits, uint32_t max_gap);
+int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const int32_t** rec_gap, const uint32_t** pile,
+                                     const uint32_t** gap_pile, const uint32_t** edit_hist, const uint64_t** counters);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
