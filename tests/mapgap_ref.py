@@ -6,8 +6,10 @@ shares no code with genomeassembler_dev_amd/readmap.py or the library; the heads
         records[r] = [c, d_1, cost, chains, overlap] ([-1, 0, 0, 0, 0] for a read with no place); gap_records[r] = [q, inserted,
         deleted, d_q] (zeros for a read with no place); pile[c][p] = [A, C, G, T]; gap_pile[c][p] = [deletions, insertions];
         edit_hist: max_edits + 1 bins; counters: eight, in the order of FIELDS
-    chains_of / breakpoint / pieces_of: the rule's steps 4, 5 and 6, one function each
-and the hand-built cases and the generators the host and the GPU tests share.
+    chains_of / breakpoint / pieces_of: the rule's steps 4, 5 and 6, one function each; breakpoint_linear: step 5 in one pass, which
+        pieces_of takes for a window of more than LINEAR_FROM positions
+and the hand-built cases, the generators and the edge cases (long_read_case, ragged_case, tie_case, contig_ends_case, slot_case) the host
+and the GPU tests share.
 """
 import random
 
@@ -45,10 +47,36 @@ def breakpoint(read, contig, a, b):
     return best
 
 
+def breakpoint_linear(read, contig, a, b):
+    """breakpoint() in one pass over the window instead of one per t: the left diagonal's mismatches as prefix counts from J_a + 1 on,
+    the right diagonal's as suffix counts back from J_b, and the smallest t among equal minima.  breakpoint() stays the definition;
+    tests/test_mapgap_host.py holds the two equal"""
+    G = max(0, a[2] - b[2])
+    lo, hi = a[0] + 1, b[0] - G
+    if hi < lo:
+        return None
+    left = [0] * (hi - lo + 1)                                      # left[t - lo]: mismatches on a's diagonal in [lo, t)
+    for t in range(lo + 1, hi + 1):
+        left[t - lo] = left[t - lo - 1] + (read[t - 1] != contig[a[2] + t - 1])
+    right = [0] * (hi - lo + 1)                                     # right[t - lo]: mismatches on b's diagonal in [t + G, J_b)
+    for t in range(hi - 1, lo - 1, -1):
+        right[t - lo] = right[t - lo + 1] + (read[t + G] != contig[b[2] + t + G])
+    m = min(x + y for x, y in zip(left, right))
+    return next((lo + i, m) for i, (x, y) in enumerate(zip(left, right)) if x + y == m)
+
+
+LINEAR_FROM = 256       # pieces_of takes a window wider than this with breakpoint_linear (breakpoint() is quadratic in the window)
+
+
+def window_of(a, b):
+    """(first t, last t) of the join of heads a and b"""
+    return a[0] + 1, b[0] - max(0, a[2] - b[2])
+
+
 def pieces_of(read, contig, chain, cuts=None):
     """step 6: [(s, e, d)]: read bases [s, e) on diagonal d, one per head; cuts: the breakpoints (None: the rule's own)"""
     if cuts is None:
-        cuts = [breakpoint(read, contig, a, b)[0] for a, b in zip(chain, chain[1:])]
+        cuts = [(breakpoint_linear if b[0] - a[0] > LINEAR_FROM else breakpoint)(read, contig, a, b)[0] for a, b in zip(chain, chain[1:])]
     out, s = [], max(0, -chain[0][2])
     for i, (J, c, d) in enumerate(chain):
         e = cuts[i] if i + 1 < len(chain) else min(len(read), len(contig) - d)
@@ -224,6 +252,20 @@ def planted_indel_read(genome, start, read_len, at, g, rnd):
     return (genome[start:start + at] + ins + genome[start + at:])[:read_len]
 
 
+def multi_indel_read(genome, start, read_len, indels, rnd):
+    """planted_indel_read for several indels [(at, g)] at increasing read positions `at`: the read starts at genome[start]; at read
+    position `at` g > 0 skips g genome bases and g < 0 inserts -g bases (chosen as planted_indel_read chooses them)"""
+    read, pos = "", start
+    for at, g in indels:
+        assert at > len(read), "increasing read positions, each behind the bases the indel before it inserted"
+        pos, read = pos + at - len(read), read + genome[pos:pos + at - len(read)]
+        if g > 0:
+            pos += g
+        for _ in range(-g):
+            read += rnd.choice([x for x in "ACGT" if x not in (genome[pos - 1], genome[pos], read[-1:] if len(read) > at else "")])
+    return (read + genome[pos:])[:read_len]
+
+
 def indel_reads(genome_len, read_len, coverage, seed, sub_rate=0.01, indel_rate=0.003):
     from genomeassembler_dev_amd import synth
     g = synth.make_segment(seed, genome_len, planted=False)
@@ -266,3 +308,148 @@ def indel_variant_case():
 _TIE = R5[:8] + R5[9:14] + "C" + R5[15:]
 HAND.append((6, [R5], _TIE, 2, 1, [0, 0, 2, 1, 23], [2, 0, 1, 1], "mapped_one", [(0, 0, R5[0:8]), (0, 9, _TIE[8:23])], [(0, 8, "D")]))
 HAND_HEADS[_TIE] = [(0, 0, 0), (14, 0, 1)]
+
+
+# ---- the edge cases of tests/test_mapgap_edges_gpu.py; their CPU preconditions (the genome as its own contig) are tests/test_mapgap_host.py's
+def clean_reads(g, read_len, coverage, seed):
+    from genomeassembler_dev_amd import synth
+    return [r.tobytes().decode() for r in synth.simulate_reads(g, read_len, coverage, seed)]
+
+
+def strides(a, b):
+    """how often the kernel's breakpoint loop goes round for the join of heads a and b: 64 positions of the window a time"""
+    lo, hi = window_of(a, b)
+    return (hi - lo) // 64 + 1
+
+
+# A chain of q heads needs q pairwise different diagonals (step 3 ignores a head that returns to a kept one): these gaps give the
+# cumulative diagonals 1, 3, 2, 5, 4, 7, 8
+CHAIN_GAPS = (1, 2, -1, 3, -1, 3, 1)
+CHAIN_INDELS = [(150 * (i + 1), g) for i, g in enumerate(CHAIN_GAPS)]
+CHAIN_START, NINTH_START, FAR_START = 100, 2000, 3500
+
+
+def long_read_case(k, seed=123):
+    """(g, genome, planted, clean): a 6 kb genome (array and string), the planted reads {name: (read, start, the gaps a chain over all
+    kept heads joins)} and error-free 150-base reads at 30x.
+        one_del2 / one_ins2 / one_del16: 400 bases, one indel at 200 / 257 / 321: windows of 4, 5 and 6 strides
+        ins16: 300 bases, 16 bases inserted at 120
+        eight: 1200 bases, seven indels 150 bases apart: a chain of eight heads
+        ninth: the same and a deletion k + 9 bases in front of the end: a ninth head, dropped; the chain's last piece runs to the read's
+            end on the eighth head's diagonal, one base off
+        ninth_far: 1500 bases, the eighth indel 300 bases in front of the end: the same with a cost near the limit of 255 (the tail is
+            shortened ten bases a time while the cost on the genome exceeds 255)"""
+    from genomeassembler_dev_amd import synth
+    g = synth.make_segment(seed, 6000, planted=False)
+    genome = g.tobytes().decode()
+    rnd = random.Random(seed)
+    planted = {}
+    for name, n, at, gap in (("one_del2", 400, 200, 2), ("one_ins2", 400, 257, -2), ("one_del16", 400, 321, 16), ("ins16", 300, 120, -16)):
+        start = rnd.randrange(200, 5000)
+        planted[name] = (planted_indel_read(genome, start, n, at, gap, rnd), start, [gap])
+    planted["eight"] = (multi_indel_read(genome, CHAIN_START, 1200, CHAIN_INDELS, rnd), CHAIN_START, list(CHAIN_GAPS))
+    # (a start of its own each: two reads with the same deletion would put its k-mers into a min_count = 2 build)
+    planted["ninth"] = (multi_indel_read(genome, NINTH_START, 1200, CHAIN_INDELS + [(1200 - (k + 9), 1)], rnd), NINTH_START, list(CHAIN_GAPS))
+    far = multi_indel_read(genome, FAR_START, 1500, CHAIN_INDELS + [(1200, 1)], rnd)
+    while place_gapped([genome], [far], k, MAX_MISMATCH, 3)["records"][0][0] < 0:
+        far = far[:-10]
+    planted["ninth_far"] = (far, FAR_START, list(CHAIN_GAPS))
+    return g, genome, planted, clean_reads(g, 150, 30, 7)
+
+
+def one_read(contigs, read, k, max_edits, max_gap):
+    """(record, gap record) of one read alone"""
+    t = place_gapped(contigs, [read], k, max_edits, max_gap)
+    return t["records"][0], t["gap_records"][0]
+
+
+RAGGED_K = 21
+
+
+def ragged_case(seed=47):
+    """(g, genome, segs, long): the segments [[], reads, short, reads[:10], junk, []] on a 6 kb genome.  reads: ten error-free 150-base
+    reads first, then the ragged ones (`long`: name -> index in reads): a read shorter than k, an empty read, a read of exactly 4096
+    k-mers without three genome bases at its position 4000 (a window of 63 strides; t reaches 4000), one of 4096 k-mers with two bases
+    inserted at 4050, one of 4097 k-mers with the deletion (skipped); then error-free reads at 30x.  junk: 20 random reads of 100 bases"""
+    from genomeassembler_dev_amd import synth
+    k = RAGGED_K
+    g = synth.make_segment(seed, 6000, planted=False)
+    genome = g.tobytes().decode()
+    rnd = random.Random(seed)
+    clean = clean_reads(g, 150, 30, 11)
+    n = MAX_KMERS + k - 1
+    ragged = [genome[300:300 + k - 1], "", planted_indel_read(genome, 500, n, 4000, 3, rnd), planted_indel_read(genome, 900, n, 4050, -2, rnd),
+              planted_indel_read(genome, 700, n + 1, 4000, 3, rnd)]
+    reads = clean[:10] + ragged + clean[10:]
+    long = dict(short=10, empty=11, del3=12, ins2=13, skipped=14)
+    short = [genome[i:i + 12] for i in range(0, 80, 4)]
+    junk = ["".join(rnd.choice("ACGT") for _ in range(100)) for _ in range(20)]
+    return g, genome, [[], reads, short, reads[:10], junk, []], long
+
+
+def tie_case():
+    """(A, B, reads, names): two unrelated 400-base sequences, three copies of each as reads (a build with min_count = 3 gives A and B) and
+    four reads in front of them (names: read -> index):
+        AB: A's last 81 bases without the middle one, then B's first 81 without the middle one: two chains of two heads, overlap 80, cost 1
+        BA: the same with the roles exchanged
+        AB_sub / BA_sub: the same with one substitution 10 bases into the first half: the second chain is the cheaper one"""
+    from genomeassembler_dev_amd import synth
+    A = synth.make_segment(201, 400, planted=False).tobytes().decode()
+    B = synth.make_segment(202, 400, planted=False).tobytes().decode()
+
+    def cut(s):
+        return s[:40] + s[41:]
+
+    def sub(r):
+        return r[:10] + "ACGT"[("ACGT".index(r[10]) + 1) % 4] + r[11:]
+    ab, ba = cut(A[-81:]) + cut(B[:81]), cut(B[-81:]) + cut(A[:81])
+    reads = [ab, ba, sub(ab), sub(ba)] + [A, B] * 3
+    return A, B, reads, dict(AB=0, BA=1, AB_sub=2, BA_sub=3)
+
+
+CONTIG_ENDS_K, CONTIG_ENDS_SEED, CONTIG_ENDS_GAP, CONTIG_ENDS_EDITS = 21, 28, 3, 6
+CONTIG_ENDS_MIN_COUNT = 2       # keeps the planted reads' own k-mers out of the graph: the repeat and thin coverage cut it, not the indels
+
+
+def contig_ends_case(seed=CONTIG_ENDS_SEED):
+    """(g, reads, n_planted): a 3 kb genome with a 150-base repeat (a build cuts it into several contigs), 60 reads of 80 bases with one
+    indel each whose starts lie within 100 bases of either end of either copy of the repeat, then error-free 80-base reads at 20x"""
+    from genomeassembler_dev_amd import synth
+    g, p1, p2 = synth.plant_repeat(synth.make_segment(seed, 3000, planted=False), 150, seed)
+    genome = g.tobytes().decode()
+    rnd = random.Random(seed)
+    planted = []
+    for i in range(60):
+        end = rnd.choice((p1, p1 + 150, p2, p2 + 150))
+        start = max(0, min(len(genome) - 100, end + rnd.randrange(-100, 21)))
+        planted.append(planted_indel_read(genome, start, 80, rnd.randrange(25, 52), rnd.choice((1, 2, 3, -1, -2, -3)), rnd))
+    return g, planted + clean_reads(g, 80, 20, seed), len(planted)
+
+
+def contig_end_properties(contigs, reads, k, max_edits, max_gap):
+    """what part 4 asks of a draw, on the build's contigs: (accepted chains of two or more heads clipped at a contig end, reads with two
+    consecutive heads on different contigs and a diagonal step within max_gap, mapped_multi)"""
+    where = where_of(contigs, k)
+    clipped = crossing = 0
+    for read in reads:
+        if not k <= len(read) <= MAX_KMERS + k - 1:
+            continue
+        heads, _ = heads_of(where, read, k)
+        crossing += any(a[1] != b[1] and 0 < abs(b[2] - a[2]) <= max_gap for a, b in zip(heads, heads[1:]))
+        for chain in chains_of(heads, max_gap):
+            if len(chain) >= 2:
+                cost, ov, _ = chain_cost(read, contigs[chain[0][1]], chain)
+                ins = sum(max(0, a[2] - b[2]) for a, b in zip(chain, chain[1:]))
+                clipped += cost <= max_edits and ov < len(read) - ins
+    return clipped, crossing, place_gapped(contigs, reads, k, max_edits, max_gap)["counters"][5]
+
+
+def slot_case():
+    """part 5: (segs, steps): two segments from 4 kb genomes, one error-free and one from indel_reads, an even number of reads each,
+    and the five builds (k, min_count, strands) with the parameters (max_mismatch, max_edits, max_gap) of the mappings after each"""
+    from genomeassembler_dev_amd import synth
+    clean = clean_reads(synth.make_segment(81, 4000, planted=False), 80, 20, 81)
+    _, noisy = indel_reads(4000, 80, 20, 82)
+    segs = [clean[:len(clean) & ~1], noisy[:len(noisy) & ~1]]
+    steps = [((21, 2, 1), (255, 255, 16)), ((33, 2, 1), (0, 0, 0)), ((21, 1000, 1), (4, 6, 3)), ((33, 1, 2), (2, 255, 1)), ((21, 2, 1), (4, 6, 3))]
+    return segs, steps

@@ -90,6 +90,15 @@ def test_the_helper_names_field_and_segment_and_tells_stale_from_wrong():
     wrong = hc.expected_snapshot([x[0], dict(x[1], counts=np.array([3, 1, 7])), x[2]], 3)
     assert hc.first_difference(wrong, X) == (hc.MULT, 1, 6, 7, 1)
     assert "a wrong value" in hc.difference(wrong, X, dict(Y=Y))
+    # Y's distinct offsets with X's left in place from element 2 on (a stale line of the scan's output): no build's count of segment 1
+    # fits what was found, but the element itself is X's offset there, and the message says so
+    offs = np.frombuffer(Y[hc.SEG_OFF], dtype="<u8").copy()
+    offs[2:] = np.frombuffer(X[hc.SEG_OFF], dtype="<u8")[2:]
+    line = (offs.tobytes(),) + Y[1:]
+    assert hc.first_difference(line, Y)[:3] == (hc.SEG_OFF, 1, 2)
+    msg = hc.difference(line, Y, dict(X=X))
+    assert "a wrong value" in msg and "element 2 itself equals the offset of X there" in msg and "stale line" in msg
+    assert "stale line" not in hc.difference(stale, X, dict(Y=Y))
     # a contig too many in segment 0: the contig segment offsets come first, then nothing else is looked at
     more = hc.expected_snapshot([dict(x[0], contigs=["ACGTA", "CCGT", "GTA"]), x[1], x[2]], 3)
     assert hc.first_difference(more, X)[:3] == (hc.CSEG_OFF, 0, 1)

@@ -3,7 +3,9 @@ and the Python surface know them; the CPU restatement of the rule (tests/mapgap_
 counters and pileup adds written out by hand, its breakpoints are the joint optimum (brute force) and its cost is never below the
 semi-global edit distance; readmap.GappedReadMap's host arithmetic agrees with its restatement.  The checks on the restatement itself
 (hand cases, brute force, one indel) take their reads from synth.simulate_reads_indel or pass their tables through GappedReadMap as
-well, so each of them needs the package's new surface."""
+well, so each of them needs the package's new surface.  The one-pass breakpoint (mapgap_ref.breakpoint_linear) is held equal to the
+definition, and the cases of tests/test_mapgap_edges_gpu.py (long reads, the ragged batch, ties, contig ends, the slot steps) have their
+preconditions asserted here, with the genome or the CPU restatement of the build in place of the device's contigs."""
 import ctypes as C
 import inspect
 import itertools
@@ -196,6 +198,157 @@ def test_gapped_read_map_arithmetic():
     assert folded == gr.fold_gaps(contigs, h["gap_pile"]) and folded[0] == [[0, 0], [0, 0], [6, 0], [1, 6], [0, 0]]
     with pytest.raises(ValueError):
         _gapped(contigs, h, 5, 0, 1).gap_pileup(0, fold_twins=True)
+
+
+def _sub(rnd, x):
+    return "ACGT"[("ACGT".index(x) + 1 + rnd.randrange(3)) % 4]
+
+
+def test_breakpoint_linear_is_breakpoint():
+    """the one-pass form against the definition: every join of every hand case, the worked example's reads, and 200 random windows of
+    width 1 to 300 with substitutions on both sides"""
+    joins = 0
+    for k, contigs, read, _, mg in (h[:5] for h in gr.HAND):
+        for chain in gr.chains_of(mr.heads_of(mr.where_of(contigs, k), read, k)[0], mg):
+            for a, b in zip(chain, chain[1:]):
+                assert gr.breakpoint_linear(read, contigs[a[1]], a, b) == gr.breakpoint(read, contigs[a[1]], a, b), (read, a, b)
+                joins += 1
+    assert joins >= 7
+    genome, reads = gr.indel_reads(4000, 80, 20, 5)
+    where, joins = mr.where_of([genome], 21), 0
+    for read in reads:
+        for chain in gr.chains_of(mr.heads_of(where, read, 21)[0], 3):
+            for a, b in zip(chain, chain[1:]):
+                assert gr.breakpoint_linear(read, genome, a, b) == gr.breakpoint(read, genome, a, b), (read, a, b)
+                joins += 1
+    assert joins >= 73
+    from genomeassembler_dev_amd import synth
+    contig = synth.make_segment(7, 2000, planted=False).tobytes().decode()
+    rnd, ties = random.Random(7), 0
+    for trial in range(200):
+        width, g = 1 + trial * 3 // 2, rnd.choice((-16, -3, -2, -1, 1, 2, 3, 16))
+        G = max(0, -g)
+        Ja, da = rnd.randrange(0, 5), rnd.randrange(20, 1000)
+        a, b = (Ja, 0, da), (Ja + width + G, 0, da + g)                  # the window [Ja + 1, Ja + width]: `width` positions
+        assert gr.window_of(a, b) == (Ja + 1, Ja + width)
+        read = list(contig[da:da + b[0] + 10])                        # the left diagonal throughout, then substitutions: against the left
+        for x in range(len(read)):                                    # diagonal, against the right one, and bases of the right diagonal
+            r = rnd.random()
+            if r < 0.5:
+                read[x] = contig[b[2] + x]
+            elif r < 0.6:
+                read[x] = _sub(rnd, read[x])
+        got, want = gr.breakpoint_linear(read, contig, a, b), gr.breakpoint(read, contig, a, b)
+        assert got == want, (trial, width, g)
+        costs = [gr.chain_cost(read, contig, [a, b], [t])[0] for t in range(Ja + 1, Ja + width + 1)]
+        ties += costs.count(min(costs)) > 1 and costs.index(min(costs)) + Ja + 1 == got[0]
+    assert 1 + 199 * 3 // 2 >= 299 and ties > 20, ties                   # widths 1 .. 299; equal minima met, the smallest t taken
+
+
+def test_multi_indel_read_is_planted_indel_read_repeated():
+    from genomeassembler_dev_amd import synth
+    genome = synth.make_segment(123, 3000, planted=False).tobytes().decode()
+    for at, g in ((40, 1), (40, -1), (90, 16), (64, -16)):
+        assert gr.multi_indel_read(genome, 300, 200, [(at, g)], random.Random(1)) == gr.planted_indel_read(genome, 300, 200, at, g, random.Random(1))
+    r = gr.multi_indel_read(genome, 50, 120, [(30, 2), (60, -3), (90, 1)], random.Random(2))
+    assert len(r) == 120 and r[:30] == genome[50:80] and r[30:60] == genome[82:112] and r[63:90] == genome[112:139] and r[90:] == genome[140:170]
+    assert all(r[60 + i] not in (genome[111], genome[112]) for i in range(3)) and r[60] != r[61] != r[62]
+
+
+@pytest.mark.parametrize("k", [21, 32, 63])
+def test_long_read_preconditions(k):
+    """part 1 of tests/test_mapgap_edges_gpu.py with the genome as its own contig: strides, q, costs, the dropped ninth head"""
+    _, genome, planted, _ = gr.long_read_case(k)
+    where = mr.where_of([genome], k)
+    heads = {name: mr.heads_of(where, read, k) for name, (read, _, _) in planted.items()}
+    assert [len(planted[n][0]) for n in ("one_del2", "one_ins2", "one_del16", "ins16", "eight", "ninth")] == [400, 400, 400, 300, 1200, 1200]
+    for name, want in (("one_del2", 4), ("one_ins2", 5), ("one_del16", 6), ("ins16", 2)):
+        (a, b), dropped = heads[name]
+        assert dropped == 0 and gr.strides(a, b) == want, (name, a, b)
+    for name, (read, start, gaps) in planted.items():
+        ins, dele = sum(-g for g in gaps if g < 0), sum(g for g in gaps if g > 0)
+        rec, gap = gr.one_read([genome], read, k, 255, 16)
+        assert rec[:2] == [0, start] and rec[3] == 1 and gap == [len(gaps) + 1, ins, dele, start + sum(gaps)], (name, rec, gap)
+        assert rec[4] == len(read) - ins
+        if name in ("one_del2", "one_ins2", "one_del16", "ins16", "eight"):
+            assert rec[2] == ins + dele and heads[name][1] == 0, (name, rec)
+            assert gr.one_read([genome], read, k, rec[2] - 1, 16)[0] == mr.NO_PLACE
+    # max_gap = 3 does not join the 16-base deletion: two chains of one head, both over the whole read
+    rec, gap = gr.one_read([genome], planted["one_del16"][0], k, 255, 3)
+    assert rec[3] == 2 and gap[:3] == [1, 0, 0] and rec[2] > 16 and gr.one_read([genome], planted["one_del16"][0], k, 16, 3)[0] == mr.NO_PLACE
+    assert len(heads["eight"][0]) == 8 and gr.one_read([genome], planted["eight"][0], k, 12, 3)[1] == [8, 2, 10, gr.CHAIN_START + 8]
+    assert len({h[2] for h in heads["eight"][0]}) == 8 and max(gr.strides(a, b) for a, b in zip(heads["eight"][0], heads["eight"][0][1:])) == 3
+    # the ninth head is dropped; the tail behind it lies one base off the eighth diagonal: about three mismatches in four bases
+    for name, tail in (("ninth", k + 9), ("ninth_far", len(planted["ninth_far"][0]) - 1200)):
+        read = planted[name][0]
+        assert len(heads[name][0]) == 8 and heads[name][1] == 1 and len({h[2] for h in heads[name][0]}) == 8
+        cost = gr.one_read([genome], read, k, 255, 3)[0][2]
+        assert 12 + tail // 2 <= cost <= 12 + tail, (name, cost)
+        assert gr.one_read([genome], read, k, cost, 3)[1][0] == 8 and gr.one_read([genome], read, k, cost - 1, 3)[0] == mr.NO_PLACE
+    assert 200 <= gr.one_read([genome], planted["ninth_far"][0], k, 255, 3)[0][2] <= 255
+    # alternating +1, -1 returns to a kept diagonal: no chain of more than two heads
+    flip = gr.multi_indel_read(genome, 100, 700, [(150 * i, (1, -1)[i % 2]) for i in range(1, 4)], random.Random(1))
+    assert len(mr.heads_of(where, flip, k)[0]) == 2
+
+
+def test_ragged_case_preconditions():
+    """part 2: the long reads' records and gap records, their windows, the junk"""
+    k = gr.RAGGED_K
+    _, genome, segs, at = gr.ragged_case()
+    reads, junk = segs[1], segs[4]
+    where = mr.where_of([genome], k)
+    assert [len(reads[at[n]]) - k + 1 for n in ("short", "empty", "del3", "ins2", "skipped")] == [0, -20, 4096, 4096, 4097]
+    (a, b), _ = mr.heads_of(where, reads[at["del3"]], k)
+    lo, hi = gr.window_of(a, b)
+    assert gr.strides(a, b) == 63 and lo == 1 and 3990 <= hi <= 4000 and gr.breakpoint_linear(reads[at["del3"]], genome, a, b)[0] == hi
+    t = gr.place_gapped([genome], reads[10:15], k, 6, 3)
+    assert t["records"] == [mr.NO_PLACE, mr.NO_PLACE, [0, 500, 3, 1, 4116], [0, 900, 2, 1, 4114], mr.NO_PLACE]
+    assert t["gap_records"] == [gr.NO_GAPS, gr.NO_GAPS, [2, 0, 3, 503], [2, 2, 0, 898], gr.NO_GAPS] and t["counters"] == [2, 1, 0, 0, 2, 0, 0, 2]
+    assert gr.place_gapped([genome], junk, k, 6, 3)["counters"] == [0, 0, 20, 0, 0, 0, 0, 0]
+    assert len(segs) == 6 and segs[0] == segs[5] == [] and all(len(r) < k for r in segs[2]) and segs[3] == reads[:10]
+
+
+def test_tie_case_preconditions():
+    """part 3: two accepted chains of two heads with equal overlap and cost: the one that starts first wins, on either contig; with a
+    substitution in the first half the second wins on cost"""
+    k = 21
+    A, B, reads, at = gr.tie_case()
+    assert lr.expected_cached(reads, k, min_count=3)["ref"]["contigs"] in ([A, B], [B, A])
+    for contigs in ([A, B], [B, A]):
+        where = mr.where_of(contigs, k)
+        ia, ib = contigs.index(A), contigs.index(B)
+        for name, first, second in (("AB", ia, ib), ("BA", ib, ia)):
+            read = reads[at[name]]
+            chains = gr.chains_of(mr.heads_of(where, read, k)[0], 3)
+            assert [len(c) for c in chains] == [2, 2] and [c[0][1] for c in chains] == [first, second]
+            assert [gr.chain_cost(read, contigs[c[0][1]], c)[:2] for c in chains] == [(1, 80), (1, 80)]
+            d = 319                                                   # (both sequences have 400 bases: the last 81 start at 319)
+            for me in (1, 2):
+                assert gr.one_read(contigs, read, k, me, 3) == ([first, d, 1, 2, 80], [2, 0, 1, d + 1]), (name, me)
+            assert gr.one_read(contigs, reads[at[name + "_sub"]], k, 2, 3) == ([second, -80, 1, 2, 80], [2, 0, 1, -79]), name
+            assert gr.one_read(contigs, reads[at[name + "_sub"]], k, 1, 3)[0] == [second, -80, 1, 1, 80]
+    assert gr.one_read([A, B], reads[at["AB"]], k, 2, 3)[0] == [0, 319, 1, 2, 80] and gr.one_read([A, B], reads[at["AB_sub"]], k, 2, 3)[0] == [1, -80, 1, 2, 80]
+    assert gr.one_read([A, B], reads[at["BA"]], k, 2, 3)[0][0] == 1        # the winner is the contig with the higher index
+
+
+@pytest.mark.parametrize("strands", [1, 2])
+def test_contig_ends_case_preconditions(strands):
+    """part 4, on the contigs the CPU restatement of the build gives: a clipped accepted chain, neighbouring heads on different contigs
+    within max_gap, mapped_multi > 0"""
+    k, me, mg = gr.CONTIG_ENDS_K, gr.CONTIG_ENDS_EDITS, gr.CONTIG_ENDS_GAP
+    _, reads, n_planted = gr.contig_ends_case()
+    contigs = lr.expected_cached(reads, k, min_count=gr.CONTIG_ENDS_MIN_COUNT, strands=strands)["ref"]["contigs"]
+    assert len(contigs) > 2 and n_planted == 60
+    clipped, crossing, multi = gr.contig_end_properties(contigs, reads, k, me, mg)
+    print(f"strands {strands}: {len(contigs)} contigs, clipped chains {clipped}, crossing heads {crossing}, mapped_multi {multi}")
+    assert clipped >= 1 and crossing >= 1 and multi > 0
+
+
+def test_slot_case_preconditions():
+    segs, steps = gr.slot_case()
+    assert all(len(s) % 2 == 0 and len(s) > 900 for s in segs) and len(steps) == 5
+    assert [s[0] for s in steps] == [(21, 2, 1), (33, 2, 1), (21, 1000, 1), (33, 1, 2), (21, 2, 1)]
+    assert [s[1] for s in steps] == [(255, 255, 16), (0, 0, 0), (4, 6, 3), (2, 255, 1), (4, 6, 3)]
 
 
 def test_the_indel_variant_case():
