@@ -14,6 +14,11 @@ from .pairs import PairPlaces
 from .readmap import GappedReadMap, ReadMap
 
 
+def _arr(p, ctype, n):
+    """a copy of the n entries of `ctype` a fetch handed out at pointer p"""
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, ctype)
+
+
 def weighted_median_half(mult_sum, n_edges):
     """floor(median / 2) of the contigs' mean multiplicities mult_sum / n_edges, each weighted by n_edges: the median is the mean of
     the first contig, in ascending order of mean, at which the running weight reaches half the total.  Exact integers."""
@@ -231,17 +236,13 @@ class SegmentBatch:
             span_len = min(self._longest_read(), MAX_SPAN_LEN)
         if not 0 <= int(span_len) <= MAX_SPAN_LEN:
             raise ValueError(f"span_len must be 0..{MAX_SPAN_LEN} (0: no span support)")
-        seg, o, raw = self.contigs_raw()
+        seg, _, contigs = self._contigs_by_segment()
         total = int(seg[-1])
         check(lib().gasm_batch_contig_links(self.h, int(span_len)))
         ps = [C.c_void_p() for _ in range(5)]
         check(lib().gasm_batch_fetch_contig_links(self.h, *[C.byref(p) for p in ps]))
-
-        def arr(p, ct, n):
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
-        succ, pred, lsup = (arr(p, C.c_uint32, 4 * total) for p in ps[:3])
-        ssup, skipped = arr(ps[3], C.c_uint32, 16 * total), arr(ps[4], C.c_uint64, self.n_segments)
-        contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+        succ, pred, lsup = (_arr(p, C.c_uint32, 4 * total) for p in ps[:3])
+        ssup, skipped = _arr(ps[3], C.c_uint32, 16 * total), _arr(ps[4], C.c_uint64, self.n_segments)
         ms, _ = self.contig_coverage()
         return ContigLinks(self.k, int(span_len), self.strands(), seg, contigs, succ, pred, lsup, ssup, skipped, ms)
 
@@ -265,12 +266,9 @@ class SegmentBatch:
         check(lib().gasm_batch_place_pairs(self.h, max_insert))
         ps, orient = [C.c_void_p() for _ in range(3)], C.c_uint32()
         check(lib().gasm_batch_fetch_pair_places(self.h, *[C.byref(p) for p in ps], C.byref(orient)))
-
-        def arr(p, ct, n):
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
         o, n_pairs = int(orient.value), self.n_reads // 2
-        rec = arr(ps[0], C.c_int32, 4 * o * n_pairs)
-        hist, cnt = arr(ps[1], C.c_uint32, self.n_segments * (max_insert + 1)), arr(ps[2], C.c_uint64, self.n_segments * len(PAIR_FIELDS))
+        rec = _arr(ps[0], C.c_int32, 4 * o * n_pairs)
+        hist, cnt = _arr(ps[1], C.c_uint32, self.n_segments * (max_insert + 1)), _arr(ps[2], C.c_uint64, self.n_segments * len(PAIR_FIELDS))
         return PairPlaces(self.k, self.strands(), max_insert, o, self.contigs(), rec, hist, cnt)
 
     def map_reads(self, max_mismatch=4):
@@ -285,14 +283,10 @@ class SegmentBatch:
         check(lib().gasm_batch_map_reads(self.h, max_mismatch))
         ps = [C.c_void_p() for _ in range(4)]
         check(lib().gasm_batch_fetch_read_map(self.h, *[C.byref(p) for p in ps]))
-
-        def arr(p, ct, n):
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
-        seg, o, raw = self.contigs_raw()
-        contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+        seg, o, contigs = self._contigs_by_segment()
         total = int(o[-1]) if int(seg[-1]) else 0
-        rec, pile = arr(ps[0], C.c_int32, 4 * self.n_reads), arr(ps[1], C.c_uint32, 4 * total)
-        hist, cnt = arr(ps[2], C.c_uint32, self.n_segments * (max_mismatch + 1)), arr(ps[3], C.c_uint64, self.n_segments * len(MAP_FIELDS))
+        rec, pile = _arr(ps[0], C.c_int32, 4 * self.n_reads), _arr(ps[1], C.c_uint32, 4 * total)
+        hist, cnt = _arr(ps[2], C.c_uint32, self.n_segments * (max_mismatch + 1)), _arr(ps[3], C.c_uint64, self.n_segments * len(MAP_FIELDS))
         strands = self.strands()
         return ReadMap(self.k, strands, max_mismatch, contigs, rec, pile, hist, cnt,
                        [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
@@ -311,15 +305,11 @@ class SegmentBatch:
         check(lib().gasm_batch_map_reads_gapped(self.h, max_edits, max_gap))
         ps = [C.c_void_p() for _ in range(6)]
         check(lib().gasm_batch_fetch_read_map_gapped(self.h, *[C.byref(p) for p in ps]))
-
-        def arr(p, ct, n):
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
-        seg, o, raw = self.contigs_raw()
-        contigs = [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+        seg, o, contigs = self._contigs_by_segment()
         total = int(o[-1]) if int(seg[-1]) else 0
-        rec, gap = arr(ps[0], C.c_int32, 4 * self.n_reads), arr(ps[1], C.c_int32, 4 * self.n_reads)
-        pile, gpile = arr(ps[2], C.c_uint32, 4 * total), arr(ps[3], C.c_uint32, 2 * total)
-        hist, cnt = arr(ps[4], C.c_uint32, self.n_segments * (max_edits + 1)), arr(ps[5], C.c_uint64, self.n_segments * len(MAPG_FIELDS))
+        rec, gap = _arr(ps[0], C.c_int32, 4 * self.n_reads), _arr(ps[1], C.c_int32, 4 * self.n_reads)
+        pile, gpile = _arr(ps[2], C.c_uint32, 4 * total), _arr(ps[3], C.c_uint32, 2 * total)
+        hist, cnt = _arr(ps[4], C.c_uint32, self.n_segments * (max_edits + 1)), _arr(ps[5], C.c_uint64, self.n_segments * len(MAPG_FIELDS))
         strands = self.strands()
         return GappedReadMap(self.k, strands, max_edits, max_gap, contigs, rec, gap, pile, gpile, hist, cnt,
                              [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
@@ -468,6 +458,11 @@ class SegmentBatch:
         raw = C.string_at(data, int(o[-1])) if nc and o[-1] else b""
         return seg, o, raw
 
+    def _contigs_by_segment(self):
+        """(seg_contig_off, contig base offsets, the contig strings of every segment)"""
+        seg, o, raw = self.contigs_raw()
+        return seg, o, [[raw[int(o[c]):int(o[c + 1])].decode() for c in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
+
     def contigs(self, segment=None, one_per_pair=False):
         """contig strings per segment (or of one segment).  one_per_pair (after a strands = 2 build): of every contig and its
         reverse-complement twin only the first is kept (c <= twin[c]: self-twins stay)"""
@@ -489,7 +484,7 @@ class SegmentBatch:
         check(lib().gasm_batch_fetch_contig_twins(self.h, C.byref(p)))
         seg = self.contigs_raw()[0]
         n = int(seg[-1])
-        tw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        tw = _arr(p, C.c_uint32, n)
         out = [tw[int(seg[s]):int(seg[s + 1])] for s in range(self.n_segments)]
         return out if segment is None else out[segment]
 
@@ -499,12 +494,9 @@ class SegmentBatch:
         check(lib().gasm_batch_fetch_scores_table(self.h, int(table), *[C.byref(p) for p in ps]))
         seg, _, _ = self.contigs_raw()
         n = int(seg[-1])
-
-        def arr(p, ct):
-            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
-        return dict(bp_score=arr(ps[0], C.c_double), bp_score_norm_by_break_freqs=arr(ps[1], C.c_double),
-                    bp_score_norm_by_len=arr(ps[2], C.c_double), kmer_breaks=arr(ps[3], C.c_int32),
-                    sequence_len=arr(ps[4], C.c_int32), seg_contig_off=seg)
+        return dict(bp_score=_arr(ps[0], C.c_double, n), bp_score_norm_by_break_freqs=_arr(ps[1], C.c_double, n),
+                    bp_score_norm_by_len=_arr(ps[2], C.c_double, n), kmer_breaks=_arr(ps[3], C.c_int32, n),
+                    sequence_len=_arr(ps[4], C.c_int32, n), seg_contig_off=seg)
 
     def score_fixed(self, table=0):
         """(int64 fixed-point breakage sums per contig, shift): bp_score == fx * 2**-shift exactly; table: which table of
@@ -513,8 +505,7 @@ class SegmentBatch:
         check(lib().gasm_batch_fetch_score_fixed_table(self.h, int(table), C.byref(p), C.byref(sh)))
         seg, _, _ = self.contigs_raw()
         n = int(seg[-1])
-        fx = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(n,)).copy() if n else np.zeros(0, np.int64)
-        return fx, sh.value
+        return _arr(p, C.c_int64, n), sh.value
 
     def guided(self):
         """breakage-score-guided scaffolds (not in the reference) of a built + scored batch:
@@ -526,8 +517,7 @@ class SegmentBatch:
         n = int(seg[-1])
         off = np.ctypeslib.as_array(C.cast(ps[1], C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
         raw = C.string_at(ps[2], int(off[-1])) if n and off[-1] else b""
-        arr = lambda p, ct: np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
-        bp, nl, br = arr(ps[3], C.c_double), arr(ps[4], C.c_double), arr(ps[5], C.c_int32)
+        bp, nl, br = _arr(ps[3], C.c_double, n), _arr(ps[4], C.c_double, n), _arr(ps[5], C.c_int32, n)
         return [[dict(sequence=raw[int(off[i]):int(off[i + 1])].decode(), bp_score=bp[i], bp_score_norm_by_len=nl[i], kmer_breaks=int(br[i]))
                  for i in range(int(seg[s]), int(seg[s + 1]))] for s in range(self.n_segments)]
 

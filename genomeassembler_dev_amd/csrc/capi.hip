@@ -956,19 +956,34 @@ int gasm_batch_fetch_lowcov_stats(gasm_batch* b, const uint32_t** contigs, const
     API_GUARD_END
 }
 
+// ---- the passes over the last build.  A queueing entry: batch non-null, its own arguments in range (`args`: what its check gave, the
+// error already set), built, the pending build finished.  A fetching entry: no null argument, built
+static int batch_pass_ready(gasm_batch* b, const char* entry, int args = GASM_OK) {
+    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
+    if (args != GASM_OK) return args;
+    if (!b->built) { gasm_set_error("%s before a build", entry); return GASM_ERR_STATE; }
+    return batch_finish(b);
+}
+static int batch_fetch_ready(const gasm_batch* b, const char* entry, bool no_null) {
+    if (!b || !no_null) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (!b->built) { gasm_set_error("%s before a build", entry); return GASM_ERR_STATE; }
+    return GASM_OK;
+}
+static int at_most(const char* name, u32 v, u32 max) {
+    if (v > max) { gasm_set_error("%s must be <= %u (got %u)", name, max, v); return GASM_ERR_INVALID; }
+    return GASM_OK;
+}
+
 int gasm_batch_contig_coverage(gasm_batch* b) {
     API_GUARD_BEGIN
-    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_contig_coverage before a build"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
+    GCHK(batch_pass_ready(b, "gasm_batch_contig_coverage"));
     return pipeline_contig_coverage(b->S().cx, b->build_reads(b->S()), b->S().bs);
     API_GUARD_END
 }
 
 int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, const uint32_t** n_edges) {
     API_GUARD_BEGIN
-    if (!b || !mult_sum || !n_edges) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_contig_coverage before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_contig_coverage", mult_sum && n_edges));
     BuildState& bs = b->S().bs;
     GCHK(pipeline_fetch_contig_coverage(b->S().cx, b->build_reads(b->S()), bs));
     *mult_sum = bs.h_ccov_m.data(); *n_edges = bs.h_ccov_n.data();
@@ -978,10 +993,7 @@ int gasm_batch_fetch_contig_coverage(gasm_batch* b, const uint64_t** mult_sum, c
 
 int gasm_batch_contig_links(gasm_batch* b, uint32_t span_len) {
     API_GUARD_BEGIN
-    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (span_len > GASM_MAX_SPAN_LEN) { gasm_set_error("span_len must be <= %d (got %u)", GASM_MAX_SPAN_LEN, span_len); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_contig_links before a build"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
+    GCHK(batch_pass_ready(b, "gasm_batch_contig_links", at_most("span_len", span_len, GASM_MAX_SPAN_LEN)));
     return pipeline_contig_links(b->S().cx, b->build_reads(b->S()), b->S().bs, span_len);
     API_GUARD_END
 }
@@ -989,78 +1001,69 @@ int gasm_batch_contig_links(gasm_batch* b, uint32_t span_len) {
 int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const uint32_t** pred, const uint32_t** link_support, const uint32_t** span_support,
                                   const uint64_t** skipped) {
     API_GUARD_BEGIN
-    if (!b || !succ || !pred || !link_support || !span_support || !skipped) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_contig_links before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_contig_links", succ && pred && link_support && span_support && skipped));
     BuildState& bs = b->S().bs;
     GCHK(pipeline_fetch_contig_links(b->S().cx, b->build_reads(b->S()), bs));
-    *succ = bs.h_succ.data(); *pred = bs.h_pred.data(); *link_support = bs.h_link_support.data(); *span_support = bs.h_span_support.data();
-    *skipped = bs.h_links_skipped.data();
+    *succ = bs.links.host<uint32_t>(LINKS_SUCC); *pred = bs.links.host<uint32_t>(LINKS_PRED); *link_support = bs.links.host<uint32_t>(LINKS_LSUP);
+    *span_support = bs.links.host<uint32_t>(LINKS_SSUP); *skipped = bs.links.host<uint64_t>(LINKS_SKIPPED);
     return GASM_OK;
     API_GUARD_END
 }
 
 int gasm_batch_place_pairs(gasm_batch* b, uint32_t max_insert) {
     API_GUARD_BEGIN
-    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (max_insert < 1 || max_insert > GASM_MAX_INSERT) { gasm_set_error("max_insert must be 1..%d (got %u)", GASM_MAX_INSERT, max_insert); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_place_pairs before a build"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
+    int args = GASM_OK;
+    if (max_insert < 1 || max_insert > GASM_MAX_INSERT) { gasm_set_error("max_insert must be 1..%d (got %u)", GASM_MAX_INSERT, max_insert); args = GASM_ERR_INVALID; }
+    GCHK(batch_pass_ready(b, "gasm_batch_place_pairs", args));
     return pipeline_place_pairs(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, max_insert);
     API_GUARD_END
 }
 
 int gasm_batch_fetch_pair_places(gasm_batch* b, const int32_t** rec, const uint32_t** insert_hist, const uint64_t** counters, uint32_t* orientations) {
     API_GUARD_BEGIN
-    if (!b || !rec || !insert_hist || !counters || !orientations) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_pair_places before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_pair_places", rec && insert_hist && counters && orientations));
     BuildState& bs = b->S().bs;
     GCHK(pipeline_fetch_pair_places(b->S().cx, b->rd, bs));
-    *rec = bs.h_pair_rec.data(); *insert_hist = bs.h_pair_hist.data(); *counters = bs.h_pair_counters.data(); *orientations = bs.pairs_orient;
+    *rec = bs.pairs.host<int32_t>(PAIRS_REC); *insert_hist = bs.pairs.host<uint32_t>(PAIRS_HIST); *counters = bs.pairs.host<uint64_t>(PAIRS_CNT);
+    *orientations = bs.pairs.param[0];
     return GASM_OK;
     API_GUARD_END
 }
 
 int gasm_batch_map_reads(gasm_batch* b, uint32_t max_mismatch) {
     API_GUARD_BEGIN
-    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (max_mismatch > GASM_MAP_MAX_MISMATCH) { gasm_set_error("max_mismatch must be <= %d (got %u)", GASM_MAP_MAX_MISMATCH, max_mismatch); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_map_reads before a build"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
-    return pipeline_map_reads(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, max_mismatch);
+    GCHK(batch_pass_ready(b, "gasm_batch_map_reads", at_most("max_mismatch", max_mismatch, GASM_MAP_MAX_MISMATCH)));
+    return pipeline_map_reads(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, false, max_mismatch, 0);
     API_GUARD_END
 }
 
 int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t** pile, const uint32_t** mismatch_hist, const uint64_t** counters) {
     API_GUARD_BEGIN
-    if (!b || !rec || !pile || !mismatch_hist || !counters) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_read_map before a build"); return GASM_ERR_STATE; }
-    BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, bs));
-    *rec = bs.h_map_rec.data(); *pile = bs.h_map_pile.data(); *mismatch_hist = bs.h_map_hist.data(); *counters = bs.h_map_counters.data();
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_read_map", rec && pile && mismatch_hist && counters));
+    const PassState& ps = b->S().bs.map;
+    GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, b->S().bs, false));
+    *rec = ps.host<int32_t>(MAP_REC); *pile = ps.host<uint32_t>(MAP_PILE); *mismatch_hist = ps.host<uint32_t>(MAP_HIST); *counters = ps.host<uint64_t>(MAP_CNT);
     return GASM_OK;
     API_GUARD_END
 }
 
 int gasm_batch_map_reads_gapped(gasm_batch* b, uint32_t max_edits, uint32_t max_gap) {
     API_GUARD_BEGIN
-    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (max_edits > GASM_MAP_MAX_MISMATCH) { gasm_set_error("max_edits must be <= %d (got %u)", GASM_MAP_MAX_MISMATCH, max_edits); return GASM_ERR_INVALID; }
-    if (max_gap > GASM_MAP_MAX_GAP) { gasm_set_error("max_gap must be <= %d (got %u)", GASM_MAP_MAX_GAP, max_gap); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_map_reads_gapped before a build"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
-    return pipeline_map_reads_gapped(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, max_edits, max_gap);
+    int args = at_most("max_edits", max_edits, GASM_MAP_MAX_MISMATCH);
+    if (args == GASM_OK) args = at_most("max_gap", max_gap, GASM_MAP_MAX_GAP);
+    GCHK(batch_pass_ready(b, "gasm_batch_map_reads_gapped", args));
+    return pipeline_map_reads(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, true, max_edits, max_gap);
     API_GUARD_END
 }
 
 int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const int32_t** rec_gap, const uint32_t** pile, const uint32_t** gap_pile,
                                      const uint32_t** edit_hist, const uint64_t** counters) {
     API_GUARD_BEGIN
-    if (!b || !rec || !rec_gap || !pile || !gap_pile || !edit_hist || !counters) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_read_map_gapped before a build"); return GASM_ERR_STATE; }
-    BuildState& bs = b->S().bs;
-    GCHK(pipeline_fetch_read_map_gapped(b->S().cx, b->rd, bs));
-    *rec = bs.h_mapg_rec.data(); *rec_gap = bs.h_mapg_gap.data(); *pile = bs.h_mapg_pile.data(); *gap_pile = bs.h_mapg_gpile.data();
-    *edit_hist = bs.h_mapg_hist.data(); *counters = bs.h_mapg_counters.data();
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_read_map_gapped", rec && rec_gap && pile && gap_pile && edit_hist && counters));
+    const PassState& ps = b->S().bs.mapg;
+    GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, b->S().bs, true));
+    *rec = ps.host<int32_t>(MAPG_REC); *rec_gap = ps.host<int32_t>(MAPG_GAP); *pile = ps.host<uint32_t>(MAPG_PILE); *gap_pile = ps.host<uint32_t>(MAPG_GPILE);
+    *edit_hist = ps.host<uint32_t>(MAPG_HIST); *counters = ps.host<uint64_t>(MAPG_CNT);
     return GASM_OK;
     API_GUARD_END
 }
@@ -1091,17 +1094,14 @@ int gasm_batch_fetch_solid_stats(gasm_batch* b, const uint64_t** distinct_before
 
 int gasm_batch_kmer_spectrum(gasm_batch* b) {
     API_GUARD_BEGIN
-    if (!b) { gasm_set_error("batch is null"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_kmer_spectrum before a build"); return GASM_ERR_STATE; }
-    GCHK(batch_finish(b));
+    GCHK(batch_pass_ready(b, "gasm_batch_kmer_spectrum"));
     return pipeline_kmer_spectrum(b->S().cx, b->build_reads(b->S()), b->S().bs);
     API_GUARD_END
 }
 
 int gasm_batch_fetch_kmer_spectrum(gasm_batch* b, const uint64_t** hist) {
     API_GUARD_BEGIN
-    if (!b || !hist) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
-    if (!b->built) { gasm_set_error("gasm_batch_fetch_kmer_spectrum before a build"); return GASM_ERR_STATE; }
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_kmer_spectrum", hist != nullptr));
     BuildState& bs = b->S().bs;
     GCHK(pipeline_fetch_kmer_spectrum(b->S().cx, b->build_reads(b->S()), bs));
     *hist = bs.h_spectrum.data();

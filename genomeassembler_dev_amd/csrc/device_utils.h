@@ -61,6 +61,24 @@ __device__ __forceinline__ u32 wave_incl_scan(u32 v) {
 // the value of lane 63 (e.g. the total after wave_incl_scan), uniform
 __device__ __forceinline__ u32 wave_last(u32 v) { return (u32)__builtin_amdgcn_readlane((int)v, 63); }
 
+// lane i's value (i wave-uniform) as a scalar
+__device__ __forceinline__ int lane_value(int v, u32 i) { return __builtin_amdgcn_readfirstlane(__shfl(v, (int)i, 64)); }
+// word `src` (wave-uniform) of a 64-bit value that every lane holds one of
+__device__ __forceinline__ u64 lane_word(u64 v, u32 src) {
+    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)v, (int)src);
+    const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)src);
+    return ((u64)hi << 32) | lo;
+}
+// the smallest value of the 64 lanes, uniform
+__device__ __forceinline__ u32 wave_min_u32(u32 v) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const u32 x = (u32)__shfl_xor((int)v, o, 64);
+        v = x < v ? x : v;
+    }
+    return (u32)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 template <int NT>
 __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* s_tmp, u32* total) {
     constexpr int NW = NT / 64;

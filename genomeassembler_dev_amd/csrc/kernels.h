@@ -282,6 +282,17 @@ __global__ void k_sim_extract(const u64* gwords, const u64* gbase, const u64* se
 template <int LS>
 __global__ void k_read_kmer_count(const u64* words, const u64* read_off, const u64* seg_read_off, u32 fixed_len, u32 n_segments, u32* out);
 
+// ---- the passes that lay reads over a finished build (their shared frame: contig_index.h)
+// what they need of the build beside the k-mer directory, one kernel argument as GraphView is (host: contig_index(bs))
+struct ContigIndex {
+    const u64* link;       // per edge: head << 32 | done << 31 | distance
+    const u32* e_cid;      // at a head: its contig
+    const u64* c_off;      // per contig: its first base in the batch's contig text (+ the end of the last)
+    const u32* seg_cstart; // n_segments + 1 contig indices
+    const u8* text;        // the contigs' ASCII, as the build emitted it
+    int have_graph;        // 0: the build holds no contig at all, and the arrays above may not exist
+};
+
 // ---- kernels_correct.hip: read correction against the distinct k-mers of a finished build (include/gasm.h, "Read correction")
 #define GASM_CORRECT_STATS 6          // = GASM_CORRECT_FIELDS of include/gasm.h (checked in pipeline.hip)
 #define GASM_CORRECT_KMER_CAP 4096    // = GASM_CORRECT_MAX_KMERS: k-mers of a read whose weak bits one wave keeps (64 lanes x 64 bits)
@@ -291,37 +302,36 @@ __global__ void k_read_correct(ReadSet rs, GraphView gv, int have_graph, u32 rea
 
 // ---- kernels_links.hip: the links between the contigs of a finished build and the reads' support for them (include/gasm.h, "Contig links")
 #define GASM_THREAD_KMER_CAP 4096     // = GASM_THREAD_MAX_KMERS: k-mers of a read whose in-set bits one wave keeps (64 words of 64 bits in LDS)
-// succ / pred: 4 entries per contig, filled with GASM_NONE32 by the caller; text: the contigs' ASCII
+// succ / pred: 4 entries per contig, filled with GASM_NONE32 by the caller
 template <class K>
-__global__ void k_contig_links(GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, u32 n_segments, u32* succ,
-                               u32* pred);
-// text: the contigs' ASCII; link_support: 4 per contig, span_support: 16 per contig, skipped: one per segment, all zeroed by the caller
+__global__ void k_contig_links(GraphView gv, ContigIndex ci, u32 n_segments, u32* succ, u32* pred);
+// link_support: 4 per contig, span_support: 16 per contig, skipped: one per segment, all zeroed by the caller
 template <class K>
-__global__ void k_read_thread(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph, u32 span_len,
-                              u32 reads_per_wg, u32 chunks, u32* link_support, u32* span_support, unsigned long long* skipped);
+__global__ void k_read_thread(ReadSet rs, GraphView gv, ContigIndex ci, u32 span_len, u32 reads_per_wg, u32 chunks, u32* link_support, u32* span_support,
+                              unsigned long long* skipped);
 // read pairs (include/gasm.h, "Read pairs"): orient = 1 or 2 orientations per pair; rec: 4 int32 per oriented pair (16-byte aligned), n_pairs
 // pairs per orientation; hist: max_insert + 1 bins per segment, counters: GASM_PAIR_COUNTERS per segment, both zeroed by the caller
 #define GASM_PAIR_COUNTERS 6          // = GASM_PAIR_FIELDS of include/gasm.h (checked in pipeline.hip)
 template <class K>
-__global__ void k_pair_place(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, int have_graph, u32 orient, u32 max_insert,
-                             u64 n_pairs, u32 chunks, int32_t* rec, u32* hist, unsigned long long* counters);
-// read mapping (include/gasm.h, "Read mapping"): rec: 4 int32 per read (16-byte aligned); text: the contigs' ASCII; pile: 4 u32 per base of it,
-// hist: max_mismatch + 1 bins per segment, counters: GASM_MAP_COUNTERS per segment, the three zeroed by the caller
-#define GASM_MAP_COUNTERS 7           // = GASM_MAP_FIELDS of include/gasm.h (checked in pipeline.hip)
-#define GASM_MAP_BLOCKS 8             // = GASM_MAP_MAX_BLOCKS: distinct heads of a read that are verified (one per lane 0 .. 7 of its wave)
-template <class K>
-__global__ void k_read_map(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph,
-                           u32 max_mismatch, u32 reads_per_wg, u32 chunks, int32_t* rec, u32* pile, u32* hist, unsigned long long* counters);
+__global__ void k_pair_place(ReadSet rs, GraphView gv, ContigIndex ci, u32 orient, u32 max_insert, u64 n_pairs, u32 chunks, int32_t* rec, u32* hist,
+                             unsigned long long* counters);
 
-// ---- kernels_mapgap.hip: gapped read mapping (include/gasm.h, "Gapped read mapping"): rec, rec_gap: 4 int32 per read each (16-byte aligned);
-// text: the contigs' ASCII; pile: 4 u32 per base of it, gap_pile: 2 u32 per base of it (deletions, insertions), hist: max_edits + 1 bins per
-// segment, counters: GASM_MAPG_COUNTERS per segment, the four zeroed by the caller
-#define GASM_MAPG_COUNTERS 8          // = GASM_MAPG_FIELDS of include/gasm.h (checked in pipeline.hip)
+// ---- kernels_map.hip: read mapping, ungapped (include/gasm.h, "Read mapping") and gapped ("Gapped read mapping"): one body, GAPPED = false
+// is the launch "k_read_map", GAPPED = true the launch "k_read_map_gapped"
+#define GASM_MAP_COUNTERS 7           // = GASM_MAP_FIELDS of include/gasm.h (checked in pipeline.hip)
+#define GASM_MAPG_COUNTERS 8          // = GASM_MAPG_FIELDS: the same seven and the gapped reads
+#define GASM_MAP_BLOCKS 8             // = GASM_MAP_MAX_BLOCKS: distinct heads of a read that are kept (one per lane 0 .. 7 of its wave)
 #define GASM_MAPG_GAP 16              // = GASM_MAP_MAX_GAP: the longest gap between two heads of a chain (its skipped bases take one lane each)
-template <class K>
-__global__ void k_read_map_gapped(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, const u64* c_off, const u32* seg_cstart, const u8* text, int have_graph,
-                                  u32 max_edits, u32 max_gap, u32 reads_per_wg, u32 chunks, int32_t* rec, int32_t* rec_gap, u32* pile, u32* gap_pile, u32* hist,
-                                  unsigned long long* counters);
+// rec: 4 int32 per read (16-byte aligned); pile: 4 u32 per base of the contig text; hist: max_edits + 1 bins per segment (ungapped: max_edits
+// is max_mismatch); counters: GASM_MAP_COUNTERS or GASM_MAPG_COUNTERS per segment.  Gapped only (else not read): rec_gap, 4 int32 per
+// read (16-byte aligned), and gap_pile, 2 u32 per base of the text (deletions, insertions).  All but the records zeroed by the caller
+struct MapOut {
+    int32_t *rec, *rec_gap;
+    u32 *pile, *gap_pile, *hist;
+    unsigned long long* counters;
+};
+template <class K, bool GAPPED>
+__global__ void k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 reads_per_wg, u32 chunks, MapOut out);
 
 // ---- kernels_score.hip
 struct SeedTable {

@@ -1,9 +1,9 @@
 // kernels_correct.hip — spectral read correction (include/gasm.h, "Read correction"): substitutions in the reads are repaired
 // against the distinct k-mers of a finished build.
 //   k_read_correct    one wave per read: membership of every k-mer, the weak runs, the candidates of every run, the fix
-#include "kernels.h"
-
-#define GASM_CORRECT_WAVES (GASM_WG / 64)
+// The pass's frame (segment, wave, the loop over a wave's reads, the counter flush): contig_index.h; of a finished build it needs the
+// k-mer set only.
+#include "contig_index.h"
 
 // is `key` one of the distinct k-mers of segment `seg`?  (bucket, bin, a one-or-two-key search, one key load)
 template <class K>
@@ -20,16 +20,8 @@ __device__ __forceinline__ K128 kflip(const K128& a, u32 x, int s) {
     return K128{a.hi ^ m.hi, a.lo ^ m.lo};
 }
 
-// word `src` (wave-uniform) of a 64-bit value that every lane holds one of
-__device__ __forceinline__ u64 lane_word(u64 v, u32 src) {
-    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)v, (int)src);
-    const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)src);
-    return ((u64)hi << 32) | lo;
-}
-
-// One wave per read, GASM_CORRECT_WAVES reads of one segment per workgroup and round (a segment's k-mers and directories stay in
-// one XCD's L2: seg_chunk).  The kernel is a gather: every k-mer costs the three dependent requests of graph_lower_bound + the key
-// (bucket pair, bin pair, key), and 64 lanes of a wave have 64 such chains in flight — there is nothing to stage in LDS and the
+// One wave per read, GASM_READ_WAVES reads of one segment per workgroup and round (ReadPass).  The kernel is a gather: every k-mer
+// costs the three dependent requests of graph_lower_bound + the key (bucket pair, bin pair, key), and 64 lanes of a wave have 64 such chains in flight — there is nothing to stage in LDS and the
 // registers are few, so the occupancy is the launch bound's.
 //   pass 1   lane j takes k-mer starts j, j + 64, ...; the weak bits of 64 starts are one __ballot, kept by lane w for word w (a read of
 //            GASM_CORRECT_KMER_CAP = 64 x 64 k-mers fills the wave's 64 lanes; no LDS).  No weak bit: the read is clean and the wave
@@ -45,115 +37,97 @@ __device__ __forceinline__ u64 lane_word(u64 v, u32 src) {
 // Every test reads the INPUT stream, every fix goes to the OUTPUT stream (a copy of the input made by the caller): runs are judged on
 // the read as given.
 // have_graph = 0: the build holds no k-mer at all (its arrays may not exist): every k-mer is weak.
-// stats: GASM_CORRECT_STATS counters per segment, zeroed by the caller; a workgroup sums its reads in LDS and adds each non-zero
-// counter once.
+// stats: GASM_CORRECT_STATS counters per segment (in the order of include/gasm.h: no k-mer, clean, corrected, partial, left, bases),
+// zeroed by the caller (flush_wave_counters).
 template <class K>
 __global__ void __launch_bounds__(GASM_WG) k_read_correct(ReadSet rs, GraphView gv, int have_graph, u32 reads_per_wg, u32 chunks,
                                                           unsigned long long* __restrict__ out_words, u32* __restrict__ stats) {
-    __shared__ u32 s_stat[GASM_CORRECT_STATS];
-    u32 seg, chunk;
-    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
-    if (threadIdx.x < GASM_CORRECT_STATS) s_stat[threadIdx.x] = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63u;
-    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int k = gv.k;
-    const u64 rbeg = rs.seg_read_off[seg], rend = rs.seg_read_off[seg + 1];
-    u32 c_nokmer = 0, c_clean = 0, c_corrected = 0, c_partial = 0, c_left = 0, c_bases = 0;      // of this wave's reads (wave-uniform)
-    for (u64 base = rbeg + (u64)chunk * reads_per_wg; base < rend; base += (u64)chunks * reads_per_wg) {
-        const u64 end = base + reads_per_wg < rend ? base + reads_per_wg : rend;
-        for (u64 r = base + wv; r < end; r += GASM_CORRECT_WAVES) {
-            u64 p0;
-            u32 len;
-            read_span(rs, r, &p0, &len);
-            if (len < (u32)k) { ++c_nokmer; continue; }
-            const u32 n = len - (u32)k + 1;
-            if (n > GASM_CORRECT_KMER_CAP || !have_graph) { ++c_left; continue; }
-            // ---- pass 1: the weak bits
-            const u32 nw = (n + 63u) >> 6;
-            u64 mymask = 0, any = 0;
-            for (u32 w = 0; w < nw; ++w) {
-                const u32 j = (w << 6) + lane;
-                bool weak = false;
-                if (j < n) weak = !kmer_trusted<K>(gv, seg, kmer_key_at<K>(rs.words, p0 + j, k));
-                const u64 m = __ballot(weak);
-                if (lane == w) mymask = m;
-                any |= m;
-            }
-            if (!any) { ++c_clean; continue; }
-            // ---- the runs (one more, empty, word closes a run that fills the last word to its end)
-            u32 n_runs = 0, n_fixed = 0, a = 0;
-            bool in_run = false;
-            for (u32 w = 0; w <= nw; ++w) {
-                const u64 m = w < nw ? lane_word(mymask, w) : 0ull;
-                u32 pos = 0;
-                while (pos < 64) {
-                    if (!in_run) {
-                        const u64 mm = m >> pos;
-                        if (!mm) break;
-                        pos += (u32)__builtin_ctzll(mm);
-                        a = (w << 6) + pos;
-                        in_run = true;
-                        continue;
+    __shared__ u32 s_cnt[GASM_CORRECT_STATS];
+    ReadPass rp;
+    if (!read_pass_begin(rp, rs, gv, nullptr, chunks, s_cnt)) return;
+    const u32 seg = rp.seg, lane = rp.lane;
+    const int k = rp.k;
+    enum { NOKMER, CLEAN, CORRECTED, PARTIAL, LEFT, BASES };
+    u32 c_cnt[GASM_CORRECT_STATS] = {0, 0, 0, 0, 0, 0};                           // of this wave's reads (wave-uniform)
+    for_wave_reads(rp, reads_per_wg, chunks, [&](u64 r) {
+        u64 p0;
+        u32 len;
+        read_span(rs, r, &p0, &len);
+        if (len < (u32)k) { ++c_cnt[NOKMER]; return; }
+        const u32 n = len - (u32)k + 1;
+        if (n > GASM_CORRECT_KMER_CAP || !have_graph) { ++c_cnt[LEFT]; return; }
+        // ---- pass 1: the weak bits
+        const u32 nw = (n + 63u) >> 6;
+        u64 mymask = 0, any = 0;
+        for (u32 w = 0; w < nw; ++w) {
+            const u32 j = (w << 6) + lane;
+            bool weak = false;
+            if (j < n) weak = !kmer_trusted<K>(gv, seg, kmer_key_at<K>(rs.words, p0 + j, k));
+            const u64 m = __ballot(weak);
+            if (lane == w) mymask = m;
+            any |= m;
+        }
+        if (!any) { ++c_cnt[CLEAN]; return; }
+        // ---- the runs (one more, empty, word closes a run that fills the last word to its end)
+        u32 n_runs = 0, n_fixed = 0, a = 0;
+        bool in_run = false;
+        for (u32 w = 0; w <= nw; ++w) {
+            const u64 m = w < nw ? lane_word(mymask, w) : 0ull;
+            u32 pos = 0;
+            while (pos < 64) {
+                if (!in_run) {
+                    const u64 mm = m >> pos;
+                    if (!mm) break;
+                    pos += (u32)__builtin_ctzll(mm);
+                    a = (w << 6) + pos;
+                    in_run = true;
+                    continue;
+                }
+                const u64 z = ~m >> pos;                 // the zero bits of m from pos on
+                if (!z) break;                           // the run goes on in the next word
+                pos += (u32)__builtin_ctzll(z);
+                const u32 b = (w << 6) + pos - 1;
+                in_run = false;
+                ++n_runs;
+                // ---- run [a, b]: where a single substitution would sit, if the rule tries this run at all
+                const u32 L = b - a + 1;
+                u32 p;
+                bool tried;
+                if (a == 0 && b == n - 1) { tried = false; p = 0; }                      // the whole read is weak
+                else if (a > 0 && b < n - 1) { tried = L == (u32)k; p = b; }             // interior: exactly k k-mers
+                else if (a == 0) { tried = L <= (u32)k; p = b; }                         // (a longer one holds k-mers without position b:
+                                                                                         // weak whatever stands there, no candidate fits)
+                else { tried = L <= (u32)k; p = a + (u32)k - 1; }                        // touches the end
+                if (!tried) continue;
+                const u32 total = 3 * L;
+                u32 fail = 0;                                                            // bit x - 1: candidate x does not fit
+                for (u32 it = 0; it < total && fail != 7u; it += 64) {
+                    const u32 idx = it + lane;
+                    const u32 c = (idx >= L ? 1u : 0u) + (idx >= 2 * L ? 1u : 0u);
+                    bool bad = false;
+                    if (idx < total) {
+                        const u32 j = a + idx - c * L;                                   // j <= p <= j + k - 1 for every j of the run
+                        const K key = kflip(kmer_key_at<K>(rs.words, p0 + j, k), c + 1, 2 * (k - 1 - (int)(p - j)));
+                        bad = !kmer_trusted<K>(gv, seg, key);
                     }
-                    const u64 z = ~m >> pos;                 // the zero bits of m from pos on
-                    if (!z) break;                           // the run goes on in the next word
-                    pos += (u32)__builtin_ctzll(z);
-                    const u32 b = (w << 6) + pos - 1;
-                    in_run = false;
-                    ++n_runs;
-                    // ---- run [a, b]: where a single substitution would sit, if the rule tries this run at all
-                    const u32 L = b - a + 1;
-                    u32 p;
-                    bool tried;
-                    if (a == 0 && b == n - 1) { tried = false; p = 0; }                      // the whole read is weak
-                    else if (a > 0 && b < n - 1) { tried = L == (u32)k; p = b; }             // interior: exactly k k-mers
-                    else if (a == 0) { tried = L <= (u32)k; p = b; }                         // (a longer one holds k-mers without position b:
-                                                                                             // weak whatever stands there, no candidate fits)
-                    else { tried = L <= (u32)k; p = a + (u32)k - 1; }                        // touches the end
-                    if (!tried) continue;
-                    const u32 total = 3 * L;
-                    u32 fail = 0;                                                            // bit x - 1: candidate x does not fit
-                    for (u32 it = 0; it < total && fail != 7u; it += 64) {
-                        const u32 idx = it + lane;
-                        const u32 c = (idx >= L ? 1u : 0u) + (idx >= 2 * L ? 1u : 0u);
-                        bool bad = false;
-                        if (idx < total) {
-                            const u32 j = a + idx - c * L;                                   // j <= p <= j + k - 1 for every j of the run
-                            const K key = kflip(kmer_key_at<K>(rs.words, p0 + j, k), c + 1, 2 * (k - 1 - (int)(p - j)));
-                            bad = !kmer_trusted<K>(gv, seg, key);
-                        }
-                        if (__ballot(bad && c == 0)) fail |= 1u;
-                        if (__ballot(bad && c == 1)) fail |= 2u;
-                        if (__ballot(bad && c == 2)) fail |= 4u;
-                    }
-                    if (fail == 6u || fail == 5u || fail == 3u) {                            // exactly one candidate fits
-                        const u32 x = fail == 6u ? 1u : fail == 5u ? 2u : 3u;
-                        const u64 P = p0 + p;
-                        if (lane == 0) atomicXor(&out_words[P >> 5], (unsigned long long)x << (62 - 2 * (u32)(P & 31)));
-                        ++n_fixed;
-                        ++c_bases;
-                    }
+                    if (__ballot(bad && c == 0)) fail |= 1u;
+                    if (__ballot(bad && c == 1)) fail |= 2u;
+                    if (__ballot(bad && c == 2)) fail |= 4u;
+                }
+                if (fail == 6u || fail == 5u || fail == 3u) {                            // exactly one candidate fits
+                    const u32 x = fail == 6u ? 1u : fail == 5u ? 2u : 3u;
+                    const u64 P = p0 + p;
+                    if (lane == 0) atomicXor(&out_words[P >> 5], (unsigned long long)x << (62 - 2 * (u32)(P & 31)));
+                    ++n_fixed;
+                    ++c_cnt[BASES];
                 }
             }
-            if (n_fixed == n_runs) ++c_corrected;
-            else if (n_fixed) ++c_partial;
-            else ++c_left;
         }
-    }
-    if (lane == 0) {
-        if (c_nokmer) atomicAdd(&s_stat[0], c_nokmer);
-        if (c_clean) atomicAdd(&s_stat[1], c_clean);
-        if (c_corrected) atomicAdd(&s_stat[2], c_corrected);
-        if (c_partial) atomicAdd(&s_stat[3], c_partial);
-        if (c_left) atomicAdd(&s_stat[4], c_left);
-        if (c_bases) atomicAdd(&s_stat[5], c_bases);
-    }
-    __syncthreads();
-    if (threadIdx.x < GASM_CORRECT_STATS) {
-        const u32 v = s_stat[threadIdx.x];
-        if (v) atomicAdd(&stats[(size_t)seg * GASM_CORRECT_STATS + threadIdx.x], v);
-    }
+        if (n_fixed == n_runs) ++c_cnt[CORRECTED];
+        else if (n_fixed) ++c_cnt[PARTIAL];
+        else ++c_cnt[LEFT];
+    });
+    flush_wave_counters(c_cnt, s_cnt, stats + (size_t)seg * GASM_CORRECT_STATS);
 }
 
 template __global__ void k_read_correct<u64>(ReadSet, GraphView, int, u32, u32, unsigned long long*, u32*);

@@ -3,10 +3,9 @@
 //   k_read_thread     one wave per read: every k-mer's contig and offset, the crossings from contig to contig (link support) and the
 //                     short contigs a read passes through from an in-edge to an out-edge (span support)
 //   k_pair_place      one lane per mate: where the two mates of a read pair lie on the contigs (include/gasm.h, "Read pairs")
-// All read the build's arrays only.  Where an edge lies (ContigIndex, kmer_contig) and a base of a packed stream (base_at): contig_index.h.
+// All read the build's arrays only.  Where an edge lies (ContigIndex, kmer_contig), a base of a packed stream (base_at) and the frame of
+// the two passes over the reads (ReadPass: segment, wave, the segment's edges and contigs, the counter flush): contig_index.h.
 #include "contig_index.h"
-
-#define GASM_THREAD_WAVES (GASM_WG / 64)
 
 // ================================================================================================================
 // succ / pred.  Contig c ends at node v(c) = its last k-1 bases and starts at node u(c) = its first k-1 bases (from the contig text, as
@@ -18,10 +17,10 @@
 //   x + u(c); 0xFFFFFFFF (the caller filled both arrays with it) where there is none.
 // ================================================================================================================
 template <class K>
-__global__ void __launch_bounds__(GASM_WG) k_contig_links(GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid, const u64* __restrict__ c_off,
-                                                          const u32* __restrict__ seg_cstart, const u8* __restrict__ text, u32 n_segments,
-                                                          u32* __restrict__ succ, u32* __restrict__ pred) {
-    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
+__global__ void __launch_bounds__(GASM_WG) k_contig_links(GraphView gv, ContigIndex ci, u32 n_segments, u32* __restrict__ succ, u32* __restrict__ pred) {
+    const u64* __restrict__ const c_off = ci.c_off;
+    const u32* __restrict__ const seg_cstart = ci.seg_cstart;
+    const u8* __restrict__ const text = ci.text;
     const u32 n = seg_cstart[n_segments];
     const u32 nb = 1u << gv.bbits;
     const int k = gv.k;
@@ -53,8 +52,8 @@ __global__ void __launch_bounds__(GASM_WG) k_contig_links(GraphView gv, const u6
         }
     }
 }
-template __global__ void k_contig_links<u64>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
-template __global__ void k_contig_links<K128>(GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, u32, u32*, u32*);
+template __global__ void k_contig_links<u64>(GraphView, ContigIndex, u32, u32*, u32*);
+template __global__ void k_contig_links<K128>(GraphView, ContigIndex, u32, u32*, u32*);
 
 // are the bits lo .. hi (inclusive) of the in-set words all set?  Word `w_now` is `m_now` (this chunk's ballot), the words behind it are
 // in LDS; lo >> 6 >= w_now
@@ -70,8 +69,8 @@ __device__ __forceinline__ bool run_in_set(const u64* in, u32 lo, u32 hi, u32 w_
 }
 
 // ================================================================================================================
-// Threading.  One wave per read, GASM_THREAD_WAVES reads of one segment per workgroup and round (seg_chunk: a segment's k-mers and
-// directories stay in one XCD's L2), chunks of 64 k-mer positions, as k_read_correct.  A gather like it: a look-up costs the three
+// Threading.  One wave per read, GASM_READ_WAVES reads of one segment per workgroup and round (ReadPass), chunks of 64 k-mer
+// positions, as k_read_correct.  A gather like it: a look-up costs the three
 // dependent requests of graph_lower_bound + the key, then the edge's link and the head's contig id — but only the first position of a
 // chunk and the positions behind a place where the read leaves its contig's text make one (below): the kernel is bound by the requests
 // it sends to L2, and most positions of a read follow their predecessor inside one contig.
@@ -84,92 +83,77 @@ __device__ __forceinline__ bool run_in_set(const u64* in, u32 lo, u32 hi, u32 w_
 // r is unbranched inside: after a crossing into r, a run of n(r) + 1 further positions in the set is r followed by one of its
 // out-edges (include/gasm.h), so the run of bits is the whole test.  x = first base of k-mer j, y = last base of k-mer j + 1 + n(r).
 //   link_support[4 a + last base of k-mer j + 1] += 1 per crossing, span_support[16 r + 4 x + y] += 1 per span (a, r: indices in the
-//   batch); skipped[seg] += 1 per read of more than GASM_THREAD_KMER_CAP k-mers.  All zeroed by the caller; integer atomics: exact.
-// text: the contigs' ASCII, as the build emitted it.  have_graph = 0: the build holds no contig at all (its arrays may not exist): only `skipped` is counted.
+//   batch); skipped[seg] += 1 per read of more than GASM_THREAD_KMER_CAP k-mers (the pass's one counter: flush_wave_counters).  All
+//   zeroed by the caller; integer atomics: exact.
+// ci.have_graph = 0: only `skipped` is counted.
 // ================================================================================================================
 template <class K>
-__global__ void __launch_bounds__(GASM_WG) k_read_thread(ReadSet rs, GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
-                                                         const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, const u8* __restrict__ text,
-                                                         int have_graph, u32 span_len, u32 reads_per_wg, u32 chunks, u32* __restrict__ link_support,
-                                                         u32* __restrict__ span_support, unsigned long long* __restrict__ skipped) {
-    __shared__ u64 s_in[GASM_THREAD_WAVES][GASM_THREAD_KMER_CAP / 64];
-    __shared__ u32 s_skip;
-    u32 seg, chunk;
-    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
-    if (threadIdx.x == 0) s_skip = 0;
-    __syncthreads();
-    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
-    const u32 lane = threadIdx.x & 63u;
-    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    u64* const in = s_in[wv];
-    const int k = gv.k;
-    u32 elo = 0, ehi = 0, c_lo = 0, c_hi = 0;
-    if (have_graph) {
-        const u32 nb = 1u << gv.bbits;
-        elo = gv.dstart[seg * nb]; ehi = gv.dstart[(seg + 1) * nb];
-        c_lo = seg_cstart[seg]; c_hi = seg_cstart[seg + 1];
-    }
-    const bool graph = elo < ehi && c_lo < c_hi;
-    const u64 rbeg = rs.seg_read_off[seg], rend = rs.seg_read_off[seg + 1];
-    u32 c_skip = 0;                                                           // of this wave's reads (wave-uniform)
-    for (u64 base = rbeg + (u64)chunk * reads_per_wg; base < rend; base += (u64)chunks * reads_per_wg) {
-        const u64 end = base + reads_per_wg < rend ? base + reads_per_wg : rend;
-        for (u64 r = base + wv; r < end; r += GASM_THREAD_WAVES) {
-            u64 p0;
-            u32 len;
-            read_span(rs, r, &p0, &len);
-            if (len < (u32)k) continue;
-            const u32 n = len - (u32)k + 1;
-            if (n > GASM_THREAD_KMER_CAP) { ++c_skip; continue; }
-            if (!graph) continue;
-            u32 nx_cid = GASM_NONE32, nx_off = 0;                             // position 64 (w + 1): lane 0 of the chunk before (none yet)
-            // the first position of every chunk, looked up by lane w for chunk w: one round of dependent requests for the whole read
-            const u32 nw = (n + 63u) >> 6;
-            u32 f_cid = GASM_NONE32, f_off = 0;
-            if (lane < nw && !kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kmer_key_at<K>(rs.words, p0 + (lane << 6), k), &f_cid, &f_off)) f_cid = GASM_NONE32;
-            for (u32 w = nw; w-- > 0;) {
-                const u32 j = (w << 6) + lane;
-                u32 cid = GASM_NONE32, off = 0;
-                // ---- the chunk's first position was looked up ahead of the loop.  Where it lies in a contig, the positions behind it that
-                // read on as the contig's text does lie in the same contig at the next offsets (k-mer j + 1 is k-mer j without its first
-                // base plus one more): one compare of the read's bases with the contig's text tells how far, and only the lanes behind
-                // the first difference, or behind the contig's end, look up for themselves
-                const u32 s_cid = (u32)__builtin_amdgcn_readlane((int)f_cid, (int)w), s_off = (u32)__builtin_amdgcn_readlane((int)f_off, (int)w);
-                bool known = lane == 0;
-                if (known) { cid = s_cid; off = s_off; }
-                if (s_cid != GASM_NONE32) {
-                    const u64 cb = c_off[s_cid], edges = c_off[s_cid + 1] - cb - (u64)(k - 1);
-                    const bool same = lane == 0 || (j < n && (u64)s_off + lane < edges &&
-                                                    base_at(rs.words, p0 + j + (u32)k - 1) == base_code(text[cb + s_off + lane + (u32)k - 1]));
-                    const u64 differ = ~__ballot(same);
-                    if (lane < (differ ? (u32)__builtin_ctzll(differ) : 64u)) { cid = s_cid; off = s_off + lane; known = true; }
-                }
-                if (!known && j < n && !kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kmer_key_at<K>(rs.words, p0 + j, k), &cid, &off)) cid = GASM_NONE32;
-                const u64 m = __ballot(cid != GASM_NONE32);
-                if (lane == 0) in[w] = m;
-                __builtin_amdgcn_wave_barrier();
-                u32 ncid = (u32)__shfl_down((int)cid, 1, 64), noff = (u32)__shfl_down((int)off, 1, 64);
-                if (lane == 63) { ncid = nx_cid; noff = nx_off; }
-                nx_cid = (u32)__builtin_amdgcn_readfirstlane((int)cid);
-                nx_off = (u32)__builtin_amdgcn_readfirstlane((int)off);
-                if (cid == GASM_NONE32 || ncid == GASM_NONE32 || (ncid == cid && noff == off + 1)) continue;
-                // ---- a crossing of (cid, ncid) between positions j and j + 1
-                atomicAdd(&link_support[4 * (size_t)cid + base_at(rs.words, p0 + j + (u32)k)], 1u);
-                if (!span_len) continue;
-                const u64 rlen = c_off[ncid + 1] - c_off[ncid];
-                if (rlen > (u64)span_len || rlen < (u64)k) continue;
-                const u32 last = j + 1 + (u32)(rlen - (u64)(k - 1));          // the position of the out-edge behind ncid
-                if (last >= n || !run_in_set(in, j + 1, last, w, m)) continue;
-                atomicAdd(&span_support[16 * (size_t)ncid + 4 * base_at(rs.words, p0 + j) + base_at(rs.words, p0 + last + (u32)k - 1)], 1u);
+__global__ void __launch_bounds__(GASM_WG) k_read_thread(ReadSet rs, GraphView gv, ContigIndex ci, u32 span_len, u32 reads_per_wg, u32 chunks,
+                                                         u32* __restrict__ link_support, u32* __restrict__ span_support,
+                                                         unsigned long long* __restrict__ skipped) {
+    __shared__ u64 s_in[GASM_READ_WAVES][GASM_THREAD_KMER_CAP / 64];
+    __shared__ u32 s_cnt[1];
+    ReadPass rp;
+    if (!read_pass_begin(rp, rs, gv, &ci, chunks, s_cnt)) return;
+    const u64* __restrict__ const c_off = ci.c_off;
+    const u8* __restrict__ const text = ci.text;
+    const u32 lane = rp.lane;
+    u64* const in = s_in[rp.wv];
+    const int k = rp.k;
+    u32 c_cnt[1] = {0};                                                       // of this wave's reads (wave-uniform)
+    for_wave_reads(rp, reads_per_wg, chunks, [&](u64 r) {
+        u64 p0;
+        u32 len;
+        read_span(rs, r, &p0, &len);
+        if (len < (u32)k) return;
+        const u32 n = len - (u32)k + 1;
+        if (n > GASM_THREAD_KMER_CAP) { ++c_cnt[0]; return; }
+        if (!rp.graph) return;
+        u32 nx_cid = GASM_NONE32, nx_off = 0;                             // position 64 (w + 1): lane 0 of the chunk before (none yet)
+        // the first position of every chunk, looked up by lane w for chunk w: one round of dependent requests for the whole read
+        const u32 nw = (n + 63u) >> 6;
+        u32 f_cid = GASM_NONE32, f_off = 0;
+        if (lane < nw && !kmer_contig<K>(gv, ci, rp, kmer_key_at<K>(rs.words, p0 + (lane << 6), k), &f_cid, &f_off)) f_cid = GASM_NONE32;
+        for (u32 w = nw; w-- > 0;) {
+            const u32 j = (w << 6) + lane;
+            u32 cid = GASM_NONE32, off = 0;
+            // ---- the chunk's first position was looked up ahead of the loop.  Where it lies in a contig, the positions behind it that
+            // read on as the contig's text does lie in the same contig at the next offsets (k-mer j + 1 is k-mer j without its first
+            // base plus one more): one compare of the read's bases with the contig's text tells how far, and only the lanes behind
+            // the first difference, or behind the contig's end, look up for themselves
+            const u32 s_cid = (u32)__builtin_amdgcn_readlane((int)f_cid, (int)w), s_off = (u32)__builtin_amdgcn_readlane((int)f_off, (int)w);
+            bool known = lane == 0;
+            if (known) { cid = s_cid; off = s_off; }
+            if (s_cid != GASM_NONE32) {
+                const u64 cb = c_off[s_cid], edges = c_off[s_cid + 1] - cb - (u64)(k - 1);
+                const bool same = lane == 0 || (j < n && (u64)s_off + lane < edges &&
+                                                base_at(rs.words, p0 + j + (u32)k - 1) == base_code(text[cb + s_off + lane + (u32)k - 1]));
+                const u64 differ = ~__ballot(same);
+                if (lane < (differ ? (u32)__builtin_ctzll(differ) : 64u)) { cid = s_cid; off = s_off + lane; known = true; }
             }
+            if (!known && j < n && !kmer_contig<K>(gv, ci, rp, kmer_key_at<K>(rs.words, p0 + j, k), &cid, &off)) cid = GASM_NONE32;
+            const u64 m = __ballot(cid != GASM_NONE32);
+            if (lane == 0) in[w] = m;
+            __builtin_amdgcn_wave_barrier();
+            u32 ncid = (u32)__shfl_down((int)cid, 1, 64), noff = (u32)__shfl_down((int)off, 1, 64);
+            if (lane == 63) { ncid = nx_cid; noff = nx_off; }
+            nx_cid = (u32)__builtin_amdgcn_readfirstlane((int)cid);
+            nx_off = (u32)__builtin_amdgcn_readfirstlane((int)off);
+            if (cid == GASM_NONE32 || ncid == GASM_NONE32 || (ncid == cid && noff == off + 1)) continue;
+            // ---- a crossing of (cid, ncid) between positions j and j + 1
+            atomicAdd(&link_support[4 * (size_t)cid + base_at(rs.words, p0 + j + (u32)k)], 1u);
+            if (!span_len) continue;
+            const u64 rlen = c_off[ncid + 1] - c_off[ncid];
+            if (rlen > (u64)span_len || rlen < (u64)k) continue;
+            const u32 last = j + 1 + (u32)(rlen - (u64)(k - 1));          // the position of the out-edge behind ncid
+            if (last >= n || !run_in_set(in, j + 1, last, w, m)) continue;
+            atomicAdd(&span_support[16 * (size_t)ncid + 4 * base_at(rs.words, p0 + j) + base_at(rs.words, p0 + last + (u32)k - 1)], 1u);
         }
-    }
-    if (lane == 0 && c_skip) atomicAdd(&s_skip, c_skip);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_skip) atomicAdd(&skipped[seg], (unsigned long long)s_skip);
+    });
+    flush_wave_counters(c_cnt, s_cnt, skipped + rp.seg);
 }
-template __global__ void k_read_thread<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, u32*, u32*, unsigned long long*);
-template __global__ void k_read_thread<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, u32*, u32*, unsigned long long*);
+template __global__ void k_read_thread<u64>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32*, u32*, unsigned long long*);
+template __global__ void k_read_thread<K128>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32*, u32*, unsigned long long*);
 
 // ================================================================================================================
 // Read pairs (include/gasm.h, "Read pairs").  Reads 2p and 2p + 1 of a segment are the mates of pair p; an ORIENTED pair (first, second)
@@ -178,7 +162,7 @@ template __global__ void k_read_thread<K128>(ReadSet, GraphView, const u64*, con
 // numbering and would save one ALU op per look-up of a kernel that waits on L2).  orient = 2 (after a strands = 2 build) adds
 // (mate 2, mate 1): four scans per pair, two otherwise.
 // Layout: ONE LANE PER SCAN, lane = (pair in the wave) * 2 orient + orientation * 2 + role, role 0 = `first`, role 1 = `second`: 32 or 16
-// pairs per wave, 4 waves of pairs per workgroup and round, the workgroups of a segment on one XCD (seg_chunk), as k_read_thread.
+// pairs per wave, 4 waves of pairs per workgroup and round, in k_read_thread's frame (ReadPass) with a loop of its own: over pairs.
 //   1. every lane looks up position 0 of its mate: after a good build nearly every mate hits there, so one round of dependent requests
 //      (graph_lower_bound's three + the key, the edge's link, the head's contig id) places 64 scans at once;
 //   2. the lanes that missed are taken one after the other by the whole wave: 64 positions per chunk from position 1 on, one look-up per
@@ -186,39 +170,26 @@ template __global__ void k_read_thread<K128>(ReadSet, GraphView, const u64*, con
 //   3. the two roles of an oriented pair sit in neighbouring lanes: the even lane takes (c2, E) from the odd one, writes the record as
 //      one 16-byte store, classifies, and adds to its histogram bin (a no-return atomic; the bins of a segment are few and hot, which
 //      the memory side serialises — measured in profiles/pairs/README.md).  The six counters are ballots summed per wave in
-//      scalars, then through LDS per workgroup, then six atomics per workgroup, as s_skip of k_read_thread.
+//      scalars, then flush_wave_counters.
 // A pair with a mate of more than GASM_THREAD_KMER_CAP k-mers is skipped before any look-up.  rec: 4 int32 per oriented pair at
 // (o * n_pairs + p) * 4 (16-byte aligned), every pair of every segment written; hist: max_insert + 1 bins per segment, counters:
 // GASM_PAIR_COUNTERS per segment, both zeroed by the caller.  Every segment holds an even number of reads (the host checked).
-// have_graph = 0: the build holds no contig at all (its arrays may not exist): no mate is placed.
+// ci.have_graph = 0: no mate is placed.
 // ================================================================================================================
 template <class K>
-__global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
-                                                        const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, int have_graph, u32 orient,
-                                                        u32 max_insert, u64 n_pairs, u32 chunks, int32_t* __restrict__ rec, u32* __restrict__ hist,
-                                                        unsigned long long* __restrict__ counters) {
+__global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv, ContigIndex ci, u32 orient, u32 max_insert, u64 n_pairs, u32 chunks,
+                                                        int32_t* __restrict__ rec, u32* __restrict__ hist, unsigned long long* __restrict__ counters) {
     __shared__ u32 s_cnt[GASM_PAIR_COUNTERS];
-    u32 seg, chunk;
-    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
-    if (threadIdx.x < GASM_PAIR_COUNTERS) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
-    const u32 lane = threadIdx.x & 63u;
-    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int k = gv.k;
-    u32 elo = 0, ehi = 0, c_lo = 0, c_hi = 0;
-    if (have_graph) {
-        const u32 nb = 1u << gv.bbits;
-        elo = gv.dstart[seg * nb]; ehi = gv.dstart[(seg + 1) * nb];
-        c_lo = seg_cstart[seg]; c_hi = seg_cstart[seg + 1];
-    }
-    const bool graph = elo < ehi && c_lo < c_hi;
-    const u64 pbeg = rs.seg_read_off[seg] >> 1, pend = rs.seg_read_off[seg + 1] >> 1;
+    ReadPass rp;
+    if (!read_pass_begin(rp, rs, gv, &ci, chunks, s_cnt)) return;
+    const u32 seg = rp.seg, lane = rp.lane, wv = rp.wv, c_lo = rp.c_lo;
+    const int k = rp.k;
+    const u64 pbeg = rp.rbeg >> 1, pend = rp.rend >> 1;
     const u32 two = orient == 2 ? 1u : 0u;
     const u32 role = lane & 1u, o = two ? (lane >> 1) & 1u : 0u, lp = lane >> (1 + two);
-    const u32 pairs_per_wave = 32u >> two, pairs_per_wg = GASM_THREAD_WAVES * pairs_per_wave;
+    const u32 pairs_per_wave = 32u >> two, pairs_per_wg = GASM_READ_WAVES * pairs_per_wave;
     u32 c_cnt[GASM_PAIR_COUNTERS] = {0, 0, 0, 0, 0, 0};                       // of this wave's oriented pairs (wave-uniform)
-    for (u64 base = pbeg + (u64)chunk * pairs_per_wg; base < pend; base += (u64)chunks * pairs_per_wg) {
+    for (u64 base = pbeg + (u64)rp.chunk * pairs_per_wg; base < pend; base += (u64)chunks * pairs_per_wg) {
         const u64 p = base + (u64)wv * pairs_per_wave + lp;
         const bool valid = p < pend;
         u64 p0 = 0;
@@ -234,7 +205,7 @@ __global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv
             const u32 on = olen >= (u32)k ? olen - (u32)k + 1 : 0;
             skip = n > GASM_THREAD_KMER_CAP || on > GASM_THREAD_KMER_CAP;
         }
-        const bool active = valid && !skip && graph && n > 0;
+        const bool active = valid && !skip && rp.graph && n > 0;
         // ---- 1. position 0 of every mate
         bool found = false;
         u32 r_cid = GASM_NONE32;
@@ -243,7 +214,7 @@ __global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv
             K key = kmer_key_at<K>(rs.words, p0, k);
             if (role) key = key_revcomp<K>(key, k);
             u32 cid, off;
-            if (kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, key, &cid, &off)) {
+            if (kmer_contig<K>(gv, ci, rp, key, &cid, &off)) {
                 found = true; r_cid = cid; r_pos = role ? (int)off + k : (int)off;
             }
         }
@@ -252,7 +223,7 @@ __global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv
         while (need) {
             const int L = __builtin_ctzll(need);
             need &= need - 1;
-            const u64 b_p0 = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(p0 >> 32), L) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)p0, L);
+            const u64 b_p0 = lane_word(p0, (u32)L);
             const u32 b_n = (u32)__builtin_amdgcn_readlane((int)n, L);
             const bool b_rc = (L & 1) != 0;
             for (u32 j0 = 1; j0 < b_n; j0 += 64) {
@@ -262,7 +233,7 @@ __global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv
                 if (j < b_n) {
                     K key = kmer_key_at<K>(rs.words, b_p0 + j, k);
                     if (b_rc) key = key_revcomp<K>(key, k);
-                    hit = kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, key, &cid, &off);
+                    hit = kmer_contig<K>(gv, ci, rp, key, &cid, &off);
                 }
                 const u64 m = __ballot(hit);
                 if (!m) continue;
@@ -291,150 +262,7 @@ __global__ void __launch_bounds__(GASM_WG) k_pair_place(ReadSet rs, GraphView gv
 #pragma unroll
         for (u32 f = 0; f < GASM_PAIR_COUNTERS; ++f) c_cnt[f] += (u32)__popcll(__ballot(cls == f));
     }
-    if (lane == 0) {
-#pragma unroll
-        for (u32 f = 0; f < GASM_PAIR_COUNTERS; ++f)
-            if (c_cnt[f]) atomicAdd(&s_cnt[f], c_cnt[f]);
-    }
-    __syncthreads();
-    if (threadIdx.x < GASM_PAIR_COUNTERS && s_cnt[threadIdx.x]) atomicAdd(&counters[(size_t)seg * GASM_PAIR_COUNTERS + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    flush_wave_counters(c_cnt, s_cnt, counters + (size_t)seg * GASM_PAIR_COUNTERS);
 }
-template __global__ void k_pair_place<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, int, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);
-template __global__ void k_pair_place<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, int, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);
-
-// ================================================================================================================
-// Read mapping (include/gasm.h, "Read mapping").  One wave per read, GASM_THREAD_WAVES reads of one segment per workgroup and round, the
-// workgroups of a segment on one XCD (seg_chunk), chunks of 64 k-mer positions taken first to last, as k_read_thread.
-//   SEEDS.  One look-up per lane and chunk (kmer_contig): lane's position j, its contig and its diagonal d = offset - j.
-//   HEADS.  A seeded lane compares its (contig, d) with the PREVIOUS SEEDED lane's: the highest set bit of the seed ballot below the
-//   lane inside the chunk (one cross-lane move), the scalar carry (prev_c, prev_d) across the chunk seam.  One ballot per chunk.
-//   HEAD LOOP, wave-uniform: a head is taken by count-trailing-zeros, its (contig, d) fetched from its lane, compared with the kept
-//   heads — head i of the read sits in lane i's registers (my_c, my_d), so the compare is one ballot and the list takes no LDS —, then
-//   verified with the 64 lanes striding over the overlap: read base from the packed stream, contig base from the build's ASCII text,
-//   ballot and popcount, stopping once m > max_mismatch.  An accepted block walks its overlap once more for the pileup: one no-return
-//   atomic add per lane and base.  The histogram add is per block, the record one 16-byte store by lane 0.
-//   COUNTERS as in k_pair_place: per wave in scalars, one LDS atomic per non-zero counter and wave, one global atomic per non-zero
-//   counter and workgroup.
-// Every index is bounded before use: a head's contig is inside the segment (kmer_contig), the overlap [lo, hi) is clamped to the read and
-// to the contig's bases, so d + i lies in [0, len(c)) and the pileup entry inside the contig's 4 len(c) words.
-// rec: 4 int32 per read (16-byte aligned), every read of every segment written; pile: 4 u32 per base of the contig text, hist:
-// max_mismatch + 1 per segment, counters: GASM_MAP_COUNTERS per segment, all three zeroed by the caller.
-// have_graph = 0: the build holds no contig at all (its arrays may not exist): only short, skipped and unseeded are counted.
-// ================================================================================================================
-template <class K>
-__global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, const u64* __restrict__ link, const u32* __restrict__ e_cid,
-                                                      const u64* __restrict__ c_off, const u32* __restrict__ seg_cstart, const u8* __restrict__ text,
-                                                      int have_graph, u32 max_mismatch, u32 reads_per_wg, u32 chunks, int32_t* __restrict__ rec,
-                                                      u32* __restrict__ pile, u32* __restrict__ hist, unsigned long long* __restrict__ counters) {
-    __shared__ u32 s_cnt[GASM_MAP_COUNTERS];
-    u32 seg, chunk;
-    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
-    if (threadIdx.x < GASM_MAP_COUNTERS) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const ContigIndex ci{link, e_cid, c_off, seg_cstart};
-    const u32 lane = threadIdx.x & 63u;
-    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int k = gv.k;
-    u32 elo = 0, ehi = 0, c_lo = 0, c_hi = 0;
-    if (have_graph) {
-        const u32 nb = 1u << gv.bbits;
-        elo = gv.dstart[seg * nb]; ehi = gv.dstart[(seg + 1) * nb];
-        c_lo = seg_cstart[seg]; c_hi = seg_cstart[seg + 1];
-    }
-    const bool graph = elo < ehi && c_lo < c_hi;
-    const u64 rbeg = rs.seg_read_off[seg], rend = rs.seg_read_off[seg + 1];
-    u32 c_cnt[GASM_MAP_COUNTERS] = {0, 0, 0, 0, 0, 0, 0};                     // of this wave's reads (wave-uniform)
-    for (u64 base = rbeg + (u64)chunk * reads_per_wg; base < rend; base += (u64)chunks * reads_per_wg) {
-        const u64 end = base + reads_per_wg < rend ? base + reads_per_wg : rend;
-        for (u64 r = base + wv; r < end; r += GASM_THREAD_WAVES) {
-            u64 p0;
-            u32 len;
-            read_span(rs, r, &p0, &len);
-            const u32 n = len >= (u32)k ? len - (u32)k + 1 : 0;
-            u32 cls;                                                          // the read's counter
-            u32 n_heads = 0, n_acc = 0, dropped = 0, b_ov = 0, b_m = 0, b_c = 0;
-            int b_d = 0;
-            bool seeded_any = false;
-            if (n == 0) cls = 0;
-            else if (n > GASM_THREAD_KMER_CAP) cls = 1;
-            else if (!graph) cls = 2;
-            else {
-                u32 my_c = GASM_NONE32, prev_c = GASM_NONE32;                 // lane i: kept head i; the last seeded position before this chunk
-                int my_d = 0, prev_d = 0;
-                const u32 nw = (n + 63u) >> 6;
-                for (u32 w = 0; w < nw; ++w) {
-                    const u32 j = (w << 6) + lane;
-                    u32 cid = GASM_NONE32, off = 0;
-                    if (j < n && !kmer_contig<K>(gv, ci, seg, elo, ehi, c_lo, c_hi, kmer_key_at<K>(rs.words, p0 + j, k), &cid, &off)) cid = GASM_NONE32;
-                    const int d = (int)off - (int)j;
-                    const u64 sm = __ballot(cid != GASM_NONE32);
-                    if (!sm) continue;
-                    seeded_any = true;
-                    // ---- heads: compare with the previous seeded lane (inside the chunk), or with the carry
-                    const u64 below = sm & ((1ull << lane) - 1ull);
-                    const int src = below ? 63 - __builtin_clzll(below) : (int)lane;
-                    u32 pc = (u32)__shfl((int)cid, src, 64);
-                    int pd = __shfl(d, src, 64);
-                    if (!below) { pc = prev_c; pd = prev_d; }
-                    u64 hb = __ballot(cid != GASM_NONE32 && (pc != cid || pd != d));
-                    const int last = 63 - __builtin_clzll(sm);
-                    prev_c = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)cid, last, 64));
-                    prev_d = __builtin_amdgcn_readfirstlane(__shfl(d, last, 64));
-                    // ---- the head loop (wave-uniform)
-                    while (hb) {
-                        const int L = __builtin_ctzll(hb);
-                        hb &= hb - 1;
-                        const u32 h_c = (u32)__builtin_amdgcn_readfirstlane(__shfl((int)cid, L, 64));
-                        const int h_d = __builtin_amdgcn_readfirstlane(__shfl(d, L, 64));
-                        if (__ballot(lane < n_heads && my_c == h_c && my_d == h_d)) continue;      // A, B, A
-                        if (n_heads == GASM_MAP_BLOCKS) { ++dropped; continue; }
-                        if (lane == n_heads) { my_c = h_c; my_d = h_d; }
-                        ++n_heads;
-                        // ---- verify: read base i against contig base d + i over [lo, hi)
-                        const u64 cb = c_off[h_c];
-                        const long long clen = (long long)(c_off[h_c + 1] - cb);
-                        const long long lo = h_d < 0 ? -(long long)h_d : 0;
-                        long long hi = clen - (long long)h_d;
-                        if (hi > (long long)len) hi = (long long)len;
-                        if (hi <= lo) continue;                                // (no finished build gives this: a k-mer of c lies inside c)
-                        u32 m = 0;
-                        for (long long i0 = lo; i0 < hi && m <= max_mismatch; i0 += 64) {
-                            const long long i = i0 + lane;
-                            const bool differ = i < hi && base_at(rs.words, p0 + (u64)i) != base_code(text[cb + (u64)((long long)h_d + i)]);
-                            m += (u32)__popcll(__ballot(differ));
-                        }
-                        if (m > max_mismatch) continue;
-                        // ---- accepted: pileup, histogram, best block
-                        for (long long i0 = lo; i0 < hi; i0 += 64) {
-                            const long long i = i0 + lane;
-                            if (i < hi) atomicAdd(&pile[4 * (cb + (u64)((long long)h_d + i)) + base_at(rs.words, p0 + (u64)i)], 1u);
-                        }
-                        if (lane == 0) atomicAdd(&hist[(size_t)seg * (max_mismatch + 1) + m], 1u);
-                        const u32 ov = (u32)(hi - lo);
-                        if (n_acc == 0 || ov > b_ov || (ov == b_ov && m < b_m)) { b_ov = ov; b_m = m; b_c = h_c; b_d = h_d; }
-                        ++n_acc;
-                    }
-                }
-                cls = !seeded_any ? 2u : n_acc == 0 ? 3u : n_acc == 1 ? 4u : 5u;
-            }
-            if (lane == 0) {
-                int4 v;
-                v.x = n_acc ? (int)(b_c - c_lo) : -1; v.y = n_acc ? b_d : 0;
-                v.z = n_acc ? (int)(b_m | (n_acc << 16)) : 0; v.w = (int)b_ov;
-                *reinterpret_cast<int4*>(rec + r * 4) = v;
-            }
-#pragma unroll
-            for (u32 f = 0; f < 6; ++f) c_cnt[f] += cls == f ? 1u : 0u;
-            c_cnt[6] += dropped;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (u32 f = 0; f < GASM_MAP_COUNTERS; ++f)
-            if (c_cnt[f]) atomicAdd(&s_cnt[f], c_cnt[f]);
-    }
-    __syncthreads();
-    if (threadIdx.x < GASM_MAP_COUNTERS && s_cnt[threadIdx.x]) atomicAdd(&counters[(size_t)seg * GASM_MAP_COUNTERS + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-}
-template __global__ void k_read_map<u64>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, int32_t*, u32*, u32*, unsigned long long*);
-template __global__ void k_read_map<K128>(ReadSet, GraphView, const u64*, const u32*, const u64*, const u32*, const u8*, int, u32, u32, u32, int32_t*, u32*, u32*, unsigned long long*);
+template __global__ void k_pair_place<u64>(ReadSet, GraphView, ContigIndex, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);
+template __global__ void k_pair_place<K128>(ReadSet, GraphView, ContigIndex, u32, u32, u64, u32, int32_t*, u32*, unsigned long long*);

@@ -106,6 +106,48 @@ struct RoundStats {
     std::vector<u32> h_contigs, h_kmers;    // pipeline_fetch_round_stats: [s * max_rounds + r]
 };
 
+// The tables a pass over a finished build writes, back to back in one device array in the order given, each at a multiple of its
+// alignment (records that are stored 16 bytes at a time on 16, 64-bit counters on 8).  The queue function clears the array from the
+// first `zeroed` table to its end with one memset, so the zeroed tables come last
+struct PassTable {
+    size_t n, elem, align;                  // elements, bytes per element, alignment in bytes
+    bool zeroed;
+    size_t off = 0;                         // set by PassLayout
+    size_t bytes() const { return n * elem; }
+};
+struct PassLayout {
+    std::vector<PassTable> t;
+    size_t bytes = 0, zero_from = 0;        // of the whole array; where the first zeroed table starts
+    PassLayout(std::initializer_list<PassTable> tables) : t(tables) {
+        bool z = false;
+        for (PassTable& x : t) {
+            x.off = (bytes + x.align - 1) / x.align * x.align;
+            if (x.zeroed && !z) { z = true; zero_from = x.off; }
+            bytes = x.off + x.bytes();
+        }
+        if (!z) zero_from = bytes;
+    }
+    template <class T> T* at(const DBuf& d, size_t i) const { return reinterpret_cast<T*>(static_cast<char*>(d.p) + t[i].off); }
+};
+// What such a pass leaves: its device array, after its fetch the host copy of every table (in 8-byte words, one entry more than the table
+// holds, so there is a pointer to hand out for an empty one), and what the layout of the last call depended on
+struct PassState {
+    DBuf d;
+    std::vector<std::vector<u64>> h;
+    bool queued = false;                    // the pass ran on the arrays of this build (pipeline_build clears it)
+    u32 param[2] = {0, 0};
+    template <class T> const T* host(size_t i) const { return reinterpret_cast<const T*>(h[i].data()); }
+};
+// the tables of the four passes, in layout order: u32 succ[4P], pred[4P], link_support[4P], span_support[16P], u64 skipped[S];
+// int32 rec[4 * orientations * pairs], u32 insert_hist[S * (max_insert + 1)], u64 counters[S * GASM_PAIR_FIELDS];
+// int32 rec[4 * reads], u32 pile[4 * contig bases], mismatch_hist[S * (max_mismatch + 1)], u64 counters[S * GASM_MAP_FIELDS];
+// int32 rec[4 * reads], rec_gap[4 * reads], u32 pile[4 * contig bases], gap_pile[2 * contig bases], edit_hist[S * (max_edits + 1)],
+// u64 counters[S * GASM_MAPG_FIELDS]
+enum { LINKS_SUCC, LINKS_PRED, LINKS_LSUP, LINKS_SSUP, LINKS_SKIPPED };
+enum { PAIRS_REC, PAIRS_HIST, PAIRS_CNT };
+enum { MAP_REC, MAP_PILE, MAP_HIST, MAP_CNT };
+enum { MAPG_REC, MAPG_GAP, MAPG_PILE, MAPG_GPILE, MAPG_HIST, MAPG_CNT };
+
 struct BuildState {
     // ---- plan (host-side, from the reads): key width, tile shape, partition
     int k = 0, bbits = 0, fbits = 9, words = 1, bb_cap = 0;
@@ -162,33 +204,10 @@ struct BuildState {
     std::vector<u64> h_ccov_m;
     std::vector<u32> h_ccov_n;
     bool coverage_queued = false;           // k_contig_cov ran on the arrays of this build
-    DBuf d_links;                           // contig links of the last build (pipeline_contig_links): u32 succ[4P], pred[4P], link_support[4P],
-                                            // span_support[16P], then u64 skipped[S]
-    std::vector<u32> h_succ, h_pred, h_link_support, h_span_support;
-    std::vector<u64> h_links_skipped;
-    bool links_queued = false;              // k_contig_links and k_read_thread ran on the arrays of this build
-    DBuf d_pairs;                           // read-pair places of the last build (pipeline_place_pairs): int32 rec[4 * orientations * pairs], then
-                                            // u32 insert_hist[S * (max_insert + 1)] (padded to 8 bytes), then u64 counters[S * GASM_PAIR_FIELDS]
-    std::vector<int32_t> h_pair_rec;
-    std::vector<u32> h_pair_hist;
-    std::vector<u64> h_pair_counters;
-    u32 pairs_orient = 0, pairs_max_insert = 0;     // of the last placement
-    bool pairs_queued = false;              // k_pair_place ran on the arrays of this build
-    DBuf d_map;                             // read mapping of the last build (pipeline_map_reads): int32 rec[4 * reads], then u32 pile[4 * contig bases],
-                                            // u32 mismatch_hist[S * (max_mismatch + 1)] (padded to 8 bytes), then u64 counters[S * GASM_MAP_FIELDS]
-    std::vector<int32_t> h_map_rec;
-    std::vector<u32> h_map_pile, h_map_hist;
-    std::vector<u64> h_map_counters;
-    u32 map_max_mismatch = 0;               // of the last mapping
-    bool map_queued = false;                // k_read_map ran on the arrays of this build
-    DBuf d_mapg;                            // gapped read mapping of the last build (pipeline_map_reads_gapped): int32 rec[4 * reads], rec_gap[4 * reads],
-                                            // then u32 pile[4 * contig bases], gap_pile[2 * contig bases], edit_hist[S * (max_edits + 1)] (padded to
-                                            // 8 bytes), then u64 counters[S * GASM_MAPG_FIELDS]
-    std::vector<int32_t> h_mapg_rec, h_mapg_gap;
-    std::vector<u32> h_mapg_pile, h_mapg_gpile, h_mapg_hist;
-    std::vector<u64> h_mapg_counters;
-    u32 mapg_max_edits = 0;                 // of the last gapped mapping
-    bool mapg_queued = false;               // k_read_map_gapped ran on the arrays of this build
+    // the passes that lay reads over the last build, each with the tables listed at its enum below: contig links (pipeline_contig_links),
+    // read-pair places (pipeline_place_pairs; param: orientations, max_insert), read mapping and gapped read mapping (pipeline_map_reads;
+    // param: max_mismatch / max_edits) — the two mappings independent of each other
+    PassState links, pairs, map, mapg;
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -278,29 +297,24 @@ int pipeline_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // Contig links (kernels_links.hip; the rule: include/gasm.h "Contig links") of the finished build: queue k_contig_links and k_read_thread on the
 // build's stream behind it (they read the build's arrays, the contig text and the reads `rd` the build was made from — the both-strand stream
-// of a strands = 2 build, so every read and its reverse complement are threaded), then fetch h_succ / h_pred / h_link_support (4 per contig),
-// h_span_support (16 per contig) and h_links_skipped (per segment; reads, each once whatever the strands).  Positioned reads (pooled
+// of a strands = 2 build, so every read and its reverse complement are threaded), then fetch bs.links' tables: succ / pred / link support
+// (4 per contig), span support (16 per contig) and skipped (per segment; reads, each once whatever the strands).  Positioned reads (pooled
 // builds): GASM_ERR_STATE
 int pipeline_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 span_len);
 int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // Read pairs (k_pair_place in kernels_links.hip; the rule: include/gasm.h "Read pairs") of the finished build: queue the kernel on the build's
 // stream behind it (it reads the build's arrays and the batch's OWN reads `rd`, in which reads 2p and 2p + 1 are pair p — `rd_build` is what
-// the build was made from: the both-strand stream of a strands = 2 build, which then makes two orientations per pair), then fetch h_pair_rec
-// (4 per oriented pair), h_pair_hist (max_insert + 1 per segment) and h_pair_counters (GASM_PAIR_FIELDS per segment).  A segment with an odd
-// number of reads: GASM_ERR_INVALID.  Positioned reads (pooled builds): GASM_ERR_STATE
+// the build was made from: the both-strand stream of a strands = 2 build, which then makes two orientations per pair), then fetch bs.pairs'
+// tables: records (4 per oriented pair), insert histogram (max_insert + 1 per segment) and counters (GASM_PAIR_FIELDS per segment).  A
+// segment with an odd number of reads: GASM_ERR_INVALID.  Positioned reads (pooled builds): GASM_ERR_STATE
 int pipeline_place_pairs(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_insert);
 int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
-// Read mapping (k_read_map in kernels_links.hip; the rule: include/gasm.h "Read mapping") of the finished build: queue the kernel on the build's
-// stream behind it (it reads the build's arrays and the batch's OWN reads `rd`, as given, whatever the build's strands), then fetch h_map_rec
-// (4 per read), h_map_pile (4 per contig base), h_map_hist (max_mismatch + 1 per segment) and h_map_counters (GASM_MAP_FIELDS per segment)
-int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_mismatch);
-int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
-// Gapped read mapping (k_read_map_gapped in kernels_mapgap.hip; the rule: include/gasm.h "Gapped read mapping") of the finished build, beside
-// pipeline_map_reads and independent of it (an array, host vectors and a flag of its own): then fetch h_mapg_rec and h_mapg_gap (4 per read
-// each), h_mapg_pile (4 per contig base), h_mapg_gpile (2 per contig base), h_mapg_hist (max_edits + 1 per segment) and h_mapg_counters
-// (GASM_MAPG_FIELDS per segment)
-int pipeline_map_reads_gapped(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_edits, u32 max_gap);
-int pipeline_fetch_read_map_gapped(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
+// Read mapping of the finished build (k_read_map in kernels_map.hip; the rules: include/gasm.h "Read mapping" and "Gapped read mapping"):
+// queue the kernel on the build's stream behind it (it reads the build's arrays and the batch's OWN reads `rd`, as given, whatever the
+// build's strands), then fetch the tables.  gapped = false: into bs.map, max_edits is max_mismatch, max_gap is not used; gapped = true: into
+// bs.mapg, beside the other and independent of it
+int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap);
+int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool gapped);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

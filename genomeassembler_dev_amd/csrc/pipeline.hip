@@ -461,7 +461,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_ccov, &d_links, &d_pairs, &d_map, &d_mapg, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_ccov, &links.d, &pairs.d, &map.d, &mapg.d, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -525,6 +525,13 @@ static GraphView graph_view(const BuildState& bs) {
     gv.bbits = bs.bbits;
     gv.fbits = bs.fbits;
     return gv;
+}
+
+// does the finished build hold a contig (and so the arrays of a ContigIndex)?
+static bool have_contigs(const BuildState& bs) { return bs.n_contigs && bs.d_total && bs.n_kmers; }
+
+static ContigIndex contig_index(const BuildState& bs) {
+    return ContigIndex{bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), have_contigs(bs) ? 1 : 0};
 }
 
 // k_bucket_dedup over the key width and the table size of `bs`: 64-bit keys have both tables, 128-bit keys the small one
@@ -927,10 +934,7 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, const BuildOpts&
     bs.fetched_twins = false;
     bs.spectrum_queued = false;
     bs.coverage_queued = false;
-    bs.links_queued = false;
-    bs.pairs_queued = false;
-    bs.map_queued = false;
-    bs.mapg_queued = false;
+    for (PassState* ps : {&bs.links, &bs.pairs, &bs.map, &bs.mapg}) ps->queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -1136,77 +1140,84 @@ int pipeline_fetch_contig_coverage(gasm_ctx* ctx, DevReads& rd, BuildState& bs) 
 }
 
 static_assert(GASM_THREAD_KMER_CAP == GASM_THREAD_MAX_KMERS, "kernels.h and gasm.h disagree on read threading");
+static_assert(GASM_PAIR_COUNTERS == GASM_PAIR_FIELDS, "kernels.h and gasm.h disagree on read pairs");
+static_assert(GASM_MAP_COUNTERS == GASM_MAP_FIELDS && GASM_MAP_BLOCKS == GASM_MAP_MAX_BLOCKS, "kernels.h and gasm.h disagree on read mapping");
+static_assert(GASM_MAPG_COUNTERS == GASM_MAPG_FIELDS && GASM_MAPG_GAP == GASM_MAP_MAX_GAP, "kernels.h and gasm.h disagree on gapped read mapping");
+static_assert(GASM_CORRECT_STATS == GASM_CORRECT_FIELDS && GASM_CORRECT_KMER_CAP == GASM_CORRECT_MAX_KMERS, "kernels.h and gasm.h disagree on read correction");
 
-// contig links: on the stream of the build, behind it; reads the directory, the dense keys, the ranking's links, the contig ids, offsets and
-// text and the packed reads, writes an array of its own (succ, pred, link support, span support, skipped reads)
+// ---- the passes that lay reads over a finished build: each on the stream of the build, behind it; each reads the build's arrays and the
+// packed reads and writes an array of its own (PassState), laid out by a PassLayout that the fetch derives again
+
+// workgroups per segment of a pass over the reads of `rd` that takes units_per_wg units (reads; pairs: reads_per_unit = 2) per workgroup
+// and round: as many as the largest segment needs, at most 8 per CU over all segments — the kernels loop where a segment holds more than
+// the grid covers at once
+static u32 read_pass_chunks(const gasm_ctx* ctx, const DevReads& rd, u32 units_per_wg, u32 reads_per_unit = 1) {
+    u64 most = 1;
+    for (u32 s = 0; s < rd.n_segments; ++s) most = std::max(most, (rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]) / reads_per_unit);
+    const u32 groups = (rd.n_segments + 7u) / 8u;
+    return std::max(1u, std::min<u32>(ceil_div_u64(most, units_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
+}
+
+// the pass's array at the size of the layout, its zeroed tables cleared
+static int pass_begin(gasm_ctx* ctx, PassState& ps, const PassLayout& l) {
+    GCHK(ps.d.ensure(l.bytes));
+    HIPCHK(hipMemsetAsync(l.at<char>(ps.d, 0) + l.zero_from, 0, l.bytes - l.zero_from, ctx->stream));
+    return GASM_OK;
+}
+
+// every table of the layout into the pass's host copies; `entry`, `queue`: the public names for the error
+static int pass_fetch(gasm_ctx* ctx, PassState& ps, const PassLayout& l, const char* entry, const char* queue) {
+    if (!ps.queued) { gasm_set_error("%s before %s (of the last build)", entry, queue); return GASM_ERR_STATE; }
+    ps.h.resize(l.t.size());
+    for (size_t i = 0; i < l.t.size(); ++i) {
+        ps.h[i].assign(l.t[i].bytes() / 8 + 1, 0);
+        if (l.t[i].bytes()) HIPCHK(hipMemcpyAsync(ps.h[i].data(), l.at<char>(ps.d, i), l.t[i].bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GASM_OK;
+}
+
+static PassLayout links_layout(u32 P, u32 S) {
+    const size_t p = P;
+    return {{4 * p, 4, 4, false}, {4 * p, 4, 4, false}, {4 * p, 4, 4, true}, {16 * p, 4, 4, true}, {S, 8, 8, true}};
+}
+
+// contig links: succ and pred (filled with "none"), link support, span support, skipped reads
 int pipeline_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs, u32 span_len) {
     if (rd.positioned) { gasm_set_error("contig links need the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
     GCHK(pipeline_build_finish(ctx, rd, bs, nullptr));
     HIPCHK(hipSetDevice(ctx->device));
     const u32 S = rd.n_segments, P = bs.n_contigs;
-    const size_t tables = (size_t)P * 28 * 4, bytes = tables + (size_t)S * 8;
-    GCHK(bs.d_links.ensure(bytes));
-    u32* const d_succ = bs.d_links.as<u32>();
-    u32 *const d_pred = d_succ + (size_t)P * 4, *const d_lsup = d_succ + (size_t)P * 8, *const d_ssup = d_succ + (size_t)P * 12;
-    unsigned long long* const d_skip = reinterpret_cast<unsigned long long*>(d_succ + (size_t)P * 28);
-    if (P) HIPCHK(hipMemsetAsync(d_succ, 0xFF, (size_t)P * 8 * 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(d_lsup, 0, bytes - (size_t)P * 8 * 4, ctx->stream));
-    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
+    const PassLayout l = links_layout(P, S);
+    GCHK(pass_begin(ctx, bs.links, l));
+    if (P) HIPCHK(hipMemsetAsync(bs.links.d.p, 0xFF, l.zero_from, ctx->stream));
     const GraphView gv = graph_view(bs);
-    if (have_graph) {
+    const ContigIndex ci = contig_index(bs);
+    if (ci.have_graph) {
         const u32 grid = (u32)std::min<u64>(ceil_div_u64(P, GASM_WG), (u64)ctx->n_cu * 8);
-        GLAUNCH_K(ctx, bs.words, "k_contig_links", k_contig_links<K>, dim3(grid), dim3(GASM_WG), 0, gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(),
-                  bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), S, d_succ, d_pred);
+        GLAUNCH_K(ctx, bs.words, "k_contig_links", k_contig_links<K>, dim3(grid), dim3(GASM_WG), 0, gv, ci, S, l.at<u32>(bs.links.d, LINKS_SUCC),
+                  l.at<u32>(bs.links.d, LINKS_PRED));
     }
     if (rd.n_reads && S) {
-        u64 most = 1;
-        for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
-        // 64 reads per workgroup and round, 16 per wave, as the correction kernel: the kernel loops where a segment holds more reads than
-        // the grid covers at once
-        const u32 reads_per_wg = 64;
-        const u32 groups = (S + 7u) / 8u;
-        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
-        GLAUNCH_K(ctx, bs.words, "k_read_thread", k_read_thread<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), gv, bs.d_link.as<u64>(), bs.d_ecid.as<u32>(),
-                  bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), have_graph, span_len, reads_per_wg, chunks, d_lsup, d_ssup, d_skip);
+        const u32 reads_per_wg = 64, chunks = read_pass_chunks(ctx, rd, reads_per_wg);      // 16 reads per wave, as the correction kernel
+        GLAUNCH_K(ctx, bs.words, "k_read_thread", k_read_thread<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), gv, ci, span_len, reads_per_wg, chunks,
+                  l.at<u32>(bs.links.d, LINKS_LSUP), l.at<u32>(bs.links.d, LINKS_SSUP), l.at<unsigned long long>(bs.links.d, LINKS_SKIPPED));
     }
-    bs.links_queued = true;
+    bs.links.queued = true;
     return GASM_OK;
 }
 
 int pipeline_fetch_contig_links(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
-    if (!bs.links_queued) { gasm_set_error("gasm_batch_fetch_contig_links before gasm_batch_contig_links (of the last build)"); return GASM_ERR_STATE; }
-    const u32 S = rd.n_segments, P = bs.n_contigs;
-    bs.h_succ.assign((size_t)P * 4 + 1, 0); bs.h_pred.assign((size_t)P * 4 + 1, 0); bs.h_link_support.assign((size_t)P * 4 + 1, 0);     // (one entry
-    bs.h_span_support.assign((size_t)P * 16 + 1, 0); bs.h_links_skipped.assign((size_t)S + 1, 0);           // more: a pointer to hand out for no contig at all)
-    const u32* const d = bs.d_links.as<u32>();
-    if (P) {
-        HIPCHK(hipMemcpyAsync(bs.h_succ.data(), d, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_pred.data(), d + (size_t)P * 4, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_link_support.data(), d + (size_t)P * 8, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_span_support.data(), d + (size_t)P * 12, (size_t)P * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (S) HIPCHK(hipMemcpyAsync(bs.h_links_skipped.data(), d + (size_t)P * 28, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (bs.opts.strands == 2) for (u32 s = 0; s < S; ++s) bs.h_links_skipped[s] /= 2;      // (a read and its reverse complement are equally long)
+    GCHK(pass_fetch(ctx, bs.links, links_layout(bs.n_contigs, rd.n_segments), "gasm_batch_fetch_contig_links", "gasm_batch_contig_links"));
+    if (bs.opts.strands == 2) for (u32 s = 0; s < rd.n_segments; ++s) bs.links.h[LINKS_SKIPPED][s] /= 2;      // (a read and its reverse complement are equally long)
     return GASM_OK;
 }
 
-static_assert(GASM_PAIR_COUNTERS == GASM_PAIR_FIELDS, "kernels.h and gasm.h disagree on read pairs");
+static PassLayout pairs_layout(u64 n_pairs, u32 orient, u32 S, u32 max_insert) {
+    return {{(size_t)n_pairs * orient * 4, 4, 16, false}, {(size_t)S * ((size_t)max_insert + 1), 4, 4, true}, {(size_t)S * GASM_PAIR_FIELDS, 8, 8, true}};
+}
 
-// where the three tables of a placement lie in d_pairs
-struct PairTables {
-    size_t rec_words, hist_words, hist_off, cnt_off, bytes;
-    PairTables(u64 n_pairs, u32 orient, u32 S, u32 max_insert) {
-        rec_words = (size_t)n_pairs * orient * 4;
-        hist_words = (size_t)S * ((size_t)max_insert + 1);
-        hist_off = rec_words * 4;                                           // (a multiple of 16: the records are stored 16 bytes at a time)
-        cnt_off = (hist_off + hist_words * 4 + 7) & ~(size_t)7;
-        bytes = cnt_off + (size_t)S * GASM_PAIR_FIELDS * 8;
-    }
-};
-
-// read pairs: on the stream of the build, behind it; reads the directory, the dense keys, the ranking's links, the contig ids and offsets and
-// the packed reads, writes an array of its own (records, insert histogram, counters)
+// read pairs: records, insert histogram, counters
 int pipeline_place_pairs(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_insert) {
     if (rd.positioned) { gasm_set_error("read pairs need the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
     const u32 S = rd.n_segments;
@@ -1218,183 +1229,67 @@ int pipeline_place_pairs(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildS
         }
     GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
     HIPCHK(hipSetDevice(ctx->device));
-    const u32 P = bs.n_contigs, orient = bs.opts.strands == 2 ? 2u : 1u;
+    const u32 orient = bs.opts.strands == 2 ? 2u : 1u;
     const u64 n_pairs = rd.n_reads / 2;
-    const PairTables t(n_pairs, orient, S, max_insert);
-    GCHK(bs.d_pairs.ensure(t.bytes));
-    u8* const d = bs.d_pairs.as<u8>();
-    HIPCHK(hipMemsetAsync(d + t.hist_off, 0, t.bytes - t.hist_off, ctx->stream));
-    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
+    const PassLayout l = pairs_layout(n_pairs, orient, S, max_insert);
+    GCHK(pass_begin(ctx, bs.pairs, l));
     if (n_pairs && S) {
-        u64 most = 1;
-        for (u32 s = 0; s < S; ++s) most = std::max(most, (rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]) / 2);
-        // a wave holds 64 scans (a mate of an oriented pair each), a workgroup four waves of them: the kernel loops where a segment holds
-        // more pairs than the grid covers at once
-        const u32 pairs_per_wg = (GASM_WG / 64) * (32u / orient);
-        const u32 groups = (S + 7u) / 8u;
-        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, pairs_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
-        GLAUNCH_K(ctx, bs.words, "k_pair_place", k_pair_place<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), bs.d_link.as<u64>(),
-                  bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), have_graph, orient, max_insert, n_pairs, chunks,
-                  reinterpret_cast<int32_t*>(d), reinterpret_cast<u32*>(d + t.hist_off), reinterpret_cast<unsigned long long*>(d + t.cnt_off));
+        // a wave holds 64 scans (a mate of an oriented pair each), a workgroup four waves of them
+        const u32 chunks = read_pass_chunks(ctx, rd, (GASM_WG / 64) * (32u / orient), 2);
+        GLAUNCH_K(ctx, bs.words, "k_pair_place", k_pair_place<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs), orient, max_insert,
+                  n_pairs, chunks, l.at<int32_t>(bs.pairs.d, PAIRS_REC), l.at<u32>(bs.pairs.d, PAIRS_HIST), l.at<unsigned long long>(bs.pairs.d, PAIRS_CNT));
     }
-    bs.pairs_orient = orient;
-    bs.pairs_max_insert = max_insert;
-    bs.pairs_queued = true;
+    bs.pairs.param[0] = orient;
+    bs.pairs.param[1] = max_insert;
+    bs.pairs.queued = true;
     return GASM_OK;
 }
 
 int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
-    if (!bs.pairs_queued) { gasm_set_error("gasm_batch_fetch_pair_places before gasm_batch_place_pairs (of the last build)"); return GASM_ERR_STATE; }
-    const u32 S = rd.n_segments;
-    const PairTables t(rd.n_reads / 2, bs.pairs_orient, S, bs.pairs_max_insert);
-    bs.h_pair_rec.assign(t.rec_words + 1, 0); bs.h_pair_hist.assign(t.hist_words + 1, 0);       // (one entry more: a pointer to hand out for
-    bs.h_pair_counters.assign((size_t)S * GASM_PAIR_FIELDS + 1, 0);                             // no pair and no segment at all)
-    const u8* const d = bs.d_pairs.as<u8>();
-    if (t.rec_words) HIPCHK(hipMemcpyAsync(bs.h_pair_rec.data(), d, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (S) {
-        HIPCHK(hipMemcpyAsync(bs.h_pair_hist.data(), d + t.hist_off, t.hist_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_pair_counters.data(), d + t.cnt_off, (size_t)S * GASM_PAIR_FIELDS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return GASM_OK;
+    return pass_fetch(ctx, bs.pairs, pairs_layout(rd.n_reads / 2, bs.pairs.param[0], rd.n_segments, bs.pairs.param[1]), "gasm_batch_fetch_pair_places",
+                      "gasm_batch_place_pairs");
 }
 
-static_assert(GASM_MAP_COUNTERS == GASM_MAP_FIELDS && GASM_MAP_BLOCKS == GASM_MAP_MAX_BLOCKS, "kernels.h and gasm.h disagree on read mapping");
+static PassLayout map_layout(bool gapped, u64 n_reads, u64 contig_bases, u32 S, u32 max_edits) {
+    const PassTable rec{(size_t)n_reads * 4, 4, 16, false}, pile{(size_t)contig_bases * 4, 4, 4, true}, gpile{(size_t)contig_bases * 2, 4, 4, true},
+        hist{(size_t)S * ((size_t)max_edits + 1), 4, 4, true};
+    if (gapped) return {rec, rec, pile, gpile, hist, {(size_t)S * GASM_MAPG_FIELDS, 8, 8, true}};
+    return {rec, pile, hist, {(size_t)S * GASM_MAP_FIELDS, 8, 8, true}};
+}
 
-// where the four tables of a mapping lie in d_map
-struct MapTables {
-    size_t rec_words, pile_words, hist_words, pile_off, hist_off, cnt_off, bytes;
-    MapTables(u64 n_reads, u64 contig_bases, u32 S, u32 max_mismatch) {
-        rec_words = (size_t)n_reads * 4;
-        pile_words = (size_t)contig_bases * 4;
-        hist_words = (size_t)S * ((size_t)max_mismatch + 1);
-        pile_off = rec_words * 4;                                           // (a multiple of 16: the records are stored 16 bytes at a time)
-        hist_off = pile_off + pile_words * 4;
-        cnt_off = (hist_off + hist_words * 4 + 7) & ~(size_t)7;
-        bytes = cnt_off + (size_t)S * GASM_MAP_FIELDS * 8;
-    }
-};
-
-// read mapping: on the stream of the build, behind it; reads the directory, the dense keys, the ranking's links, the contig ids, offsets and
-// text and the packed reads, writes an array of its own (records, pileup, mismatch histogram, counters)
-int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_mismatch) {
+// read mapping, both forms: records, pileup, histogram, counters; gapped: and gap records and the gap pileup
+int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap) {
     if (rd.positioned) { gasm_set_error("read mapping needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
     GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
     HIPCHK(hipSetDevice(ctx->device));
-    const u32 S = rd.n_segments, P = bs.n_contigs;
-    const MapTables t(rd.n_reads, P ? bs.contig_bases : 0, S, max_mismatch);
-    GCHK(bs.d_map.ensure(t.bytes));
-    u8* const d = bs.d_map.as<u8>();
-    HIPCHK(hipMemsetAsync(d + t.pile_off, 0, t.bytes - t.pile_off, ctx->stream));
-    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
-    if (rd.n_reads && S) {
-        u64 most = 1;
-        for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
-        // a wave per read, GASM_WG / 64 reads per workgroup and round: the kernel loops where a segment holds more reads than the grid
-        // covers at once
-        const u32 reads_per_wg = GASM_WG / 64;
-        const u32 groups = (S + 7u) / 8u;
-        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
-        GLAUNCH_K(ctx, bs.words, "k_read_map", k_read_map<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), bs.d_link.as<u64>(),
-                  bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), have_graph, max_mismatch, reads_per_wg, chunks,
-                  reinterpret_cast<int32_t*>(d), reinterpret_cast<u32*>(d + t.pile_off), reinterpret_cast<u32*>(d + t.hist_off),
-                  reinterpret_cast<unsigned long long*>(d + t.cnt_off));
-    }
-    bs.map_max_mismatch = max_mismatch;
-    bs.map_queued = true;
-    return GASM_OK;
-}
-
-int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
-    if (!bs.map_queued) { gasm_set_error("gasm_batch_fetch_read_map before gasm_batch_map_reads (of the last build)"); return GASM_ERR_STATE; }
     const u32 S = rd.n_segments;
-    const MapTables t(rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, S, bs.map_max_mismatch);
-    bs.h_map_rec.assign(t.rec_words + 1, 0); bs.h_map_pile.assign(t.pile_words + 1, 0);         // (one entry more: a pointer to hand out for
-    bs.h_map_hist.assign(t.hist_words + 1, 0); bs.h_map_counters.assign((size_t)S * GASM_MAP_FIELDS + 1, 0);     // no read, contig or segment at all)
-    const u8* const d = bs.d_map.as<u8>();
-    if (t.rec_words) HIPCHK(hipMemcpyAsync(bs.h_map_rec.data(), d, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (t.pile_words) HIPCHK(hipMemcpyAsync(bs.h_map_pile.data(), d + t.pile_off, t.pile_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (S) {
-        HIPCHK(hipMemcpyAsync(bs.h_map_hist.data(), d + t.hist_off, t.hist_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_map_counters.data(), d + t.cnt_off, (size_t)S * GASM_MAP_FIELDS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return GASM_OK;
-}
-
-static_assert(GASM_MAPG_COUNTERS == GASM_MAPG_FIELDS && GASM_MAPG_GAP == GASM_MAP_MAX_GAP, "kernels.h and gasm.h disagree on gapped read mapping");
-
-// where the six tables of a gapped mapping lie in d_mapg
-struct MapGapTables {
-    size_t rec_words, pile_words, gpile_words, hist_words, gap_off, pile_off, gpile_off, hist_off, cnt_off, bytes;
-    MapGapTables(u64 n_reads, u64 contig_bases, u32 S, u32 max_edits) {
-        rec_words = (size_t)n_reads * 4;
-        pile_words = (size_t)contig_bases * 4;
-        gpile_words = (size_t)contig_bases * 2;
-        hist_words = (size_t)S * ((size_t)max_edits + 1);
-        gap_off = rec_words * 4;                                            // (multiples of 16: both records are stored 16 bytes at a time)
-        pile_off = 2 * gap_off;
-        gpile_off = pile_off + pile_words * 4;
-        hist_off = gpile_off + gpile_words * 4;
-        cnt_off = (hist_off + hist_words * 4 + 7) & ~(size_t)7;
-        bytes = cnt_off + (size_t)S * GASM_MAPG_FIELDS * 8;
-    }
-};
-
-// gapped read mapping: on the stream of the build, behind it; reads what pipeline_map_reads reads, writes an array of its own (records, gap
-// records, pileup, gap pileup, edit histogram, counters)
-int pipeline_map_reads_gapped(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, u32 max_edits, u32 max_gap) {
-    if (rd.positioned) { gasm_set_error("read mapping needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
-    GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
-    HIPCHK(hipSetDevice(ctx->device));
-    const u32 S = rd.n_segments, P = bs.n_contigs;
-    const MapGapTables t(rd.n_reads, P ? bs.contig_bases : 0, S, max_edits);
-    GCHK(bs.d_mapg.ensure(t.bytes));
-    u8* const d = bs.d_mapg.as<u8>();
-    HIPCHK(hipMemsetAsync(d + t.pile_off, 0, t.bytes - t.pile_off, ctx->stream));
-    const int have_graph = P && bs.d_total && bs.n_kmers ? 1 : 0;
+    PassState& ps = gapped ? bs.mapg : bs.map;
+    const PassLayout l = map_layout(gapped, rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, S, max_edits);
+    GCHK(pass_begin(ctx, ps, l));
     if (rd.n_reads && S) {
-        u64 most = 1;
-        for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
-        // the grid of pipeline_map_reads: a wave per read, GASM_WG / 64 reads per workgroup and round
-        const u32 reads_per_wg = GASM_WG / 64;
-        const u32 groups = (S + 7u) / 8u;
-        const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
-        GLAUNCH_K(ctx, bs.words, "k_read_map_gapped", k_read_map_gapped<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), bs.d_link.as<u64>(),
-                  bs.d_ecid.as<u32>(), bs.d_c_off.as<u64>(), bs.d_seg_cstart.as<u32>(), bs.d_contig_ascii.as<u8>(), have_graph, max_edits, max_gap, reads_per_wg,
-                  chunks, reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + t.gap_off), reinterpret_cast<u32*>(d + t.pile_off),
-                  reinterpret_cast<u32*>(d + t.gpile_off), reinterpret_cast<u32*>(d + t.hist_off), reinterpret_cast<unsigned long long*>(d + t.cnt_off));
+        const u32 reads_per_wg = GASM_WG / 64, chunks = read_pass_chunks(ctx, rd, reads_per_wg);       // a wave per read
+        if (gapped) {
+            const MapOut out{l.at<int32_t>(ps.d, MAPG_REC), l.at<int32_t>(ps.d, MAPG_GAP), l.at<u32>(ps.d, MAPG_PILE), l.at<u32>(ps.d, MAPG_GPILE),
+                             l.at<u32>(ps.d, MAPG_HIST), l.at<unsigned long long>(ps.d, MAPG_CNT)};
+            GLAUNCH_K(ctx, bs.words, "k_read_map_gapped", (k_read_map<K, true>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
+                      max_edits, max_gap, reads_per_wg, chunks, out);
+        } else {
+            const MapOut out{l.at<int32_t>(ps.d, MAP_REC), nullptr, l.at<u32>(ps.d, MAP_PILE), nullptr, l.at<u32>(ps.d, MAP_HIST),
+                             l.at<unsigned long long>(ps.d, MAP_CNT)};
+            GLAUNCH_K(ctx, bs.words, "k_read_map", (k_read_map<K, false>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
+                      max_edits, 0u, reads_per_wg, chunks, out);
+        }
     }
-    bs.mapg_max_edits = max_edits;
-    bs.mapg_queued = true;
+    ps.param[0] = max_edits;
+    ps.queued = true;
     return GASM_OK;
 }
 
-int pipeline_fetch_read_map_gapped(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
-    if (!bs.mapg_queued) { gasm_set_error("gasm_batch_fetch_read_map_gapped before gasm_batch_map_reads_gapped (of the last build)"); return GASM_ERR_STATE; }
-    const u32 S = rd.n_segments;
-    const MapGapTables t(rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, S, bs.mapg_max_edits);
-    bs.h_mapg_rec.assign(t.rec_words + 1, 0); bs.h_mapg_gap.assign(t.rec_words + 1, 0);         // (one entry more: a pointer to hand out for
-    bs.h_mapg_pile.assign(t.pile_words + 1, 0); bs.h_mapg_gpile.assign(t.gpile_words + 1, 0);   // no read, contig or segment at all)
-    bs.h_mapg_hist.assign(t.hist_words + 1, 0); bs.h_mapg_counters.assign((size_t)S * GASM_MAPG_FIELDS + 1, 0);
-    const u8* const d = bs.d_mapg.as<u8>();
-    if (t.rec_words) {
-        HIPCHK(hipMemcpyAsync(bs.h_mapg_rec.data(), d, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_mapg_gap.data(), d + t.gap_off, t.rec_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (t.pile_words) {
-        HIPCHK(hipMemcpyAsync(bs.h_mapg_pile.data(), d + t.pile_off, t.pile_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_mapg_gpile.data(), d + t.gpile_off, t.gpile_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (S) {
-        HIPCHK(hipMemcpyAsync(bs.h_mapg_hist.data(), d + t.hist_off, t.hist_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(bs.h_mapg_counters.data(), d + t.cnt_off, (size_t)S * GASM_MAPG_FIELDS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return GASM_OK;
+int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool gapped) {
+    PassState& ps = gapped ? bs.mapg : bs.map;
+    return pass_fetch(ctx, ps, map_layout(gapped, rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, rd.n_segments, ps.param[0]),
+                      gapped ? "gasm_batch_fetch_read_map_gapped" : "gasm_batch_fetch_read_map", gapped ? "gasm_batch_map_reads_gapped" : "gasm_batch_map_reads");
 }
-
-static_assert(GASM_CORRECT_STATS == GASM_CORRECT_FIELDS && GASM_CORRECT_KMER_CAP == GASM_CORRECT_MAX_KMERS, "kernels.h and gasm.h disagree on read correction");
 
 // read correction: on the stream of the build, behind it; reads the packed reads, dstart, the fine directory and the dense keys, writes a
 // copy of the reads and a stats array, both the caller's
@@ -1411,14 +1306,9 @@ int pipeline_correct_reads(gasm_ctx* ctx, DevReads& rd, BuildState& bs, DBuf& ou
     GCHK(d_stats.ensure((size_t)S * GASM_CORRECT_FIELDS * 4));
     HIPCHK(hipMemsetAsync(d_stats.p, 0, (size_t)S * GASM_CORRECT_FIELDS * 4, ctx->stream));
     if (!rd.n_reads) return GASM_OK;
-    u64 most = 1;
-    for (u32 s = 0; s < S; ++s) most = std::max(most, rd.h_seg_read_off[s + 1] - rd.h_seg_read_off[s]);
-    // 64 reads per workgroup and round, 16 per wave: enough to amortise the workgroup's six atomics; the kernel loops where a segment
-    // holds more reads than the grid covers at once
-    const u32 reads_per_wg = 64;
-    const u32 groups = (S + 7u) / 8u;
-    const u32 chunks = std::max(1u, std::min<u32>(ceil_div_u64(most, reads_per_wg), std::max(1u, (u32)ctx->n_cu * 8u / groups)));
-    const int have_graph = bs.n_kmers && bs.d_total ? 1 : 0;
+    // 64 reads per workgroup and round, 16 per wave: enough to amortise the workgroup's six atomics
+    const u32 reads_per_wg = 64, chunks = read_pass_chunks(ctx, rd, reads_per_wg);
+    const int have_graph = bs.n_kmers && bs.d_total ? 1 : 0;                // (the k-mer set is all it needs: a build without a contig has one)
     GLAUNCH_K(ctx, bs.words, "k_read_correct", k_read_correct<K>, seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), have_graph, reads_per_wg,
               chunks, reinterpret_cast<unsigned long long*>(out_words.p), d_stats.as<u32>());
     return GASM_OK;

@@ -50,17 +50,35 @@ def check_gapped(b, segs, k, max_edits, max_gap, sample=None):
     return rm, out
 
 
-@pytest.mark.parametrize("k,read_len,genome_len", [(31, 100, 2500), (32, 100, 2500), (33, 100, 2500), (63, 150, 3000)])
+def gap_zero_batches(k, read_len, genome_len):
+    """(segments, min_count, the max_edits to try): spoiled reads of a random genome, or (read_len = 0) the two hand-built batches of
+    test_map_gpu.test_hand_built_cap_and_ties_on_the_device — a read with more than MAP_MAX_BLOCKS heads, ties between blocks — where
+    the two forms of the kernel could disagree without random reads showing it"""
+    if read_len:
+        genome = synth.make_segment(41, genome_len, planted=False).tobytes().decode()
+        reads, _, _ = mr.spoiled_reads(genome, read_len, k, 41)
+        return [([reads, reads[:40]], 2, (0, 5))]
+    return [([[mr.NINE_READ] + mr.NINE * 3], 3, sorted({c[0] for c in mr.NINE_CASES})),
+            ([list(dict.fromkeys(r for r, _, _ in mr.TIE_CASES)) + mr.TIE * 3], 3, sorted({m for _, m, _ in mr.TIE_CASES}))]
+
+
+@pytest.mark.parametrize("k,read_len,genome_len", [(31, 100, 2500), (32, 100, 2500), (33, 100, 2500), (63, 150, 3000),
+                                                   pytest.param(5, 0, 0, id="hand-built-cap-and-ties")])
 def test_max_gap_zero_is_map_reads(k, read_len, genome_len):
-    genome = synth.make_segment(41, genome_len, planted=False).tobytes().decode()
-    reads, _, _ = mr.spoiled_reads(genome, read_len, k, 41)
-    segs = [reads, reads[:40]]
+    dropped = [gap_zero_is_map_reads(segs, k, min_count, edits) for segs, min_count, edits in gap_zero_batches(k, read_len, genome_len)]
+    assert read_len or dropped[0] >= 1                                  # (the hand-built batch does go past the cap of heads)
+
+
+def gap_zero_is_map_reads(segs, k, min_count, edits):
+    """both entries' tables agree; returns the most blocks_dropped any max_edits gave"""
     b = ga.SegmentBatch.from_strings(segs)
-    b.build(k, min_count=2)
-    for me in (0, 5):
+    b.build(k, min_count=min_count)
+    dropped = 0
+    for me in edits:
         plain = b.map_reads(me)
+        dropped = max(dropped, sum(int(plain.counters(s)[6]) for s in range(len(segs))))
         rm, _ = check_gapped(b, segs, k, me, 0)
-        for s in range(2):
+        for s in range(len(segs)):
             assert rm.records(s).tolist() == plain.records(s).tolist() and rm.edit_hist(s).tolist() == plain.mismatch_hist(s).tolist()
             assert [p.tolist() for p in rm.pileup(s)] == [p.tolist() for p in plain.pileup(s)]
             assert rm.counters(s).tolist() == plain.counters(s).tolist() + [0]
@@ -70,6 +88,7 @@ def test_max_gap_zero_is_map_reads(k, read_len, genome_len):
             assert g[placed, 3].tolist() == rm.records(s)[placed, 1].tolist()
             assert not any(p.any() for p in rm.gap_pileup(s))
     b.close()
+    return dropped
 
 
 def test_hand_built_cases_on_the_device():
