@@ -485,6 +485,21 @@ def map_reads_gapped(reads, k, max_edits=6, max_gap=3, ctx=None, **build):
         b.close()
 
 
+def calc_breakscore_mapped(reads, k, kmer=8, tables=None, max_edits=6, max_gap=3, partial=False, ctx=None, **build):
+    """breakage scores of the contigs of one segment's reads (a list of str) from the reads' mapped starts: build, gapped mapping
+    within max_edits edits and gaps of at most max_gap, mapped scoring — a readmap.MappedScores that speaks of segment 0 (scores(),
+    score_fixed(), starts(0), counters(0), scored_fraction(0), window_counts(0, c); the rule and its limits: include/gasm.h "Mapped
+    scoring").  A read with errors scores where its first base lies; calc_breakscore scores it only as an exact substring.  tables,
+    partial: as SegmentBatch.score_mapped; build: as for contig_graph."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        b.build_simplified(int(k), **build).map_reads_gapped(max_edits, max_gap)
+        return b.score_mapped(kmer, tables, "gapped", partial)
+    finally:
+        b.close()
+
+
 def resolve_repeats(reads, k, min_support=2, ctx=None, **build):
     """the contigs of one segment's reads with the repeats shorter than a read put back into their flanks, where the reads that run
     through a repeat say so unambiguously (links.ContigLinks.resolve_repeats: the rule and its limits); a sorted list of str.

@@ -7,11 +7,11 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAPG_FIELDS, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 from .pairs import PairPlaces
-from .readmap import GappedReadMap, ReadMap
+from .readmap import GappedReadMap, MappedScores, ReadMap
 
 
 def _arr(p, ctype, n):
@@ -313,6 +313,40 @@ class SegmentBatch:
         strands = self.strands()
         return GappedReadMap(self.k, strands, max_edits, max_gap, contigs, rec, gap, pile, gpile, hist, cnt,
                              [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
+
+    def score_mapped(self, kmer=8, tables=None, source="gapped", partial=False):
+        """breakage scores from the records of the last map_reads_gapped() (source="gapped") or map_reads() ("ungapped") over the last
+        build (gasm_batch_score_mapped; the rule: include/gasm.h "Mapped scoring") as a readmap.MappedScores: a read scores at the
+        contig base under its first base, so reads with errors count too.  tables: None (the normalised query table), one row of
+        qtable.ROWS probabilities, or 1 to _lib.MAX_TABLES rows.  partial: reads that start on a contig and run off its end score too.
+        A pass of its own: what scores(), score_fixed(), guided() and the mappings returned stays what it was."""
+        t = np.ascontiguousarray(qtable.load_normalised() if tables is None else tables, dtype=np.float64)
+        if t.ndim == 1:
+            t = t.reshape(1, -1)
+        if t.ndim != 2 or t.shape[1] != qtable.ROWS:
+            raise ValueError(f"tables must be rows of {qtable.ROWS} probabilities")
+        if not 1 <= t.shape[0] <= MAX_TABLES:
+            raise ValueError(f"tables must hold 1..{MAX_TABLES} rows")
+        if source not in MAPSCORE_SOURCES:
+            raise ValueError(f"source must be one of {sorted(MAPSCORE_SOURCES)}")
+        if int(kmer) < 0:
+            raise ValueError("kmer must be >= 0")
+        T = int(t.shape[0])
+        check(lib().gasm_batch_score_mapped(self.h, MAPSCORE_SOURCES[source], int(kmer), t.ctypes.data_as(C.c_void_p), T, MAPSCORE_PARTIAL if partial else 0))
+        seg, o, contigs = self._contigs_by_segment()
+        n = int(seg[-1])
+        total = int(o[-1]) if n else 0
+        per_table = []
+        for i in range(T):
+            ps, sh = [C.c_void_p() for _ in range(6)], C.c_int()
+            check(lib().gasm_batch_fetch_mapped_scores(self.h, i, *[C.byref(p) for p in ps], C.byref(sh)))
+            per_table.append((dict(bp_score=_arr(ps[0], C.c_double, n), bp_score_norm_by_break_freqs=_arr(ps[1], C.c_double, n),
+                                   bp_score_norm_by_len=_arr(ps[2], C.c_double, n), kmer_breaks=_arr(ps[3], C.c_int32, n),
+                                   sequence_len=_arr(ps[4], C.c_int32, n), seg_contig_off=seg), _arr(ps[5], C.c_int64, n), sh.value))
+        sp, cp = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_mapped_starts(self.h, C.byref(sp), C.byref(cp)))
+        return MappedScores(int(kmer), source, bool(partial), contigs, per_table, _arr(sp, C.c_uint32, total),
+                            _arr(cp, C.c_uint64, self.n_segments * len(MAPSCORE_FIELDS)))
 
     def suggest_cov_cutoff(self, segment):
         """a cov_cutoff for build_simplified() from the last build's own contigs of `segment`: half the length-weighted median of the

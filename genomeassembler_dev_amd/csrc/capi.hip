@@ -68,6 +68,9 @@ struct gasm_batch {
     ScoreTable tb[GASM_MAX_TABLES];
     std::vector<double> table_copy[GASM_MAX_TABLES];
     void table_ptrs(ScoreTable** tbs) { for (u32 t = 0; t < GASM_MAX_TABLES; ++t) tbs[t] = &tb[t]; }
+    // the tables of gasm_batch_score_mapped, its own: what gasm_batch_score(_tables) set stays what it was
+    ScoreTable mtb[GASM_MAX_TABLES];
+    std::vector<double> mtable_copy[GASM_MAX_TABLES];
     GuidedState guided;
     // Step slots, taken in turn (GASM_PINGPONG=0 switches it off): consecutive steps of a resident pipeline are independent
     // of each other — same reads, own graph, own scores — so step n + 1 is queued on the next slot's stream with that slot's
@@ -833,6 +836,7 @@ void gasm_batch_free(gasm_batch* b) {
     for (StepSlot& x : b->slot) { if (x.cx && x.cx != b->ctx) (void)hipStreamSynchronize(x.cx->stream); x.bs.release(); x.dp.release(); x.ss.release(); }
     b->rd.release(); b->rd2.release(); b->guided.release(); b->d_rkc.release(); b->d_correct.release();
     for (ScoreTable& t : b->tb) t.release();
+    for (ScoreTable& t : b->mtb) t.release();
     delete b;
 }
 
@@ -1064,6 +1068,81 @@ int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const i
     GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, b->S().bs, true));
     *rec = ps.host<int32_t>(MAPG_REC); *rec_gap = ps.host<int32_t>(MAPG_GAP); *pile = ps.host<uint32_t>(MAPG_PILE); *gap_pile = ps.host<uint32_t>(MAPG_GPILE);
     *edit_hist = ps.host<uint32_t>(MAPG_HIST); *counters = ps.host<uint64_t>(MAPG_CNT);
+    return GASM_OK;
+    API_GUARD_END
+}
+
+// ---- mapped scoring (kernels_score.hip, k_score_mapped; the rule: include/gasm.h "Mapped scoring")
+int gasm_batch_score_mapped(gasm_batch* b, int source, int kmer, const double* tables, uint32_t n_tables, uint32_t flags) {
+    API_GUARD_BEGIN
+    int args = GASM_OK;
+    if (b && !tables) { gasm_set_error("gasm_batch_score_mapped: null argument"); args = GASM_ERR_INVALID; }
+    else if (source != GASM_MAPSCORE_UNGAPPED && source != GASM_MAPSCORE_GAPPED) { gasm_set_error("source must be GASM_MAPSCORE_UNGAPPED or GASM_MAPSCORE_GAPPED (got %d)", source); args = GASM_ERR_INVALID; }
+    else if (flags & ~(uint32_t)GASM_MAPSCORE_PARTIAL) { gasm_set_error("unknown flag bits 0x%x", flags & ~(uint32_t)GASM_MAPSCORE_PARTIAL); args = GASM_ERR_INVALID; }
+    else if (n_tables < 1 || n_tables > GASM_MAX_TABLES) { gasm_set_error("n_tables must be 1..%d (got %u)", GASM_MAX_TABLES, n_tables); args = GASM_ERR_INVALID; }
+    else if (kmer < 0) { gasm_set_error("kmer must be >= 0"); args = GASM_ERR_INVALID; }
+    GCHK(batch_pass_ready(b, "gasm_batch_score_mapped", args));
+    StepSlot& x = b->S();
+    const bool gapped = source == GASM_MAPSCORE_GAPPED;
+    if (b->rd.positioned) { gasm_set_error("mapped scoring needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
+    if (!(gapped ? x.bs.mapg : x.bs.map).queued) {
+        gasm_set_error("gasm_batch_score_mapped before %s (of the last build)", gapped ? "gasm_batch_map_reads_gapped" : "gasm_batch_map_reads");
+        return GASM_ERR_STATE;
+    }
+    // No FP64 fallback: every table must have a fixed-point shift for these reads, checked before anything is set or queued
+    u64 max_reads = 0;
+    for (u32 s = 0; s < b->rd.n_segments; ++s) max_reads = std::max(max_reads, b->rd.h_seg_read_off[s + 1] - b->rd.h_seg_read_off[s]);
+    for (u32 t = 0; t < n_tables; ++t) {
+        double absmax = 0;
+        const bool finite = gasm_host::table_range(tables + (size_t)t * GASM_TABLE_ROWS, GASM_TABLE_ROWS, &absmax);
+        const int shift = gasm_host::fixed_point_shift(absmax, finite, max_reads);
+        if (shift < 0 || shift > 1000) { gasm_set_error("gasm_batch_score_mapped: table %u has no fixed-point shift (a NaN or infinite entry, or a range the 64-bit fixed point cannot hold)", t); return GASM_ERR_INVALID; }
+    }
+    ScoreTable* tbs[GASM_MAX_TABLES];
+    bool same[GASM_MAX_TABLES], all_same = true;
+    for (u32 t = 0; t < GASM_MAX_TABLES; ++t) tbs[t] = &b->mtb[t];
+    for (u32 t = 0; t < n_tables; ++t) {
+        const std::vector<double>& have = b->mtable_copy[t];
+        same[t] = !have.empty() && memcmp(have.data(), tables + (size_t)t * GASM_TABLE_ROWS, GASM_TABLE_ROWS * sizeof(double)) == 0;
+        all_same = all_same && same[t];
+    }
+    if (!all_same) {
+        for (StepSlot& y : b->slot) if (y.cx) HIPCHK(hipStreamSynchronize(y.cx->stream));      // (whatever still scores with the old tables)
+        for (u32 t = 0; t < n_tables; ++t) {
+            if (same[t]) continue;
+            const double* src = tables + (size_t)t * GASM_TABLE_ROWS;
+            GCHK(tbs[t]->set_standard(b->ctx, src));
+            b->mtable_copy[t].assign(src, src + GASM_TABLE_ROWS);
+        }
+    }
+    return pipeline_score_mapped(x.cx, b->build_reads(x), b->rd, x.bs, gapped, kmer, tbs, n_tables, (flags & GASM_MAPSCORE_PARTIAL) != 0);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_mapped_scores(gasm_batch* b, uint32_t t, const double** bp_score, const double** norm_by_break_freqs, const double** norm_by_len,
+                                   const int32_t** kmer_breaks, const int32_t** sequence_len, const int64_t** fx, int* shift) {
+    API_GUARD_BEGIN
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_mapped_scores", bp_score && norm_by_break_freqs && norm_by_len && kmer_breaks && sequence_len && fx && shift));
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_mapped_scores(b->S().cx, b->rd, bs));
+    const u32 T = bs.mapscore.param[0];
+    if (t >= T) { gasm_set_error("table %u of a mapped score with %u table(s)", t, T); return GASM_ERR_INVALID; }
+    const size_t P = bs.n_contigs;
+    const double* f = bs.mapscore.host<double>(MAPSC_F64) + (size_t)t * 3 * P;
+    *bp_score = f; *norm_by_break_freqs = f + P; *norm_by_len = f + 2 * P;
+    *kmer_breaks = bs.mapscore.host<int32_t>(MAPSC_I32); *sequence_len = bs.mapscore.host<int32_t>(MAPSC_I32) + P;
+    *fx = bs.mapscore.host<int64_t>(MAPSC_FX) + (size_t)t * P;
+    *shift = bs.mapscore_shift[t];
+    return GASM_OK;
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_mapped_starts(gasm_batch* b, const uint32_t** start_pile, const uint64_t** counters) {
+    API_GUARD_BEGIN
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_mapped_starts", start_pile && counters));
+    BuildState& bs = b->S().bs;
+    GCHK(pipeline_fetch_mapped_scores(b->S().cx, b->rd, bs));
+    *start_pile = bs.mapscore.host<uint32_t>(MAPSC_PILE); *counters = bs.mapscore.host<uint64_t>(MAPSC_COUNTERS);
     return GASM_OK;
     API_GUARD_END
 }

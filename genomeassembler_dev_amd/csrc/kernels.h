@@ -352,6 +352,14 @@ template <class K, int T>
 __global__ void k_score_reads_graph(ReadSet rs, GraphView gv, const u64* link, const u32* e_cid, PathSet ps, FixTables dfix, int kmer,
                                     u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* cnt, unsigned long long* sum, u64 sum_stride, int verify,
                                     u32* verify_flag);
+// mapped scoring (include/gasm.h, "Mapped scoring"): rec (GAPPED: and rec_gap) are a read mapping's records over the build of `ci`, 4 int32 per
+// read; cnt, sum (table t at sum + t * sum_stride), start_pile (one per base of the contig text) and counters (GASM_MAPSCORE_CLASSES per segment)
+// zeroed by the caller; LDS as k_score_reads_graph
+#define GASM_MAPSCORE_CLASSES 4       // = GASM_MAPSCORE_FIELDS of include/gasm.h (checked in pipeline.hip)
+template <int T, bool GAPPED>
+__global__ void k_score_mapped(ReadSet rs, ContigIndex ci, const int32_t* rec, const int32_t* rec_gap, FixTables dfix, int kmer, u32 partial,
+                               u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* cnt, unsigned long long* sum, u64 sum_stride, u32* start_pile,
+                               unsigned long long* counters);
 __global__ void k_levenshtein(PathSet ps, u32 n_paths, const u64* twords, u32 nt, int infix, u8* carry_ws, u64 carry_stride, int32_t* out);
 __global__ void k_levenshtein2(PathSet ps, u32 n_paths, const u64* twords, u32 nt, int infix, uint4* carry_ws, u64 carry_stride, int32_t* out);
 __global__ void k_score_zero(u32* cnt, unsigned long long* sum, u64 sum_stride, u32 n_tables, const u32* n_paths_p);

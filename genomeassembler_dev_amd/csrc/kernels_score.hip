@@ -22,21 +22,49 @@
 #define GASM_DIRECT_ROWS 87380
 __device__ __forceinline__ u32 direct_base(u32 L) { return ((1u << (2 * L)) - 4u) / 3u; }
 
-// Window of the break at hit position j (lib/DeNovoAssembler.cpp:366-386).  Returns false when the window is empty
-// (only for an empty path); *idx is the direct-table index of the (possibly end-truncated) window.
-__device__ __forceinline__ bool break_window(const u64* __restrict__ words, u64 pbase, u32 plen, u32 j, int kmer, u32* idx) {
+// Window of the break at hit position j (lib/DeNovoAssembler.cpp:366-386): path bases [*start, *start + *wd), 1 <= *wd <= 8
+// (end-truncated where the path ends first).  Returns false when the window is empty (only for an empty path).  The one
+// definition of where the window lies: break_window reads it from a packed path, break_window_text from ASCII text.
+__device__ __forceinline__ bool break_span(u32 plen, u32 j, int kmer, u32* start, u32* wd) {
     const int st = (int)j - kmer / 2;
-    const u32 start = st > 0 ? (u32)st : 0u;
+    const u32 s = st > 0 ? (u32)st : 0u;
     u32 width = 8;
-    if (start == 0) {
+    if (s == 0) {
         if (j == 1) width = 2;
         else if (j == 2) width = 4;
         else if (j == 3) width = 6;
     }
-    if (start >= plen) return false;
-    const u32 avail = plen - start;
-    const u32 wd = width < avail ? width : avail;
+    if (s >= plen) return false;
+    const u32 avail = plen - s;
+    *start = s;
+    *wd = width < avail ? width : avail;
+    return true;
+}
+
+// *idx is the direct-table index of the window of the break at hit position j of the packed path at pbase.
+__device__ __forceinline__ bool break_window(const u64* __restrict__ words, u64 pbase, u32 plen, u32 j, int kmer, u32* idx) {
+    u32 start, wd;
+    if (!break_span(plen, j, kmer, &start, &wd)) return false;
     *idx = direct_base(wd) + (u32)kmer_at(words, pbase + start, (int)wd);
+    return true;
+}
+
+// The same index from the build's ASCII contig text (upper-case ACGT, as k_contig_emit wrote it): the contig's plen bases start
+// at text[pbase].  A full window is one 8-byte load (it lies inside the contig), a truncated one is read byte by byte.
+__device__ __forceinline__ bool break_window_text(const u8* __restrict__ text, u64 pbase, u32 plen, u32 j, int kmer, u32* idx) {
+    u32 start, wd;
+    if (!break_span(plen, j, kmer, &start, &wd)) return false;
+    const u8* const p = text + pbase + start;
+    u32 v = 0;
+    if (wd == 8) {
+        u64 w;
+        __builtin_memcpy(&w, p, 8);
+#pragma unroll
+        for (u32 i = 0; i < 8; ++i) v = (v << 2) | base_code((u8)(w >> (8 * i)));
+    } else {
+        for (u32 i = 0; i < wd; ++i) v = (v << 2) | base_code(p[i]);
+    }
+    *idx = direct_base(wd) + v;
     return true;
 }
 
@@ -307,6 +335,110 @@ __global__ void __launch_bounds__(GASM_WG) k_score_finish(PathSet ps, const u32*
         seq_len[p] = (int32_t)len;
     }
 }
+
+// Mapped scoring (include/gasm.h, "Mapped scoring"): the records of a read mapping over the build turned into breakage sums.
+// k_score_reads_graph finds a read's place by an exact match of its first k-mer; here the place is the record the mapping kernel
+// left — contig c (inside the segment) and diagonal d_1 of the read's best alignment, so the read's first base lies over base d_1
+// of c and that is the break.  One thread per read, a workgroup = one slice of one segment's reads (seg_chunk): one 16-byte load
+// of the record (GAPPED: one more of the gap record, for the inserted bases), the read's length, the contig's extent (one
+// 16-byte load of c_off[c], c_off[c + 1]), the window from the contig's ASCII text (break_window_text: break_window's index),
+// T independent gathers.  Accumulators as in k_score_reads_graph: per-segment LDS sums and counts where the segment's contigs
+// fit lds_paths, flushed once per workgroup, else global atomics; start_pile gets one global add per scored read; the four class
+// counters are counted per wave (a ballot each), summed in LDS and added once per workgroup.  Not templated on the key width:
+// it reads records, not k-mers.  A record is data from another kernel: c is checked against the segment's contigs and d_1
+// against the contig before either is used as an index (a record that fails counts as unplaced).
+// ci.have_graph = 0 (a build without a contig): every read is unplaced and none of ci's arrays is touched.
+template <int T, bool GAPPED>
+__global__ void __launch_bounds__(GASM_WG) k_score_mapped(ReadSet rs, ContigIndex ci, const int32_t* __restrict__ rec,
+                                                          const int32_t* __restrict__ rec_gap, FixTables dfix, int kmer, u32 partial,
+                                                          u32 reads_per_wg, u32 chunks, u32 lds_paths, u32* __restrict__ cnt,
+                                                          unsigned long long* __restrict__ sum, u64 sum_stride, u32* __restrict__ start_pile,
+                                                          unsigned long long* __restrict__ counters) {
+    extern __shared__ unsigned long long s_sum[];
+    __shared__ u32 s_cls[GASM_MAPSCORE_CLASSES];
+    u32* s_cnt = reinterpret_cast<u32*>(s_sum + (size_t)T * lds_paths);
+    u32 seg, chunk;
+    if (!seg_chunk(rs.n_segments, chunks, &seg, &chunk)) return;
+    const u64 r0 = rs.seg_read_off[seg] + (u64)chunk * reads_per_wg;
+    const u64 rseg_end = rs.seg_read_off[seg + 1];
+    if (r0 >= rseg_end) return;
+    const u64 r1 = r0 + reads_per_wg < rseg_end ? r0 + reads_per_wg : rseg_end;
+    u32 pfirst = 0, np = 0;
+    if (ci.have_graph) { pfirst = ci.seg_cstart[seg]; np = ci.seg_cstart[seg + 1] - pfirst; }
+    const bool in_lds = np <= lds_paths;
+    if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) s_sum[(size_t)t * lds_paths + i] = 0;
+        s_cnt[i] = 0;
+    }
+    if (threadIdx.x < GASM_MAPSCORE_CLASSES) s_cls[threadIdx.x] = 0;
+    __syncthreads();
+    for (u64 rb = r0; rb < r1; rb += GASM_WG) {
+        const u64 r = rb + threadIdx.x;
+        const bool valid = r < r1;
+        u32 cls = 0;                                      // 0 unplaced, 1 start_clipped, 2 end_clipped, 3 whole
+        u32 c = 0, d1 = 0, plen = 0;
+        u64 pb = 0;
+        if (valid) {
+            int4 rc;
+            __builtin_memcpy(&rc, rec + 4 * r, 16);
+            if (rc.x >= 0 && (u32)rc.x < np) {
+                u64 p0; u32 len;
+                read_span(rs, r, &p0, &len);
+                c = pfirst + (u32)rc.x;
+                const gasm_u64x2 po = load_pair(ci.c_off + c);   // the contig's first base and its end
+                pb = po.x;
+                plen = (u32)(po.y - po.x);
+                if (rc.y < 0) cls = 1;
+                else if ((u32)rc.y < plen) {
+                    long long ins = 0;
+                    if (GAPPED) { int4 g; __builtin_memcpy(&g, rec_gap + 4 * r, 16); ins = g.y; }
+                    d1 = (u32)rc.y;
+                    cls = (long long)rc.w + ins < (long long)len ? 2u : 3u;
+                }
+            }
+        }
+#pragma unroll
+        for (u32 i = 0; i < GASM_MAPSCORE_CLASSES; ++i) {
+            const u32 n = (u32)__popcll(__ballot(valid && cls == i));
+            if ((threadIdx.x & 63u) == 0 && n) atomicAdd(&s_cls[i], n);
+        }
+        if (cls < (partial ? 2u : 3u)) continue;
+        u32 idx = 0;
+        const bool hit = break_window_text(ci.text, pb, plen, d1, kmer, &idx);
+        long long fx[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) fx[t] = hit ? dfix.p[t][idx] : 0;
+        atomicAdd(&start_pile[pb + d1], 1u);
+        if (in_lds) {
+            atomicAdd(&s_cnt[c - pfirst], 1u);
+#pragma unroll
+            for (int t = 0; t < T; ++t) atomicAdd(&s_sum[(size_t)t * lds_paths + (c - pfirst)], (unsigned long long)fx[t]);
+        } else {
+            atomicAdd(&cnt[c], 1u);
+#pragma unroll
+            for (int t = 0; t < T; ++t) atomicAdd(&sum[(u64)t * sum_stride + c], (unsigned long long)fx[t]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < GASM_MAPSCORE_CLASSES && s_cls[threadIdx.x]) atomicAdd(&counters[(u64)seg * GASM_MAPSCORE_CLASSES + threadIdx.x], (unsigned long long)s_cls[threadIdx.x]);
+    if (in_lds) for (u32 i = threadIdx.x; i < np; i += GASM_WG) {
+        const u32 n = s_cnt[i];
+        if (n) {
+            atomicAdd(&cnt[pfirst + i], n);
+#pragma unroll
+            for (int t = 0; t < T; ++t) atomicAdd(&sum[(u64)t * sum_stride + pfirst + i], s_sum[(size_t)t * lds_paths + i]);
+        }
+    }
+}
+
+#define GASM_INST_MAPSCORE(T)                                                                                                              \
+    template __global__ void k_score_mapped<T, false>(ReadSet, ContigIndex, const int32_t*, const int32_t*, FixTables, int, u32, u32, u32, u32, u32*, \
+                                                      unsigned long long*, u64, u32*, unsigned long long*);                               \
+    template __global__ void k_score_mapped<T, true>(ReadSet, ContigIndex, const int32_t*, const int32_t*, FixTables, int, u32, u32, u32, u32, u32*,  \
+                                                     unsigned long long*, u64, u32*, unsigned long long*);
+GASM_INST_MAPSCORE(1) GASM_INST_MAPSCORE(2) GASM_INST_MAPSCORE(3) GASM_INST_MAPSCORE(4) GASM_INST_MAPSCORE(5) GASM_INST_MAPSCORE(6)
+GASM_INST_MAPSCORE(7) GASM_INST_MAPSCORE(8)
 
 __device__ __forceinline__ u32 wave_sum_u32(u32 v) {
 #pragma unroll

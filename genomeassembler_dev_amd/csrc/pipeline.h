@@ -147,6 +147,9 @@ enum { LINKS_SUCC, LINKS_PRED, LINKS_LSUP, LINKS_SSUP, LINKS_SKIPPED };
 enum { PAIRS_REC, PAIRS_HIST, PAIRS_CNT };
 enum { MAP_REC, MAP_PILE, MAP_HIST, MAP_CNT };
 enum { MAPG_REC, MAPG_GAP, MAPG_PILE, MAPG_GPILE, MAPG_HIST, MAPG_CNT };
+// mapped scoring (T = param[0] tables over P contigs): double out[3 T P] (table t: bp, norm_by_break_freqs, norm_by_len, P each), int32 out[2 P]
+// (kmer_breaks, sequence_len), u32 cnt[P], u64 fx[T P], u32 start_pile[contig bases], u64 counters[S * GASM_MAPSCORE_FIELDS]
+enum { MAPSC_F64, MAPSC_I32, MAPSC_CNT, MAPSC_FX, MAPSC_PILE, MAPSC_COUNTERS };
 
 struct BuildState {
     // ---- plan (host-side, from the reads): key width, tile shape, partition
@@ -208,6 +211,9 @@ struct BuildState {
     // read-pair places (pipeline_place_pairs; param: orientations, max_insert), read mapping and gapped read mapping (pipeline_map_reads;
     // param: max_mismatch / max_edits) — the two mappings independent of each other
     PassState links, pairs, map, mapg;
+    // mapped scoring (pipeline_score_mapped; param: tables, source) from the records of map or mapg, and its tables' fixed-point shifts
+    PassState mapscore;
+    int mapscore_shift[GASM_MAX_TABLES] = {};
     DBuf d_spectrum;                        // k-mer spectrum of the last build (u32[S * 256], pipeline_kmer_spectrum)
     DBuf d_twin;                            // strands = 2: twin map (u32 per contig, then k_contig_twin's flag word), made by the first fetch
     std::vector<u32> h_twin;
@@ -315,6 +321,12 @@ int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // bs.mapg, beside the other and independent of it
 int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap);
 int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool gapped);
+// Mapped scoring of the finished build (k_score_mapped in kernels_score.hip; the rule: include/gasm.h "Mapped scoring"): queue the kernel and a
+// k_score_finish per table on the build's stream behind it, then fetch the tables.  It reads the records of bs.map (gapped = false) or bs.mapg,
+// which must have been queued over this build (else GASM_ERR_STATE), the build's contig text and the batch's OWN reads' lengths.  tbs: T tables
+// of the pass's own, each with a fixed-point shift for these reads (else GASM_ERR_INVALID, nothing queued)
+int pipeline_score_mapped(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, int kmer, ScoreTable* const* tbs, u32 T, bool partial);
+int pipeline_fetch_mapped_scores(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // multiplicity histogram of the finished build's dense arrays: queue (k_kmer_spectrum, reads dstart / dk_cnt only), then fetch
 // n_segments x 256 counts
 int pipeline_kmer_spectrum(gasm_ctx* ctx, DevReads& rd, BuildState& bs);

@@ -461,7 +461,7 @@ PathSet DevPaths::view() const {
 void DevPaths::release() { d_words.release(); d_p_off.release(); d_seg_path_off.release(); d_seg_base_off.release(); }
 
 void BuildState::release() {
-    for (DBuf* b : {&d_solid_removed, &d_ccov, &links.d, &pairs.d, &map.d, &mapg.d, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
+    for (DBuf* b : {&d_solid_removed, &d_ccov, &links.d, &pairs.d, &map.d, &mapg.d, &mapscore.d, &d_spectrum, &d_twin, &d_keys, &d_keys2, &d_mult, &d_hist, &d_toff, &d_tcnt, &d_fdir, &d_bstart, &d_bucket_d, &d_dstart, &d_flags, &d_dk_key, &d_dk_cnt,
                     &d_eflag, &d_nxt, &d_link, &d_clen, &d_ecid, &d_ecoff, &d_rtab, &d_seg_cbases, &d_seg_cstart,
                     &d_seg_bstart, &d_c_off, &d_contig_ascii})
         b->release();
@@ -495,6 +495,10 @@ static int ensure_lds_attrs(gasm_ctx* ctx) {
             return GASM_OK;
         }));
     GASM_LDS_ATTR(k_rank_lds, 160 * 1024 - 64)
+#define GASM_MAPSCORE_LDS_ATTR(T) GASM_LDS_ATTR((k_score_mapped<T, false>), GASM_SCORE_PATH_CAP * 12) GASM_LDS_ATTR((k_score_mapped<T, true>), GASM_SCORE_PATH_CAP * 12)
+    GASM_MAPSCORE_LDS_ATTR(1) GASM_MAPSCORE_LDS_ATTR(2) GASM_MAPSCORE_LDS_ATTR(3) GASM_MAPSCORE_LDS_ATTR(4) GASM_MAPSCORE_LDS_ATTR(5) GASM_MAPSCORE_LDS_ATTR(6)
+    GASM_MAPSCORE_LDS_ATTR(7) GASM_MAPSCORE_LDS_ATTR(8)
+#undef GASM_MAPSCORE_LDS_ATTR
 #undef GASM_SCORE_LDS_ATTR
 #undef GASM_LDS_ATTR
     ctx->lds_attrs_set = true;
@@ -934,7 +938,7 @@ int pipeline_build(gasm_ctx* ctx, DevReads& rd, BuildState& bs, const BuildOpts&
     bs.fetched_twins = false;
     bs.spectrum_queued = false;
     bs.coverage_queued = false;
-    for (PassState* ps : {&bs.links, &bs.pairs, &bs.map, &bs.mapg}) ps->queued = false;
+    for (PassState* ps : {&bs.links, &bs.pairs, &bs.map, &bs.mapg, &bs.mapscore}) ps->queued = false;
     const u32 S = rd.n_segments;
     zero_results(bs, S);
     bs.part_single = bs.scan_in_dedup = bs.ranked_in_lds = false;
@@ -1143,6 +1147,7 @@ static_assert(GASM_THREAD_KMER_CAP == GASM_THREAD_MAX_KMERS, "kernels.h and gasm
 static_assert(GASM_PAIR_COUNTERS == GASM_PAIR_FIELDS, "kernels.h and gasm.h disagree on read pairs");
 static_assert(GASM_MAP_COUNTERS == GASM_MAP_FIELDS && GASM_MAP_BLOCKS == GASM_MAP_MAX_BLOCKS, "kernels.h and gasm.h disagree on read mapping");
 static_assert(GASM_MAPG_COUNTERS == GASM_MAPG_FIELDS && GASM_MAPG_GAP == GASM_MAP_MAX_GAP, "kernels.h and gasm.h disagree on gapped read mapping");
+static_assert(GASM_MAPSCORE_CLASSES == GASM_MAPSCORE_FIELDS, "kernels.h and gasm.h disagree on mapped scoring");
 static_assert(GASM_CORRECT_STATS == GASM_CORRECT_FIELDS && GASM_CORRECT_KMER_CAP == GASM_CORRECT_MAX_KMERS, "kernels.h and gasm.h disagree on read correction");
 
 // ---- the passes that lay reads over a finished build: each on the stream of the build, behind it; each reads the build's arrays and the
@@ -1738,6 +1743,84 @@ static int score_launch_graph(gasm_ctx* ctx, DevReads& rd, DevPaths& dp, int kme
     ss.h_pd_off.clear();
     ss.launched = true;
     return GASM_OK;
+}
+
+// Mapped scoring: the records of the build's read mapping (bs.map or bs.mapg) into breakage sums under T tables, read starts per contig base
+// and class counters.  Behind the finished build on its stream: the sizes are the report's.  One memset of the accumulators, one
+// k_score_mapped, a k_score_finish per table (as it is: seg_empty = nullptr, the contigs' extents from c_off — it reads no packed path then)
+static PassLayout mapscore_layout(u32 T, u32 P, u64 contig_bases, u32 S) {
+    const size_t p = P;
+    return {{3 * (size_t)T * p, 8, 8, false}, {2 * p, 4, 4, false}, {p, 4, 4, true}, {(size_t)T * p, 8, 8, true}, {(size_t)contig_bases, 4, 4, true},
+            {(size_t)S * GASM_MAPSCORE_FIELDS, 8, 8, true}};
+}
+
+int pipeline_score_mapped(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, int kmer, ScoreTable* const* tbs, u32 T, bool partial) {
+    if (rd.positioned) { gasm_set_error("mapped scoring needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
+    if (T < 1 || T > GASM_MAX_TABLES) { gasm_set_error("n_tables must be 1..%d (got %u)", GASM_MAX_TABLES, T); return GASM_ERR_INVALID; }
+    if (kmer < 0) { gasm_set_error("kmer must be >= 0"); return GASM_ERR_INVALID; }
+    GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
+    const PassState& src = gapped ? bs.mapg : bs.map;
+    if (!src.queued) { gasm_set_error("mapped scoring needs a read mapping of that source over the last build"); return GASM_ERR_STATE; }
+    const u64 max_reads = max_seg_reads(rd);
+    for (u32 t = 0; t < T; ++t)
+        if (tbs[t]->fixed_shift(max_reads) < 0) { gasm_set_error("table %u has no fixed-point shift for these reads: mapped scoring has no FP64 form", t); return GASM_ERR_INVALID; }
+    HIPCHK(hipSetDevice(ctx->device));
+    GCHK(ensure_lds_attrs(ctx));
+    const u32 S = rd.n_segments, P = bs.n_contigs;
+    const u64 bases = P ? bs.contig_bases : 0;
+    FixTables ft = {};
+    for (u32 t = 0; t < T; ++t) {
+        GCHK(tbs[t]->set_fixed(ctx, tbs[t]->fixed_shift(max_reads)));
+        ft.p[t] = tbs[t]->d_fix.as<long long>();
+        bs.mapscore_shift[t] = tbs[t]->fix_shift;
+    }
+    PassState& ps = bs.mapscore;
+    ps.queued = false;
+    const PassLayout l = mapscore_layout(T, P, bases, S);
+    GCHK(pass_begin(ctx, ps, l));
+    const PassLayout ml = map_layout(gapped, rd.n_reads, bases, S, src.param[0]);
+    const ContigIndex ci = contig_index(bs);
+    u32* const d_cnt = l.at<u32>(ps.d, MAPSC_CNT);
+    unsigned long long* const d_fx = l.at<unsigned long long>(ps.d, MAPSC_FX);
+    if (rd.n_reads && S) {
+        const u32 reads_per_wg = GASM_WG;     // one read per thread: a record load, the contig's extent, a window, T gathers
+        const u32 rchunks = (u32)ceil_div_u64(max_reads, reads_per_wg);
+        // the LDS accumulators as score_launch_graph sizes them (the build is finished: its contig count is there)
+        u32 lds_paths = std::min<u32>(std::max<u32>(bs.have_actual ? bs.paths_est : 1024u, 1u), (u32)(GASM_SCORE_PATH_CAP * 12 / (4 + 8 * T)));
+        if (const int cap = env_int("GASM_DBG_SCORE_LDS_PATHS", 0)) lds_paths = std::min<u32>(lds_paths, (u32)std::max(1, cap));
+        const size_t lds_bytes = (size_t)lds_paths * (4 + 8 * (size_t)T);
+        const int32_t* const rec = ml.at<int32_t>(src.d, gapped ? (size_t)MAPG_REC : (size_t)MAP_REC);
+        const int32_t* const rec_gap = gapped ? ml.at<int32_t>(src.d, MAPG_GAP) : nullptr;
+#define GASM_LAUNCH_MAPSCORE(TT)                                                                                                                      \
+    if (gapped) GLAUNCH(ctx, "k_score_mapped_gapped", (k_score_mapped<TT, true>), seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), ci, rec, rec_gap, \
+                        ft, kmer, partial ? 1u : 0u, reads_per_wg, rchunks, lds_paths, d_cnt, d_fx, (u64)P, l.at<u32>(ps.d, MAPSC_PILE),               \
+                        l.at<unsigned long long>(ps.d, MAPSC_COUNTERS));                                                                               \
+    else GLAUNCH(ctx, "k_score_mapped", (k_score_mapped<TT, false>), seg_grid(rchunks, S), dim3(GASM_WG), lds_bytes, rd.view(), ci, rec, rec_gap, ft, kmer, \
+                 partial ? 1u : 0u, reads_per_wg, rchunks, lds_paths, d_cnt, d_fx, (u64)P, l.at<u32>(ps.d, MAPSC_PILE),                                 \
+                 l.at<unsigned long long>(ps.d, MAPSC_COUNTERS))
+        GASM_TABLES_SWITCH(T, GASM_LAUNCH_MAPSCORE)
+#undef GASM_LAUNCH_MAPSCORE
+    }
+    if (ci.have_graph) {
+        PathSet pth = {};
+        pth.p_off = ci.c_off; pth.seg_path_off = ci.seg_cstart; pth.n_segments = S;      // (words: not read without seg_empty)
+        const u32 grid_p = (u32)std::max<u64>(1, std::min<u64>(ceil_div_u64(P, GASM_WG), (u64)ctx->n_cu * 8));
+        int32_t* const o_br = l.at<int32_t>(ps.d, MAPSC_I32);
+        for (u32 t = 0; t < T; ++t) {
+            double* const o_bp = l.at<double>(ps.d, MAPSC_F64) + (size_t)t * 3 * P;
+            GLAUNCH(ctx, "k_score_finish", k_score_finish, dim3(grid_p), dim3(GASM_WG), 0, pth, d_cnt, d_fx + (size_t)t * P, ft.p[t], (const u64*)nullptr, kmer,
+                    std::ldexp(1.0, -tbs[t]->fix_shift), o_bp, o_bp + P, o_bp + 2 * (size_t)P, o_br, o_br + P, bs.d_seg_cstart.as<u32>() + S);
+        }
+    }
+    ps.param[0] = T;
+    ps.param[1] = gapped ? 1u : 0u;
+    ps.queued = true;
+    return GASM_OK;
+}
+
+int pipeline_fetch_mapped_scores(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
+    return pass_fetch(ctx, bs.mapscore, mapscore_layout(bs.mapscore.param[0], bs.n_contigs, bs.n_contigs ? bs.contig_bases : 0, rd.n_segments),
+                      "gasm_batch_fetch_mapped_scores", "gasm_batch_score_mapped");
 }
 
 bool pipeline_score_uses_graph(const DevReads& rd, const BuildState& graph, ScoreTable* const* tbs, u32 T) {

@@ -3,7 +3,7 @@ base the four base counts of the reads laid over it, per segment a mismatch hist
 include/gasm.h "Read mapping") — and the host arithmetic on top: depth, mapped fraction, error rate, consensus, variants."""
 import numpy as np
 
-from ._lib import MAP_FIELDS, MAPG_FIELDS
+from ._lib import MAP_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS
 
 RECORD = np.dtype([("contig", np.int32), ("diagonal", np.int32), ("mismatches", np.int32), ("blocks", np.int32), ("overlap", np.int32)])
 _BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -196,4 +196,83 @@ class GappedReadMap(ReadMap):
             t = np.frombuffer(s.encode(), dtype=np.uint8)
             keep = ~((dp >= int(min_depth)) & (2 * g[:, 0].astype(np.int64) > dp)) if len(t) else np.zeros(0, bool)
             out.append(t[keep].tobytes().decode())
+        return out
+
+
+def break_window(contig, j, kmer=8):
+    """the break window of a hit at position j of `contig`, as a string: the scorer's (lib/DeNovoAssembler.cpp:366-386) — the octamer
+    from max(0, j - kmer // 2), 2 / 4 / 6 bases wide for j = 1 / 2 / 3 where it starts at the contig's first base, cut at the contig's end"""
+    start = max(0, int(j) - int(kmer) // 2)
+    width = {1: 2, 2: 4, 3: 6}.get(int(j), 8) if start == 0 else 8
+    return contig[start:start + width]
+
+
+class MappedScores:
+    """what SegmentBatch.score_mapped() returns (the rule and its limits: include/gasm.h "Mapped scoring"): per table the scorer's
+    per-contig numbers from the reads' mapped starts, per contig base the reads scored with their start there, per segment the four
+    class counters — and the host arithmetic on top."""
+
+    def __init__(self, kmer, source, partial, contigs, per_table, start_pile, counters):
+        """contigs: per segment the list of contig strings; per_table: per table (the dict of SegmentBatch.scores(), int64 fx per
+        contig, shift); start_pile: one uint32 per contig base of the batch; counters: len(MAPSCORE_FIELDS) per segment"""
+        self.kmer, self.source, self.partial = int(kmer), source, bool(partial)
+        self._contigs = [list(c) for c in contigs]
+        self.n_segments = len(self._contigs)
+        self._tables = list(per_table)
+        self.n_tables = len(self._tables)
+        self._cnt = np.asarray(counters, dtype=np.uint64).reshape(self.n_segments, len(MAPSCORE_FIELDS))
+        lens = [len(s) for cs in self._contigs for s in cs]
+        self._pile = np.asarray(start_pile, dtype=np.uint32).reshape(-1)
+        if len(self._pile) != sum(lens):
+            raise ValueError("the start pile does not have one count per contig base")
+        self._base_off = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+        self._seg_c = np.concatenate([[0], np.cumsum([len(cs) for cs in self._contigs])])
+
+    def _seg(self, segment):
+        if not 0 <= int(segment) < self.n_segments:
+            raise IndexError(f"segment {segment} of {self.n_segments}")
+        return int(segment)
+
+    def _table(self, table):
+        if not 0 <= int(table) < self.n_tables:
+            raise IndexError(f"table {table} of {self.n_tables}")
+        return self._tables[int(table)]
+
+    def contigs(self, segment):
+        return list(self._contigs[self._seg(segment)])
+
+    def scores(self, table=0):
+        """the dict of SegmentBatch.scores(): per-contig arrays in contigs_raw() order, and seg_contig_off"""
+        return dict(self._table(table)[0])
+
+    def score_fixed(self, table=0):
+        """(int64 fixed-point breakage sums per contig, shift): bp_score == fx * 2**-shift exactly"""
+        t = self._table(table)
+        return t[1].copy(), t[2]
+
+    def starts(self, segment):
+        """one uint32 array per contig: the reads scored with their start on every base"""
+        s = self._seg(segment)
+        c0 = int(self._seg_c[s])
+        return [self._pile[int(self._base_off[c0 + c]):int(self._base_off[c0 + c + 1])].copy() for c in range(len(self._contigs[s]))]
+
+    def counters(self, segment, as_dict=False):
+        c = self._cnt[self._seg(segment)].copy()
+        return {name: int(v) for name, v in zip(MAPSCORE_FIELDS, c)} if as_dict else c
+
+    def scored_fraction(self, segment):
+        """scored reads / reads (whole, with partial also end_clipped); 0.0 for a segment without reads"""
+        c = self.counters(segment)
+        n = int(c.sum())
+        return (int(c[3]) + (int(c[2]) if self.partial else 0)) / n if n else 0.0
+
+    def window_counts(self, segment, contig):
+        """{window string: reads scored with that break window} of one contig of the segment, from starts() and the contig's text: the
+        numerators of the reference's path_freq"""
+        s = self._seg(segment)
+        text, pile = self._contigs[s][contig], self.starts(s)[contig]
+        out = {}
+        for j in np.nonzero(pile)[0]:
+            w = break_window(text, int(j), self.kmer)
+            out[w] = out.get(w, 0) + int(pile[j])
         return out

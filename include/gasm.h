@@ -778,6 +778,69 @@ int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t
 int gasm_batch_map_reads_gapped(gasm_batch* b, uint32_t max_edits, uint32_t max_gap);
 int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const int32_t** rec_gap, const uint32_t** pile,
                                      const uint32_t** gap_pile, const uint32_t** edit_hist, const uint64_t** counters);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Mapped scoring: breakage scores from mapped reads, so that reads with errors count too.  gasm_batch_score matches exactly: a read
+ * scores iff it is a substring of a contig, so a read with one wrong base scores nothing although its start, the breakpoint, is
+ * good.  The two read mappings leave, for every read, the contig and the diagonal d of its best alignment: the contig base under the
+ * read's first base is d.  This pass turns those records into breaks.  A pass of its own, with arrays and tables of its own:
+ * gasm_batch_score*, gasm_batch_map_reads* and their tables stay as they are, and a batch that never calls it launches exactly what it
+ * launched without.
+ * The rule.  INPUTS.  The contigs of the batch's LAST FINISHED BUILD, whatever its options; the records of gasm_batch_map_reads
+ * (source = GASM_MAPSCORE_UNGAPPED) or of gasm_batch_map_reads_gapped (GASM_MAPSCORE_GAPPED) made OVER THAT BUILD; kmer, as
+ * gasm_batch_score takes it; n_tables in 1..GASM_MAX_TABLES tables of GASM_TABLE_ROWS doubles; flags.
+ *   PER READ of len bases take rec = (c, d_1, cost | n << 16, overlap); for the gapped source also ins = rec_gap[1], the inserted
+ *   bases, for the ungapped source ins = 0.  Exactly one class applies, tested in this order:
+ *   1. c < 0: UNPLACED.  This covers short, skipped, unseeded and rejected reads.
+ *   2. d_1 < 0: START_CLIPPED.  The read's first base lies in front of the contig, so its break is not on this contig.  It is never
+ *      scored.
+ *   3. overlap + ins < len: END_CLIPPED.  The read starts on the contig and runs off its end.  It is scored only with the flag
+ *      GASM_MAPSCORE_PARTIAL.
+ *   4. Otherwise: WHOLE.  It is scored.
+ *   A SCORED READ adds 1 to kmer_breaks[c], 1 to start_pile[c_off[c] + d_1], and for every table t fix_t[window] to the 64-bit sum
+ *   fx[t][c].  window is the break window of a hit at position j = d_1 of contig c, exactly the scorer's (lib/DeNovoAssembler.cpp:
+ *   366-386: the octamer around the break, 2 / 4 / 6 bases wide for j = 1 / 2 / 3, cut where the contig ends).  fix_t =
+ *   llrint(p * 2^shift_t), shift_t by gasm_batch_score's rule with n = the most reads of one segment.
+ *   THE BEST ALIGNMENT ONLY.  A read is one fragment with one break, so accepted alignments other than the record's do not score.
+ *   This differs from the pileups, which count every accepted block or chain.
+ *   OUTPUTS per contig and table, formed as gasm_batch_score forms them: bp_score = fx * 2^-shift, norm_by_break_freqs = bp_score /
+ *   kmer_breaks (0 without hits), norm_by_len = bp_score / len, sequence_len.  start_pile: one uint32 per base of the batch's contig
+ *   text, the reads scored with their start there.  counters[s * GASM_MAPSCORE_FIELDS + f], f in this order: unplaced,
+ *   start_clipped, end_clipped, whole; they sum to the segment's reads.  All sums are integer atomics: the results do not depend on
+ *   the order the reads are taken in.
+ *   NO FP64 FALLBACK.  A table with a non-finite entry, or one without a shift in [0, 1000], makes the call return GASM_ERR_INVALID,
+ *   and nothing is queued.  A read shorter than k is unplaced and scores nothing: a stated difference from gasm_batch_score, where an
+ *   empty read hits every path at position 0.
+ *   STRANDS.  Nothing is added: the records are of the reads as given, so a reverse-strand read scores on the twin, as it does in
+ *   gasm_batch_score.
+ *   THE PROPERTY that ties it to gasm_batch_score.  Take a batch that has no read shorter than k and no read of more than
+ *   GASM_THREAD_MAX_KMERS k-mers.  After any build of it, mapped scoring from gasm_batch_map_reads(b, 0) without
+ *   GASM_MAPSCORE_PARTIAL gives, for every table and bit for bit, the results of gasm_batch_score_tables with the same tables: fx,
+ *   shift, kmer_breaks, sequence_len, bp_score, norm_by_break_freqs and norm_by_len.  (A read is a substring of a contig iff its
+ *   first k-mer's head on that contig verifies with 0 mismatches and overlap = len; that block has the largest possible overlap; and
+ *   no second contig can hold all of the read's k-mers.)  The same holds for the gapped source at max_edits = max_gap = 0.
+ *   LIMITS.  An accepted alignment can still be the wrong place: a repeat copy within max_edits.  An indel within k of a read's start
+ *   leaves the read unplaced: the mapping's own limit.  gasm_batch_guided keeps using gasm_batch_score's sums.  Pooled builds
+ *   (gasm_pool_*) get none of this.
+ * gasm_batch_score_mapped          finishes the pending build and queues k_score_mapped and the final sums on the step slot of the last
+ *                                  build, behind it.  GASM_ERR_STATE before a build, without a mapping of that source over the last
+ *                                  build, and for the positioned reads of pooled builds; GASM_ERR_INVALID for a null batch or table, a
+ *                                  bad source, unknown flag bits, n_tables out of range, a kmer that gasm_batch_score refuses, or a table
+ *                                  without a shift.
+ * gasm_batch_fetch_mapped_scores   table t's results, one entry per contig in the order of gasm_batch_fetch_contigs; host copies, valid
+ * gasm_batch_fetch_mapped_starts   until the next call or build.  t >= n_tables: GASM_ERR_INVALID; without a mapped score over the
+ *                                  last build: GASM_ERR_STATE.
+ * What to do with them is host code: genomeassembler_dev_amd/readmap.py, MappedScores.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAPSCORE_UNGAPPED 0
+#define GASM_MAPSCORE_GAPPED 1
+#define GASM_MAPSCORE_PARTIAL 1u /* flags */
+#define GASM_MAPSCORE_FIELDS 4   /* unplaced, start_clipped, end_clipped, whole: they sum to the segment's reads */
+int gasm_batch_score_mapped(gasm_batch* b, int source, int kmer, const double* tables, uint32_t n_tables, uint32_t flags);
+int gasm_batch_fetch_mapped_scores(gasm_batch* b, uint32_t t, const double** bp_score, const double** norm_by_break_freqs,
+                                   const double** norm_by_len, const int32_t** kmer_breaks, const int32_t** sequence_len,
+                                   const int64_t** fx, int* shift);
+int gasm_batch_fetch_mapped_starts(gasm_batch* b, const uint32_t** start_pile /* one per contig base */,
+                                   const uint64_t** counters /* n_segments x GASM_MAPSCORE_FIELDS */);
 uint64_t gasm_batch_total_kmers(const gasm_batch* b);   /* k-mers extracted by the last build */
 uint64_t gasm_batch_total_reads(const gasm_batch* b);
 
