@@ -472,29 +472,31 @@ def map_reads(reads, k, max_mismatch=4, ctx=None, **build):
         b.close()
 
 
-def map_reads_gapped(reads, k, max_edits=6, max_gap=3, ctx=None, **build):
+def map_reads_gapped(reads, k, max_edits=6, max_gap=3, end_gap=0, ctx=None, **build):
     """map_reads for reads with insertions and deletions: heads on neighbouring diagonals, at most max_gap apart, are joined and the
     read is verified as one alignment of at most max_edits edits: a readmap.GappedReadMap that speaks of segment 0 (ReadMap's methods,
-    and gap_records(0), gap_pileup(0), indels(0); the rule and its limits: include/gasm.h "Gapped read mapping").  build: as for
-    contig_graph."""
+    and gap_records(0), gap_pileup(0), indels(0); the rule and its limits: include/gasm.h "Gapped read mapping").  end_gap > 0: one gap
+    of at most end_gap bases is also tried at each end of every chain, which places most reads with an indel within k of an end
+    ("End gaps"; end_records(0), end_counters(0)).  build: as for contig_graph."""
     from .batch import SegmentBatch
     b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
     try:
-        return b.build_simplified(int(k), **build).map_reads_gapped(max_edits, max_gap)
+        return b.build_simplified(int(k), **build).map_reads_gapped(max_edits, max_gap, end_gap)
     finally:
         b.close()
 
 
-def calc_breakscore_mapped(reads, k, kmer=8, tables=None, max_edits=6, max_gap=3, partial=False, ctx=None, **build):
+def calc_breakscore_mapped(reads, k, kmer=8, tables=None, max_edits=6, max_gap=3, partial=False, ctx=None, end_gap=0, **build):
     """breakage scores of the contigs of one segment's reads (a list of str) from the reads' mapped starts: build, gapped mapping
     within max_edits edits and gaps of at most max_gap, mapped scoring — a readmap.MappedScores that speaks of segment 0 (scores(),
     score_fixed(), starts(0), counters(0), scored_fraction(0), window_counts(0, c); the rule and its limits: include/gasm.h "Mapped
     scoring").  A read with errors scores where its first base lies; calc_breakscore scores it only as an exact substring.  tables,
-    partial: as SegmentBatch.score_mapped; build: as for contig_graph."""
+    partial: as SegmentBatch.score_mapped; end_gap: as SegmentBatch.map_reads_gapped (above 0 a read with an indel near its start is
+    placed, with its break on the right base); build: as for contig_graph."""
     from .batch import SegmentBatch
     b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
     try:
-        b.build_simplified(int(k), **build).map_reads_gapped(max_edits, max_gap)
+        b.build_simplified(int(k), **build).map_reads_gapped(max_edits, max_gap, end_gap)
         return b.score_mapped(kmer, tables, "gapped", partial)
     finally:
         b.close()

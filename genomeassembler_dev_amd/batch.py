@@ -7,7 +7,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 from .pairs import PairPlaces
@@ -291,18 +291,25 @@ class SegmentBatch:
         return ReadMap(self.k, strands, max_mismatch, contigs, rec, pile, hist, cnt,
                        [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
 
-    def map_reads_gapped(self, max_edits=6, max_gap=3):
+    def map_reads_gapped(self, max_edits=6, max_gap=3, end_gap=0):
         """map_reads() for reads that carry insertions and deletions as well (gasm_batch_map_reads_gapped; the rule: include/gasm.h "Gapped
         read mapping") as a readmap.GappedReadMap: heads of a read on neighbouring diagonals of one contig, at most max_gap apart, are
         joined into a chain and verified as one alignment of a cost (mismatches + gap lengths) of at most max_edits.  max_edits: 0 ..
-        _lib.MAP_MAX_MISMATCH, max_gap: 0 .. _lib.MAP_MAX_GAP (0: the tables of map_reads(max_edits)).  A pass of its own: what
-        map_reads() returned stays what it was."""
+        _lib.MAP_MAX_MISMATCH, max_gap: 0 .. _lib.MAP_MAX_GAP (0: the tables of map_reads(max_edits)).  end_gap: 0 .. _lib.MAP_MAX_GAP;
+        above 0 one gap of at most end_gap bases is also tried at each end of every chain, between the read's end and the outermost
+        seed (gasm_batch_map_reads_gapped_ends; the rule: "End gaps"), and the map has end_records() and end_counters().  A pass of its
+        own: what map_reads() returned stays what it was."""
         if not 0 <= int(max_edits) <= MAP_MAX_MISMATCH:
             raise ValueError(f"max_edits must be 0..{MAP_MAX_MISMATCH}")
         if not 0 <= int(max_gap) <= MAP_MAX_GAP:
             raise ValueError(f"max_gap must be 0..{MAP_MAX_GAP}")
-        max_edits, max_gap = int(max_edits), int(max_gap)
-        check(lib().gasm_batch_map_reads_gapped(self.h, max_edits, max_gap))
+        if not 0 <= int(end_gap) <= MAP_MAX_GAP:
+            raise ValueError(f"end_gap must be 0..{MAP_MAX_GAP}")
+        max_edits, max_gap, end_gap = int(max_edits), int(max_gap), int(end_gap)
+        if end_gap:
+            check(lib().gasm_batch_map_reads_gapped_ends(self.h, max_edits, max_gap, end_gap))
+        else:
+            check(lib().gasm_batch_map_reads_gapped(self.h, max_edits, max_gap))
         ps = [C.c_void_p() for _ in range(6)]
         check(lib().gasm_batch_fetch_read_map_gapped(self.h, *[C.byref(p) for p in ps]))
         seg, o, contigs = self._contigs_by_segment()
@@ -311,8 +318,13 @@ class SegmentBatch:
         pile, gpile = _arr(ps[2], C.c_uint32, 4 * total), _arr(ps[3], C.c_uint32, 2 * total)
         hist, cnt = _arr(ps[4], C.c_uint32, self.n_segments * (max_edits + 1)), _arr(ps[5], C.c_uint64, self.n_segments * len(MAPG_FIELDS))
         strands = self.strands()
+        ends = {}
+        if end_gap:
+            pe = [C.c_void_p() for _ in range(2)]
+            check(lib().gasm_batch_fetch_read_map_ends(self.h, *[C.byref(p) for p in pe]))
+            ends = dict(end_gap=end_gap, rec_end=_arr(pe[0], C.c_int32, 4 * self.n_reads), end_counters=_arr(pe[1], C.c_uint64, self.n_segments * len(MAPEND_FIELDS)))
         return GappedReadMap(self.k, strands, max_edits, max_gap, contigs, rec, gap, pile, gpile, hist, cnt,
-                             [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None))
+                             [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None), **ends)
 
     def score_mapped(self, kmer=8, tables=None, source="gapped", partial=False):
         """breakage scores from the records of the last map_reads_gapped() (source="gapped") or map_reads() ("ungapped") over the last

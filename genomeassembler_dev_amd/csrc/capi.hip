@@ -1072,6 +1072,31 @@ int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const i
     API_GUARD_END
 }
 
+// ---- end gaps (kernels_map.hip, k_read_map_ends; the rule: include/gasm.h "End gaps"): the gapped mapping's own state, two more tables
+int gasm_batch_map_reads_gapped_ends(gasm_batch* b, uint32_t max_edits, uint32_t max_gap, uint32_t end_gap) {
+    API_GUARD_BEGIN
+    int args = at_most("max_edits", max_edits, GASM_MAP_MAX_MISMATCH);
+    if (args == GASM_OK) args = at_most("max_gap", max_gap, GASM_MAP_MAX_GAP);
+    if (args == GASM_OK) args = at_most("end_gap", end_gap, GASM_MAP_MAX_GAP);
+    GCHK(batch_pass_ready(b, "gasm_batch_map_reads_gapped_ends", args));
+    return pipeline_map_reads(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, true, max_edits, max_gap, end_gap);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_read_map_ends(gasm_batch* b, const int32_t** rec_end, const uint64_t** end_counters) {
+    API_GUARD_BEGIN
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_read_map_ends", rec_end && end_counters));
+    const PassState& ps = b->S().bs.mapg;
+    if (ps.queued && !ps.param[1]) {
+        gasm_set_error("gasm_batch_fetch_read_map_ends: the last gapped mapping over the last build tried no end gaps (gasm_batch_map_reads_gapped_ends with end_gap > 0 does)");
+        return GASM_ERR_STATE;
+    }
+    GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, b->S().bs, true));
+    *rec_end = ps.host<int32_t>(MAPG_END); *end_counters = ps.host<uint64_t>(MAPG_ENDCNT);
+    return GASM_OK;
+    API_GUARD_END
+}
+
 // ---- mapped scoring (kernels_score.hip, k_score_mapped; the rule: include/gasm.h "Mapped scoring")
 int gasm_batch_score_mapped(gasm_batch* b, int source, int kmer, const double* tables, uint32_t n_tables, uint32_t flags) {
     API_GUARD_BEGIN

@@ -317,7 +317,7 @@ __global__ void k_pair_place(ReadSet rs, GraphView gv, ContigIndex ci, u32 orien
                              unsigned long long* counters);
 
 // ---- kernels_map.hip: read mapping, ungapped (include/gasm.h, "Read mapping") and gapped ("Gapped read mapping"): one body, GAPPED = false
-// is the launch "k_read_map", GAPPED = true the launch "k_read_map_gapped"
+// is the launch "k_read_map", GAPPED = true the launch "k_read_map_gapped", GAPPED and ENDS the launch "k_read_map_ends"
 #define GASM_MAP_COUNTERS 7           // = GASM_MAP_FIELDS of include/gasm.h (checked in pipeline.hip)
 #define GASM_MAPG_COUNTERS 8          // = GASM_MAPG_FIELDS: the same seven and the gapped reads
 #define GASM_MAP_BLOCKS 8             // = GASM_MAP_MAX_BLOCKS: distinct heads of a read that are kept (one per lane 0 .. 7 of its wave)
@@ -325,13 +325,18 @@ __global__ void k_pair_place(ReadSet rs, GraphView gv, ContigIndex ci, u32 orien
 // rec: 4 int32 per read (16-byte aligned); pile: 4 u32 per base of the contig text; hist: max_edits + 1 bins per segment (ungapped: max_edits
 // is max_mismatch); counters: GASM_MAP_COUNTERS or GASM_MAPG_COUNTERS per segment.  Gapped only (else not read): rec_gap, 4 int32 per
 // read (16-byte aligned), and gap_pile, 2 u32 per base of the text (deletions, insertions).  All but the records zeroed by the caller
+// ENDS = true (with GAPPED; include/gasm.h, "End gaps"; the launch "k_read_map_ends") only (else not read): end_gap, rec_end, 4 int32 per read
+// (16-byte aligned), and end_counters, GASM_MAPEND_COUNTERS per segment, zeroed by the caller
+#define GASM_MAPEND_COUNTERS 4        // = GASM_MAPEND_FIELDS: front, back, rescued, start_moved
 struct MapOut {
     int32_t *rec, *rec_gap;
     u32 *pile, *gap_pile, *hist;
     unsigned long long* counters;
+    int32_t* rec_end;
+    unsigned long long* end_counters;
 };
-template <class K, bool GAPPED>
-__global__ void k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 reads_per_wg, u32 chunks, MapOut out);
+template <class K, bool GAPPED, bool ENDS>
+__global__ void k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 end_gap, u32 reads_per_wg, u32 chunks, MapOut out);
 
 // ---- kernels_score.hip
 struct SeedTable {

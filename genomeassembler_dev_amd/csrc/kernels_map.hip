@@ -1,5 +1,5 @@
 // kernels_map.hip — read mapping onto the contigs of a finished build, without gaps (include/gasm.h, "Read mapping") and with them
-// ("Gapped read mapping"): ONE body, k_read_map<K, GAPPED>.  The heads of a read are found once for both; GAPPED = true joins the heads
+// ("Gapped read mapping"): ONE body, k_read_map<K, GAPPED, ENDS>.  The heads of a read are found once for both; GAPPED = true joins the heads
 // that lie on neighbouring diagonals of one contig into a chain and verifies it as one alignment with gaps, GAPPED = false takes every
 // head as a chain of its own and compiles the rest out (the join loop, the breakpoints, my_J, my_t, the gap record, the gap pileup, the
 // eighth counter).
@@ -26,11 +26,20 @@
 // read position against [0, len) and its contig position against [0, len(c)) although the rule's argument (include/gasm.h) says that the
 // pieces lie inside both; a gap-pileup add checks its contig position likewise.
 // ci.have_graph = 0: only short, skipped and unseeded are counted.
+// ENDS = true (with GAPPED; the launch "k_read_map_ends"; include/gasm.h, "End gaps") tries one gap at each end of every chain, between the
+// read's end and the chain's outermost seed, before the pieces are verified.  Per end: one strided pass takes m0, the end's mismatches on
+// the ungapped diagonal, and the wave leaves when m0 < 2 (nearly every read).  Else for |g| = 1 .. min(end_gap, m0 - 1), the deletion
+// before the insertion, the breakpoint search of the joins runs once over the end's window (two ballots per 64 positions, running counts,
+// a wave minimum over cost << 16 | t: t stays below 2^13 and a cost below 2^13 as well, both far inside their halves) and a candidate is
+// kept only if it costs strictly less than the best so far, which starts at m0: that is the rule's key.  A taken gap adds a piece in front
+// of or behind the chain's (for_pieces), its gap to the gap pileup as a join's, and the chain's savings say whether the gaps rescued it.
+// ENDS = false compiles all of it out.
 #include "contig_index.h"
 
-template <class K, bool GAPPED>
-__global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 reads_per_wg, u32 chunks,
-                                                      MapOut out) {
+template <class K, bool GAPPED, bool ENDS>
+__global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 end_gap, u32 reads_per_wg,
+                                                      u32 chunks, MapOut out) {
+    static_assert(GAPPED || !ENDS, "end gaps belong to the gapped form");
     constexpr u32 N_CNT = GAPPED ? GASM_MAPG_COUNTERS : GASM_MAP_COUNTERS;
     __shared__ u32 s_cnt[N_CNT];
     ReadPass rp;
@@ -41,6 +50,7 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
     const int k = rp.k;
     const u64 below_lane = (1ull << lane) - 1ull;
     u32 c_cnt[N_CNT] = {};                                                    // of this wave's reads (wave-uniform)
+    u32 c_end[ENDS ? GASM_MAPEND_COUNTERS : 1] = {};                          // front, back, rescued, start_moved
     for_wave_reads(rp, reads_per_wg, chunks, [&](u64 r) {
         u64 p0;
         u32 len;
@@ -49,6 +59,7 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
         u32 cls;                                                              // the read's counter
         u32 n_heads = 0, n_acc = 0, dropped = 0, b_ov = 0, b_cost = 0, b_c = 0, b_q = 0, b_ins = 0, b_del = 0;
         int b_d = 0, b_dq = 0;
+        int b_gf = 0, b_tf = 0, b_gb = 0, b_tb = 0;                           // ENDS: the best chain's end gaps
         bool seeded_any = false;
         if (n == 0) cls = 0;
         else if (n > GASM_THREAD_KMER_CAP) cls = 1;
@@ -140,15 +151,79 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                     }
                 }
                 h = e + 1;
+                // ---- ENDS: one gap or none at either end (include/gasm.h, "End gaps", 5a and 5b)
+                int gf = 0, tf = 0, gb = 0, tb = 0;                            // the taken gaps and their breakpoints (g = 0: none)
+                u32 saved = 0;                                                 // m0 - cost over the taken gaps
+                if constexpr (ENDS) {
+                    const int J1 = lane_value(my_J, h0), Jq = lane_value(my_J, e);
+                    for (int side = 0; side < 2; ++side) {
+                        // the window [w0, w1) of the end, its ungapped diagonal dn (the chain's nearest) and whether it is eligible
+                        const int w0 = side ? Jq + k : 0, w1 = side ? (int)len : J1;
+                        const int dn = side ? d : d1;
+                        if (w1 <= w0 || (side ? (long long)dn + (long long)len > clen : dn < 0)) continue;
+                        u32 m0 = 0;
+                        for (int x0 = w0; x0 < w1; x0 += 64) {
+                            const int x = x0 + (int)lane;
+                            m0 += (u32)__popcll(__ballot(x < w1 && differ((long long)x, dn)));
+                        }
+                        if (m0 < 2) continue;
+                        u32 best_cost = m0;
+                        int best_g = 0, best_t = 0;
+                        for (int ag = 1; (u32)ag <= end_gap && (u32)ag < best_cost; ++ag)
+                            for (int sg = 0; sg < 2; ++sg) {                   // the deletion first
+                                const int g = sg ? -ag : ag, G = sg ? ag : 0;
+                                // front: the piece [0, t) on dl = d_1 - g, then [t + G, J_1) on d_1; back: [B, t) on d_q, then [t + G, len)
+                                // on dr = d_q + g.  t in [tlo, thi]; the left count runs from w0, the right one to w1 = whi + G
+                                const int dl = side ? dn : dn - g, dr = side ? dn + g : dn;
+                                const int whi = w1 - G, tlo = side ? w0 : 1, thi = side ? whi - 1 : whi;
+                                if (thi < tlo || (side ? (long long)dr + (long long)len > clen : dl < 0)) continue;
+                                const bool one_chunk = whi - w0 < 64;
+                                u32 b_total = 0;
+                                if (!one_chunk)
+                                    for (int t0 = w0; t0 < whi; t0 += 64) {
+                                        const int t = t0 + (int)lane;
+                                        b_total += (u32)__popcll(__ballot(t < whi && differ((long long)t + G, dr)));
+                                    }
+                                u32 a_run = 0, b_run = 0, best = 0xFFFFFFFFu;
+                                for (int t0 = w0; t0 <= whi; t0 += 64) {
+                                    const int t = t0 + (int)lane;
+                                    const u64 ma = __ballot(t <= whi && differ((long long)t, dl));
+                                    const u64 mb = __ballot(t < whi && differ((long long)t + G, dr));
+                                    if (one_chunk) b_total = (u32)__popcll(mb);
+                                    const u32 cost_t = (u32)ag + a_run + (u32)__popcll(ma & below_lane) + b_total - b_run - (u32)__popcll(mb & below_lane);
+                                    const u32 m = wave_min_u32(t >= tlo && t <= thi ? (cost_t << 16) | (u32)t : 0xFFFFFFFFu);
+                                    best = m < best ? m : best;
+                                    a_run += (u32)__popcll(ma);
+                                    b_run += (u32)__popcll(mb);
+                                }
+                                if ((best >> 16) < best_cost) { best_cost = best >> 16; best_g = g; best_t = (int)(best & 0xFFFFu); }
+                            }
+                        if (best_g == 0) continue;
+                        saved += m0 - best_cost;
+                        const int ag = best_g < 0 ? -best_g : best_g;
+                        gaps += (u32)ag; ins += best_g < 0 ? (u32)ag : 0u; del += best_g > 0 ? (u32)ag : 0u;
+                        if (side) { gb = best_g; tb = best_t; } else { gf = best_g; tf = best_t; }
+                    }
+                }
                 // the chain's pieces in turn: piece i is read bases [lo, hi) on head i's diagonal di, and en its end before the clamps (the
                 // breakpoint behind head i; of the last piece, its hi).  piece(i, di, lo, hi, en) = false ends the walk, which then gives false
                 auto for_pieces = [&](auto&& piece) -> bool {
                     long long s = d1 < 0 ? -(long long)d1 : 0;
+                    if constexpr (ENDS)
+                        if (gf) {                                              // the piece in front of the front gap: [0, t_f) on d_1 - g_f
+                            const int d0 = d1 - gf;
+                            long long hi = clen - (long long)d0;
+                            if (hi > (long long)tf) hi = (long long)tf;
+                            if (!piece(e, d0, d0 < 0 ? -(long long)d0 : 0ll, hi, (long long)tf)) return false;
+                            s = (long long)tf + (gf < 0 ? -(long long)gf : 0);
+                        }
                     for (u32 i = h0; i <= e; ++i) {
                         const int di = lane_value(my_d, i);
                         long long hi = clen - (long long)di;
                         if (hi > (long long)len) hi = (long long)len;
-                        const long long en = i == e ? hi : (long long)lane_value(my_t, i);
+                        long long en = i == e ? hi : (long long)lane_value(my_t, i);
+                        if constexpr (ENDS)
+                            if (i == e && gb) en = (long long)tb;
                         if (en < hi) hi = en;
                         const long long lo = s < -(long long)di ? -(long long)di : s;
                         if (!piece(i, di, lo, hi, en)) return false;
@@ -157,6 +232,14 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                             s = en + (g < 0 ? -(long long)g : 0);
                         }
                     }
+                    if constexpr (ENDS)
+                        if (gb) {                                              // the piece behind the back gap: [t_b + G, len) on d_q + g_b
+                            const int dl = d + gb;
+                            long long hi = clen - (long long)dl;
+                            if (hi > (long long)len) hi = (long long)len;
+                            const long long sb = (long long)tb + (gb < 0 ? -(long long)gb : 0);
+                            if (!piece(e, dl, sb < -(long long)dl ? -(long long)dl : sb, hi, hi)) return false;
+                        }
                     return true;
                 };
                 // ---- verify the pieces
@@ -188,9 +271,26 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                     }
                     return true;
                 });
+                if constexpr (ENDS) {                                          // the end gaps' adds to the gap pileup, as a join's
+                    for (int side = 0; side < 2; ++side) {
+                        const int g = side ? gb : gf;
+                        if (!g) continue;
+                        const long long p = side ? (long long)d + tb : (long long)(d1 - gf) + tf;      // left diagonal + breakpoint
+                        if (g > 0) {
+                            const long long pp = p + lane;
+                            if ((int)lane < g && pp >= 0 && pp < clen) atomicAdd(&out.gap_pile[2 * (cb + (u64)pp)], 1u);
+                        } else if (lane == 0 && p >= 0 && p < clen)
+                            atomicAdd(&out.gap_pile[2 * (cb + (u64)p) + 1], 1u);
+                    }
+                    c_end[0] += gf ? 1u : 0u; c_end[1] += gb ? 1u : 0u; c_end[2] += cost + saved > max_edits ? 1u : 0u;
+                }
                 if (lane == 0) atomicAdd(&out.hist[(size_t)rp.seg * (max_edits + 1) + cost], 1u);
                 if (n_acc == 0 || ov > b_ov || (ov == b_ov && cost < b_cost)) {
                     b_ov = ov; b_cost = cost; b_c = c; b_d = d1; b_q = e - h0 + 1; b_ins = ins; b_del = del; b_dq = d;
+                    if constexpr (ENDS) {
+                        b_d = d1 - gf; b_q += (gf ? 1u : 0u) + (gb ? 1u : 0u); b_dq = d + gb;
+                        b_gf = gf; b_tf = tf; b_gb = gb; b_tb = tb;
+                    }
                 }
                 ++n_acc;
             }
@@ -206,15 +306,27 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                 w.x = (int)b_q; w.y = (int)b_ins; w.z = (int)b_del; w.w = n_acc ? b_dq : 0;
                 *reinterpret_cast<int4*>(out.rec_gap + r * 4) = w;
             }
+            if constexpr (ENDS) {
+                int4 w;
+                w.x = n_acc ? b_gf : 0; w.y = n_acc ? b_tf : 0; w.z = n_acc ? b_gb : 0; w.w = n_acc ? b_tb : 0;
+                *reinterpret_cast<int4*>(out.rec_end + r * 4) = w;
+            }
         }
 #pragma unroll
         for (u32 q = 0; q < 6; ++q) c_cnt[q] += cls == q ? 1u : 0u;
         c_cnt[6] += dropped;
         if constexpr (GAPPED) c_cnt[7] += n_acc && b_q >= 2 ? 1u : 0u;
+        if constexpr (ENDS) c_end[3] += n_acc && b_gf ? 1u : 0u;
     });
+    if constexpr (ENDS)                                                       // (rare: one global atomic per non-zero counter and wave)
+        if (lane == 0)
+            for (u32 q = 0; q < GASM_MAPEND_COUNTERS; ++q)
+                if (c_end[q]) atomicAdd(&out.end_counters[(size_t)rp.seg * GASM_MAPEND_COUNTERS + q], (unsigned long long)c_end[q]);
     flush_wave_counters(c_cnt, s_cnt, out.counters + (size_t)rp.seg * N_CNT);
 }
-template __global__ void k_read_map<u64, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<K128, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<u64, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<K128, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<K128, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, true, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<K128, true, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, true, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<K128, true, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);

@@ -3,7 +3,7 @@ base the four base counts of the reads laid over it, per segment a mismatch hist
 include/gasm.h "Read mapping") — and the host arithmetic on top: depth, mapped fraction, error rate, consensus, variants."""
 import numpy as np
 
-from ._lib import MAP_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS
+from ._lib import MAP_FIELDS, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS
 
 RECORD = np.dtype([("contig", np.int32), ("diagonal", np.int32), ("mismatches", np.int32), ("blocks", np.int32), ("overlap", np.int32)])
 _BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -120,11 +120,15 @@ class GappedReadMap(ReadMap):
     """what SegmentBatch.map_reads_gapped() returns (the rule and its limits: include/gasm.h "Gapped read mapping"): ReadMap's tables
     over chains — the records' third column is the chain's cost (mismatches + gap lengths), the fourth the accepted chains, the
     histogram is over costs — and beside them per read the gap record of its best chain, per contig base the deletions that skip it and
-    the insertions in front of it, and an eighth counter, gapped."""
+    the insertions in front of it, and an eighth counter, gapped.  A map made with end_gap > 0 ("End gaps": one gap tried at each end
+    of every chain) also holds per read the end gaps of its best chain and per segment four counters; its records' diagonal is the
+    first piece's, its gap records count the end pieces, and depth, error_rate, indels and consensus take them as they take a join."""
 
-    def __init__(self, k, strands, max_edits, max_gap, contigs, rec, rec_gap, pile, gap_pile, edit_hist, counters, twins=None, seg_read_off=None):
+    def __init__(self, k, strands, max_edits, max_gap, contigs, rec, rec_gap, pile, gap_pile, edit_hist, counters, twins=None, seg_read_off=None,
+                 end_gap=0, rec_end=None, end_counters=None):
         """as ReadMap, with rec_gap: 4 int32 per read of the batch (pieces, inserted bases, deleted bases, last diagonal); gap_pile: 2
-        uint32 per contig base (deletions, insertions); counters: len(MAPG_FIELDS) per segment"""
+        uint32 per contig base (deletions, insertions); counters: len(MAPG_FIELDS) per segment; end_gap > 0: rec_end, 4 int32 per
+        read (front gap, its breakpoint, back gap, its breakpoint), and end_counters, len(MAPEND_FIELDS) per segment"""
         self._cnt8 = np.asarray(counters, dtype=np.uint64).reshape(len(contigs), len(MAPG_FIELDS))
         super().__init__(k, strands, max_edits, contigs, rec, pile, edit_hist, self._cnt8[:, :len(MAP_FIELDS)], twins, seg_read_off)
         self.max_edits, self.max_gap = int(max_edits), int(max_gap)
@@ -132,6 +136,13 @@ class GappedReadMap(ReadMap):
         self._gpile = np.asarray(gap_pile, dtype=np.uint32).reshape(-1, 2)
         if len(self._gap) != len(self._rec) or len(self._gpile) != len(self._pile):
             raise ValueError("the gap tables do not fit the records and the pileup")
+        self.end_gap = int(end_gap)
+        self._end = self._endcnt = None
+        if self.end_gap:
+            self._end = np.asarray(rec_end, dtype=np.int32).reshape(-1, 4)
+            self._endcnt = np.asarray(end_counters, dtype=np.uint64).reshape(len(contigs), len(MAPEND_FIELDS))
+            if len(self._end) != len(self._rec):
+                raise ValueError("the end records do not fit the records")
 
     def counters(self, segment, as_dict=False):
         c = self._cnt8[self._seg(segment)].copy()
@@ -145,6 +156,22 @@ class GappedReadMap(ReadMap):
         no place"""
         s = self._seg(segment)
         return self._gap[int(self._read_off[s]):int(self._read_off[s + 1])].copy()
+
+    def end_records(self, segment):
+        """(reads, 4) int32: front gap (> 0 a deletion, < 0 an insertion, 0 none), its breakpoint, back gap, its breakpoint of every
+        read's best chain; zeros for a read with no place.  Only for a map made with end_gap > 0"""
+        if self._end is None:
+            raise ValueError("this map was made without end gaps (map_reads_gapped(end_gap=...))")
+        s = self._seg(segment)
+        return self._end[int(self._read_off[s]):int(self._read_off[s + 1])].copy()
+
+    def end_counters(self, segment, as_dict=False):
+        """the segment's four end counters (_lib.MAPEND_FIELDS): accepted chains with a front gap, with a back gap, accepted chains
+        that the end gaps rescued, reads whose start a front gap moved.  Only for a map made with end_gap > 0"""
+        if self._endcnt is None:
+            raise ValueError("this map was made without end gaps (map_reads_gapped(end_gap=...))")
+        c = self._endcnt[self._seg(segment)].copy()
+        return {name: int(v) for name, v in zip(MAPEND_FIELDS, c)} if as_dict else c
 
     def gap_pileup(self, segment, fold_twins=False):
         """one (len(c), 2) uint32 array per contig: the accepted chains whose deletion skips the base, and those with an insertion in

@@ -779,6 +779,70 @@ int gasm_batch_map_reads_gapped(gasm_batch* b, uint32_t max_edits, uint32_t max_
 int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const int32_t** rec_gap, const uint32_t** pile,
                                      const uint32_t** gap_pile, const uint32_t** edit_hist, const uint64_t** counters);
 /* ------------------------------------------------------------------------------------------------------------------
+ * End gaps: gapped read mapping that also tries ONE GAP AT EACH END of every chain, between the read's end and the chain's outermost
+ * seed.  Gapped read mapping joins heads, so it sees only an indel with a seed on both sides; an indel closer than k to an end of the
+ * read leaves no seed beyond it (the first of its LIMITS above).  This form closes most of that limit with the breakpoint search of
+ * step 5, run once more at each end of a chain.  A third form of the pass; the other two are untouched, and with end_gap = 0 this one
+ * gives the gapped mapping's tables.  Since the first piece's diagonal is what rec holds, mapped scoring (below) needs no change: a
+ * read with an indel near its start is placed, and its break lands on the right contig base.  What the LIMITS of gapped read mapping
+ * and of mapped scoring say about an indel within k of a read's end or start holds for gasm_batch_map_reads_gapped and for end_gap = 0.
+ * The rule.  INPUTS.  As for gapped read mapping, plus end_gap in 0..GASM_MAP_MAX_GAP.
+ *   PER READ of len bases:
+ *   1-5. UNCHANGED.  Short, skipped, seeds, heads, chains and the breakpoints of the joins are exactly those of gapped read mapping.
+ *      A chain has the heads (J_i, c, d_i), i = 1..q; clen = len(c).  mism(lo, hi, d) is the number of x in [lo, hi) with
+ *      read[x] != c[d + x].
+ *   5a. BACK END.  The window starts at B = J_q + k.  The end is ELIGIBLE iff d_q + len <= clen: the read's last base lies on the
+ *      contig on the ungapped diagonal.  m0 = mism(B, len, d_q).  A CANDIDATE is (g, t) with 0 < |g| <= end_gap, G = max(0, -g),
+ *      d_q + g + len <= clen and t in [B, len - G - 1]: the piece behind the gap is non-empty, the part in front of it may be empty.
+ *      Its cost is |g| + mism(B, t, d_q) + mism(t + G, len, d_q + g).  The BEST candidate is the smallest under the key (cost, |g|,
+ *      deletion before insertion, t): lowest cost, then shortest gap, then a deletion (g > 0) before an insertion, then the smallest t.
+ *      It is TAKEN iff its cost is strictly below m0.  Hence nothing is taken when m0 < 2, and no |g| >= m0 needs to be tried.
+ *   5b. FRONT END.  The window is [0, J_1).  The end is eligible iff d_1 >= 0 and J_1 > 0.  m0 = mism(0, J_1, d_1).  A candidate is
+ *      (g, t) with 0 < |g| <= end_gap, G = max(0, -g), d_0 = d_1 - g >= 0 and t in [1, J_1 - G]: the piece in front of the gap, read
+ *      bases [0, t) on d_0, is non-empty.  Its cost is |g| + mism(0, t, d_0) + mism(t + G, J_1, d_1).  The same key; taken iff the cost
+ *      is strictly below m0.
+ *      The two end windows and all join windows are pairwise disjoint: [0, J_1) lies in front of J_1 + 1, where the first join window
+ *      starts, and [J_q + k, len) lies behind J_q, where the last one ends; the bases a piece holds outside the windows do not depend
+ *      on any choice.  Each choice is therefore made on its own, and together they are the joint optimum under "at most one gap per
+ *      end".
+ *   6'. PIECES.  A taken front gap (g_0, t_0) puts a piece [0, t_0) on d_0 in front of piece 1, which then starts at t_0 + G_0.  A
+ *      taken back gap (g_b, t_b) ends piece q at t_b and adds a piece [t_b + G_b, len) on d_q + g_b.  Every piece lies inside the
+ *      contig.  Front: d_0 >= 0 is asked, and a base x < t_0 <= J_1 - G_0 lies at d_0 + x = d_1 + x - g_0 < d_1 + J_1 < clen (for a
+ *      deletion because g_0 > 0, for an insertion because x + G_0 < J_1).  Back: d_q + g_b + len <= clen is asked, and a base x >=
+ *      t_b + G_b lies at d_q + g_b + x >= d_q + t_b >= d_q + J_q >= 0 (for a deletion because g_b > 0, for an insertion because
+ *      x - G_b >= t_b).  Both pieces next to a gap are non-empty: t_0 >= 1, piece 1 holds k-mer J_1 >= t_0 + G_0; piece q holds
+ *      k-mer J_q, which ends at B <= t_b; and t_b + G_b < len.
+ *   7-9. UNCHANGED in wording.  COST is the mismatches over all pieces plus all gap lengths, end gaps included; OVERLAP the sum of the
+ *      piece lengths; a chain is ACCEPTED iff cost <= max_edits.  Pileup and gap pileup take an end gap exactly as step 8 takes a
+ *      join: a deletion adds its skipped contig bases, an insertion adds 1 in front of the contig base at (left diagonal) + t.  Best
+ *      chain and classes as before.
+ *   PROPERTIES.  For every chain the cost with end gaps is at most its cost without (a gap is taken only where it is cheaper), so
+ *   every read placed without end gaps is placed with them.  On error-free reads m0 = 0 everywhere: the six tables are the gapped
+ *   mapping's and the two new ones are zero.
+ *   OUTPUTS.  The six arrays of the gapped mapping, with the same shapes.  rec[4 r + 1] is the diagonal of the FIRST piece: d_0
+ *   where a front gap was taken.  rec_gap counts pieces, inserted bases and deleted bases with the end pieces in; its last word is
+ *   the LAST piece's diagonal.  The eighth counter, gapped, stays "the best chain has 2 or more pieces".  And two more:
+ *     rec_end[4 r + 0..3] = g_front, t_front, g_back, t_back of the read's best chain; the two values of an end without a gap are
+ *       0; all four are zero for a read with no place.
+ *     end_counters[s * GASM_MAPEND_FIELDS + f], f in this order: front, the accepted chains with a front gap; back, likewise;
+ *       rescued, the accepted chains whose cost plus the savings m0 - cost of their taken end gaps exceeds max_edits (chains that
+ *       would not have been accepted without); start_moved, the reads whose best chain has a front gap.
+ *   LIMITS.  An end clipped by the contig's end is not extended (not eligible).  At most one gap per end.  A gap next to the read's
+ *   very end can be explained away by substitutions, which is why the comparison is strict: such a gap is not taken.  A short
+ *   matching stub behind a gap can be chance (about 1 read in 1000 at 3 % substitutions).  And the limits of the chains themselves.
+ * gasm_batch_map_reads_gapped_ends   as gasm_batch_map_reads_gapped, and end_gap > GASM_MAP_MAX_GAP: GASM_ERR_INVALID.  It fills the
+ *                                    gapped mapping's own state: gasm_batch_fetch_read_map_gapped and gasm_batch_score_mapped(source =
+ *                                    GASM_MAPSCORE_GAPPED) work on it unchanged.  end_gap > 0 queues k_read_map_ends; end_gap = 0
+ *                                    queues exactly the k_read_map_gapped of gasm_batch_map_reads_gapped and leaves no end tables.
+ * gasm_batch_fetch_read_map_ends     host copies, valid until the next call or build.  GASM_ERR_STATE before a build, without a gapped
+ *                                    mapping over the last build, and when the last one tried no end gaps (it was not made by
+ *                                    gasm_batch_map_reads_gapped_ends, or with end_gap = 0).
+ * What to do with them is host code: genomeassembler_dev_amd/readmap.py, GappedReadMap.end_records, end_counters.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAPEND_FIELDS 4
+int gasm_batch_map_reads_gapped_ends(gasm_batch* b, uint32_t max_edits, uint32_t max_gap, uint32_t end_gap);
+int gasm_batch_fetch_read_map_ends(gasm_batch* b, const int32_t** rec_end, const uint64_t** end_counters);
+/* ------------------------------------------------------------------------------------------------------------------
  * Mapped scoring: breakage scores from mapped reads, so that reads with errors count too.  gasm_batch_score matches exactly: a read
  * scores iff it is a substring of a contig, so a read with one wrong base scores nothing although its start, the breakpoint, is
  * good.  The two read mappings leave, for every read, the contig and the diagonal d of its best alignment: the contig base under the
