@@ -26,6 +26,7 @@ MAP_FIELDS = ("short", "skipped", "unseeded", "rejected", "mapped_one", "mapped_
 MAP_MAX_GAP = 16           # GASM_MAP_MAX_GAP: the longest gap map_reads_gapped() joins two heads over
 MAPG_FIELDS = MAP_FIELDS + ("gapped",)   # GASM_MAPG_FIELDS counters, in the header's order
 MAPEND_FIELDS = ("front", "back", "rescued", "start_moved")   # GASM_MAPEND_FIELDS counters of map_reads_gapped(end_gap > 0), in the header's order
+MAP_MAX_PIECES = 10        # GASM_MAP_MAX_PIECES: the pieces align_reads() keeps per read, MAP_MAX_BLOCKS + 2
 MAPSCORE_FIELDS = ("unplaced", "start_clipped", "end_clipped", "whole")   # GASM_MAPSCORE_FIELDS counters of score_mapped(), in the header's order
 MAPSCORE_SOURCES = {"ungapped": 0, "gapped": 1}   # GASM_MAPSCORE_UNGAPPED / GASM_MAPSCORE_GAPPED
 MAPSCORE_PARTIAL = 1       # GASM_MAPSCORE_PARTIAL: score_mapped() also scores reads that run off their contig's end
@@ -173,6 +174,8 @@ SYMBOLS = {
     "gasm_batch_fetch_read_map_gapped": (_int, [_vp, _PP, _PP, _PP, _PP, _PP, _PP]),
     "gasm_batch_map_reads_gapped_ends": (_int, [_vp, _u32, _u32, _u32]),
     "gasm_batch_fetch_read_map_ends": (_int, [_vp, _PP, _PP]),
+    "gasm_batch_map_reads_aligned": (_int, [_vp, _u32, _u32, _u32]),
+    "gasm_batch_fetch_read_alignments": (_int, [_vp, _PP, _PP, C.POINTER(_u32)]),
     "gasm_batch_score_mapped": (_int, [_vp, _int, _int, _vp, _u32, _u32]),
     "gasm_batch_fetch_mapped_scores": (_int, [_vp, _u32, _PP, _PP, _PP, _PP, _PP, _PP, C.POINTER(_int)]),
     "gasm_batch_fetch_mapped_starts": (_int, [_vp, _PP, _PP]),

@@ -486,6 +486,18 @@ def map_reads_gapped(reads, k, max_edits=6, max_gap=3, end_gap=0, ctx=None, **bu
         b.close()
 
 
+def align_reads(reads, k, max_edits=6, max_gap=3, end_gap=3, ctx=None, **build):
+    """map_reads_gapped that keeps every read's alignment: a readmap.AlignedReadMap that speaks of segment 0 (GappedReadMap's methods, and
+    pieces(0), cigars(0), to_sam(0, reads), insert_pileup(0), insertions(0), consensus(0) with the insertions applied; include/gasm.h
+    "Alignments").  build: as for contig_graph."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_strings([list(reads)], ctx=ctx)
+    try:
+        return b.build_simplified(int(k), **build).align_reads(max_edits, max_gap, end_gap)
+    finally:
+        b.close()
+
+
 def calc_breakscore_mapped(reads, k, kmer=8, tables=None, max_edits=6, max_gap=3, partial=False, ctx=None, end_gap=0, **build):
     """breakage scores of the contigs of one segment's reads (a list of str) from the reads' mapped starts: build, gapped mapping
     within max_edits edits and gaps of at most max_gap, mapped scoring — a readmap.MappedScores that speaks of segment 0 (scores(),

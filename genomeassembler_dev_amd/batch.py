@@ -7,11 +7,11 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAP_MAX_PIECES, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 from .pairs import PairPlaces
-from .readmap import GappedReadMap, MappedScores, ReadMap
+from .readmap import AlignedReadMap, GappedReadMap, MappedScores, ReadMap
 
 
 def _arr(p, ctype, n):
@@ -53,6 +53,7 @@ class SegmentBatch:
         self.k = None
         self._table = None
         self._seg_read_off = seg.copy()
+        self._read_len = np.diff(ro.astype(np.int64)) if ro is not None else np.full(self.n_reads, int(fixed_len), np.int64)
 
     @classmethod
     def from_strings(cls, segments, ctx=None):
@@ -83,6 +84,7 @@ class SegmentBatch:
                                              self.n_segments, C.byref(h)))
         self.h, self.k, self._table = h, None, None
         self._seg_read_off = seg.copy()
+        self._read_len = np.diff(ro.astype(np.int64)) if ro is not None else np.full(self.n_reads, int(fixed_len), np.int64)
         return self
 
     @classmethod
@@ -252,6 +254,16 @@ class SegmentBatch:
             self._max_read_len = int(np.diff(off).max()) if len(off) > 1 else 0
         return self._max_read_len
 
+    def _read_lengths(self):
+        """the reads' lengths, int64: from the offsets the batch was made with; a batch made on the device or from files (simulate,
+        from_fastq, correct_reads) asks the library once (gasm_batch_fetch_reads hands out the offsets beside the bases: only the
+        offsets are copied here)"""
+        if getattr(self, "_read_len", None) is None:
+            d, o = C.c_void_p(), C.c_void_p()
+            check(lib().gasm_batch_fetch_reads(self.h, C.byref(d), C.byref(o)))
+            self._read_len = np.diff(_arr(o, C.c_uint64, self.n_reads + 1).astype(np.int64))
+        return self._read_len
+
     def place_pairs(self, max_insert=None):
         """where the batch's read pairs lie on the last build's contigs (gasm_batch_place_pairs; the rule: include/gasm.h "Read pairs") as
         a pairs.PairPlaces: per segment the records (c1, S, c2, E) of every oriented pair, the insert histogram and the six counters.
@@ -325,6 +337,37 @@ class SegmentBatch:
             ends = dict(end_gap=end_gap, rec_end=_arr(pe[0], C.c_int32, 4 * self.n_reads), end_counters=_arr(pe[1], C.c_uint64, self.n_segments * len(MAPEND_FIELDS)))
         return GappedReadMap(self.k, strands, max_edits, max_gap, contigs, rec, gap, pile, gpile, hist, cnt,
                              [t.tolist() for t in self.contig_twins()] if strands == 2 else None, getattr(self, "_seg_read_off", None), **ends)
+
+    def align_reads(self, max_edits=6, max_gap=3, end_gap=3):
+        """map_reads_gapped(max_edits, max_gap, end_gap) that keeps every read's alignment (gasm_batch_map_reads_aligned; include/gasm.h
+        "Alignments") as a readmap.AlignedReadMap: GappedReadMap's tables, the same values, and per read the pieces of its best chain
+        (pieces(), cigars(), to_sam()) and per contig base the bases of the insertions in front of it (insert_pileup(), insertions(),
+        consensus() with the insertions applied).  end_gap = 0 is legal: no end gap is taken and the end tables are zero.  It is the
+        batch's gapped mapping: score_mapped(source="gapped") reads it, and a later map_reads_gapped() replaces it."""
+        if not 0 <= int(max_edits) <= MAP_MAX_MISMATCH:
+            raise ValueError(f"max_edits must be 0..{MAP_MAX_MISMATCH}")
+        if not 0 <= int(max_gap) <= MAP_MAX_GAP:
+            raise ValueError(f"max_gap must be 0..{MAP_MAX_GAP}")
+        if not 0 <= int(end_gap) <= MAP_MAX_GAP:
+            raise ValueError(f"end_gap must be 0..{MAP_MAX_GAP}")
+        max_edits, max_gap, end_gap = int(max_edits), int(max_gap), int(end_gap)
+        check(lib().gasm_batch_map_reads_aligned(self.h, max_edits, max_gap, end_gap))
+        ps, pe, pa, cols = [C.c_void_p() for _ in range(6)], [C.c_void_p() for _ in range(2)], [C.c_void_p() for _ in range(2)], C.c_uint32()
+        check(lib().gasm_batch_fetch_read_map_gapped(self.h, *[C.byref(p) for p in ps]))
+        check(lib().gasm_batch_fetch_read_map_ends(self.h, *[C.byref(p) for p in pe]))
+        check(lib().gasm_batch_fetch_read_alignments(self.h, *[C.byref(p) for p in pa], C.byref(cols)))
+        seg, o, contigs = self._contigs_by_segment()
+        total = int(o[-1]) if int(seg[-1]) else 0
+        W = int(cols.value)
+        rec, gap = _arr(ps[0], C.c_int32, 4 * self.n_reads), _arr(ps[1], C.c_int32, 4 * self.n_reads)
+        pile, gpile = _arr(ps[2], C.c_uint32, 4 * total), _arr(ps[3], C.c_uint32, 2 * total)
+        hist, cnt = _arr(ps[4], C.c_uint32, self.n_segments * (max_edits + 1)), _arr(ps[5], C.c_uint64, self.n_segments * len(MAPG_FIELDS))
+        strands = self.strands()
+        return AlignedReadMap(self.k, strands, max_edits, max_gap, end_gap, contigs, rec, gap, pile, gpile, hist, cnt,
+                              _arr(pe[0], C.c_int32, 4 * self.n_reads), _arr(pe[1], C.c_uint64, self.n_segments * len(MAPEND_FIELDS)),
+                              _arr(pa[0], C.c_int32, 2 * MAP_MAX_PIECES * self.n_reads), _arr(pa[1], C.c_uint32, 4 * W * total), W,
+                              self._read_lengths(), [t.tolist() for t in self.contig_twins()] if strands == 2 else None,
+                              getattr(self, "_seg_read_off", None))
 
     def score_mapped(self, kmer=8, tables=None, source="gapped", partial=False):
         """breakage scores from the records of the last map_reads_gapped() (source="gapped") or map_reads() ("ungapped") over the last

@@ -1087,12 +1087,38 @@ int gasm_batch_fetch_read_map_ends(gasm_batch* b, const int32_t** rec_end, const
     API_GUARD_BEGIN
     GCHK(batch_fetch_ready(b, "gasm_batch_fetch_read_map_ends", rec_end && end_counters));
     const PassState& ps = b->S().bs.mapg;
-    if (ps.queued && !ps.param[1]) {
+    if (ps.queued && !(ps.param[1] & MAPG_HAS_ENDS)) {
         gasm_set_error("gasm_batch_fetch_read_map_ends: the last gapped mapping over the last build tried no end gaps (gasm_batch_map_reads_gapped_ends with end_gap > 0 does)");
         return GASM_ERR_STATE;
     }
     GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, b->S().bs, true));
     *rec_end = ps.host<int32_t>(MAPG_END); *end_counters = ps.host<uint64_t>(MAPG_ENDCNT);
+    return GASM_OK;
+    API_GUARD_END
+}
+
+// ---- alignments (kernels_map.hip, k_read_map_trace; include/gasm.h "Alignments"): the gapped mapping's own state with the end tables (zero
+// for end_gap = 0) and two more tables behind them
+int gasm_batch_map_reads_aligned(gasm_batch* b, uint32_t max_edits, uint32_t max_gap, uint32_t end_gap) {
+    API_GUARD_BEGIN
+    int args = at_most("max_edits", max_edits, GASM_MAP_MAX_MISMATCH);
+    if (args == GASM_OK) args = at_most("max_gap", max_gap, GASM_MAP_MAX_GAP);
+    if (args == GASM_OK) args = at_most("end_gap", end_gap, GASM_MAP_MAX_GAP);
+    GCHK(batch_pass_ready(b, "gasm_batch_map_reads_aligned", args));
+    return pipeline_map_reads(b->S().cx, b->build_reads(b->S()), b->rd, b->S().bs, true, max_edits, max_gap, end_gap, true);
+    API_GUARD_END
+}
+
+int gasm_batch_fetch_read_alignments(gasm_batch* b, const int32_t** rec_piece, const uint32_t** ins_pile, uint32_t* ins_cols) {
+    API_GUARD_BEGIN
+    GCHK(batch_fetch_ready(b, "gasm_batch_fetch_read_alignments", rec_piece && ins_pile && ins_cols));
+    const PassState& ps = b->S().bs.mapg;
+    if (ps.queued && !(ps.param[1] & MAPG_HAS_TRACE)) {
+        gasm_set_error("gasm_batch_fetch_read_alignments: the last gapped mapping over the last build kept no alignments (gasm_batch_map_reads_aligned does)");
+        return GASM_ERR_STATE;
+    }
+    GCHK(pipeline_fetch_read_map(b->S().cx, b->rd, b->S().bs, true));
+    *rec_piece = ps.host<int32_t>(MAPG_PIECE); *ins_pile = ps.host<uint32_t>(MAPG_INS); *ins_cols = ps.param[1] >> MAPG_COLS_SHIFT;
     return GASM_OK;
     API_GUARD_END
 }

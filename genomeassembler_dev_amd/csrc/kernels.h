@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "device_utils.h"
 #include "keyops.h"
 
@@ -317,7 +319,8 @@ __global__ void k_pair_place(ReadSet rs, GraphView gv, ContigIndex ci, u32 orien
                              unsigned long long* counters);
 
 // ---- kernels_map.hip: read mapping, ungapped (include/gasm.h, "Read mapping") and gapped ("Gapped read mapping"): one body, GAPPED = false
-// is the launch "k_read_map", GAPPED = true the launch "k_read_map_gapped", GAPPED and ENDS the launch "k_read_map_ends"
+// is the launch "k_read_map", GAPPED = true the launch "k_read_map_gapped", GAPPED and ENDS the launch "k_read_map_ends", all three flags
+// the launch "k_read_map_trace" (include/gasm.h, "Alignments")
 #define GASM_MAP_COUNTERS 7           // = GASM_MAP_FIELDS of include/gasm.h (checked in pipeline.hip)
 #define GASM_MAPG_COUNTERS 8          // = GASM_MAPG_FIELDS: the same seven and the gapped reads
 #define GASM_MAP_BLOCKS 8             // = GASM_MAP_MAX_BLOCKS: distinct heads of a read that are kept (one per lane 0 .. 7 of its wave)
@@ -328,6 +331,10 @@ __global__ void k_pair_place(ReadSet rs, GraphView gv, ContigIndex ci, u32 orien
 // ENDS = true (with GAPPED; include/gasm.h, "End gaps"; the launch "k_read_map_ends") only (else not read): end_gap, rec_end, 4 int32 per read
 // (16-byte aligned), and end_counters, GASM_MAPEND_COUNTERS per segment, zeroed by the caller
 #define GASM_MAPEND_COUNTERS 4        // = GASM_MAPEND_FIELDS: front, back, rescued, start_moved
+// TRACE = true (with GAPPED and ENDS; the launch "k_read_map_trace") only (else not read): rec_piece, GASM_MAP_PIECES pieces of 2 int32 per read
+// (s | e << 16, d; 16-byte aligned; every read's are written), and ins_pile, max(max_gap, end_gap) columns of 4 u32 per base of the text,
+// zeroed by the caller.  They come in a struct of their own behind MapOut's, so that the three other forms keep their kernel arguments
+#define GASM_MAP_PIECES (GASM_MAP_BLOCKS + 2)      // = GASM_MAP_MAX_PIECES: a chain over every kept head and a piece beyond the gap at each end
 struct MapOut {
     int32_t *rec, *rec_gap;
     u32 *pile, *gap_pile, *hist;
@@ -335,8 +342,14 @@ struct MapOut {
     int32_t* rec_end;
     unsigned long long* end_counters;
 };
-template <class K, bool GAPPED, bool ENDS>
-__global__ void k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 end_gap, u32 reads_per_wg, u32 chunks, MapOut out);
+struct MapOutTrace : MapOut {
+    int32_t* rec_piece;
+    u32* ins_pile;
+};
+template <bool TRACE>
+using MapOutOf = std::conditional_t<TRACE, MapOutTrace, MapOut>;
+template <class K, bool GAPPED, bool ENDS, bool TRACE>
+__global__ void k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 end_gap, u32 reads_per_wg, u32 chunks, MapOutOf<TRACE> out);
 
 // ---- kernels_score.hip
 struct SeedTable {

@@ -1,5 +1,5 @@
 // kernels_map.hip — read mapping onto the contigs of a finished build, without gaps (include/gasm.h, "Read mapping") and with them
-// ("Gapped read mapping"): ONE body, k_read_map<K, GAPPED, ENDS>.  The heads of a read are found once for both; GAPPED = true joins the heads
+// ("Gapped read mapping"): ONE body, k_read_map<K, GAPPED, ENDS, TRACE>.  The heads of a read are found once for both; GAPPED = true joins the heads
 // that lie on neighbouring diagonals of one contig into a chain and verifies it as one alignment with gaps, GAPPED = false takes every
 // head as a chain of its own and compiles the rest out (the join loop, the breakpoints, my_J, my_t, the gap record, the gap pileup, the
 // eighth counter).
@@ -34,12 +34,43 @@
 // kept only if it costs strictly less than the best so far, which starts at m0: that is the rule's key.  A taken gap adds a piece in front
 // of or behind the chain's (for_pieces), its gap to the gap pileup as a join's, and the chain's savings say whether the gaps rescued it.
 // ENDS = false compiles all of it out.
+// TRACE = true (with GAPPED and ENDS; the launch "k_read_map_trace"; include/gasm.h, "Alignments") keeps the alignment that the other forms
+// discard.  for_pieces is wave-uniform, so while a chain is verified lane i takes piece i of it (its clamped [lo, hi) and its diagonal) into
+// two registers (cand_pc); a chain that becomes the read's best copies them to best_pc, zero in the lanes behind its last piece,
+// and at the end lanes 0 .. GASM_MAP_PIECES - 1 store 8 bytes each into rec_piece: no LDS, no second walk.  Every accepted chain adds
+// its inserted bases to ins_pile, one lane per base (trace_insertion), beside its add to gap_pile[2p + 1] and under the same bounds check.
+// TRACE = false compiles all of it out: TracePieces<false> and TraceChain<false> are empty, and the other forms keep their kernel arguments
+// (MapOutOf).
 #include "contig_index.h"
 
-template <class K, bool GAPPED, bool ENDS>
+// TRACE, lane i: piece i of a chain, s | e << 16 and its diagonal; of the chain at hand also n, the pieces walked so far (wave-uniform)
+template <bool TRACE>
+struct TracePieces {
+    int se = 0, d = 0;
+};
+template <>
+struct TracePieces<false> {};
+template <bool TRACE>
+struct TraceChain : TracePieces<TRACE> {
+    u32 n = 0;
+};
+template <>
+struct TraceChain<false> {};
+
+// TRACE: an insertion of G read bases [t, t + G) of the read at p0 in front of base p of the contig at cb: column l of the W gets read base
+// t + l, a lane each
+__device__ __forceinline__ void trace_insertion(u32* __restrict__ ins_pile, const u64* __restrict__ words, u64 p0, u32 len, u64 cb, long long clen, u32 W, u32 lane,
+                                                long long p, long long t, int G) {
+    const long long x = t + lane;
+    if ((int)lane < G && lane < W && p >= 0 && p < clen && x >= 0 && x < (long long)len)
+        atomicAdd(&ins_pile[((cb + (u64)p) * W + lane) * 4 + base_at(words, p0 + (u64)x)], 1u);
+}
+
+template <class K, bool GAPPED, bool ENDS, bool TRACE>
 __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, ContigIndex ci, u32 max_edits, u32 max_gap, u32 end_gap, u32 reads_per_wg,
-                                                      u32 chunks, MapOut out) {
+                                                      u32 chunks, MapOutOf<TRACE> out) {
     static_assert(GAPPED || !ENDS, "end gaps belong to the gapped form");
+    static_assert(ENDS || !TRACE, "the alignment tables belong to the form with end gaps");
     constexpr u32 N_CNT = GAPPED ? GASM_MAPG_COUNTERS : GASM_MAP_COUNTERS;
     __shared__ u32 s_cnt[N_CNT];
     ReadPass rp;
@@ -60,6 +91,8 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
         u32 n_heads = 0, n_acc = 0, dropped = 0, b_ov = 0, b_cost = 0, b_c = 0, b_q = 0, b_ins = 0, b_del = 0;
         int b_d = 0, b_dq = 0;
         int b_gf = 0, b_tf = 0, b_gb = 0, b_tb = 0;                           // ENDS: the best chain's end gaps
+        [[maybe_unused]] TracePieces<TRACE> best_pc;                          // TRACE, lane i: piece i of the best chain
+        [[maybe_unused]] TraceChain<TRACE> cand_pc;                           // TRACE, lane i: piece i of the chain at hand
         bool seeded_any = false;
         if (n == 0) cls = 0;
         else if (n > GASM_THREAD_KMER_CAP) cls = 1;
@@ -244,8 +277,13 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                 };
                 // ---- verify the pieces
                 u32 cost = gaps, ov = 0;
+                if constexpr (TRACE) cand_pc.n = 0;
                 if (!for_pieces([&](u32, int di, long long lo, long long hi, long long) {
                         if (hi <= lo) return false;                            // (no finished build gives this: include/gasm.h, step 6)
+                        if constexpr (TRACE) {
+                            if (lane == cand_pc.n) { cand_pc.se = (int)((u32)lo | (u32)hi << 16); cand_pc.d = di; }
+                            ++cand_pc.n;
+                        }
                         for (long long i0 = lo; i0 < hi && cost <= max_edits; i0 += 64) {
                             const long long x = i0 + lane;
                             cost += (u32)__popcll(__ballot(x < hi && differ(x, di)));
@@ -268,6 +306,8 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                             if ((int)lane < g && pp >= 0 && pp < clen) atomicAdd(&out.gap_pile[2 * (cb + (u64)pp)], 1u);
                         } else if (lane == 0 && p >= 0 && p < clen)            // an insertion in front of contig base p
                             atomicAdd(&out.gap_pile[2 * (cb + (u64)p) + 1], 1u);
+                        if constexpr (TRACE)
+                            if (g < 0) trace_insertion(out.ins_pile, rs.words, p0, len, cb, clen, max_gap > end_gap ? max_gap : end_gap, lane, p, en, -g);
                     }
                     return true;
                 });
@@ -281,6 +321,8 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                             if ((int)lane < g && pp >= 0 && pp < clen) atomicAdd(&out.gap_pile[2 * (cb + (u64)pp)], 1u);
                         } else if (lane == 0 && p >= 0 && p < clen)
                             atomicAdd(&out.gap_pile[2 * (cb + (u64)p) + 1], 1u);
+                        if constexpr (TRACE)
+                            if (g < 0) trace_insertion(out.ins_pile, rs.words, p0, len, cb, clen, max_gap > end_gap ? max_gap : end_gap, lane, p, side ? tb : tf, -g);
                     }
                     c_end[0] += gf ? 1u : 0u; c_end[1] += gb ? 1u : 0u; c_end[2] += cost + saved > max_edits ? 1u : 0u;
                 }
@@ -291,11 +333,20 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                         b_d = d1 - gf; b_q += (gf ? 1u : 0u) + (gb ? 1u : 0u); b_dq = d + gb;
                         b_gf = gf; b_tf = tf; b_gb = gb; b_tb = tb;
                     }
+                    if constexpr (TRACE) {                                     // (zero behind the last piece: an earlier best may have had more)
+                        best_pc.se = lane < cand_pc.n ? cand_pc.se : 0; best_pc.d = lane < cand_pc.n ? cand_pc.d : 0;
+                    }
                 }
                 ++n_acc;
             }
             cls = !seeded_any ? 2u : n_acc == 0 ? 3u : n_acc == 1 ? 4u : 5u;
         }
+        if constexpr (TRACE)
+            if (lane < GASM_MAP_PIECES) {
+                int2 v;
+                v.x = n_acc ? best_pc.se : 0; v.y = n_acc ? best_pc.d : 0;
+                *reinterpret_cast<int2*>(out.rec_piece + (r * GASM_MAP_PIECES + lane) * 2) = v;
+            }
         if (lane == 0) {
             int4 v;
             v.x = n_acc ? (int)(b_c - rp.c_lo) : -1; v.y = n_acc ? b_d : 0;
@@ -324,9 +375,11 @@ __global__ void __launch_bounds__(GASM_WG) k_read_map(ReadSet rs, GraphView gv, 
                 if (c_end[q]) atomicAdd(&out.end_counters[(size_t)rp.seg * GASM_MAPEND_COUNTERS + q], (unsigned long long)c_end[q]);
     flush_wave_counters(c_cnt, s_cnt, out.counters + (size_t)rp.seg * N_CNT);
 }
-template __global__ void k_read_map<u64, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<K128, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<u64, true, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<K128, true, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<u64, true, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
-template __global__ void k_read_map<K128, true, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, false, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<K128, false, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, true, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<K128, true, false, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, true, true, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<K128, true, true, false>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOut);
+template __global__ void k_read_map<u64, true, true, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOutTrace);
+template __global__ void k_read_map<K128, true, true, true>(ReadSet, GraphView, ContigIndex, u32, u32, u32, u32, u32, MapOutTrace);

@@ -147,7 +147,11 @@ enum { LINKS_SUCC, LINKS_PRED, LINKS_LSUP, LINKS_SSUP, LINKS_SKIPPED };
 enum { PAIRS_REC, PAIRS_HIST, PAIRS_CNT };
 enum { MAP_REC, MAP_PILE, MAP_HIST, MAP_CNT };
 // (behind them, when the mapping tried end gaps: int32 rec_end[4 * reads], u64 end_counters[S * GASM_MAPEND_FIELDS])
-enum { MAPG_REC, MAPG_GAP, MAPG_PILE, MAPG_GPILE, MAPG_HIST, MAPG_CNT, MAPG_END, MAPG_ENDCNT };
+// (behind those, when the mapping kept the alignments: int32 rec_piece[2 * GASM_MAP_MAX_PIECES * reads], u32 ins_pile[4 * ins_cols * contig bases])
+enum { MAPG_REC, MAPG_GAP, MAPG_PILE, MAPG_GPILE, MAPG_HIST, MAPG_CNT, MAPG_END, MAPG_ENDCNT, MAPG_PIECE, MAPG_INS };
+// param[1] of the gapped mapping's PassState, what its layout depends on beside max_edits (param[0]): the end tables are there, the
+// alignment tables are there, and from MAPG_COLS_SHIFT up the columns of the insertion pileup
+enum : u32 { MAPG_HAS_ENDS = 1u, MAPG_HAS_TRACE = 2u, MAPG_COLS_SHIFT = 8u };
 // mapped scoring (T = param[0] tables over P contigs): double out[3 T P] (table t: bp, norm_by_break_freqs, norm_by_len, P each), int32 out[2 P]
 // (kmer_breaks, sequence_len), u32 cnt[P], u64 fx[T P], u32 start_pile[contig bases], u64 counters[S * GASM_MAPSCORE_FIELDS]
 enum { MAPSC_F64, MAPSC_I32, MAPSC_CNT, MAPSC_FX, MAPSC_PILE, MAPSC_COUNTERS };
@@ -210,7 +214,7 @@ struct BuildState {
     bool coverage_queued = false;           // k_contig_cov ran on the arrays of this build
     // the passes that lay reads over the last build, each with the tables listed at its enum below: contig links (pipeline_contig_links),
     // read-pair places (pipeline_place_pairs; param: orientations, max_insert), read mapping and gapped read mapping (pipeline_map_reads;
-    // param: max_mismatch / max_edits, and for mapg whether end gaps were tried) — the two mappings independent of each other
+    // param: max_mismatch / max_edits, and for mapg the MAPG_HAS_* bits and the insertion columns) — the two mappings independent of each other
     PassState links, pairs, map, mapg;
     // mapped scoring (pipeline_score_mapped; param: tables, source) from the records of map or mapg, and its tables' fixed-point shifts
     PassState mapscore;
@@ -321,7 +325,8 @@ int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs);
 // build's strands), then fetch the tables.  gapped = false: into bs.map, max_edits is max_mismatch, max_gap is not used; gapped = true: into
 // bs.mapg, beside the other and independent of it
 // end_gap > 0 (gapped only): k_read_map_ends, which tries one gap at each end of every chain ("End gaps") and leaves two more tables
-int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap, u32 end_gap = 0);
+// trace (gapped only, any end_gap): k_read_map_trace alone, which leaves those eight and the piece records and the insertion pileup ("Alignments")
+int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap, u32 end_gap = 0, bool trace = false);
 int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool gapped);
 // Mapped scoring of the finished build (k_score_mapped in kernels_score.hip; the rule: include/gasm.h "Mapped scoring"): queue the kernel and a
 // k_score_finish per table on the build's stream behind it, then fetch the tables.  It reads the records of bs.map (gapped = false) or bs.mapg,

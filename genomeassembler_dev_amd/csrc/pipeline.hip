@@ -1148,6 +1148,7 @@ static_assert(GASM_PAIR_COUNTERS == GASM_PAIR_FIELDS, "kernels.h and gasm.h disa
 static_assert(GASM_MAP_COUNTERS == GASM_MAP_FIELDS && GASM_MAP_BLOCKS == GASM_MAP_MAX_BLOCKS, "kernels.h and gasm.h disagree on read mapping");
 static_assert(GASM_MAPG_COUNTERS == GASM_MAPG_FIELDS && GASM_MAPG_GAP == GASM_MAP_MAX_GAP, "kernels.h and gasm.h disagree on gapped read mapping");
 static_assert(GASM_MAPEND_COUNTERS == GASM_MAPEND_FIELDS, "kernels.h and gasm.h disagree on end gaps");
+static_assert(GASM_MAP_PIECES == GASM_MAP_MAX_PIECES && GASM_MAP_MAX_PIECES == GASM_MAP_MAX_BLOCKS + 2, "kernels.h and gasm.h disagree on alignments");
 static_assert(GASM_MAPSCORE_CLASSES == GASM_MAPSCORE_FIELDS, "kernels.h and gasm.h disagree on mapped scoring");
 static_assert(GASM_CORRECT_STATS == GASM_CORRECT_FIELDS && GASM_CORRECT_KMER_CAP == GASM_CORRECT_MAX_KMERS, "kernels.h and gasm.h disagree on read correction");
 
@@ -1257,10 +1258,14 @@ int pipeline_fetch_pair_places(gasm_ctx* ctx, DevReads& rd, BuildState& bs) {
 }
 
 // (ends: the end records and the end counters behind the six tables of the gapped form, which keep their places; the end records are zeroed
-// with the rest, so they come behind the first zeroed table)
-static PassLayout map_layout(bool gapped, u64 n_reads, u64 contig_bases, u32 S, u32 max_edits, bool ends = false) {
+// with the rest, so they come behind the first zeroed table; trace: behind those the piece records and the insertion pileup of ins_cols
+// columns ("Alignments"), zeroed likewise)
+static PassLayout map_layout(bool gapped, u64 n_reads, u64 contig_bases, u32 S, u32 max_edits, bool ends = false, bool trace = false, u32 ins_cols = 0) {
     const PassTable rec{(size_t)n_reads * 4, 4, 16, false}, pile{(size_t)contig_bases * 4, 4, 4, true}, gpile{(size_t)contig_bases * 2, 4, 4, true},
         hist{(size_t)S * ((size_t)max_edits + 1), 4, 4, true};
+    if (gapped && ends && trace)
+        return {rec, rec, pile, gpile, hist, {(size_t)S * GASM_MAPG_FIELDS, 8, 8, true}, {(size_t)n_reads * 4, 4, 16, true}, {(size_t)S * GASM_MAPEND_FIELDS, 8, 8, true},
+                {(size_t)n_reads * GASM_MAP_PIECES * 2, 4, 16, true}, {(size_t)contig_bases * ins_cols * 4, 4, 16, true}};
     if (gapped && ends)
         return {rec, rec, pile, gpile, hist, {(size_t)S * GASM_MAPG_FIELDS, 8, 8, true}, {(size_t)n_reads * 4, 4, 16, true}, {(size_t)S * GASM_MAPEND_FIELDS, 8, 8, true}};
     if (gapped) return {rec, rec, pile, gpile, hist, {(size_t)S * GASM_MAPG_FIELDS, 8, 8, true}};
@@ -1268,44 +1273,55 @@ static PassLayout map_layout(bool gapped, u64 n_reads, u64 contig_bases, u32 S, 
 }
 
 // read mapping, all forms: records, pileup, histogram, counters; gapped: and gap records and the gap pileup; end_gap > 0 (gapped only): and
-// end records and end counters, by k_read_map_ends.  end_gap = 0 launches exactly k_read_map_gapped
-int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap, u32 end_gap) {
+// end records and end counters, by k_read_map_ends.  end_gap = 0 launches exactly k_read_map_gapped.  trace (gapped only, any end_gap): all
+// eight and the piece records and the insertion pileup, by k_read_map_trace alone
+int pipeline_map_reads(gasm_ctx* ctx, DevReads& rd_build, DevReads& rd, BuildState& bs, bool gapped, u32 max_edits, u32 max_gap, u32 end_gap, bool trace) {
     if (rd.positioned) { gasm_set_error("read mapping needs the reads back to back (pooled builds place them by position)"); return GASM_ERR_STATE; }
     GCHK(pipeline_build_finish(ctx, rd_build, bs, nullptr));
     HIPCHK(hipSetDevice(ctx->device));
     const u32 S = rd.n_segments;
     PassState& ps = gapped ? bs.mapg : bs.map;
-    const bool ends = gapped && end_gap > 0;
-    const PassLayout l = map_layout(gapped, rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, S, max_edits, ends);
+    trace = trace && gapped;
+    const bool ends = gapped && (end_gap > 0 || trace);
+    const u32 ins_cols = trace ? std::max(max_gap, end_gap) : 0u;
+    const PassLayout l = map_layout(gapped, rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, S, max_edits, ends, trace, ins_cols);
     GCHK(pass_begin(ctx, ps, l));
     if (rd.n_reads && S) {
         const u32 reads_per_wg = GASM_WG / 64, chunks = read_pass_chunks(ctx, rd, reads_per_wg);       // a wave per read
-        if (ends) {
+        if (trace) {
+            const MapOutTrace out{{l.at<int32_t>(ps.d, MAPG_REC), l.at<int32_t>(ps.d, MAPG_GAP), l.at<u32>(ps.d, MAPG_PILE), l.at<u32>(ps.d, MAPG_GPILE),
+                                   l.at<u32>(ps.d, MAPG_HIST), l.at<unsigned long long>(ps.d, MAPG_CNT), l.at<int32_t>(ps.d, MAPG_END), l.at<unsigned long long>(ps.d, MAPG_ENDCNT)},
+                                  l.at<int32_t>(ps.d, MAPG_PIECE), l.at<u32>(ps.d, MAPG_INS)};
+            GLAUNCH_K(ctx, bs.words, "k_read_map_trace", (k_read_map<K, true, true, true>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
+                      max_edits, max_gap, end_gap, reads_per_wg, chunks, out);
+        } else if (ends) {
             const MapOut out{l.at<int32_t>(ps.d, MAPG_REC), l.at<int32_t>(ps.d, MAPG_GAP), l.at<u32>(ps.d, MAPG_PILE), l.at<u32>(ps.d, MAPG_GPILE),
                              l.at<u32>(ps.d, MAPG_HIST), l.at<unsigned long long>(ps.d, MAPG_CNT), l.at<int32_t>(ps.d, MAPG_END), l.at<unsigned long long>(ps.d, MAPG_ENDCNT)};
-            GLAUNCH_K(ctx, bs.words, "k_read_map_ends", (k_read_map<K, true, true>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
+            GLAUNCH_K(ctx, bs.words, "k_read_map_ends", (k_read_map<K, true, true, false>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
                       max_edits, max_gap, end_gap, reads_per_wg, chunks, out);
         } else if (gapped) {
             const MapOut out{l.at<int32_t>(ps.d, MAPG_REC), l.at<int32_t>(ps.d, MAPG_GAP), l.at<u32>(ps.d, MAPG_PILE), l.at<u32>(ps.d, MAPG_GPILE),
                              l.at<u32>(ps.d, MAPG_HIST), l.at<unsigned long long>(ps.d, MAPG_CNT), nullptr, nullptr};
-            GLAUNCH_K(ctx, bs.words, "k_read_map_gapped", (k_read_map<K, true, false>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
+            GLAUNCH_K(ctx, bs.words, "k_read_map_gapped", (k_read_map<K, true, false, false>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
                       max_edits, max_gap, 0u, reads_per_wg, chunks, out);
         } else {
             const MapOut out{l.at<int32_t>(ps.d, MAP_REC), nullptr, l.at<u32>(ps.d, MAP_PILE), nullptr, l.at<u32>(ps.d, MAP_HIST),
                              l.at<unsigned long long>(ps.d, MAP_CNT), nullptr, nullptr};
-            GLAUNCH_K(ctx, bs.words, "k_read_map", (k_read_map<K, false, false>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
+            GLAUNCH_K(ctx, bs.words, "k_read_map", (k_read_map<K, false, false, false>), seg_grid(chunks, S), dim3(GASM_WG), 0, rd.view(), graph_view(bs), contig_index(bs),
                       max_edits, 0u, 0u, reads_per_wg, chunks, out);
         }
     }
     ps.param[0] = max_edits;
-    ps.param[1] = ends ? 1u : 0u;
+    ps.param[1] = (ends ? MAPG_HAS_ENDS : 0u) | (trace ? MAPG_HAS_TRACE : 0u) | ins_cols << MAPG_COLS_SHIFT;
     ps.queued = true;
     return GASM_OK;
 }
 
 int pipeline_fetch_read_map(gasm_ctx* ctx, DevReads& rd, BuildState& bs, bool gapped) {
     PassState& ps = gapped ? bs.mapg : bs.map;
-    return pass_fetch(ctx, ps, map_layout(gapped, rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, rd.n_segments, ps.param[0], gapped && ps.param[1]),
+    const u32 form = gapped ? ps.param[1] : 0u;
+    return pass_fetch(ctx, ps, map_layout(gapped, rd.n_reads, bs.n_contigs ? bs.contig_bases : 0, rd.n_segments, ps.param[0], (form & MAPG_HAS_ENDS) != 0,
+                                          (form & MAPG_HAS_TRACE) != 0, form >> MAPG_COLS_SHIFT),
                       gapped ? "gasm_batch_fetch_read_map_gapped" : "gasm_batch_fetch_read_map", gapped ? "gasm_batch_map_reads_gapped" : "gasm_batch_map_reads");
 }
 

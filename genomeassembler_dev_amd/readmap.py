@@ -3,7 +3,7 @@ base the four base counts of the reads laid over it, per segment a mismatch hist
 include/gasm.h "Read mapping") — and the host arithmetic on top: depth, mapped fraction, error rate, consensus, variants."""
 import numpy as np
 
-from ._lib import MAP_FIELDS, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS
+from ._lib import MAP_FIELDS, MAP_MAX_PIECES, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS
 
 RECORD = np.dtype([("contig", np.int32), ("diagonal", np.int32), ("mismatches", np.int32), ("blocks", np.int32), ("overlap", np.int32)])
 _BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -223,6 +223,134 @@ class GappedReadMap(ReadMap):
             t = np.frombuffer(s.encode(), dtype=np.uint8)
             keep = ~((dp >= int(min_depth)) & (2 * g[:, 0].astype(np.int64) > dp)) if len(t) else np.zeros(0, bool)
             out.append(t[keep].tobytes().decode())
+        return out
+
+
+def cigar(read_len, pieces):
+    """the CIGAR of a read of read_len bases with the pieces [(s, e, d)] (include/gasm.h, "Alignments"): soft clips for the read bases
+    in front of the first and behind the last piece, an M run per piece, between two pieces the step of the diagonal as D (> 0) or I;
+    "*" without pieces"""
+    if not pieces:
+        return "*"
+    out = [f"{pieces[0][0]}S"] if pieces[0][0] > 0 else []
+    for i, (s, e, d) in enumerate(pieces):
+        if i:
+            g = d - pieces[i - 1][2]
+            out.append(f"{g}D" if g > 0 else f"{-g}I")
+        out.append(f"{e - s}M")
+    if read_len - pieces[-1][1] > 0:
+        out.append(f"{read_len - pieces[-1][1]}S")
+    return "".join(out)
+
+
+class AlignedReadMap(GappedReadMap):
+    """what SegmentBatch.align_reads() returns (include/gasm.h "Alignments"): GappedReadMap's tables of a mapping with end gaps, and
+    beside them per read the pieces of its best chain — its CIGAR and its SAM line follow — and per contig base the bases of the
+    insertions in front of it, column by column, so that insertions() names what was inserted and consensus() applies it.  It holds
+    the reads' lengths, not the reads.  The insertion columns are indexed from the insertion's first base, without its length: a
+    twin's insertion cannot be reversed column by column, so insert_pileup() and insertions() speak of the contig's own strand only."""
+
+    def __init__(self, k, strands, max_edits, max_gap, end_gap, contigs, rec, rec_gap, pile, gap_pile, edit_hist, counters, rec_end, end_counters,
+                 rec_piece, ins_pile, ins_cols, read_len, twins=None, seg_read_off=None):
+        """as GappedReadMap (the end tables also for end_gap = 0, where they are zero), with rec_piece: 2 * MAP_MAX_PIECES int32 per
+        read of the batch (s | e << 16, d); ins_pile: ins_cols columns of 4 uint32 per contig base; read_len: one length per read"""
+        super().__init__(k, strands, max_edits, max_gap, contigs, rec, rec_gap, pile, gap_pile, edit_hist, counters, twins, seg_read_off)
+        self.end_gap, self.ins_cols = int(end_gap), int(ins_cols)
+        self._end = np.asarray(rec_end, dtype=np.int32).reshape(-1, 4)
+        self._endcnt = np.asarray(end_counters, dtype=np.uint64).reshape(len(contigs), len(MAPEND_FIELDS))
+        self._piece = np.asarray(rec_piece, dtype=np.int32).reshape(-1, MAP_MAX_PIECES, 2)
+        flat = np.asarray(ins_pile, dtype=np.uint32).reshape(-1)
+        if len(flat) != 4 * self.ins_cols * len(self._pile):
+            raise ValueError("the insertion pileup does not have ins_cols columns per contig base")
+        self._ipile = flat.reshape(len(self._pile) if self.ins_cols else 0, self.ins_cols, 4)
+        self._len = np.asarray(read_len, dtype=np.int64).reshape(-1)
+        if not len(self._end) == len(self._piece) == len(self._len) == len(self._rec):
+            raise ValueError("the end records, the piece records and the read lengths do not fit the records")
+
+    def read_lengths(self, segment):
+        s = self._seg(segment)
+        return self._len[int(self._read_off[s]):int(self._read_off[s + 1])].copy()
+
+    def pieces(self, segment):
+        """per read the list [(s, e, d)] of its best chain's pieces, in read order: read bases [s, e) on diagonal d (read base x lies on
+        contig base d + x).  Empty for a read with no place"""
+        s = self._seg(segment)
+        a, b = int(self._read_off[s]), int(self._read_off[s + 1])
+        q = self._gap[a:b, 0]
+        return [[(int(w) & 0xFFFF, (int(w) >> 16) & 0xFFFF, int(d)) for w, d in p[:n]] for p, n in zip(self._piece[a:b].tolist(), q.tolist())]
+
+    def cigars(self, segment):
+        """one CIGAR string per read; "*" for a read with no place (readmap.cigar)"""
+        return [cigar(int(n), p) for n, p in zip(self.read_lengths(segment), self.pieces(segment))]
+
+    def to_sam(self, segment, reads=None, names=None):
+        """the segment's reads as SAM text: @HD, one @SQ per contig (s{segment}_c{contig}; after a both-strand build both twins), one
+        line per read in read order.  A placed read: FLAG 0 (the reads are mapped as given), POS the contig base under its first
+        aligned base + 1, MAPQ 255 (not available), its CIGAR, NM:i: the record's cost and XC:i: its accepted chains.  A read with
+        no place: FLAG 4.  reads: the segment's read strings for SEQ (else "*"); names: their names (else r0, r1, ...)"""
+        s = self._seg(segment)
+        rec, ps, lens = self.records(s), self.pieces(s), self.read_lengths(s)
+        for given, what in ((reads, "reads"), (names, "names")):
+            if given is not None and len(given) != len(rec):
+                raise ValueError(f"{what} must hold one entry per read of the segment")
+        out = ["@HD\tVN:1.6\tSO:unknown"] + [f"@SQ\tSN:s{s}_c{c}\tLN:{len(t)}" for c, t in enumerate(self._contigs[s])]
+        for i, (r, p) in enumerate(zip(rec.tolist(), ps)):
+            name = names[i] if names is not None else f"r{i}"
+            seq = reads[i] if reads is not None and len(reads[i]) else "*"
+            if r[0] < 0:
+                out.append(f"{name}\t4\t*\t0\t0\t*\t*\t0\t0\t{seq}\t*")
+            else:
+                out.append(f"{name}\t0\ts{s}_c{r[0]}\t{p[0][2] + p[0][0] + 1}\t255\t{cigar(int(lens[i]), p)}\t*\t0\t0\t{seq}\t*\tNM:i:{r[2]}\tXC:i:{r[3]}")
+        return "\n".join(out) + "\n"
+
+    def insert_pileup(self, segment):
+        """one (len(c), ins_cols, 4) uint32 array per contig: [p, l, x] = the accepted chains whose insertion in front of base p has
+        base x (A, C, G, T) as its l-th base.  The own strand only: there is no fold over twins"""
+        s = self._seg(segment)
+        c0 = int(self._seg_c[s])
+        if not self.ins_cols:
+            return [np.zeros((len(t), 0, 4), np.uint32) for t in self._contigs[s]]
+        return [self._ipile[int(self._base_off[c0 + c]):int(self._base_off[c0 + c + 1])].copy() for c in range(len(self._contigs[s]))]
+
+    def insertions(self, segment, min_depth=8, min_frac=0.2):
+        """sorted [(contig, position, inserted string, count, depth)] for every position of a depth (GappedReadMap.depth) of at least
+        min_depth in front of which the insertions' first column has a count > 0 that reaches min_frac of the depth: the count is that
+        column's sum; the string takes the strongest base (the first in ACGT of equals) of every leading column whose sum is still
+        > 0 and reaches min_frac of the depth"""
+        out = []
+        for c, (ip, dp) in enumerate(zip(self.insert_pileup(segment), self.depth(segment))):
+            if not ip.shape[1]:
+                continue
+            n = ip.sum(axis=2, dtype=np.int64)
+            ok = (n > 0) & (n >= float(min_frac) * dp[:, None])
+            for i in np.nonzero((dp >= int(min_depth)) & ok[:, 0])[0]:
+                cols = int(np.argmin(ok[i])) if not ok[i].all() else ip.shape[1]
+                out.append((c, int(i), "".join("ACGT"[int(x)] for x in ip[i, :cols].argmax(axis=1)), int(n[i, 0]), int(dp[i])))
+        return sorted(out)
+
+    def consensus(self, segment, min_depth=3, fold_twins=False, insertions=True):
+        """GappedReadMap.consensus with the insertions applied: in front of every base of a depth of at least min_depth the strongest
+        base (the first in ACGT of equals) of every leading column whose sum holds a strict majority of that depth is inserted,
+        whether or not the base itself is dropped by a deletion majority.  insertions=False: GappedReadMap.consensus.  The insertion
+        columns cannot be folded over twins: fold_twins with insertions raises ValueError"""
+        if not insertions:
+            return super().consensus(segment, min_depth, fold_twins)
+        if fold_twins:
+            raise ValueError("the insertion columns cannot be folded over twins: consensus(fold_twins=True, insertions=False)")
+        out = []
+        for s, g, dp, ip in zip(ReadMap.consensus(self, segment, min_depth), self.gap_pileup(segment), self.depth(segment), self.insert_pileup(segment)):
+            deep = dp >= int(min_depth)
+            drop = deep & (2 * g[:, 0].astype(np.int64) > dp)
+            n = ip.sum(axis=2, dtype=np.int64)
+            text = []
+            for p, x in enumerate(s):
+                for l in range(ip.shape[1] if deep[p] else 0):
+                    if 2 * n[p, l] <= dp[p]:
+                        break
+                    text.append("ACGT"[int(ip[p, l].argmax())])
+                if not drop[p]:
+                    text.append(x)
+            out.append("".join(text))
         return out
 
 

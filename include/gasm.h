@@ -762,7 +762,8 @@ int gasm_batch_fetch_read_map(gasm_batch* b, const int32_t** rec, const uint32_t
  *   LIMITS.  An indel closer than k to an end of the read leaves no seed beyond it: that end is compared ungapped, and usually the
  *   read is rejected (of simulated 80-base reads with an indel about 45 % stay unplaced for this reason at k = 21, of 150-base reads
  *   about a third).  A spurious head between two heads of a chain cuts the chain.  A read that returns to an earlier diagonal is not
- *   chained through, because of A, B, A.  The sequence of inserted bases is not recorded.  A gap longer than max_gap is not joined.
+ *   chained through, because of A, B, A.  The sequence of inserted bases is not recorded (by this form and by end gaps; "Alignments"
+ *   below records it, and every read's pieces).  A gap longer than max_gap is not joined.
  *   Gaps cost their length: no affine score.  Pooled builds (gasm_pool_*) get none of this.
  * gasm_batch_map_reads_gapped        finishes the pending build and queues k_read_map_gapped on the step slot of the last build, behind
  *                                    it; GASM_ERR_STATE before a build and for the positioned reads of pooled builds, GASM_ERR_INVALID
@@ -842,6 +843,50 @@ int gasm_batch_fetch_read_map_gapped(gasm_batch* b, const int32_t** rec, const i
 #define GASM_MAPEND_FIELDS 4
 int gasm_batch_map_reads_gapped_ends(gasm_batch* b, uint32_t max_edits, uint32_t max_gap, uint32_t end_gap);
 int gasm_batch_fetch_read_map_ends(gasm_batch* b, const int32_t** rec_end, const uint64_t** end_counters);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Alignments: gapped read mapping with end gaps that KEEPS what it worked out: every read's pieces, from which its CIGAR and a SAM line
+ * follow, and the bases of every insertion.  The two forms above verify a complete base-level alignment of every accepted chain and
+ * keep its first and last diagonal, its piece count and its totals; the inner diagonals and the breakpoints are kept nowhere, and an
+ * insertion is counted without its bases.  A fourth form of the pass; the other three, their tables and their launches are untouched.
+ * The rule is that of "End gaps", steps 1 to 9, word for word; end_gap = 0 is legal and takes no end gap (the eight tables are then the
+ * gapped mapping's six and zero end tables).  Nothing about places, costs, pileups or counters changes; two tables are added.
+ *   OUTPUTS.  The eight arrays of "End gaps" with the same shapes and values, and:
+ *     rec_piece[(r * GASM_MAP_MAX_PIECES + i) * 2 + 0..1] = s | e << 16, d: piece i of the read's best chain holds read bases [s, e) on
+ *       diagonal d (read base x lies on contig base d + x), exactly the pieces that steps 6 / 6' verify, after the clamps to the read
+ *       and to the contig, end-gap pieces included, in read order.  rec_gap[4 r + 0] pieces are valid; the others, and all pieces of
+ *       a read with no place, are zero.  GASM_MAP_MAX_PIECES = GASM_MAP_MAX_BLOCKS + 2: a chain over every kept head and a piece
+ *       beyond the gap at each end.  e <= GASM_THREAD_MAX_KMERS + 62, so the halves cannot overflow.  80 bytes per read.
+ *     ins_pile[((p * W + l) * 4) + x], W = ins_cols = max(max_gap, end_gap) columns of 4 uint32 per contig base p, in the order of
+ *       gasm_batch_fetch_contigs; l the column, x the base code (A, C, G, T).  Every ACCEPTED chain adds to it as it adds to gap_pile:
+ *       an insertion of G read bases with breakpoint t in front of contig base p (the p that gets gap_pile[2 p + 1]) adds 1 at column
+ *       l, base read[t + l], for l in [0, G); joins and both end gaps alike.  16 W bytes per contig base (48 at the defaults, 256 at
+ *       W = 16); W = 0 gives an empty table.
+ *   INVARIANTS, all integer and independent of the order of the adds.  Column 0's four counts sum to gap_pile[2 p + 1].  The column
+ *   sums never increase with l.  The grand total is the inserted bases over all accepted chains.
+ *   CIGAR of a placed read of len bases with the pieces (s_i, e_i, d_i), i = 1..q: s_1 S if s_1 > 0; e_i - s_i M per piece; between
+ *   pieces i and i + 1, g = d_{i+1} - d_i: g D if g > 0, -g I if g < 0; len - e_q S if that is positive.  Read bases off either end of
+ *   the contig are soft clips.  The leftmost contig base is d_1 + s_1 (SAM's POS less 1).  M + I + S sum to len, M to rec[4 r + 3],
+ *   I and D to rec_gap[4 r + 1] and [4 r + 2]; the M runs number rec_gap[4 r + 0].  A read with no place has the CIGAR "*".
+ *   LIMITS.  The pieces are the best chain's only; ins_pile counts every accepted chain, as the pileups do.  The columns are indexed
+ *   from the insertion's first base, without its length: insertions of different lengths at one place share their leading columns,
+ *   and a twin's insertion (after a both-strand build) cannot be reversed column by column, so the insertion pileup is not folded over
+ *   twins.  An index by (length, column) would lift this and is not built.  No mapping quality, no pairing, no qualities.  And the
+ *   limits of "End gaps".  Pooled builds get none of this.
+ * gasm_batch_map_reads_aligned       as gasm_batch_map_reads_gapped_ends: the same checks and error codes.  It fills the gapped
+ *                                    mapping's own state: gasm_batch_fetch_read_map_gapped, gasm_batch_fetch_read_map_ends (also for
+ *                                    end_gap = 0: zero tables) and gasm_batch_score_mapped(source = GASM_MAPSCORE_GAPPED) work on it
+ *                                    unchanged.  It queues k_read_map_trace alone.  A later gasm_batch_map_reads_gapped or
+ *                                    gasm_batch_map_reads_gapped_ends forgets the two tables; a batch that never calls it launches
+ *                                    exactly what it launched without.
+ * gasm_batch_fetch_read_alignments   host copies, valid until the next call or build.  GASM_ERR_STATE before a build, without a gapped
+ *                                    mapping over the last build, and when the last one was not made by gasm_batch_map_reads_aligned;
+ *                                    GASM_ERR_INVALID for a null argument.
+ * What to do with them (pieces, CIGAR, SAM, inserted strings, consensus with insertions) is host code:
+ * genomeassembler_dev_amd/readmap.py, AlignedReadMap.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GASM_MAP_MAX_PIECES 10
+int gasm_batch_map_reads_aligned(gasm_batch* b, uint32_t max_edits, uint32_t max_gap, uint32_t end_gap);
+int gasm_batch_fetch_read_alignments(gasm_batch* b, const int32_t** rec_piece, const uint32_t** ins_pile, uint32_t* ins_cols);
 /* ------------------------------------------------------------------------------------------------------------------
  * Mapped scoring: breakage scores from mapped reads, so that reads with errors count too.  gasm_batch_score matches exactly: a read
  * scores iff it is a substring of a contig, so a read with one wrong base scores nothing although its start, the breakpoint, is
