@@ -30,6 +30,9 @@ MAP_MAX_PIECES = 10        # GASM_MAP_MAX_PIECES: the pieces align_reads() keeps
 MAPSCORE_FIELDS = ("unplaced", "start_clipped", "end_clipped", "whole")   # GASM_MAPSCORE_FIELDS counters of score_mapped(), in the header's order
 MAPSCORE_SOURCES = {"ungapped": 0, "gapped": 1}   # GASM_MAPSCORE_UNGAPPED / GASM_MAPSCORE_GAPPED
 MAPSCORE_PARTIAL = 1       # GASM_MAPSCORE_PARTIAL: score_mapped() also scores reads that run off their contig's end
+INGEST_STATS = ("records", "kept", "dropped_non_acgt", "dropped_short", "dropped_mate", "bases_in", "bases_kept", "bases_dropped", "trimmed5", "trimmed3",
+                "reads_trimmed")   # GASM_INGEST_STATS counters, in the header's order
+QUAL_BINS = 94          # GASM_QUAL_BINS: bins of the ingest's quality histogram
 MAX_TABLES = 8          # GASM_MAX_TABLES: breakage tables one calc_breakscore_tables / score_tables call takes
 # one row of gasm_batch_build_plan, in the order of the GASM_PLAN_* word indices of include/gasm.h
 PLAN_FIELDS = ("key_words", "bucket_bits", "table_slots", "single_pass", "multi_pass", "scan_in_dedup", "ranked_in_lds", "ruler_shift",
@@ -59,6 +62,27 @@ class BuildParams(C.Structure):
         for name, v in fields.items():
             setattr(p, name, int(v))
         return p
+
+
+class IngestParams(C.Structure):
+    """gasm_ingest_params (include/gasm.h): every option of an ingest; make() fills `size`"""
+    _fields_ = [("size", _u32), ("on_non_acgt", _u32), ("phred_offset", _u32), ("trim_q3", _u32), ("trim_q5", _u32), ("min_len", _u32), ("pairs", _u32),
+                ("quality_hist", _u32)]
+
+    @classmethod
+    def make(cls, non_acgt="drop", **fields):
+        p = cls(size=C.sizeof(cls), on_non_acgt=1 if non_acgt == "error" else 0)
+        for name, v in fields.items():
+            if name not in ("phred_offset", "trim_q3", "trim_q5", "min_len", "pairs", "quality_hist"):
+                raise TypeError(f"unknown ingest option {name!r}")
+            if int(v) < 0:
+                raise ValueError(f"{name} = {v} is negative")
+            setattr(p, name, int(v))
+        return p
+
+    def any(self):
+        """an option besides non_acgt is set: the ingest collects statistics (a phred_offset alone changes nothing)"""
+        return bool(self.trim_q3 or self.trim_q5 or self.min_len or self.pairs or self.quality_hist)
 
 
 # every symbol include/gasm.h declares: name -> (restype, argtypes)
@@ -142,6 +166,12 @@ SYMBOLS = {
     "gasm_packed_seg_read_off": (_vp, [_vp]),
     "gasm_packed_dropped": (_u64, [_vp]),
     "gasm_packed_free": (None, [_vp]),
+    "gasm_read_files_params": (_int, [_vp, _u32, C.POINTER(IngestParams), _PP]),
+    "gasm_read_files_device_params": (_int, [_vp, _vp, _u32, C.POINTER(IngestParams), _PP]),
+    "gasm_batch_from_files_params": (_int, [_vp, _vp, _u32, C.POINTER(IngestParams), _PP, C.POINTER(_u64)]),
+    "gasm_packed_ingest_stats": (_vp, [_vp]),
+    "gasm_packed_quality_hist": (_vp, [_vp]),
+    "gasm_batch_fetch_ingest_stats": (_int, [_vp, _PP, _PP]),
     "gasm_batch_free": (None, [_vp]),
     "gasm_batch_build": (_int, [_vp, _int, _u64]),
     "gasm_batch_score": (_int, [_vp, _int, _vp]),

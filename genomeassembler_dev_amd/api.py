@@ -446,6 +446,22 @@ def correct_reads(reads, k, min_count=2, strands=1, ctx=None):
         b.close()
 
 
+def get_contigs_from_fastq(paths, k, non_acgt="drop", trim_q3=0, trim_q5=0, min_len=0, pairs=False, phred_offset=33, quality_hist=False, ctx=None, **build):
+    """FASTQ in, contigs out, in one call: the files (one per segment, FASTQ or FASTA, plain or .gz) read, trimmed and packed on the
+    device (SegmentBatch.from_fastq with its options: the rule is include/gasm.h's "Quality trimming at ingest"), then one
+    build_simplified(k, **build) over what is left.  Returns (contigs: one list of str per segment, seqio.IngestStats or None when no
+    ingest option is set).  build: as for contig_graph."""
+    from .batch import SegmentBatch
+    b = SegmentBatch.from_fastq(paths, non_acgt=non_acgt, ctx=ctx, trim_q3=trim_q3, trim_q5=trim_q5, min_len=min_len, pairs=pairs, phred_offset=phred_offset,
+                                quality_hist=quality_hist)
+    try:
+        stats = b.ingest_stats() if b.ingest_options else None
+        b.build_simplified(int(k), **build)
+        return [b.contigs(s) for s in range(b.n_segments)], stats
+    finally:
+        b.close()
+
+
 def contig_graph(reads, k, span_len=None, ctx=None, **build):
     """the contigs of one segment's reads (a list of str) and the graph between them: (contigs, links.ContigLinks).  build: the keyword
     set of SegmentBatch.build_simplified (min_count, strands, tip_len, tip_rounds, bubble_len, bubble_rounds, cov_cutoff, cov_len,

@@ -7,7 +7,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import qtable, readkmers
-from ._lib import CORRECT_FIELDS, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAP_MAX_PIECES, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
+from ._lib import CORRECT_FIELDS, INGEST_STATS, QUAL_BINS, IngestParams, MAP_FIELDS, MAP_MAX_GAP, MAP_MAX_MISMATCH, MAP_MAX_PIECES, MAPEND_FIELDS, MAPG_FIELDS, MAPSCORE_FIELDS, MAPSCORE_PARTIAL, MAPSCORE_SOURCES, MAX_TABLES, MAX_BUBBLE_ROUNDS, MAX_COV_ROUNDS, MAX_INSERT, MAX_SPAN_LEN, MAX_TIP_ROUNDS, PAIR_FIELDS, PLAN_FIELDS, BuildParams, check, default_context, lib
 from .api import _check_build_opts, unpack_kmers
 from .links import ContigLinks
 from .pairs import PairPlaces
@@ -116,19 +116,32 @@ class SegmentBatch:
         return seg, starts
 
     @classmethod
-    def from_fastq(cls, paths, non_acgt="drop", ctx=None):
-        """one FASTQ/FASTA file (plain or .gz) per segment, read and packed by libgasm (gasm_batch_from_files); reads with a
-        base outside ACGT are dropped (count in `.dropped_reads`) or, with non_acgt='error', refused"""
+    def from_fastq(cls, paths, non_acgt="drop", ctx=None, trim_q3=0, trim_q5=0, min_len=0, pairs=False, phred_offset=33, quality_hist=False):
+        """one FASTQ/FASTA file (plain or .gz) per segment, read and packed by libgasm (gasm_batch_from_files_params); reads with a
+        base outside ACGT are dropped (count in `.dropped_reads`) or, with non_acgt='error', refused.
+        trim_q3 / trim_q5 > 0: FASTQ records are trimmed by base quality at that end (the running-sum rule of include/gasm.h,
+        "Quality trimming at ingest"; an N counts as quality 0, so a terminal N goes and the read stays); min_len: shorter spans are
+        dropped; pairs: an interleaved file's mates (records 2p, 2p + 1) are kept or dropped together, so place_pairs() still finds
+        them; quality_hist: ingest_stats() also holds the histogram suggest_trim_q() reads.  `.dropped_reads` counts every drop."""
         from .seqio import _paths
         self = cls.__new__(cls)
         self.ctx = ctx or default_context()
+        p = IngestParams.make(non_acgt, trim_q3=trim_q3, trim_q5=trim_q5, min_len=min_len, pairs=bool(pairs), phred_offset=phred_offset, quality_hist=bool(quality_hist))
         h, dropped = C.c_void_p(), C.c_uint64()
-        check(lib().gasm_batch_from_files(self.ctx.h, _paths(paths), len(paths), 1 if non_acgt == "error" else 0, C.byref(h), C.byref(dropped)))
+        check(lib().gasm_batch_from_files_params(self.ctx.h, _paths(paths), len(paths), C.byref(p), C.byref(h), C.byref(dropped)))
         self.h, self.k, self._table = h, None, None
         self.n_segments = len(paths)
         self.n_reads = int(lib().gasm_batch_total_reads(h))
         self.dropped_reads = int(dropped.value)
+        self.ingest_options = p.any()          # an option besides non_acgt was set: ingest_stats() has something to say
         return self
+
+    def ingest_stats(self):
+        """seqio.IngestStats of a batch made by from_fastq() under an option besides non_acgt (else GASM_ERR_STATE)"""
+        from .seqio import IngestStats
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().gasm_batch_fetch_ingest_stats(self.h, C.byref(a), C.byref(b)))
+        return IngestStats(_arr(a, C.c_uint64, self.n_segments * len(INGEST_STATS)), _arr(b, C.c_uint64, self.n_segments * QUAL_BINS))
 
     def _build(self, k, genome_len_hint, **opts):
         """every build*() below: check the options, hand them to the library as one gasm_build_params (gasm_batch_build_params).  The

@@ -30,6 +30,7 @@ struct gasm_packed {
     std::vector<u64> seg;
     u64 dropped = 0;
     std::vector<u8> on_device;       // per file: parsed and packed by the device path (gasm_read_files_device)
+    std::vector<u64> stats, hist;    // an ingest under options: GASM_INGEST_STATS / GASM_QUAL_BINS per file (else empty)
 };
 
 struct gasm_scores {
@@ -109,6 +110,8 @@ struct gasm_batch {
     // gasm_batch_fetch_reads: the reads as ASCII and their offsets
     std::vector<char> h_reads_ascii;
     std::vector<u64> h_reads_off;
+    // a batch made by gasm_batch_from_files_params under options: what the ingest did, per segment (else empty)
+    std::vector<u64> h_ingest_stats, h_ingest_hist;
 };
 
 // the last gasm_batch_score or gasm_batch_score_tables on slot x
@@ -726,29 +729,57 @@ int gasm_batch_create_packed(gasm_ctx* ctx, const uint64_t* words, const uint64_
     API_GUARD_END
 }
 
-static int parse_files(const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_packed& g) {
+// gasm_ingest_params, checked -> the options every reader takes (the plain entries come here with their on_non_acgt alone)
+static int ingest_opts_from(const gasm_ingest_params* p, const char* who, gasm_host::IngestOpts& o) {
+    if (!p) { gasm_set_error("%s: params is null", who); return GASM_ERR_INVALID; }
+    if (p->size != sizeof(gasm_ingest_params)) { gasm_set_error("%s: params->size is %u, not sizeof(gasm_ingest_params) = %zu", who, p->size, sizeof(gasm_ingest_params)); return GASM_ERR_INVALID; }
+    if (p->on_non_acgt > 1 || p->pairs > 1 || p->quality_hist > 1) { gasm_set_error("%s: on_non_acgt, pairs and quality_hist are 0 or 1", who); return GASM_ERR_INVALID; }
+    if (p->phred_offset != 0 && p->phred_offset != 33 && p->phred_offset != 64) { gasm_set_error("%s: phred_offset %u is neither 33 nor 64", who, p->phred_offset); return GASM_ERR_INVALID; }
+    if (p->trim_q3 > 93 || p->trim_q5 > 93) { gasm_set_error("%s: trim_q3 and trim_q5 are at most 93", who); return GASM_ERR_INVALID; }
+    o.error_on_non_acgt = p->on_non_acgt != 0;
+    o.phred_offset = p->phred_offset ? p->phred_offset : 33;
+    o.trim_q3 = p->trim_q3; o.trim_q5 = p->trim_q5; o.min_len = p->min_len;
+    o.pairs = p->pairs != 0; o.quality_hist = p->quality_hist != 0;
+    return GASM_OK;
+}
+static gasm_ingest_params plain_ingest_params(int on_non_acgt) {
+    gasm_ingest_params p = {};
+    p.size = sizeof(p);
+    p.on_non_acgt = on_non_acgt != 0;
+    return p;
+}
+
+static int parse_files(const char* const* paths, uint32_t n_files, const gasm_host::IngestOpts& o, gasm_packed& g) {
     g.pr.read_off.assign(1, 0);
     g.seg.assign((size_t)n_files + 1, 0);
     g.dropped = 0;
+    if (o.any()) { g.stats.assign((size_t)n_files * GASM_INGEST_STATS, 0); g.hist.assign((size_t)n_files * GASM_QUAL_BINS, 0); }
     for (u32 f = 0; f < n_files; ++f) {
         if (!paths[f]) { gasm_set_error("paths[%u] is null", f); return GASM_ERR_INVALID; }
         u64 kept = 0;
-        GCHK(gasm_host::read_sequence_file(paths[f], on_non_acgt != 0, g.pr, &kept, &g.dropped));
+        GCHK(gasm_host::read_sequence_file(paths[f], o, g.pr, &kept, &g.dropped, o.any() ? &g.stats[(size_t)f * GASM_INGEST_STATS] : nullptr,
+                                           o.any() ? &g.hist[(size_t)f * GASM_QUAL_BINS] : nullptr));
         g.seg[f + 1] = g.seg[f] + kept;
     }
     return GASM_OK;
 }
 
-int gasm_read_files(const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_packed** out) {
+int gasm_read_files_params(const char* const* paths, uint32_t n_files, const gasm_ingest_params* params, gasm_packed** out) {
     API_GUARD_BEGIN
     if (!out || !paths || n_files == 0) { gasm_set_error("gasm_read_files: bad argument"); return GASM_ERR_INVALID; }
     *out = nullptr;
+    gasm_host::IngestOpts o;
+    GCHK(ingest_opts_from(params, "gasm_read_files_params", o));
     gasm_packed* g = new gasm_packed();
-    const int st = parse_files(paths, n_files, on_non_acgt, *g);
+    const int st = parse_files(paths, n_files, o, *g);
     if (st != GASM_OK) { delete g; return st; }
     *out = g;
     return GASM_OK;
     API_GUARD_END
+}
+int gasm_read_files(const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_packed** out) {
+    const gasm_ingest_params p = plain_ingest_params(on_non_acgt);
+    return gasm_read_files_params(paths, n_files, &p, out);
 }
 uint64_t gasm_packed_n_reads(const gasm_packed* g) { return g ? g->pr.read_off.size() - 1 : 0; }
 uint32_t gasm_packed_n_segments(const gasm_packed* g) { return g ? (uint32_t)(g->seg.size() - 1) : 0; }
@@ -756,18 +787,22 @@ const uint64_t* gasm_packed_words(const gasm_packed* g) { return g ? g->pr.words
 const uint64_t* gasm_packed_read_off(const gasm_packed* g) { return g ? g->pr.read_off.data() : nullptr; }
 const uint64_t* gasm_packed_seg_read_off(const gasm_packed* g) { return g ? g->seg.data() : nullptr; }
 uint64_t gasm_packed_dropped(const gasm_packed* g) { return g ? g->dropped : 0; }
+const uint64_t* gasm_packed_ingest_stats(const gasm_packed* g) { return g && !g->stats.empty() ? g->stats.data() : nullptr; }
+const uint64_t* gasm_packed_quality_hist(const gasm_packed* g) { return g && !g->hist.empty() ? g->hist.data() : nullptr; }
 void gasm_packed_free(gasm_packed* g) { delete g; }
 
 // the same files through the device path (ingest.hip: record scan + 2-bit pack on the GPU, the host only inflates), results
 // copied back: what gasm_batch_from_files builds its batch from without the copy
-int gasm_read_files_device(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_packed** out) {
+int gasm_read_files_device_params(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, const gasm_ingest_params* params, gasm_packed** out) {
     API_GUARD_BEGIN
     if (!ctx || !out || !paths || n_files == 0) { gasm_set_error("gasm_read_files_device: bad argument"); return GASM_ERR_INVALID; }
     *out = nullptr;
+    gasm_host::IngestOpts o;
+    GCHK(ingest_opts_from(params, "gasm_read_files_device_params", o));
     gasm_packed* g = new gasm_packed();
     DBuf d_words;
     struct Rel { DBuf& b; ~Rel() { b.release(); } } rel{d_words};
-    const int st = ingest_files_device(ctx, paths, n_files, on_non_acgt != 0, d_words, g->pr.read_off, g->seg, &g->dropped, g->on_device);
+    const int st = ingest_files_device(ctx, paths, n_files, o, d_words, g->pr.read_off, g->seg, &g->dropped, g->on_device, g->stats, g->hist);
     if (st != GASM_OK) { delete g; return st; }
     g->pr.total_bases = g->pr.read_off.back();
     const u64 nw = (g->pr.total_bases + 31) / 32;
@@ -777,26 +812,50 @@ int gasm_read_files_device(gasm_ctx* ctx, const char* const* paths, uint32_t n_f
     return GASM_OK;
     API_GUARD_END
 }
+int gasm_read_files_device(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_packed** out) {
+    const gasm_ingest_params p = plain_ingest_params(on_non_acgt);
+    return gasm_read_files_device_params(ctx, paths, n_files, &p, out);
+}
 int gasm_packed_parsed_on_device(const gasm_packed* g, uint32_t file) { return g && file < g->on_device.size() ? g->on_device[file] : 0; }
 
-int gasm_batch_from_files(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_batch** out, uint64_t* dropped_reads) {
+int gasm_batch_from_files_params(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, const gasm_ingest_params* params, gasm_batch** out,
+                                 uint64_t* dropped_reads) {
     API_GUARD_BEGIN
     if (!ctx || !out || !paths || n_files == 0) { gasm_set_error("gasm_batch_from_files: bad argument"); return GASM_ERR_INVALID; }
     *out = nullptr;
+    gasm_host::IngestOpts o;
+    GCHK(ingest_opts_from(params, "gasm_batch_from_files_params", o));
     // record scan and 2-bit packing on the device (ingest.hip); the packed stream never leaves it
     DBuf d_words;
     struct Rel { DBuf& b; ~Rel() { b.release(); } } rel{d_words};
-    std::vector<u64> read_off, seg;
+    std::vector<u64> read_off, seg, stats, hist;
     std::vector<u8> on_device;
     u64 dropped = 0;
-    GCHK(ingest_files_device(ctx, paths, n_files, on_non_acgt != 0, d_words, read_off, seg, &dropped, on_device));
+    GCHK(ingest_files_device(ctx, paths, n_files, o, d_words, read_off, seg, &dropped, on_device, stats, hist));
     if (dropped_reads) *dropped_reads = dropped;
     const u64 n = read_off.size() - 1;
     // fixed-length reads (the usual case) need no offset array on the device
     u32 flen = n ? (u32)std::min<u64>(read_off[1], 0xFFFFFFFFull) : 0;
     bool fixed = n > 0 && flen > 0;
     for (u64 r = 0; fixed && r < n; ++r) fixed = read_off[r + 1] - read_off[r] == flen;
-    return new_batch(ctx, n_files, n, out, [&](gasm_batch* b) { return b->rd.adopt_packed(ctx, d_words, fixed ? nullptr : read_off.data(), n, fixed ? flen : 0, seg.data(), n_files); });
+    return new_batch(ctx, n_files, n, out, [&](gasm_batch* b) {
+        b->h_ingest_stats = std::move(stats);
+        b->h_ingest_hist = std::move(hist);
+        return b->rd.adopt_packed(ctx, d_words, fixed ? nullptr : read_off.data(), n, fixed ? flen : 0, seg.data(), n_files);
+    });
+    API_GUARD_END
+}
+int gasm_batch_from_files(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, int on_non_acgt, gasm_batch** out, uint64_t* dropped_reads) {
+    const gasm_ingest_params p = plain_ingest_params(on_non_acgt);
+    return gasm_batch_from_files_params(ctx, paths, n_files, &p, out, dropped_reads);
+}
+int gasm_batch_fetch_ingest_stats(gasm_batch* b, const uint64_t** stats, const uint64_t** quality_hist) {
+    API_GUARD_BEGIN
+    if (!b || !stats || !quality_hist) { gasm_set_error("null argument"); return GASM_ERR_INVALID; }
+    if (b->h_ingest_stats.empty()) { gasm_set_error("not a batch made from files under ingest options: no statistics were collected"); return GASM_ERR_STATE; }
+    *stats = b->h_ingest_stats.data();
+    *quality_hist = b->h_ingest_hist.data();
+    return GASM_OK;
     API_GUARD_END
 }
 

@@ -169,7 +169,24 @@ struct PackedReads {
     std::vector<u64> words;        // 32 bases per word, first base most significant
     std::vector<u64> read_off;     // n_reads + 1 base offsets (first entry 0)
     u64 total_bases = 0;
-    void append(const std::string& seq);
+    void append_span(const char* seq, size_t n);      // one read: n bases of ACGT / acgt
 };
+// The options of an ingest (gasm_ingest_params of include/gasm.h, checked: ingest_opts_from in capi.hip).  All but error_on_non_acgt
+// zero: the ingest the plain entries run.
+struct IngestOpts {
+    bool error_on_non_acgt = false;
+    u32 phred_offset = 33, trim_q3 = 0, trim_q5 = 0, min_len = 0;
+    bool pairs = false, quality_hist = false;
+    bool quality() const { return trim_q3 > 0 || trim_q5 > 0 || quality_hist; }     // quality lines are read at all
+    bool any() const { return quality() || min_len > 0 || pairs; }                   // statistics are collected
+};
+// classes of a record (the rule: include/gasm.h, "Quality trimming at ingest"); the class byte of the device path holds the same
+enum : u8 { ING_KEPT = 0, ING_NON_ACGT = 1, ING_SHORT = 2, ING_MATE = 3 };
+// THE rule, stated once: the raw 5' and 3' cuts a and e of one FASTQ record of L bases (qual: L bytes, each in
+// [phred_offset, phred_offset + 93], checked by the caller).  The kept span is [min(a, e), e).
+void trim_span(const char* seq, const char* qual, u32 L, const IngestOpts& o, u32* a, u32* e);
+// stats: GASM_INGEST_STATS counters of this file, hist: GASM_QUAL_BINS bins; both added to, both may be null
+int read_sequence_file(const char* path, const IngestOpts& o, PackedReads& out, u64* n_kept, u64* n_dropped, u64* stats, u64* hist);
+// the plain reader: no option but what to do with a read outside ACGT
 int read_sequence_file(const char* path, bool error_on_non_acgt, PackedReads& out, u64* n_kept, u64* n_dropped);
 }  // namespace gasm_host

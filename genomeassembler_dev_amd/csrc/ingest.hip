@@ -5,6 +5,8 @@
 //   k_ing_lines                          per line: trimmed span (CR, blanks), first byte, "holds a byte outside ACGT"
 //   k_ing_fastq_check                    four-line records?  ('@' on lines 4r, '+' on lines 4r + 2, blank lines only at the end)
 //   k_ing_fasta_records                  '>' lines numbered (scan): record of every sequence line, a record's bad flag
+//   k_ing_qual_trim / k_ing_trim_fold    under ingest options (gasm_ingest_params), in place of k_ing_fastq_records: a wave per FASTQ record
+//                                        trims it by quality, narrows its sequence line to the kept span, classifies it; then mates, counters
 //   k_ing_piece_len / scans / k_ing_read_off   kept records, their base offsets: read_off
 //   k_ing_pack                           a thread per output word gathers its 32 bases across line pieces, 2-bit, case folded
 //   k_ing_append                         a file's reads appended to the batch's stream at any base offset
@@ -14,10 +16,16 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <climits>
 
 #include "pipeline.h"
 
 namespace {
+
+using gasm_host::ING_KEPT;
+using gasm_host::ING_NON_ACGT;
+using gasm_host::ING_SHORT;
+using gasm_host::ING_MATE;
 
 constexpr u32 CH = 4096;          // bytes per chunk of the newline count
 constexpr u32 SB = 8192;          // elements per block of the device-wide scans
@@ -156,6 +164,163 @@ __global__ void __launch_bounds__(256) k_ing_fastq_records(const u8* __restrict_
     rec_bad[r] = l_bad[4 * r + 1];
     rec_line[r] = 4 * r;
 }
+// ---- quality trimming (the rule: include/gasm.h, "Quality trimming at ingest"; its definition: gasm_host::trim_span) ----------------
+constexpr u32 ING_NONE = 0xFFFFFFFFu;             // "no such record" of the two atomicMin words
+constexpr u32 QT_WAVES = 4;                       // records (waves) per workgroup and trip of k_ing_qual_trim
+constexpr u32 QT_WG_PER_CU = 8;                   // its grid: at most this many workgroups per CU, 32 waves
+// where the options' report lives in one device buffer of u64: the counters, the histogram, then the two u32 record indices
+constexpr u32 QO_STATS = 0, QO_HIST = GASM_INGEST_STATS, QO_FIRST = GASM_INGEST_STATS + GASM_QUAL_BINS, QO_WORDS = QO_FIRST + 1;
+struct QualOpts { u32 off, q3, q5, min_len; int quality, hist; };
+
+__device__ __forceinline__ int wave_incl_sum(int v, u32 ln) {
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d, 64); if ((int)ln >= d) v += o; }
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+    for (int d = 32; d; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+
+// One end of one record, the whole wave in step: 64 positions per trip counted from that end (lane 0 = the outermost), an inclusive
+// scan of cut - q with the carry of the trips before, the first lane whose sum is negative stops the pass, the greatest sum in front
+// of it is the trip's candidate (the lowest lane of equal ones: the outermost) and replaces `best` only if strictly greater.
+// Returns a (FRONT) or e.
+template <bool FRONT>
+__device__ __forceinline__ u32 trim_end(const u8* __restrict__ seq, const u8* __restrict__ qual, u32 L, u32 off, u32 cut, u32 ln) {
+    long long carry = 0, best = 0;
+    u32 res = FRONT ? 0u : L;
+    for (u32 t0 = 0; t0 < L; t0 += 64) {
+        const u32 j = t0 + ln;
+        const bool valid = j < L;
+        int v = 0;
+        if (valid) {
+            const u32 i = FRONT ? j : L - 1 - j;
+            const int q = code_of(seq[i]) < 0 ? 0 : (int)qual[i] - (int)off;
+            v = (int)cut - q;
+        }
+        const int inc = wave_incl_sum(v, ln);
+        const u64 stop = __ballot(valid && carry + inc < 0);
+        const u32 stop_lane = stop ? (u32)__ffsll((long long)stop) - 1 : 64u;
+        const bool cand = valid && ln < stop_lane;
+        const int m = wave_max(cand ? inc : INT_MIN);
+        if (m != INT_MIN && carry + m > best) {
+            best = carry + m;
+            const u32 jw = t0 + (u32)__ffsll((long long)__ballot(cand && inc == m)) - 1;
+            res = FRONT ? jw + 1 : L - 1 - jw;
+        }
+        if (stop) break;
+        carry += __shfl(inc, 63, 64);
+    }
+    return res;
+}
+
+// A wave per FASTQ record r (lines 4r .. 4r + 3).  Quality mode: the quality line must be as long as the sequence and hold bytes of
+// [off, off + 93] only (else *first_malformed = min r), its bytes go to the histogram, the two passes give a and e.  Without quality
+// mode no text is read: the record is whole.  Written: the kept span over the sequence line's (l_a, l_len), rec_bad inside the span,
+// the class before the mate rule, what each end lost.
+__global__ void __launch_bounds__(256) k_ing_qual_trim(const u8* __restrict__ text, u64* __restrict__ l_a, u32* __restrict__ l_len, const u8* __restrict__ l_bad,
+                                                       u32 n_rec, u32 n_lines, QualOpts o, u32* __restrict__ rec_bad, u32* __restrict__ rec_line,
+                                                       u8* __restrict__ cls, u32* __restrict__ rec_t5, u32* __restrict__ rec_t3, u64* __restrict__ hist,
+                                                       u32* __restrict__ first_malformed) {
+    __shared__ u32 s_hist[GASM_QUAL_BINS];
+    if (o.hist) {
+        for (u32 b = threadIdx.x; b < GASM_QUAL_BINS; b += 256) s_hist[b] = 0;
+        __syncthreads();
+    }
+    const u32 ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (u32 r = blockIdx.x * QT_WAVES + wv; r < n_rec; r += gridDim.x * QT_WAVES) {
+        const u32 i = 4 * r + 1;
+        const u64 sa = l_a[i];
+        const u32 L = l_len[i];
+        u32 a = 0, e = L;
+        bool malformed = false;
+        if (o.quality) {
+            const u32 qi = i + 2;                                   // (the last record's quality line may be missing altogether)
+            const u32 ql = qi < n_lines ? l_len[qi] : 0u;
+            const u8* qual = text + (qi < n_lines ? l_a[qi] : 0ull);
+            if (ql != L) {
+                malformed = true;
+            } else {
+                bool out_of_range = false;
+                for (u32 t0 = 0; t0 < L; t0 += 64) {
+                    const u32 j = t0 + ln;
+                    if (j < L) {
+                        const u32 q = (u32)qual[j] - o.off;
+                        if (q >= GASM_QUAL_BINS) out_of_range = true;
+                        else if (o.hist) atomicAdd(&s_hist[q], 1u);     // (counted before the record is known to be well formed: a malformed record fails its whole file, so these bins are never reported)
+                    }
+                }
+                malformed = __ballot(out_of_range) != 0;
+                if (!malformed) {
+                    if (o.q3) e = trim_end<false>(text + sa, qual, L, o.off, o.q3, ln);
+                    if (o.q5) a = trim_end<true>(text + sa, qual, L, o.off, o.q5, ln);
+                }
+            }
+        }
+        const u32 t5 = min(a, e), len = e - t5;
+        bool bad = l_bad[i] != 0;
+        if (bad && len < L) {                                       // the line holds a byte outside ACGT: does the span?
+            bool b = false;
+            for (u32 t0 = 0; t0 < len; t0 += 64) {
+                const u32 j = t0 + ln;
+                if (j < len && code_of(text[sa + t5 + j]) < 0) b = true;
+            }
+            bad = __ballot(b) != 0;
+        }
+        if (ln == 0) {
+            if (malformed) atomicMin(first_malformed, r);
+            l_a[i] = sa + t5;
+            l_len[i] = len;
+            rec_bad[r] = bad ? 1u : 0u;
+            rec_line[r] = 4 * r;
+            cls[r] = bad ? ING_NON_ACGT : len < o.min_len ? ING_SHORT : ING_KEPT;
+            rec_t5[r] = t5;
+            rec_t3[r] = L - e;
+        }
+    }
+    if (o.hist) {
+        __syncthreads();
+        for (u32 b = threadIdx.x; b < GASM_QUAL_BINS; b += 256)
+            if (s_hist[b]) atomicAdd(reinterpret_cast<unsigned long long*>(&hist[b]), (unsigned long long)s_hist[b]);
+    }
+}
+// The mate rule, what k_ing_piece_len reads as "not kept" (rec_bad), the counters of include/gasm.h, the lowest non_acgt record.
+__global__ void __launch_bounds__(256) k_ing_trim_fold(const u8* __restrict__ cls, const u32* __restrict__ l_len, const u32* __restrict__ rec_t5,
+                                                       const u32* __restrict__ rec_t3, u32 n_rec, int pairs, u32* __restrict__ rec_bad,
+                                                       u64* __restrict__ stats, u32* __restrict__ first_non_acgt) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    u64 c[GASM_INGEST_STATS];
+    for (u32 q = 0; q < GASM_INGEST_STATS; ++q) c[q] = 0;
+    if (r < n_rec) {
+        u32 k = cls[r];
+        if (pairs && k == ING_KEPT && (r ^ 1u) < n_rec && cls[r ^ 1u] != ING_KEPT) k = ING_MATE;
+        rec_bad[r] = k != ING_KEPT ? 1u : 0u;
+        if (k == ING_NON_ACGT) atomicMin(first_non_acgt, r);
+        const u32 len = l_len[4 * r + 1], t5 = rec_t5[r], t3 = rec_t3[r];
+        const bool kept = k == ING_KEPT;
+        c[0] = 1;
+        c[1] = kept; c[2] = k == ING_NON_ACGT; c[3] = k == ING_SHORT; c[4] = k == ING_MATE;
+        c[5] = (u64)len + t5 + t3;
+        c[6] = kept ? len : 0; c[7] = kept ? 0 : len;
+        c[8] = t5; c[9] = t3;
+        c[10] = kept && (t5 | t3);
+    }
+    for (u32 q = 0; q < GASM_INGEST_STATS; ++q) {
+        const u64 v = wave_sum(c[q]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(&stats[q]), (unsigned long long)v);
+    }
+}
+// FASTA under options: bases_in, the bases of every sequence line that belongs to a record
+__global__ void __launch_bounds__(256) k_ing_fasta_bases(const u32* __restrict__ hdr, const u64* __restrict__ hdr_ex, const u32* __restrict__ l_len, u32 n_lines,
+                                                         u64* __restrict__ bases_in) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    const u64 v = wave_sum(i < n_lines && !hdr[i] && hdr_ex[i] > 0 ? (u64)l_len[i] : 0ull);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(bases_in), (unsigned long long)v);
+}
 // bases line i contributes: its trimmed length if it is a sequence line of a kept record
 __global__ void __launch_bounds__(256) k_ing_piece_len(int fastq, const u32* __restrict__ hdr, const u64* __restrict__ hdr_ex, const u32* __restrict__ l_len,
                                                        const u32* __restrict__ rec_bad, u32 n_lines, u32 n_eff, u32* __restrict__ plen, u32* __restrict__ keep, u32 n_rec) {
@@ -250,17 +415,20 @@ int slurp(const char* path, std::vector<char>& text) {
 
 struct Scratch {
     DBuf text, chunk_cnt, chunk_base, ls, l_a, l_len, l_first, l_bad, info, hdr, hdr_ex, rec_bad, rec_line, plen, pbase, keep, keep_ex, bsum, totals, words, read_off;
+    DBuf cls, rec_t5, rec_t3, qout;                   // under ingest options only
     void release() {
         for (DBuf* b : {&text, &chunk_cnt, &chunk_base, &ls, &l_a, &l_len, &l_first, &l_bad, &info, &hdr, &hdr_ex, &rec_bad, &rec_line, &plen, &pbase, &keep,
-                        &keep_ex, &bsum, &totals, &words, &read_off})
+                        &keep_ex, &bsum, &totals, &words, &read_off, &cls, &rec_t5, &rec_t3, &qout})
             b->release();
     }
 };
 
 // One file's text -> its kept reads appended to (d_stream, read_off).  *handled = false: not a text the device path
 // recognises (the caller takes the host reader, which also words the error).
-int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& text, bool error_on_non_acgt, Scratch& sc, DBuf& d_stream, u64 stream_cap_words,
-                      std::vector<u64>& read_off, u64* n_kept, u64* n_dropped, bool* handled) {
+// o.any(): stats / hist are this file's GASM_INGEST_STATS counters and GASM_QUAL_BINS bins (added to).
+int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& text, const gasm_host::IngestOpts& o, Scratch& sc, DBuf& d_stream, u64 stream_cap_words,
+                      std::vector<u64>& read_off, u64* n_kept, u64* n_dropped, bool* handled, u64* stats, u64* hist) {
+    const bool error_on_non_acgt = o.error_on_non_acgt, opts = o.any();
     *handled = false;
     *n_kept = 0;
     const u64 n = text.size();
@@ -270,6 +438,7 @@ int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& 
     const char first = text[p0];
     if (first != '@' && first != '>') return GASM_OK;
     const bool fastq = first == '@';
+    if (!fastq && (o.min_len > 0 || o.pairs)) return GASM_OK;               // a FASTA record's length is a sum over lines: the host reader
     GCHK(sc.text.ensure(n + 16));
     HIPCHK(hipMemcpyAsync(sc.text.p, text.data(), n, hipMemcpyHostToDevice, ctx->stream));
     const u8* d_text = sc.text.as<u8>();
@@ -292,6 +461,10 @@ int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& 
     hipLaunchKernelGGL(k_ing_line_starts, dim3(n_chunks), dim3(256), 0, ctx->stream, d_text, n, sc.chunk_base.as<u64>(), sc.ls.as<u64>());
     GCHK(sc.l_a.ensure((size_t)n_lines * 8)); GCHK(sc.l_len.ensure((size_t)n_lines * 4)); GCHK(sc.l_first.ensure(n_lines)); GCHK(sc.l_bad.ensure(n_lines));
     const u32 lg = (n_lines + 255) / 256;
+    if (opts) {                                          // (under options the launch can be timed beside k_ing_qual_trim: tools/bench_trim.py)
+        GLAUNCH(ctx, "k_ing_lines", k_ing_lines, dim3(lg), dim3(256), 0, d_text, sc.ls.as<u64>(), n_lines, fastq ? 0 : 1, sc.l_a.as<u64>(), sc.l_len.as<u32>(),
+                sc.l_first.as<u8>(), sc.l_bad.as<u8>());
+    } else
     hipLaunchKernelGGL(k_ing_lines, dim3(lg), dim3(256), 0, ctx->stream, d_text, sc.ls.as<u64>(), n_lines, fastq ? 0 : 1, sc.l_a.as<u64>(), sc.l_len.as<u32>(),
                        sc.l_first.as<u8>(), sc.l_bad.as<u8>());
     GCHK(sc.info.ensure(16));
@@ -324,7 +497,22 @@ int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& 
     GCHK(sc.plen.ensure((size_t)n_lines * 4 + 8)); GCHK(sc.pbase.ensure((size_t)n_lines * 8 + 8));
     HIPCHK(hipMemsetAsync(sc.rec_bad.p, 0, (size_t)n_rec * 4 + 8, ctx->stream));
     const u32 rg = std::max(1u, (n_rec + 255) / 256);
-    if (fastq) hipLaunchKernelGGL(k_ing_fastq_records, dim3(rg), dim3(256), 0, ctx->stream, sc.l_bad.as<u8>(), n_rec, sc.rec_bad.as<u32>(), sc.rec_line.as<u32>());
+    if (opts) GCHK(sc.qout.ensure(QO_WORDS * 8));
+    u64* const d_q = opts ? sc.qout.as<u64>() : nullptr;
+    if (opts) {
+        HIPCHK(hipMemsetAsync(d_q, 0, QO_FIRST * 8, ctx->stream));
+        HIPCHK(hipMemsetAsync(d_q + QO_FIRST, 0xFF, 8, ctx->stream));
+    }
+    if (fastq && opts) {
+        GCHK(sc.cls.ensure((size_t)n_rec + 8)); GCHK(sc.rec_t5.ensure((size_t)n_rec * 4 + 8)); GCHK(sc.rec_t3.ensure((size_t)n_rec * 4 + 8));
+        const QualOpts qo = {o.phred_offset, o.trim_q3, o.trim_q5, o.min_len, o.quality() ? 1 : 0, o.quality_hist ? 1 : 0};
+        u32* const d_first = reinterpret_cast<u32*>(d_q + QO_FIRST);          // [0] lowest malformed record, [1] lowest non_acgt record
+        GLAUNCH(ctx, "k_ing_qual_trim", k_ing_qual_trim, dim3(std::max(1u, std::min((n_rec + QT_WAVES - 1) / QT_WAVES, (u32)ctx->n_cu * QT_WG_PER_CU))), dim3(256), 0, d_text,
+                sc.l_a.as<u64>(), sc.l_len.as<u32>(), sc.l_bad.as<u8>(), n_rec, n_lines, qo, sc.rec_bad.as<u32>(), sc.rec_line.as<u32>(), sc.cls.as<u8>(),
+                sc.rec_t5.as<u32>(), sc.rec_t3.as<u32>(), d_q + QO_HIST, d_first);
+        GLAUNCH(ctx, "k_ing_trim_fold", k_ing_trim_fold, dim3(rg), dim3(256), 0, sc.cls.as<u8>(), sc.l_len.as<u32>(), sc.rec_t5.as<u32>(), sc.rec_t3.as<u32>(), n_rec,
+                o.pairs ? 1 : 0, sc.rec_bad.as<u32>(), d_q + QO_STATS, d_first + 1);
+    } else if (fastq) hipLaunchKernelGGL(k_ing_fastq_records, dim3(rg), dim3(256), 0, ctx->stream, sc.l_bad.as<u8>(), n_rec, sc.rec_bad.as<u32>(), sc.rec_line.as<u32>());
     else hipLaunchKernelGGL(k_ing_fasta_records, dim3(lg), dim3(256), 0, ctx->stream, sc.hdr.as<u32>(), sc.hdr_ex.as<u64>(), sc.l_bad.as<u8>(), n_lines,
                             sc.rec_bad.as<u32>(), sc.rec_line.as<u32>());
     hipLaunchKernelGGL(k_ing_piece_len, dim3(std::max(lg, rg)), dim3(256), 0, ctx->stream, fastq ? 1 : 0, sc.hdr.as<u32>(), sc.hdr_ex.as<u64>(), sc.l_len.as<u32>(),
@@ -334,9 +522,32 @@ int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& 
     GCHK(scan_u32(ctx, sc.keep.as<u32>(), n_rec, sc.bsum, sc.keep_ex.as<u64>(), d_tot + 1));
     u64 tot[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, ctx->stream));
+    u64 q_out[QO_WORDS] = {0};
+    if (opts) {
+        if (!fastq) hipLaunchKernelGGL(k_ing_fasta_bases, dim3(lg), dim3(256), 0, ctx->stream, sc.hdr.as<u32>(), sc.hdr_ex.as<u64>(), sc.l_len.as<u32>(), n_lines, d_q + 5);
+        HIPCHK(hipMemcpyAsync(q_out, d_q, QO_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const u64 bases = tot[0], kept = tot[1];
-    if (kept < n_rec && error_on_non_acgt) { gasm_set_error("%s: a read holds a base outside ACGT", path); *handled = true; return GASM_ERR_NON_ACGT; }
+    if (fastq && opts) {
+        // errors as the host reader meets them, in record order: the lowest malformed or (error_on_non_acgt) non_acgt record decides
+        const u32 mal = (u32)q_out[QO_FIRST], na = (u32)(q_out[QO_FIRST] >> 32);
+        *handled = true;
+        if (error_on_non_acgt && na < mal) { gasm_set_error("%s: a read holds a base outside ACGT", path); return GASM_ERR_NON_ACGT; }
+        if (mal != ING_NONE) {
+            gasm_set_error("%s: record %llu has a malformed quality line (not as long as its sequence, or a byte outside [%u, %u])", path, (unsigned long long)mal,
+                           o.phred_offset, o.phred_offset + 93);
+            return GASM_ERR_INVALID;
+        }
+        if (o.pairs && (n_rec & 1u)) { gasm_set_error("%s: an odd number of records (%llu) with pairs = 1", path, (unsigned long long)n_rec); return GASM_ERR_INVALID; }
+        *handled = false;
+        for (u32 q = 0; q < GASM_INGEST_STATS; ++q) stats[q] += q_out[QO_STATS + q];
+        for (u32 q = 0; q < GASM_QUAL_BINS; ++q) hist[q] += q_out[QO_HIST + q];
+    } else if (opts) {                                                         // FASTA: whole records, kept or non_acgt
+        stats[0] += n_rec; stats[1] += kept; stats[2] += n_rec - kept;
+        stats[5] += q_out[5]; stats[6] += bases; stats[7] += q_out[5] - bases;
+    }
+    if (kept < n_rec && error_on_non_acgt && !(fastq && opts)) { gasm_set_error("%s: a read holds a base outside ACGT", path); *handled = true; return GASM_ERR_NON_ACGT; }
     // ---- read offsets and the packed bases of this file, then into the batch's stream
     GCHK(sc.read_off.ensure((kept + 2) * 8));
     hipLaunchKernelGGL(k_ing_read_off, dim3(rg), dim3(256), 0, ctx->stream, sc.keep.as<u32>(), sc.keep_ex.as<u64>(), sc.rec_line.as<u32>(), sc.pbase.as<u64>(), n_rec,
@@ -364,8 +575,9 @@ int parse_text_device(gasm_ctx* ctx, const char* path, const std::vector<char>& 
 
 // One file per segment, parsed and packed on the device.  d_words: the batch's 2-bit stream (+ 4 zero padding words), read_off /
 // seg: host directories.  on_device[f]: the device path read file f (else the host reader: an irregular text).
-int ingest_files_device(gasm_ctx* ctx, const char* const* paths, u32 n_files, bool error_on_non_acgt, DBuf& d_words, std::vector<u64>& read_off,
-                        std::vector<u64>& seg, u64* dropped, std::vector<u8>& on_device) {
+// stats / hist: under options (o.any()) GASM_INGEST_STATS counters and GASM_QUAL_BINS bins per file, else left empty.
+int ingest_files_device(gasm_ctx* ctx, const char* const* paths, u32 n_files, const gasm_host::IngestOpts& o, DBuf& d_words, std::vector<u64>& read_off,
+                        std::vector<u64>& seg, u64* dropped, std::vector<u8>& on_device, std::vector<u64>& stats, std::vector<u64>& hist) {
     HIPCHK(hipSetDevice(ctx->device));
     GasmRange range("gasm:ingest (device record scan + 2-bit pack)");
     std::vector<std::vector<char>> texts(n_files);
@@ -382,17 +594,21 @@ int ingest_files_device(gasm_ctx* ctx, const char* const* paths, u32 n_files, bo
     seg.assign((size_t)n_files + 1, 0);
     on_device.assign(n_files, 0);
     *dropped = 0;
+    stats.assign(o.any() ? (size_t)n_files * GASM_INGEST_STATS : 0, 0);
+    hist.assign(o.any() ? (size_t)n_files * GASM_QUAL_BINS : 0, 0);
     Scratch sc;
     struct Rel { Scratch& s; ~Rel() { s.release(); } } rel{sc};
     for (u32 f = 0; f < n_files; ++f) {
         u64 kept = 0;
         bool handled = false;
-        GCHK(parse_text_device(ctx, paths[f], texts[f], error_on_non_acgt, sc, d_words, cap_words, read_off, &kept, dropped, &handled));
+        u64* const st_f = o.any() ? &stats[(size_t)f * GASM_INGEST_STATS] : nullptr;
+        u64* const hi_f = o.any() ? &hist[(size_t)f * GASM_QUAL_BINS] : nullptr;
+        GCHK(parse_text_device(ctx, paths[f], texts[f], o, sc, d_words, cap_words, read_off, &kept, dropped, &handled, st_f, hi_f));
         if (!handled) {
             // the host reader (its grammar is the definition; it also words the error of a malformed file), then the same append
             gasm_host::PackedReads pr;
             u64 hk = 0;
-            GCHK(gasm_host::read_sequence_file(paths[f], error_on_non_acgt, pr, &hk, dropped));
+            GCHK(gasm_host::read_sequence_file(paths[f], o, pr, &hk, dropped, st_f, hi_f));
             const u64 nwh = pr.words.size();
             GCHK(sc.words.ensure((nwh + 4) * 8));
             HIPCHK(hipMemsetAsync(sc.words.p, 0, (nwh + 4) * 8, ctx->stream));

@@ -393,5 +393,5 @@ int gasm_wait_word32(gasm_ctx* ctx, const volatile u32* word, u32 ticket);
 int gasm_wait_word64(gasm_ctx* ctx, const volatile u64* word, u64 ticket);
 
 // sequence files parsed and packed on the device (ingest.hip); on_device[f] = 0 where the host reader took an irregular file
-int ingest_files_device(gasm_ctx* ctx, const char* const* paths, u32 n_files, bool error_on_non_acgt, DBuf& d_words, std::vector<u64>& read_off,
-                        std::vector<u64>& seg, u64* dropped, std::vector<u8>& on_device);
+int ingest_files_device(gasm_ctx* ctx, const char* const* paths, u32 n_files, const gasm_host::IngestOpts& o, DBuf& d_words, std::vector<u64>& read_off,
+                        std::vector<u64>& seg, u64* dropped, std::vector<u8>& on_device, std::vector<u64>& stats, std::vector<u64>& hist);

@@ -105,6 +105,39 @@ def simulate_reads_indel(genome, read_len, coverage, seed, sub_rate, indel_rate)
     return out[keep]
 
 
+def simulate_qualities(n_reads, read_len, seed, q_start=38, q_end=12, tail_frac=0.3):
+    """(n_reads, read_len) int64 base qualities in the shape of a short-read run: q_start over the read's head, then a straight decline
+    to q_end over its last tail_frac, each read shifted as a whole by a jitter of -3..3 and each base by -2..2; clipped to 2..41."""
+    rng = np.random.Generator(np.random.MT19937(seed))
+    tail = max(1, int(round(read_len * tail_frac)))
+    prof = np.full(read_len, float(q_start))
+    prof[read_len - tail:] = np.linspace(q_start, q_end, tail + 1)[1:]
+    q = np.rint(prof)[None, :].astype(np.int64) + rng.integers(-3, 4, size=(n_reads, 1)) + rng.integers(-2, 3, size=(n_reads, read_len))
+    return np.clip(q, 2, 41)
+
+
+def apply_quality_errors(reads, quals, seed):
+    """the reads (uint8 ASCII, (n, read_len)) with base i of a read substituted, with probability 10^(-q_i / 10), by one of the three
+    other bases: errors where the qualities say they are.  Returns (reads with errors, bool array of the substituted bases)."""
+    rng = np.random.Generator(np.random.MT19937(seed))
+    reads = np.asarray(reads, dtype=np.uint8)
+    err = rng.random(reads.shape) < 10.0 ** (-np.asarray(quals, dtype=np.float64) / 10.0)
+    shift = rng.integers(1, 4, size=reads.shape)
+    code = np.searchsorted(_ACGT, reads)
+    return np.where(err, _ACGT[(code + shift) % 4], reads).astype(np.uint8), err
+
+
+def write_fastq(path, reads, quals, names=None, phred_offset=33):
+    """four-line FASTQ: reads and quals are sequences of equal length (rows of arrays, or bytes / lists of int of any lengths)"""
+    with open(path, "wb") as f:
+        for i, (r, q) in enumerate(zip(reads, quals)):
+            name = names[i] if names is not None else f"r{i}"
+            seq = bytes(r) if isinstance(r, (bytes, bytearray)) else np.asarray(r, dtype=np.uint8).tobytes()
+            qs = (np.asarray(q, dtype=np.int64) + phred_offset).astype(np.uint8).tobytes()
+            f.write(b"@" + str(name).encode() + b"\n" + seq + b"\n+\n" + qs + b"\n")
+    return path
+
+
 def make_batch(n_segments, seg_len, read_len, coverage, seed0=1234, planted=True):
     """reads of n_segments segments as one (total_reads, read_len) uint8 array + seg_read_off + the genomes"""
     reads, off, genomes = [], [0], []

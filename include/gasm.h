@@ -306,6 +306,63 @@ const uint64_t* gasm_packed_read_off(const gasm_packed* g);        /* n_reads + 
 const uint64_t* gasm_packed_seg_read_off(const gasm_packed* g);    /* n_segments + 1 */
 uint64_t gasm_packed_dropped(const gasm_packed* g);
 void gasm_packed_free(gasm_packed* g);
+/* ---- Quality trimming at ingest ------------------------------------------------------------------------------------------------
+ * The file entries above with options: FASTQ records trimmed by base quality, filtered by length, mates kept together, and a report
+ * of what was done.  size must be sizeof(gasm_ingest_params), else GASM_ERR_INVALID (as gasm_build_params).  With every field but
+ * size and on_non_acgt zero an entry below is the plain entry of the same name: the same host code, the same kernel launches.  The
+ * plain entries fill the struct with their on_non_acgt and take the same path.
+ *
+ * THE RULE, per FASTQ record.  L = length of the sequence line as the reader takes it (CR and trailing blanks removed); the quality
+ * line is trimmed the same way.
+ *   Quality mode: on iff trim_q3 > 0 or trim_q5 > 0 or quality_hist != 0; only then are quality lines read at all.  In quality mode
+ *     a record whose quality line is not L bytes long, or holds a byte outside [phred_offset, phred_offset + 93], is
+ *     GASM_ERR_INVALID; the message names the file and the lowest such record index (0-based).
+ *   Base quality: q_i = byte_i - phred_offset; for trimming, a base outside ACGTacgt has q_i = 0 whatever its byte says.
+ *   3' end (BWA / cutadapt's running sum): s = 0, best = 0, e = L; for i = L-1 down to 0: s += trim_q3 - q_i; if s < 0 stop;
+ *     if s > best: best = s, e = i.  Strictly greater: of equal candidates the outermost stays and less is trimmed.
+ *     trim_q3 = 0: e = L.
+ *   5' end, over the WHOLE read (not over [0, e)): s = 0, best = 0, a = 0; for i = 0 .. L-1: s += trim_q5 - q_i; if s < 0 stop;
+ *     if s > best: best = s, a = i + 1.  trim_q5 = 0: a = 0.
+ *   Span: [a, e) is kept.  a >= e: the span is empty, trimmed3 = L - e, trimmed5 = min(a, e).
+ *   Class, exactly one per record, the earlier wins:
+ *     non_acgt  the span holds a base outside ACGT (a terminal N that was trimmed does not count); on_non_acgt = 1: GASM_ERR_NON_ACGT
+ *     short     the span has fewer than min_len bases (min_len = 0 keeps empty reads)
+ *     mate      pairs = 1 and the record's mate (record r ^ 1 of the file) is non_acgt or short.  pairs = 1 and an odd number of
+ *               records in a file: GASM_ERR_INVALID.  pairs means interleaved files only.
+ *     kept
+ *   Errors are met in record order: the lowest record that is malformed or (on_non_acgt = 1) non_acgt decides.
+ * FASTA has no qualities: the cutoffs and the histogram do not apply to it, min_len and pairs apply to whole records.
+ * Not done: adapter removal, sliding windows, per-base masking; qualities are not kept past the ingest.
+ *
+ * Statistics, per file (= segment), GASM_INGEST_STATS uint64 in this order: records, kept, dropped_non_acgt, dropped_short,
+ * dropped_mate, bases_in, bases_kept (span bases of kept records), bases_dropped (span bases of the others), trimmed5, trimmed3 (over
+ * all records), reads_trimmed (kept records that lost a base).  records = kept + the three drops; bases_in = bases_kept + bases_dropped
+ * + trimmed5 + trimmed3.  The dropped-reads count of the plain accessors is the sum of the three drops.  The histogram (quality_hist
+ * = 1, FASTQ): GASM_QUAL_BINS uint64 per file, bin q = positions of all records, before trimming, whose byte says quality q (an N
+ * under its own byte).  Both are collected when an option besides on_non_acgt is set; after a plain ingest the accessors return
+ * NULL and the fetch GASM_ERR_STATE.
+ * The device entries trim with one wave per record (csrc/ingest.hip, k_ing_qual_trim); an irregular FASTQ, and a FASTA file under
+ * min_len or pairs (record lengths there are sums over lines), are read by the host reader (gasm_packed_parsed_on_device = 0). */
+typedef struct gasm_ingest_params {
+    uint32_t size;           /* sizeof(gasm_ingest_params) */
+    uint32_t on_non_acgt;    /* 0 drop and count, 1 error */
+    uint32_t phred_offset;   /* 0 -> 33; 33 or 64 */
+    uint32_t trim_q3, trim_q5;   /* 0..93, 0 = that end is not trimmed */
+    uint32_t min_len;
+    uint32_t pairs;          /* 0 / 1 */
+    uint32_t quality_hist;   /* 0 / 1 */
+} gasm_ingest_params;
+#define GASM_INGEST_STATS 11
+#define GASM_QUAL_BINS 94
+int gasm_read_files_params(const char* const* paths, uint32_t n_files, const gasm_ingest_params* params, gasm_packed** out);
+int gasm_read_files_device_params(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, const gasm_ingest_params* params,
+                                  gasm_packed** out);
+int gasm_batch_from_files_params(gasm_ctx* ctx, const char* const* paths, uint32_t n_files, const gasm_ingest_params* params,
+                                 gasm_batch** out, uint64_t* dropped_reads);
+const uint64_t* gasm_packed_ingest_stats(const gasm_packed* g);    /* n_segments * GASM_INGEST_STATS */
+const uint64_t* gasm_packed_quality_hist(const gasm_packed* g);    /* n_segments * GASM_QUAL_BINS */
+/* the same two arrays of a batch made by gasm_batch_from_files_params */
+int gasm_batch_fetch_ingest_stats(gasm_batch* b, const uint64_t** stats, const uint64_t** quality_hist);
 void gasm_batch_free(gasm_batch* b);
 /* genome_len_hint: expected distinct k-mers per segment (0 = derive from the k-mer count); only sizes buckets.
  * build and score only QUEUE their work (no host wait); the fetches below wait for it.  A batch keeps up to four
@@ -633,7 +690,8 @@ int gasm_batch_fetch_contig_links(gasm_batch* b, const uint32_t** succ, const ui
  * The rule.  PAIRS.  Inside every segment reads 2p and 2p + 1 are the two MATES of pair p: an interleaved layout, which
  * gasm_batch_from_files yields for an interleaved FASTQ.  The pairs are forward-reverse: mate 1 is the fragment's first bases, mate 2
  * the reverse complement of its last bases.  A segment with an odd number of reads makes the call fail with GASM_ERR_INVALID.  Dropping
- * non-ACGT reads at ingest breaks the pairing: that is the caller's business.
+ * non-ACGT reads at ingest breaks the pairing: that is the caller's business (gasm_batch_from_files_params with pairs = 1 drops mates
+ * together and so keeps it).
  *   THE SET.  The graph is the one of the batch's LAST FINISHED BUILD, whatever its options, exactly as for contig links.  A k-mer is IN
  *   THE SET if the build holds it and it lies in a contig; a k-mer of an isolated cycle is not in the set.  Contig indices are the ones
  *   INSIDE THE SEGMENT; len(c) is counted in bases.
